@@ -19,8 +19,11 @@ Weak scaling: every rank runs its own 32-utterance shard (global batch 32 N = co
 train-ctc-parallel.cc:215,247-252) with the per-step H2D INSIDE the timed step (round 5; the copy of step n + 1 travels under
 step n's backward pass); `config.device_resident_frames_per_s` is the same loop with the features already resident in HBM.
 
-Rank 0 prints ONE JSON line (see the task contract) with `roofline` (dominant kernel, live HIP-event timing)
-and, at N = 1, `cpu_baseline` (the reference's own CPU code from oracle/_ref when present, else the C port).
+Rank 0 prints ONE JSON line (see the task contract) with `roofline` (dominant kernel, live HIP-event timing of the timed steps).
+A plain run does only that: set-up, warm-up, the K timed steps, the line.  `--full` adds, at N = 1, everything that takes runs of
+its own: the other GEMM arithmetic modes, the device-resident loop, the standalone gate GEMM, `cpu_baseline` (the reference's own
+CPU code from oracle/_ref when present, else the C port), the feature front end and config.secondary (the other BASELINE shapes).
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (dump_outputs).
 """
 from __future__ import annotations
 
@@ -155,13 +158,22 @@ def ctc_block(cfg, batch, ctc_ph: dict, K: int) -> dict:
                      "positions_per_lane": maxp}}
 
 
+def usable_cpus() -> int:
+    """The CPUs this process may run on (affinity mask), capped by OMP_NUM_THREADS where set -- not os.cpu_count(), the whole
+    host's.  The reference's OpenBLAS sizes its per-thread state by the CPUs it finds at load and segfaults when asked for more
+    threads than that (measured: crash above affinity + 1 threads)."""
+    n = len(os.sched_getaffinity(0))
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    return min(n, int(omp)) if omp.isdigit() and int(omp) > 0 else n
+
+
 def cpu_baseline(cfg, seconds_budget: float = 25.0) -> dict:
     """The reference's CPU path (oracle/_ref: src/net + src/cpucompute compiled unmodified; its CUDA-only CTC
     kernels run through the CPU shim) or, when that library is absent, the C port; same model, a bounded
     sample of the same workload.  Reported, never the target."""
     from oracle import refbind, net as onet
     from eesen_amd import nnet_io
-    ncores = os.cpu_count() or 1
+    ncores = usable_cpus()
     sc = dict(cfg)
     sc["T"] = 250  # 32 utterances x 250 frames = 8000 padded frames of the same 4x512 BiLSTM: ~20 s over the three thread settings
     layers = synth.make_model(max_grad=50.0, **sc)
@@ -536,16 +548,48 @@ def check_full_cfg3(comm, dev: int, rank: int, world: int, all_reduce) -> dict:
             "persistent_layers": {"fwd": info["fwd_persistent"], "bwd": info["bwd_persistent"], "of": info["lstm_layers"]}}
 
 
+DUMP_ROWS_FLOATS = 3 << 20     # per [rows x cols] output: at most 12 MB, else a seeded sample of whole rows
+DUMP_PARAMS_FLOATS = 1 << 20   # parameters and gradients: a seeded sample of 4 MB each (cfg2 has 21.2 M of each)
+
+
+def dump_outputs(path: str, net, out, diff, ctc) -> None:
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as DIR/<name>.npy -- the network output
+    (posteriors [T*S x K], row t*S + s), the CTC gradient with respect to it (ctc_diff), the parameters after the step's update
+    and the step's fresh gradients (the same seeded sample of both), and the CTC statistics of the run (objective sum,
+    sequences, frames, error tokens, reference tokens, over every step of the process).  Inputs are seeded, so two builds
+    run with the same arguments can be compared array by array.  32 MB at most in all."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(0)
+    post, cdiff = out.numpy(), diff.numpy()
+    if post.size > DUMP_ROWS_FLOATS:
+        idx = np.sort(rng.choice(post.shape[0], DUMP_ROWS_FLOATS // post.shape[1], replace=False))
+        post, cdiff = post[idx], cdiff[idx]
+    params, grads = net.GetParams(), net.GetGrads()
+    if params.size > DUMP_PARAMS_FLOATS:
+        idx = np.sort(rng.choice(params.size, DUMP_PARAMS_FLOATS, replace=False))
+        params, grads = params[idx], grads[idx]
+    st = ctc.stats()
+    arrays = {"posteriors": post, "ctc_diff": cdiff, "params": params, "grads": grads,
+              "ctc_stats": np.array([st["obj_sum"], st["sequences"], st["frames"], st["err_tokens"], st["ref_tokens"]], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip config.secondary (cfg4 / cfg5 / the recipe shape, a few timed steps each)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline, the legs that take runs of their own (other GEMM arithmetic modes, device-resident "
+                         "loop, standalone gate GEMM, CPU baseline, feature front end, config.secondary)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without config.secondary (cfg4 / cfg5 / the recipe shape, a few timed steps each)")
     ap.add_argument("--main-only", action="store_true",
-                    help="profiling runs: skip the secondary legs (f32-MFMA-GEMM comparison, PCIe-inclusive loop, standalone GEMM, CPU baseline, config.secondary)")
+                    help="the headline only, even with --full (what a plain run does; profiling runs name it)")
     ap.add_argument("--T", type=int, default=0, help="override T_max (debug)")
     ap.add_argument("--H", type=int, default=0, help="override cells per direction (debug)")
     ap.add_argument("--S", type=int, default=0, help="override utterances per GPU (debug)")
@@ -564,6 +608,9 @@ def main():
                          "256) at the fixture's bars; the result goes into the line as config.check_full_cfg3")
     ap.add_argument("--leg", default=None, help="(internal) run ONE leg of config.secondary in this process and print its record as a JSON line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    lean = args.main_only or not args.full
     if args.leg:
         print(json.dumps(secondary_legs(0)[args.leg]()), flush=True)
         return
@@ -715,7 +762,7 @@ def main():
     ctc.SetProfiling(True)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_out = step()
     barrier()
     dt = time.perf_counter() - t0
     spans = net.PhaseSpans()           # every timed span of the K steps, in record order (before PhaseTimes clears them)
@@ -732,6 +779,8 @@ def main():
     ctc_ph = ctc.PhaseTimes()
     ctc.SetProfiling(False)
     net.SetProfiling(True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, last_out, diff, ctc)   # before anything else runs on this Net
     if multi:
         dt = all_reduce([dt], Comm.MAX)[0]                                       # the slowest rank's clock
         padded, real = all_reduce([float(batch.T * batch.S), float(batch.real_frames)])
@@ -743,7 +792,7 @@ def main():
     # that both arithmetic modes are on record from the same box and process.
     f32_only = None
     bf16_split = None
-    if world == 1 and not args.main_only and gemm_products() == 3:
+    if world == 1 and not lean and gemm_products() == 3:
         # Each in its OWN process (this script with --main-only and EESEN_GEMM_MODE set): a second Net of another arithmetic inside this
         # process measured 40.1-41.3 ms for the six-product mode where a process of its own measures 35.8 (the step time of that mode is
         # bimodal with where the Net's buffers land, scripts/leg_artifact.py) -- a comparison must not depend on that draw.  This process
@@ -773,7 +822,7 @@ def main():
     # step n's backward pass; what is left is the host's pack into the pinned slot on the enqueueing thread -- hidden while the host
     # runs ahead of the device -- and the interleave kernel's share of the chip).  Same warm-up, same process, same Net.
     resident = None
-    if world == 1 and not args.main_only:
+    if world == 1 and not lean:
         for _ in range(max(2, args.warmup)):
             step_resident()
         barrier()
@@ -889,8 +938,8 @@ def main():
         # are GATED on the recurrence's arrival counters and run under it, so their in-step duration says nothing about the
         # matrix pipe.  This is the figure to hold against the >= 60 % MFMA target on the gate GEMMs.
         try:
-            if args.main_only:
-                raise RuntimeError("skipped (--main-only)")
+            if lean:
+                raise RuntimeError("skipped (a run of its own: --full)")
             import ctypes as C
             Mg, Ng, Kg = T * S, nd * 4 * H, nd * H
             rg = np.random.default_rng(1)   # random operands: all-zero inputs would flatter the clocks
@@ -991,17 +1040,17 @@ def main():
                                     "ms_per_step": 1e3 * tot_s, "exposed_ms_per_step": 1e3 * sum(ex) / K, "buckets": buckets,
                                     "note": "bus bandwidth of a ring all-reduce, 2 (N-1)/N x bytes / time, on rank 0; peak = 7 xGMI links x 153 GB/s per GPU"
                                             + ("; ONE rank: nothing crosses a link, the figure is the collective's launch + copy cost" if world == 1 else "")}
-        if world == 1 and not args.no_cpu_baseline and not args.main_only:
+        if world == 1 and not args.no_cpu_baseline and not lean:
             try:
                 line["cpu_baseline"] = cpu_baseline(cfg)
             except Exception as e:  # the baseline leg must never take the GPU number down with it
                 line["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e}"}
-        if world == 1 and not args.main_only:
+        if world == 1 and not lean:
             try:
                 line["frontend"] = frontend_leg(dev)
             except Exception as e:  # never takes the headline down
                 line["frontend"] = {"error": str(e)}
-        if world == 1 and not args.main_only and not args.no_secondary and args.config == "cfg2" and not (args.T or args.H or args.S or args.layers):
+        if world == 1 and not lean and not args.no_secondary and args.config == "cfg2" and not (args.T or args.H or args.S or args.layers):
             # the other single-GPU BASELINE configurations and the reference's own recipe shape, driver-timed in the same run
             del net, feats_dev, diff, feeder
             sec = {}

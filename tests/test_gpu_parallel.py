@@ -21,7 +21,7 @@ def test_bench_runs_under_torchrun_with_one_rank(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--T", "100",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0 and '"metric"' in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
@@ -37,6 +37,31 @@ def _bench(args, env_extra, timeout=900):
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     return json.loads(lines[0]), r.stderr
+
+
+def test_plain_bench_run_is_the_headline_only_and_dumps_its_last_step(gpu, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W`: the K timed steps and the line, none of the legs --full adds; with
+    --dump-outputs DIR the last timed step's outputs as float32 / float64 .npy files, 64 MB at most."""
+    import numpy as np
+    from eesen_amd import synth
+    d, _ = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--T", "100", "--dump-outputs", str(tmp_path)], {})
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["dtype"] == "f32" and d["value"] == pytest.approx(d["config"]["padded_frames_per_step"] * 1e3 / d["ms_per_step"], rel=1e-6)
+    assert "cpu_baseline" not in d and "frontend" not in d and "secondary" not in d["config"] and "legs_ms" not in d
+    assert d["config"]["f32_mfma_gemm_only"] is None and d["config"]["device_resident_ms_per_step"] is None
+    files = {f.name: np.load(f) for f in tmp_path.iterdir()}
+    assert set(files) == {"posteriors.npy", "ctc_diff.npy", "params.npy", "grads.npy", "ctc_stats.npy"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64 << 20
+    cfg = synth.config("cfg2")
+    batch = synth.make_batch(**{**cfg, "T": 100, "seed": 777})
+    post = files["posteriors.npy"]
+    assert post.shape == (100 * 32, cfg["K"]) == files["ctc_diff.npy"].shape
+    real = np.array([t < batch.lens[s] for t in range(100) for s in range(32)])
+    assert np.allclose(post[real].sum(1), 1.0, atol=1e-4)           # softmax rows of the real frames
+    assert files["params.npy"].shape == files["grads.npy"].shape == (1 << 20,) and np.all(np.isfinite(files["grads.npy"]))
+    assert files["ctc_stats.npy"][1] > 0 and files["ctc_stats.npy"][1] % 32 == 0
 
 
 def test_bench_secondary_leg_runs_as_a_process_of_its_own(gpu):

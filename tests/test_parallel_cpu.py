@@ -234,3 +234,17 @@ def test_bench_pipe_bound_keeps_every_fraction_at_or_below_one():
             assert bench.pipe_bound(cfg, 0)["bound_us_per_frame"] > pb["bound_us_per_frame"]
         # the forward recurrence on the 16-bit pipe moves its half of the recurrent flops there
         assert bench.pipe_bound(cfg, 3, 3)["bound_us_per_frame"] < bench.pipe_bound(cfg, 3, 0)["bound_us_per_frame"]
+
+
+def test_bench_cpu_baseline_threads_stay_within_the_cpus_the_process_may_use(monkeypatch):
+    """bench.py --full's cpu_baseline: the reference's OpenBLAS segfaults when asked for more threads than the CPUs it finds at
+    load, so the thread counts come from the affinity mask (capped by OMP_NUM_THREADS), never from the whole host's count."""
+    import bench
+    monkeypatch.setattr(os, "sched_getaffinity", lambda pid: {0, 1, 2})
+    monkeypatch.setattr(os, "cpu_count", lambda: 256)
+    monkeypatch.delenv("OMP_NUM_THREADS", raising=False)
+    assert bench.usable_cpus() == 3
+    monkeypatch.setenv("OMP_NUM_THREADS", "2")
+    assert bench.usable_cpus() == 2
+    monkeypatch.setenv("OMP_NUM_THREADS", "16")
+    assert bench.usable_cpus() == 3
