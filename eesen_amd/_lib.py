@@ -89,6 +89,17 @@ SIGNATURES = {
     "eesen_ctc_set_profiling": (_i, [_vp, _i]),
     "eesen_ctc_set_sequence_out_file": (_i, [_vp, C.c_char_p]),
     "eesen_ctc_get_phase_times": (_i, [_vp, _vp]),
+    "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
+    "eesen_ce_destroy": (_i, [_vp]),
+    "eesen_ce_eval_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "eesen_ce_set_report_step": (_i, [_vp, _i]),
+    "eesen_ce_stats": (_i, [_vp, _pd, _pl, _pl, _pl]),
+    "eesen_ce_report": (_i, [_vp, C.c_char_p, _i]),
+    "eesen_ce_progress": (_i, [_vp, _i, C.c_char_p, _i]),
+    "eesen_ce_set_guard": (_i, [_vp, _vp]),
+    "eesen_ce_dropped": (_i, [_vp, _pl]),
+    "eesen_ce_set_profiling": (_i, [_vp, _i]),
+    "eesen_ce_get_phase_times": (_i, [_vp, _vp]),
     "eesen_net_set_train_mode": (_i, [_vp, _i]),
     "eesen_net_set_dropout_seed": (_i, [_vp, C.c_ulonglong]),
     "eesen_net_set_layer_dropout": (_i, [_vp, _i, _pf]),

@@ -573,6 +573,89 @@ class Ctc:
         return dict(zip(["log", "alpha_beta", "error_diff"], out.tolist()))
 
 
+class CE:
+    """eesen::CE (ce-loss.h:32-77): frame-level cross-entropy over softmax outputs, one fused pass on the device
+    (include/eesen_hip.h `eesen_ce_*`)."""
+
+    def __init__(self, device: int = 0, stream: Optional[int] = None):
+        self.lib = _lib.load()
+        self.device = device
+        self.h = C.c_void_p()
+        check(self.lib.eesen_ce_create(device, C.c_void_p(stream) if stream else None, C.byref(self.h)))
+        self.obj = None
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h:
+            try:
+                self.lib.eesen_ce_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def EvalParallel(self, net_out: CuMatrix, targets: Sequence[int], diff: Optional[CuMatrix] = None,
+                     frame_num_utt: Optional[Sequence[int]] = None, want_obj: bool = True) -> CuMatrix:
+        """CE::EvalParallel (ce-loss.cc:94-169): targets = one class id per row t*S + s; row valid iff t < frame_num_utt[s]
+        (None: S = 1 and every row valid).  Returns diff = (y - onehot) on valid rows, 0 on padded rows (allocated when not
+        given); self.obj = this call's objective.  want_obj=False: nothing waits for the device (self.obj is None then)."""
+        fn = np.ascontiguousarray([net_out.rows] if frame_num_utt is None else frame_num_utt, np.int32)
+        tg = np.ascontiguousarray(targets, np.int32)
+        if tg.size != net_out.rows:
+            raise EesenError(-1, f"{tg.size} targets for {net_out.rows} rows")
+        if diff is None:
+            diff = CuMatrix(net_out.rows, net_out.cols, self.device, zero=False)
+        obj = C.c_double()
+        check(self.lib.eesen_ce_eval_parallel(self.h, _np_ptr(fn), fn.size, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols,
+                                              net_out.stride, _np_ptr(tg), C.c_void_p(diff.ptr), diff.stride,
+                                              C.byref(obj) if want_obj else None))
+        self.obj = obj.value if want_obj else None
+        return diff
+
+    def Eval(self, net_out: CuMatrix, targets: Sequence[int], diff: Optional[CuMatrix] = None) -> CuMatrix:
+        """CE::Eval (ce-loss.cc:30-92): one sequence, no mask, sequences += 1."""
+        return self.EvalParallel(net_out, targets, diff, None)
+
+    def SetReportStep(self, report_step: int):
+        check(self.lib.eesen_ce_set_report_step(self.h, int(report_step)))
+
+    def stats(self) -> dict:
+        o, c, f, s = C.c_double(), C.c_long(), C.c_long(), C.c_long()
+        check(self.lib.eesen_ce_stats(self.h, C.byref(o), C.byref(c), C.byref(f), C.byref(s)))
+        return dict(obj=o.value, correct=c.value, frames=f.value, sequences=s.value)
+
+    def Progress(self, wait: bool = False) -> List[str]:
+        """The progress lines of ce-loss.cc:153-167 that are ready (wait=True: after every pending call has arrived)."""
+        out, buf = [], C.create_string_buffer(4096)
+        while True:
+            check(self.lib.eesen_ce_progress(self.h, 1 if wait else 0, buf, len(buf)))
+            if not buf.value:
+                return out
+            out.append(buf.value.decode())
+
+    def Report(self) -> str:
+        """CE::Report (ce-loss.cc:171-175), with the true ratio correct / frames (INTEGRATION.md, CE)."""
+        buf = C.create_string_buffer(256)
+        check(self.lib.eesen_ce_report(self.h, buf, len(buf)))
+        return buf.value.decode()
+
+    def SetGuard(self, net: Optional[Net]):
+        """Drop minibatches computed from a timed-out persistent forward pass of `net` from the statistics (eesen_ce_set_guard)."""
+        check(self.lib.eesen_ce_set_guard(self.h, net.h if net is not None else None))
+        self._guard = net
+
+    def Dropped(self) -> int:
+        n = C.c_long()
+        check(self.lib.eesen_ce_dropped(self.h, C.byref(n)))
+        return n.value
+
+    def SetProfiling(self, accumulate: bool):
+        check(self.lib.eesen_ce_set_profiling(self.h, 2 if accumulate else 0))
+
+    def PhaseTimes(self) -> dict:
+        out = np.zeros(1, np.float32)
+        check(self.lib.eesen_ce_get_phase_times(self.h, _np_ptr(out)))
+        return dict(ce=float(out[0]))
+
+
 class Feeder:
     """Device-side minibatch assembly, double-buffered (include/eesen_hip.h `eesen_feeder_*`; replaces the host padding +
     interleave + blocking copy of /root/reference/src/netbin/train-ctc-parallel.cc:186-195).

@@ -301,6 +301,76 @@ int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->phase_times(out3); });
 }
 
+int eesen_ce_create(int device, void* stream, eesen_ce_t** out) {
+  return guard([&] { REQ_PTR(out); *out = new eesen_ce(device, stream); });
+}
+int eesen_ce_destroy(eesen_ce_t* ce) {
+  return guard([&] { delete ce; });
+}
+int eesen_ce_eval_parallel(eesen_ce_t* ce, const int* frame_num_utt, int S, const float* net_out_dev, int rows, int K, int ld,
+                           const int* targets_host, float* diff_dev, int diff_ld, double* obj_host) {
+  return guard([&] {
+    REQ_PTR(ce); REQ_PTR(frame_num_utt); REQ_PTR(net_out_dev); REQ_PTR(targets_host); REQ_PTR(diff_dev);
+    ce->eval_parallel(frame_num_utt, S, net_out_dev, rows, K, ld, targets_host, diff_dev, diff_ld, obj_host);
+  });
+}
+int eesen_ce_set_report_step(eesen_ce_t* ce, int report_step) {
+  return guard([&] { REQ_PTR(ce); ce->flush(); ce->report_step = report_step; });
+}
+int eesen_ce_stats(eesen_ce_t* ce, double* obj, long* correct, long* frames, long* sequences) {
+  return guard([&] {
+    REQ_PTR(ce);
+    ce->flush();
+    if (obj) *obj = ce->obj;
+    if (correct) *correct = ce->correct;
+    if (frames) *frames = ce->frames;
+    if (sequences) *sequences = ce->sequences;
+  });
+}
+int eesen_ce_report(eesen_ce_t* ce, char* buf, int cap) {
+  return guard([&] {
+    REQ_PTR(ce); REQ_PTR(buf);
+    const std::string s = ce->report();
+    EESEN_REQUIRE(cap > (int)s.size(), EESEN_ERR_INVALID, "eesen_ce_report: buffer too small (" + std::to_string(s.size() + 1) + " bytes needed)");
+    std::memcpy(buf, s.c_str(), s.size() + 1);
+  });
+}
+int eesen_ce_progress(eesen_ce_t* ce, int wait, char* buf, int cap) {
+  return guard([&] {
+    REQ_PTR(ce); REQ_PTR(buf);
+    EESEN_REQUIRE(cap > 0, EESEN_ERR_INVALID, "eesen_ce_progress: no buffer");
+    if (wait) ce->flush();
+    if (ce->progress.empty()) { buf[0] = 0; return; }
+    const std::string& s = ce->progress.front();
+    EESEN_REQUIRE(cap > (int)s.size(), EESEN_ERR_INVALID, "eesen_ce_progress: buffer too small (" + std::to_string(s.size() + 1) + " bytes needed)");
+    std::memcpy(buf, s.c_str(), s.size() + 1);
+    ce->progress.erase(ce->progress.begin());
+  });
+}
+int eesen_ce_set_guard(eesen_ce_t* ce, eesen_net_t* net) {
+  return guard([&] {
+    REQ_PTR(ce);
+    ce->flush();
+    if (net) EESEN_REQUIRE(net->device == ce->device && net->st == ce->st, EESEN_ERR_INVALID, "eesen_ce_set_guard: the CE and the Net must live on the same device and stream");
+    if (ce->guard_net) {   // unhook from the Net guarded so far
+      auto& g = ce->guard_net->ce_guards;
+      g.erase(std::remove(g.begin(), g.end(), static_cast<CeLoss*>(ce)), g.end());
+    }
+    ce->guard = net && net->ctl.p ? net->ctl.p + kCtlWords - 1 : nullptr;
+    ce->guard_net = ce->guard ? net : nullptr;
+    if (ce->guard_net) net->ce_guards.push_back(ce);
+  });
+}
+int eesen_ce_dropped(eesen_ce_t* ce, long* minibatches) {
+  return guard([&] { REQ_PTR(ce); REQ_PTR(minibatches); ce->flush(); *minibatches = ce->dropped; });
+}
+int eesen_ce_set_profiling(eesen_ce_t* ce, int mode) {
+  return guard([&] { REQ_PTR(ce); ce->timer.enable(mode == 2); ce->timer.set_accumulate(mode == 2); });
+}
+int eesen_ce_get_phase_times(eesen_ce_t* ce, float* out1) {
+  return guard([&] { REQ_PTR(ce); REQ_PTR(out1); ce->phase_times(out1); });
+}
+
 int eesen_dev_alloc(int device, long bytes, void** dev_ptr) {
   return guard([&] {
     REQ_PTR(dev_ptr);

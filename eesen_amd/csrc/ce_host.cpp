@@ -1,0 +1,158 @@
+// ce_host.cpp -- host side of the CE object: target checks and staging, launch, running totals, progress and report text.
+// Replaces eesen::CE::EvalParallel / Eval / Report (the reference's src/net/ce-loss.cc:30-175).  The arithmetic is in ce.hip.
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <sstream>
+
+#include "net.h"
+
+namespace eesen {
+
+CeLoss::CeLoss(int dev, void* stream) : device(dev) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0)
+    throw Error(EESEN_ERR_HIP, "no HIP device available: this library has no CPU fallback");
+  EESEN_REQUIRE(dev >= 0 && dev < n, EESEN_ERR_INVALID, "device index out of range");
+  EESEN_HIP_CHECK(hipSetDevice(dev));
+  st = reinterpret_cast<hipStream_t>(stream);  // NULL = the device's default stream (shared with the Net)
+  for (auto& x : ev) EESEN_HIP_CHECK(hipEventCreate(&x));
+}
+
+CeLoss::~CeLoss() {
+  (void)hipSetDevice(device);
+  (void)hipStreamSynchronize(st);
+  if (guard_net) {
+    auto& g = guard_net->ce_guards;
+    g.erase(std::remove(g.begin(), g.end(), this), g.end());
+  }
+  for (auto& x : ev)
+    if (x) (void)hipEventDestroy(x);
+  auto drop = [](Ctc::Pin& pin) {
+    if (pin.p) (void)hipHostFree(pin.p);
+    if (pin.ev) (void)hipEventDestroy(pin.ev);
+  };
+  for (auto& x : stage) drop(x);
+  for (auto& x : pend) drop(x.pin);
+}
+
+// The totals and the progressive report of ce-loss.cc:144-167, in call order.  obj_out (may be null): this call's objective.
+void CeLoss::fold(Pending& q, double* obj_out) {
+  if (!q.active) return;
+  EESEN_HIP_CHECK(hipEventSynchronize(q.pin.ev));
+  q.pin.busy = false;
+  q.active = false;
+  const CeSums* r = static_cast<const CeSums*>(q.pin.p);
+  if (*reinterpret_cast<const unsigned*>(r + 1) != 0) {  // computed from a timed-out forward pass (Ctc::guard): not a statistic
+    if (obj_out) *obj_out = std::numeric_limits<double>::quiet_NaN();
+    if (dropped++ == 0 || dropped % 100 == 0)
+      fprintf(stderr, "WARNING (eesen_hip) CE statistics of a minibatch computed from a timed-out forward pass were dropped (%ld so far)\n", dropped);
+    return;
+  }
+  const double ce = r->obj;
+  if (obj_out) *obj_out = ce;
+  obj += ce;
+  obj_progress += ce;
+  correct += r->correct;
+  correct_progress += r->correct;
+  sequences_progress += q.S;
+  sequences += q.S;
+  frames_progress += q.rows;   // num_frames = net_out.NumRows(): padded rows count (:102, :148-149)
+  frames += q.rows;
+  if (sequences_progress > report_step) {   // :153-167, the reference's text byte for byte (no space before "Frame-level")
+    std::ostringstream os;
+    os << "After " << sequences << " sequences (" << frames / (100.0 * 3600) << "Hr): "
+       << "CE-Obj = " << obj_progress / sequences_progress
+       << "Frame-level CE-Obj = " << obj_progress / frames_progress
+       << "   FrameAcc = " << 100.0 * (double(correct_progress) / frames_progress) << "%"
+       << " obj_progress_=  " << obj_progress
+       << " sequences_progress_=  " << sequences_progress
+       << " frames_progress_=  " << frames_progress;
+    progress.push_back(os.str());
+    sequences_progress = 0;
+    frames_progress = 0;
+    obj_progress = 0.0;
+    correct_progress = 0;
+  }
+}
+
+void CeLoss::flush() {
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  for (unsigned k = 0; k < 2; ++k) fold(pend[(pend_idx + k) & 1], nullptr);   // oldest first
+}
+
+void CeLoss::eval_parallel(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld, const int* targets,
+                           float* diff, int ldd, double* obj_host) {
+  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
+  EESEN_REQUIRE(K > 0, EESEN_ERR_INVALID, "no classes");
+  EESEN_REQUIRE(ld >= K && ldd >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  const int T = rows / S;
+  for (int s = 0; s < S; ++s)
+    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
+  // ce-loss.cc:106-113 checks every row's id (an id of a padded row is 0 there); only the valid rows' ids are read here, and a
+  // negative one -- an out-of-bounds write in the reference -- is refused as well
+  for (int t = 0; t < T; ++t)
+    for (int s = 0; s < S; ++s) {
+      if (t >= frame_num_utt[s]) continue;
+      const int id = targets[(size_t)t * S + s];
+      if (id < 0 || id >= K)
+        throw Error(EESEN_ERR_INVALID, "Class id out of network output dimension. Net outputs: " + std::to_string(K) +
+                                           ", class ID : " + std::to_string(id));
+    }
+  EESEN_HIP_CHECK(hipSetDevice(device));
+
+  // lens + targets: one stream-ordered upload through a pinned slot (the slot written here was last read two calls ago)
+  const size_t n = (size_t)S + rows;
+  const int nb = ce_eval_blocks(rows);
+  if (tg.cap < n || part.cap < (size_t)nb || res.cap < 1) EESEN_HIP_CHECK(hipStreamSynchronize(st));  // reallocation frees what queued kernels may read
+  tg.reserve(n);
+  part.reserve(nb);
+  res.reserve(1);
+  Ctc::Pin& sp = stage[stage_idx++ & 1];
+  int* pinned = static_cast<int*>(Ctc::pin_reserve(sp, n * sizeof(int)));
+  std::copy(frame_num_utt, frame_num_utt + S, pinned);
+  std::copy(targets, targets + rows, pinned + S);
+  EESEN_HIP_CHECK(hipMemcpyAsync(tg.p, pinned, n * sizeof(int), hipMemcpyHostToDevice, st));
+  EESEN_HIP_CHECK(hipEventRecord(sp.ev, st));
+  sp.busy = true;
+
+  const bool acc = timer.enabled();
+  int sp0 = -1;
+  if (acc) sp0 = timer.begin(st, 0); else EESEN_HIP_CHECK(hipEventRecord(ev[0], st));
+  ce_eval(st, net_out, ld, rows, K, S, tg.p, tg.p + S, diff, ldd, part.p, res.p);
+  if (acc) timer.end(st, sp0); else EESEN_HIP_CHECK(hipEventRecord(ev[1], st));
+
+  // the sums (and the guard word's value when they were computed) back through a pinned slot
+  Pending& q = pend[pend_idx++ & 1];
+  fold(q, nullptr);
+  CeSums* r = static_cast<CeSums*>(Ctc::pin_reserve(q.pin, sizeof(CeSums) + sizeof(unsigned)));
+  EESEN_HIP_CHECK(hipMemcpyAsync(r, res.p, sizeof(CeSums), hipMemcpyDeviceToHost, st));
+  *reinterpret_cast<unsigned*>(r + 1) = 0;
+  if (guard) EESEN_HIP_CHECK(hipMemcpyAsync(r + 1, guard, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  EESEN_HIP_CHECK(hipEventRecord(q.pin.ev, st));
+  q.pin.busy = true; q.S = S; q.rows = rows; q.active = true;
+  if (obj_host) {
+    fold(pend[pend_idx & 1], nullptr);   // the older one first: totals accumulate in call order
+    fold(q, obj_host);
+  }
+}
+
+// CE::Report (ce-loss.cc:171-175) with one deliberate change: the reference divides two int32 (correct_ / frames_), so it only
+// ever prints 0 or 100 (or divides by zero); this is the true ratio in the same shape.
+std::string CeLoss::report() {
+  flush();
+  std::ostringstream oss;
+  oss << "\nFRAME_ACCURACY >> " << 100.0 * (double(correct) / double(frames)) << "% <<";
+  return oss.str();
+}
+
+void CeLoss::phase_times(float* out1) {
+  if (timer.enabled()) { timer.collect(out1, 1); return; }   // sums since the last read
+  EESEN_HIP_CHECK(hipEventSynchronize(ev[1]));
+  float ms = 0.f;
+  EESEN_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+  out1[0] = ms * 1e-3f;
+}
+
+}  // namespace eesen

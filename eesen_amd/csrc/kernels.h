@@ -219,6 +219,18 @@ void log_sub_prior(hipStream_t st, float* m, int ld, int rows, int K, bool apply
 // ids[r] = argmax_k m[r][k], first maximum wins (CuMatrixBase::FindRowMaxId, cuda-matrix.cc:1038-1095)
 void row_argmax(hipStream_t st, const float* m, int ld, int rows, int K, int* ids);
 
+// ---------------------------------------------------------------------------------------- ce.hip
+// CE::EvalParallel (ce-loss.cc:94-169) in one pass over the softmax outputs y [rows x K] (row t*S + s valid iff t < lens[s]):
+// diff = (y - onehot(tgt)) * mask (padded rows 0), and into *out the sums over valid rows of -log y[tgt] and of
+// [argmax(y) == tgt] (row_argmax's tie rule), reduced in a fixed order through `part` (ce_eval_blocks(rows) entries).
+struct CeSums {
+  double obj;
+  long long correct;
+};
+int ce_eval_blocks(int rows);
+void ce_eval(hipStream_t st, const float* y, int ld, int rows, int K, int S, const int* lens, const int* tgt, float* diff,
+             int ldd, CeSums* part, CeSums* out);
+
 // ---------------------------------------------------------------------------------------- optim.hip
 // corr = mmt*corr + fresh; clip to +-max_grad when max_grad > 0; param -= lr_coef*corr
 // skip (may be null): device word; when non-zero at execution time the update is a no-op (see optim.hip)

@@ -188,6 +188,11 @@ Net::~Net() {
     c->guard = nullptr;
     c->guard_net = nullptr;
   }
+  for (CeLoss* c : ce_guards) {
+    (void)hipStreamSynchronize(c->st);
+    c->guard = nullptr;
+    c->guard_net = nullptr;
+  }
   if (trace.p) {  // EESEN_TRACE=1: timeline of workgroup 0 of the last persistent launches (shader-clock ticks)
     std::vector<unsigned long long> h(1280);
     if (hipMemcpy(h.data(), trace.p, h.size() * 8, hipMemcpyDeviceToHost) == hipSuccess)

@@ -197,6 +197,7 @@ struct Net {
   void fail_step_buckets() noexcept;          // Backpropagate threw with peers waiting: complete the step's collective sequence (comm.cpp)
   void flush_deferred_buckets();
   std::vector<struct Ctc*> guards;   // the Ctc objects guarding on this Net's error word (eesen_ctc_set_guard): unhooked in ~Net
+  std::vector<struct CeLoss*> ce_guards;   // the same for the CE objects (eesen_ce_set_guard)
   bool grads_sanitized = false;   // this step's gradients went through an all-reduce that zeroed them on a raised error word: update() must apply
   bool live_valid = false;        // the liveness word behind the gradient buffer was written for THIS step (backpropagate / backpropagate_zero)
   std::vector<int> bucket_log;                // layer order of the last Backpropagate's buckets (tests)
@@ -266,7 +267,7 @@ struct Ctc {
   long dropped = 0;
   std::string seq_out;         // --sequence-out-file of the trainer (ctc-loss.cc:247-250,282-291): decoded sequences are appended here
   unsigned ppzx_idx = 0, perr_idx = 0;
-  void* pin_reserve(Pin& pin, size_t bytes);  // waits for the slot's last use, grows it, returns the host pointer
+  static void* pin_reserve(Pin& pin, size_t bytes);  // waits for the slot's last use, grows it, returns the host pointer
   void flush_pzx(PendingPzx& q);
   void flush_err(PendingErr& q, int* num_err, int* num_ref);
   void flush();                // fold every deferred result into the statistics (blocks until they have arrived)
@@ -279,6 +280,39 @@ struct Ctc {
                        const int* label_ids, const int* label_off, int* num_err, int* num_ref);
   void get_alpha_beta(float* alpha_host, float* beta_host, int* Lprime);
   void phase_times(float* out3);
+};
+
+// eesen::CE (src/net/ce-loss.h:32-77): frame-level cross-entropy (ce_host.cpp, ce.hip).  As with the Ctc nothing in a training
+// step stalls the host: targets travel through two alternating pinned slots, and each call's sums come back through a pinned
+// slot that is folded into the running totals -- in call order -- when the next-but-one call needs the slot or the totals are read.
+struct CeLoss {
+  int device = 0;
+  hipStream_t st = nullptr;
+  DevBuf<int> tg;              // lens[S] then targets[rows] of the current call
+  DevBuf<CeSums> part, res;    // workgroup partials, the call's sums
+  Ctc::Pin stage[2];
+  unsigned stage_idx = 0;
+  struct Pending { Ctc::Pin pin; int S = 0; long rows = 0; bool active = false; } pend[2];
+  unsigned pend_idx = 0;
+  // running totals and the *_progress_ counters of ce-loss.cc:144-167 (the reference's are int32; these are wide)
+  double obj = 0, obj_progress = 0;
+  long correct = 0, frames = 0, sequences = 0, correct_progress = 0, frames_progress = 0, sequences_progress = 0;
+  int report_step = 100;       // the trainer's default (train-ce-parallel.cc:52); the reference's CE leaves it uninitialised
+  std::vector<std::string> progress;   // progress lines not yet handed out (eesen_ce_progress), oldest first
+  const unsigned* guard = nullptr;     // eesen_ce_set_guard: as Ctc::guard
+  struct Net* guard_net = nullptr;
+  long dropped = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  PhaseTimer timer;
+
+  CeLoss(int device, void* stream);
+  ~CeLoss();
+  void fold(Pending& q, double* obj_out);
+  void flush();                // fold every pending call into the totals (blocks until their sums have arrived)
+  void eval_parallel(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld, const int* targets,
+                     float* diff, int ldd, double* obj_host);
+  std::string report();
+  void phase_times(float* out1);
 };
 
 }  // namespace eesen

@@ -41,6 +41,7 @@ extern "C" {
 
 typedef struct eesen_net eesen_net_t; /* replaces eesen::Net, src/net/net.h:37-175           */
 typedef struct eesen_ctc eesen_ctc_t; /* replaces eesen::Ctc, src/net/ctc-loss.h:31-90       */
+typedef struct eesen_ce eesen_ce_t;   /* replaces eesen::CE, src/net/ce-loss.h:32-77          */
 
 /* ---- library / device ------------------------------------------------------------------------ */
 const char* eesen_last_error(void);
@@ -313,6 +314,40 @@ int eesen_ctc_get_alpha_beta(eesen_ctc_t* ctc, float* alpha_host, float* beta_ho
  * multi-step region needs no host synchronisation per step (0 = back to last-call timing). */
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode);
 int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3);
+
+/* ---- CE (src/net/ce-loss.h:32-77): frame-level cross-entropy ----------------------------------- */
+int eesen_ce_create(int device, void* stream, eesen_ce_t** out);
+int eesen_ce_destroy(eesen_ce_t* ce);
+/* CE::EvalParallel (src/net/ce-loss.cc:94-169) in ONE pass over the posteriors.  net_out_dev: [T*S x K] softmax outputs
+ * (device, row t*S + s, leading dimension ld), frame_num_utt: host int[S]; row t*S + s is valid iff t < frame_num_utt[s] (the
+ * trainer's frame_mask_host, train-ce-parallel.cc:176-184).  targets_host: int[rows], one class id per row; only the valid
+ * rows' ids are read, and each must lie in [0, K) (EESEN_ERR_INVALID with the reference's message otherwise).  Writes diff_dev
+ * [T*S x K] (device, diff_ld) = (y - onehot(target)) on valid rows and 0 on padded rows: d(CE)/d(logits), which the Net's
+ * <Softmax> passes through unchanged.  Accumulates, in call order: obj += sum over valid rows of -ln y[target], correct +=
+ * valid rows whose first argmax is the target, frames += rows (PADDED rows, as the reference counts), sequences += S, and the
+ * progressive report of ce-loss.cc:153-167 (eesen_ce_progress).  obj_host (may be NULL: then nothing waits for the device and
+ * the sums join the totals when they have arrived): this call's objective.  Statistics are reduced in a fixed order: the same
+ * inputs give the same bits on every run.  CE::Eval (:30-92) is this call with S = 1 and frame_num_utt[0] = rows. */
+int eesen_ce_eval_parallel(eesen_ce_t* ce, const int* frame_num_utt, int S, const float* net_out_dev, int rows, int K, int ld,
+                           const int* targets_host, float* diff_dev, int diff_ld, double* obj_host);
+/* CE::SetReportStep (ce-loss.h:47): a progress line is produced when the sequences since the last one EXCEED the step (100 until set) */
+int eesen_ce_set_report_step(eesen_ce_t* ce, int report_step);
+/* Running totals: obj (sum of -ln y[target]), correct frames, frames (padded rows), sequences.  Waits for pending calls. */
+int eesen_ce_stats(eesen_ce_t* ce, double* obj, long* correct, long* frames, long* sequences);
+/* CE::Report (ce-loss.cc:171-175): "\nFRAME_ACCURACY >> x% <<" with the TRUE ratio correct / frames (the reference divides two
+ * int32 and prints 0 or 100).  NUL-terminated into buf[cap]; EESEN_ERR_INVALID when it does not fit. */
+int eesen_ce_report(eesen_ce_t* ce, char* buf, int cap);
+/* The progress lines of ce-loss.cc:153-167 (the reference's KALDI_LOG text, byte for byte), one per call, oldest first; "" when
+ * none is ready.  A line is ready once the sums of the call that produced it have arrived: wait != 0 waits for every pending
+ * call first, wait == 0 never blocks (a line then appears up to two calls late, with the same text). */
+int eesen_ce_progress(eesen_ce_t* ce, int wait, char* buf, int cap);
+/* As eesen_ctc_set_guard: a minibatch computed while the Net's recurrence error word was set is dropped from every total
+ * (eesen_ce_dropped counts them) and its obj_host reads NaN.  net == NULL removes the guard. */
+int eesen_ce_set_guard(eesen_ce_t* ce, eesen_net_t* net);
+int eesen_ce_dropped(eesen_ce_t* ce, long* minibatches);
+/* seconds of the last eval's device work (the fused pass + its fixed-order reduction); mode 2 sums all calls since the last read */
+int eesen_ce_set_profiling(eesen_ce_t* ce, int mode);
+int eesen_ce_get_phase_times(eesen_ce_t* ce, float* out1);
 
 /* ---- dropout variants of BiLstm(Parallel) (src/net/bilstm-parallel-layer.h:46-94,209-377,604-879) ------
  * Options travel in the model file (nine tokens, src/net/bilstm-layer.h:331-373) and through set/get_layer_dropout, in token

@@ -1,4 +1,4 @@
-/* eesen_hip_net.h -- the C++ seam: eesen::Net / eesen::Ctc / eesen::CuMatrix over the C-ABI of eesen_hip.h.
+/* eesen_hip_net.h -- the C++ seam: eesen::Net / eesen::Ctc / eesen::CE / eesen::CuMatrix over the C-ABI of eesen_hip.h.
  *
  * With this header (and the four one-line forwarding headers of include/eesen_seam/, which shadow net/net.h,
  * net/ctc-loss.h, net/communicator.h and gpucompute/cuda-device.h on the include path) the reference's OWN trainer,
@@ -26,6 +26,7 @@
 
 #include "base/kaldi-common.h"     /* the reference's: int32, BaseFloat, KALDI_LOG / KALDI_ERR */
 #include "cpucompute/matrix.h"     /* the reference's host Matrix<BaseFloat> */
+#include "cpucompute/vector.h"     /* the reference's host Vector<BaseFloat> (CE's frame mask) */
 #include "net/train-opts.h"        /* the reference's NetTrainOptions (src/net/train-opts.h:29-62) */
 #include "util/kaldi-io.h"
 
@@ -288,6 +289,70 @@ class Ctc {
   std::vector<int> ids_, off_;
   std::string seq_out_;
   bool guarded_ = false;
+};
+
+/* eesen::CE (src/net/ce-loss.h:32-77): frame-level cross-entropy, one fused pass on the device (eesen_ce_eval_parallel) fed by
+ * int32 targets instead of the reference's dense one-hot matrix.  Nothing here waits for the device: the progress lines of
+ * ce-loss.cc:153-167 are printed (KALDI_LOG, the reference's text) as soon as the sums of the call that produced them have arrived. */
+class CE {
+ public:
+  CE() : h_(NULL), guarded_(false) { HipCheck(eesen_ce_create(HipDevice(), NULL, &h_)); }
+  ~CE() { if (h_) eesen_ce_destroy(h_); }
+  /* ce-loss.cc:30-92: one sequence, every row valid */
+  void Eval(const CuMatrixBase<BaseFloat>& net_out, const std::vector<int32>& target, CuMatrix<BaseFloat>* diff) {
+    lens_.assign(1, net_out.NumRows());
+    Run(net_out, target, diff, 1);
+  }
+  /* ce-loss.cc:94-169.  The library takes sequence lengths (row t*S + s valid iff t < len[s]); the seam has the trainer's 0/1
+   * frame_mask_host (train-ce-parallel.cc:143-151), which is converted: len[s] = the valid rows of column s, and a mask that is
+   * not of that shape -- a 1 after a 0 within a sequence -- is refused (KALDI_ERR semantics). */
+  void EvalParallel(const CuMatrixBase<BaseFloat>& net_out, const std::vector<int32>& target, CuMatrix<BaseFloat>* diff,
+                    const VectorBase<BaseFloat>& frame_mask_host, int sequence_number_in_batch) {
+    const int S = sequence_number_in_batch, rows = net_out.NumRows();
+    if (S <= 0 || rows % S != 0 || frame_mask_host.Dim() != rows)
+      throw std::runtime_error("eesen_hip: CE::EvalParallel: the frame mask must have one entry per row of S interleaved sequences");
+    lens_.assign(S, 0);
+    for (int s = 0; s < S; ++s) {
+      int t = 0;
+      while (t < rows / S && frame_mask_host(t * S + s) == 1.0) ++t;
+      lens_[s] = t;
+      for (; t < rows / S; ++t)
+        if (frame_mask_host(t * S + s) != 0.0)
+          throw std::runtime_error("eesen_hip: CE::EvalParallel: the frame mask of a sequence must be 1 on its first frames and 0 after them");
+    }
+    Run(net_out, target, diff, S);
+  }
+  void SetReportStep(int32 report_step) { HipCheck(eesen_ce_set_report_step(h_, report_step)); }   /* ce-loss.h:47 */
+  /* ce-loss.cc:171-175, with the true ratio correct / frames (the reference's int32 division prints 0 or 100) */
+  std::string Report() {
+    Progress(1);
+    char buf[256];
+    HipCheck(eesen_ce_report(h_, buf, (int)sizeof(buf)));
+    return buf;
+  }
+
+ private:
+  CE(const CE&);
+  CE& operator=(const CE&);
+  void Run(const CuMatrixBase<BaseFloat>& net_out, const std::vector<int32>& target, CuMatrix<BaseFloat>* diff, int S) {
+    if ((int)target.size() != net_out.NumRows()) throw std::runtime_error("eesen_hip: CE: one target per row of the network output");
+    if (!guarded_ && LastNet()) { HipCheck(eesen_ce_set_guard(h_, LastNet())); guarded_ = true; }  /* a timed-out forward pass never reaches the statistics */
+    diff->Resize(net_out.NumRows(), net_out.NumCols());
+    HipCheck(eesen_ce_eval_parallel(h_, lens_.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                    target.data(), diff->Data(), diff->Stride(), NULL));
+    Progress(0);
+  }
+  void Progress(int wait) {
+    char buf[4096];
+    for (;;) {
+      HipCheck(eesen_ce_progress(h_, wait, buf, (int)sizeof(buf)));
+      if (!buf[0]) break;
+      KALDI_LOG << buf;
+    }
+  }
+  eesen_ce_t* h_;
+  bool guarded_;
+  std::vector<int> lens_;
 };
 
 /* src/net/communicator.h: the multi-job mode of the reference trainer (--num-jobs / --job-id / --utts-per-avg) averages MODELS
