@@ -1526,16 +1526,19 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_persistent_ksplit_kernel(Lst
 // the fp32 rows' registers (128 per lane) and three v_mfma_f32_16x16x32_f16 products per 32-wide k block replace 8 x 1 fp32 ones:
 // 48 MFMAs of 16 cycles per wave and step.  What stood in the way: the A operand is the gate
 // gradient this very kernel produces step by step -- no bound is known before the launch, and fp16 has 5 exponent bits.  So the
-// PRODUCER scales: a wave of the cell phase (four sequences x 16 cells: four DPP rows) takes the maximum of its 256 gate gradients,
-// derives the power of two that brings it into [2^14, 2^15), publishes the gradients a second time as two fp16 planes of the scaled
-// values (LstmLayerDev::DGH: where a cell's four fp32 gradients sit in DG, its 16 bytes hold [4 x hi][4 x lo]: one whole-word store per
-// lane) and the inverse power in LstmLayerDev::EX (one 16-byte word per wave of the producer = per four sequences x 64 values:
+// PRODUCER scales: a wave of the cell phase (four sequences x 16 cells: four DPP rows) takes the maximum of each sequence's 64 gate
+// gradients (one DPP row), derives the power of two that brings it into [2^14, 2^15), publishes the gradients a second time as two fp16
+// planes of the scaled values (LstmLayerDev::DGH: where a cell's four fp32 gradients sit in DG, its 16 bytes hold [4 x hi][4 x lo]: one
+// whole-word store per lane) and the four inverse powers as exponent bytes of one word in LstmLayerDev::EX (byte r: sequence 4 * wave + r
+// of the tile; one power per (producer, sequence), so a sequence 2^-24 below its neighbours keeps its low bits; the word is stored
+// four times over, one 16-byte word per wave of the producer:
 // [t][dir][16-sequence tile][producer][4] -- a 128-byte line holds two producers of ONE tile and ONE K quarter, whose consumers have
 // waited for both; a line that also held another quarter's words could be read, and cached by an XCD's L2, before those were
 // written); the fp32 gradients still go to DG for the GEMMs and the bias / peephole passes, stored LAST and left in flight by the
 // drain in front of the publish.  The CONSUMER's
-// 32-wide k block lies inside one producer's 64 values, so its three products carry ONE power per output row: they go through a
-// temporary accumulator that is folded into the running one with the row's inverse power (4 FMAs per block and 16-unit tile).
+// 32-wide k block lies inside one producer's 64 values, so its three products carry ONE power per output row (= sequence): they go
+// through a temporary accumulator that is folded into the running one with the row's own inverse power, its byte of the word (4 FMAs
+// per block and 16-unit tile).
 // Same roles, hand-offs and partial-sum exchange as lstm_bwd_persistent_ksplit_kernel.  Error per product <= 3 * 2^-22 |ab|
 // (gemm.hip, "half" mode, has the argument); padding frames publish zeros (scale 2^126: 0 stays 0).
 // Shapes: as the fp32 K-split tile with an even number of k blocks per wave (H = 512, 1024).
@@ -1548,6 +1551,7 @@ __device__ __forceinline__ float dpp_row_max16(float v) {   // maximum over the 
   v = fmaxf(v, __uint_as_float((unsigned)__builtin_amdgcn_mov_dpp((int)__float_as_uint(v), 0x140, 0xf, 0xf, true)));   // row_mirror
   return v;
 }
+__device__ __forceinline__ float ex_inv(unsigned ex4, int r) { return __uint_as_float(((ex4 >> (8 * r)) & 0xffu) << 23); }   // byte r as a power of two
 template <int CPW>
 __global__ __launch_bounds__(NW * 64) void lstm_bwd_persistent_ksplit_h_kernel(LstmLayerDev L, const float* __restrict__ dY, int lddy,
                                                                                float* __restrict__ DG, unsigned long long* __restrict__ PX, unsigned* cnt,
@@ -1659,7 +1663,7 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_persistent_ksplit_h_kernel(L
       const size_t arow = ((size_t)(tn * S - tbS + sa) * ldG + (size_t)dir * K4 + (size_t)ku * KQ) * 4;
       constexpr unsigned kOob = 0x80000000u;
       f32x4 u0[CPW], u1[CPW];   // per k block two units' words of [4 x hi][4 x lo]; regrouped into the A fragments at their use (below)
-      unsigned iv[CPW];   // the inverse powers' exponent bytes of the producer's four 4-sequence groups (this lane's accumulator registers hold group kq: C/D map row = 4 * kq + reg)
+      unsigned iv[CPW];   // the inverse powers' exponent bytes of the four sequences of group kq (this lane's accumulator registers: C/D map row = 4 * kq + reg, byte reg)
       // the inverse powers first (four bytes per lane and k block: back long before the planes; the first fold needs them)
 #pragma unroll
       for (int c = 0; c < CPW; ++c) {
@@ -1701,11 +1705,12 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_persistent_ksplit_h_kernel(L
         for (int n = 0; n < 3; ++n) tmp[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, ahc), __builtin_bit_cast(f16x8_t, bl[n][c]), tmp[n], 0, 0, 0);
 #pragma unroll
         for (int n = 0; n < 3; ++n) tmp[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, ahc), __builtin_bit_cast(f16x8_t, bh[n][c]), tmp[n], 0, 0, 0);
-        const float ivc = __uint_as_float(iv[c]);
 #pragma unroll
-        for (int n = 0; n < 3; ++n)
+        for (int r = 0; r < 4; ++r) {
+          const float ivr = ex_inv(iv[c], r);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc[n][r] = fmaf(tmp[n][r], ivc, acc[n][r]);
+          for (int n = 0; n < 3; ++n) acc[n][r] = fmaf(tmp[n][r], ivr, acc[n][r]);
+        }
       }
       // C/D map of the 16x16 MFMA: col = lane & 15 (unit), row = 4 * (lane >> 4) + reg (sequence)
 #pragma unroll
@@ -1744,9 +1749,8 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_persistent_ksplit_h_kernel(L
         for (int d = 0; d < 2; ++d) tmp[d] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, ah2[d]), __builtin_bit_cast(f16x8_t, bh[3][c + d]), tmp[d], 0, 0, 0);
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
-          const float ivc = __uint_as_float(iv[c + d]);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) acc[3][r] = fmaf(tmp[d][r], ivc, acc[3][r]);
+          for (int r = 0; r < 4; ++r) acc[3][r] = fmaf(tmp[d][r], ex_inv(iv[c + d], r), acc[3][r]);
         }
         if (c == 0) {
           __builtin_amdgcn_sched_barrier(0);
@@ -1783,18 +1787,19 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_persistent_ksplit_h_kernel(L
       float dg = (1.f - g_ * g_) * (dc * i);
       float carry = dc * f;
       if (t >= len || !e_ok) { dg = di = df = dob = 0.f; carry = 0.f; }
-      // the power of two of this wave's four sequences x 64 gate gradients (four DPP rows of 16 threads), then the planes
+      // the power of two of each of this wave's four sequences (a DPP row of 16 threads: 64 gate gradients), then the planes
       float sc, inv;
+      unsigned ex4;   // the four sequences' inverse powers as exponent bytes: byte r = DPP row r = sequence 4 * wave + r of the tile
       {
         const float rm = dpp_row_max16(fmaxf(fmaxf(fabsf(dg), fabsf(di)), fmaxf(fabsf(df), fabsf(dob))));
-        const int ri = (int)__float_as_uint(rm);
-        const float wm = fmaxf(fmaxf(__uint_as_float((unsigned)__builtin_amdgcn_readlane(ri, 0)), __uint_as_float((unsigned)__builtin_amdgcn_readlane(ri, 16))),
-                               fmaxf(__uint_as_float((unsigned)__builtin_amdgcn_readlane(ri, 32)), __uint_as_float((unsigned)__builtin_amdgcn_readlane(ri, 48))));
-        half_scale(wm, sc, inv);
+        half_scale(rm, sc, inv);
+        const int ei = (int)(__float_as_uint(inv) >> 23);
+        ex4 = (unsigned)__builtin_amdgcn_readlane(ei, 0) | ((unsigned)__builtin_amdgcn_readlane(ei, 16) << 8) |
+              ((unsigned)__builtin_amdgcn_readlane(ei, 32) << 16) | ((unsigned)__builtin_amdgcn_readlane(ei, 48) << 24);
       }
 #if !defined(EESEN_PROBE_KH) || !(EESEN_PROBE_KH & 4)
       if (lane == 0 && s0 + 4 * wave < s_end) {   // one 16-byte word per wave (a whole-word write-through store; sub-dword ones cost 900 ticks of drain): [t][dir][tile][producer][4 groups]
-        const f32x4 iv4 = {inv, inv, inv, inv};
+        const f32x4 iv4 = {__uint_as_float(ex4), __uint_as_float(ex4), __uint_as_float(ex4), __uint_as_float(ex4)};
         __builtin_amdgcn_raw_buffer_store_b128(iv4, rEX, (unsigned)((((size_t)(t * L.ndir + dir) * NZ + zt) * NP + uc0 / 16) * 64 + wave * 16), 0, kSc1);
       }
 #endif

@@ -169,3 +169,12 @@ def test_cfg5_full_length_layer_persistent_equals_per_step_kernels(gpu, monkeypa
     assert e[0] < 2e-6 and e[1] < 1e-6 and e[2] < 6e-3 and e[3] < 1e-4, e
     vm = valid_mask(batch.lens, batch.T, batch.S)
     assert np.all(np.isfinite(res["1"][3])) and np.all(res["1"][2][~vm] == 0)
+    # EESEN_FWD_SPLIT=0: the persistent forward on the fp32-input MFMA must give the per-step kernels' output and ln p bit for bit
+    monkeypatch.setenv("EESEN_PERSISTENT", "1"); monkeypatch.setenv("EESEN_FWD_SPLIT", "0")
+    net = Net.from_layers(layers); ctc = Ctc()
+    net.SetSeqLengths(batch.lens)
+    out = net.Propagate(batch.feats)
+    ctc.EvalParallel(batch.lens, out, batch.labels)
+    assert net.RecurrenceInfo()["fwd_persistent"] == 1
+    assert "_bf_" not in net.Plan()["layers"][0]["forward"]["kernel"]
+    assert np.array_equal(out.numpy(), res["0"][0]) and np.array_equal(ctc.pzx, res["0"][1])
