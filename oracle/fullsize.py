@@ -2,6 +2,8 @@
 fixture of it that travels in tests/golden/ for boxes without the reference library.  TEST INFRASTRUCTURE.
 
     python -m oracle.fullsize            # (re)generate tests/golden/full_*.npz where /root/reference exists
+    python -m oracle.fullsize --backward-leg [NAME ...]   # the reference's backward pass on the fixed top gradient `od`
+                                                          # (fixed_top_gradient) -> tests/golden/full_*_bwd*.npz
 
 The step is the one of /root/reference/src/netbin/train-ctc-parallel.cc:195-207 with lr = 1, momentum = 0,
 <MaxGrad> 0, which turns the parameter delta into the gradient.  The reference's CTC exists
@@ -183,6 +185,145 @@ def reference_floors(layers, batch, r: dict, lowmem: bool = False) -> dict:
                 grad_stats64=tensor_stats(layers, r64["grads"]))
 
 
+# ------------------------------------------------------------------------------------------ the backward-only leg (no CTC)
+# Both sides backpropagate the same FIXED top gradient `od`, regenerated bit for bit from integer hashing on every host, and the
+# fixture carries the reference's answer to it.  The reference's own `diff` (13-47 MB per case) does not travel; this does.
+# The new keys live in sidecar files beside the step's fixture, each within the 1 MiB committed-file limit, so that the arrays of
+# full_<case>.npz stay byte for byte what the reference step wrote:
+#   full_<case>_bwd.npz       od_sha256, bwd_grad_stats, bwd_grad_sample (sample_index), bwd_in_diff_seq_absmax [S]
+#   full_<case>_bwd_rows.npz  bwd_in_diff_rows [n x D] and bwd_in_diff_row_index [n] (rows t*S+s of in_diff)
+BWD_PARTS = ("_bwd", "_bwd_rows")
+BWD_ROWS = 32                # in_diff rows per sequence (valid ones; t = 0 and t = len-1 among them) ...
+BWD_ROWS_CFG3 = 16           # ... and for cfg3's 256 sequences
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x: np.ndarray) -> np.ndarray:
+    """splitmix64's output function on a uint64 array (wrapping arithmetic: exact on every host)."""
+    with np.errstate(over="ignore"):
+        z = x + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def _case_key(name: str) -> np.uint64:
+    import hashlib
+    return np.uint64(int.from_bytes(hashlib.sha256(name.encode()).digest()[:8], "little"))
+
+
+def od_exponents(S: int) -> np.ndarray:
+    """e_s = 8 ((s + s // 8) mod 4): every aligned group of four sequences holds all four powers 1, 2^-8, 2^-16, 2^-24 -- in the
+    batch, in each 32-sequence window and in each shard of cfg3's interleaved deal (rank r holds s = r mod 8)."""
+    s = np.arange(S)
+    return 8 * ((s + s // 8) % 4)
+
+
+def od_zero_sequences(S: int) -> np.ndarray:
+    """Sequences whose top gradient is exactly zero (their in_diff must be exactly zero on both sides)."""
+    return np.flatnonzero(np.arange(S) % 11 == 5)
+
+
+def fixed_top_gradient(name: str, lens, T: int, S: int, K: int) -> np.ndarray:
+    """[T*S x K] fp32, row t*S+s, shaped like a CTC gradient: every class n 2^-22 with |n| < 2^18 and one hashed class per row
+    -2^-1 on top, the row scaled by 2^-e_s (od_exponents), zero on padding rows and on od_zero_sequences.  Integer hashing
+    (splitmix64 over (case, row, class)) and power-of-two scalings only: every value is exact in fp32 and the same on every host."""
+    key = _case_key(name)
+    rows = np.arange(T * S, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        h = _splitmix64(key + rows[:, None] * np.uint64(K) + np.arange(K, dtype=np.uint64)[None, :])
+        hot = _splitmix64(_splitmix64(key ^ np.uint64(0x5851F42D4C957F2D)) + rows) % np.uint64(K)
+    n = (h >> np.uint64(46)).astype(np.int64)                      # 18 bits: 0 .. 2^18 - 1
+    n = np.where((h & np.uint64(1)) == 1, -n, n)
+    od = n.astype(np.float64) * 2.0 ** -22
+    od[np.arange(T * S), hot.astype(np.int64)] -= 0.5
+    s = np.arange(T * S) % S
+    t = np.arange(T * S) // S
+    od *= np.ldexp(1.0, -od_exponents(S))[s][:, None]
+    od[(t >= np.asarray(lens)[s]) | np.isin(s, od_zero_sequences(S))] = 0.0
+    out = od.astype(np.float32)
+    assert np.array_equal(out.astype(np.float64), od)             # exact in fp32
+    return out
+
+
+def od_sha256(od: np.ndarray) -> str:
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(od, "<f4").tobytes()).hexdigest()
+
+
+def bwd_row_index(name: str, lens, T: int, S: int) -> np.ndarray:
+    """Rows t*S+s of in_diff the fixture keeps: per sequence BWD_ROWS valid rows (BWD_ROWS_CFG3 for cfg3) -- t = 0, t = len-1 and
+    evenly spaced ones between, their phase staggered across sequences -- plus its first and last padding row, if any."""
+    n = BWD_ROWS_CFG3 if name == "full_cfg3" else BWD_ROWS
+    out = []
+    for s in range(S):
+        L = int(lens[s])
+        step = (L - 1) / n
+        phase = ((s * 0.618034) % 1.0) * step
+        ts = {0, L - 1} | {int(phase + k * step) for k in range(n)}
+        if L < T:
+            ts |= {L, T - 1}
+        out += [t * S + s for t in sorted(ts)]
+    return np.array(sorted(out), np.int64)
+
+
+def bwd_compact(name: str, layers, lens, T: int, S: int, in_diff: np.ndarray, grads: np.ndarray) -> dict:
+    """The backward leg's keys (both files) from a full in_diff [T*S x D] and gradient vector: what the fixture stores and what the
+    test forms on the HIP side."""
+    idx = bwd_row_index(name, lens, T, S)
+    vm = (np.arange(T)[:, None] < np.asarray(lens)[None, :])
+    a = np.abs(np.asarray(in_diff, np.float32)).reshape(T, S, -1).max(axis=2)
+    return dict(bwd_grad_stats=tensor_stats(layers, grads), bwd_grad_sample=np.asarray(grads, np.float32)[sample_index(layers)].copy(),
+                bwd_in_diff_seq_absmax=np.where(vm, a, 0.0).max(axis=0).astype(np.float32),
+                bwd_in_diff_rows=np.asarray(in_diff, np.float32)[idx].copy(), bwd_in_diff_row_index=idx)
+
+
+def load_fixture(name: str) -> dict:
+    """full_<case>.npz with its backward-leg sidecars (where present) merged in: {key: array}."""
+    out = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    for part in BWD_PARTS:
+        p = os.path.join(GOLDEN, name + part + ".npz")
+        if os.path.exists(p):
+            out.update(np.load(p))
+    return out
+
+
+def reference_backward(layers, batch, od, blas_threads: int = 0, lowmem: bool = False) -> dict:
+    """The reference's forward pass and then its backward pass on `od` (no CTC): in_diff and the gradient (delta, lr = 1)."""
+    from oracle import refbind
+    refbind.set_blas_threads(blas_threads if blas_threads > 0 else min(16, os.cpu_count() or 1))
+    ref = _ref_net(layers)
+    before = ref.get_params()
+    ref.set_train_options(1.0, 0.0)
+    ref.set_seq_lengths(batch.lens)
+    ref.propagate(batch.feats)
+    in_diff = ref.backpropagate(od, True, lowmem=lowmem)
+    grads = before.astype(np.float64) - ref.get_params().astype(np.float64)
+    return dict(in_diff=in_diff, grads=grads.astype(np.float32))
+
+
+def backward_leg_main(names):
+    """python -m oracle.fullsize --backward-leg [NAME ...]: the reference's answer to od, written to the sidecars."""
+    from oracle import refbind
+    assert refbind.build_if_possible(), "oracle/_ref could not be built (needs /root/reference)"
+    import time
+    for name in (names or list(CASES) + ["full_cfg3"]):
+        cfg, layers, batch = case(name)
+        od = fixed_top_gradient(name, batch.lens, batch.T, batch.S, cfg["K"])
+        t0 = time.time()
+        r = reference_backward(layers, batch, od, lowmem=name in LOWMEM)
+        sec = time.time() - t0
+        c = bwd_compact(name, layers, batch.lens, batch.T, batch.S, r["in_diff"], r["grads"])
+        zero = od_zero_sequences(batch.S)
+        assert not np.any(r["in_diff"].reshape(batch.T, batch.S, -1)[:, zero]), "zero od, nonzero in_diff"
+        rows = {k: c.pop(k) for k in ("bwd_in_diff_rows", "bwd_in_diff_row_index")}
+        np.savez_compressed(os.path.join(GOLDEN, name + "_bwd.npz"), od_sha256=np.array(od_sha256(od)), **c)
+        np.savez_compressed(os.path.join(GOLDEN, name + "_bwd_rows.npz"), **rows)
+        sizes = [os.path.getsize(os.path.join(GOLDEN, name + p + ".npz")) for p in BWD_PARTS]
+        print(f"{name}: reference forward + backward on od {sec:.1f} s, {len(rows['bwd_in_diff_row_index'])} in_diff rows, "
+              f"sidecars {sizes[0] / 1024:.0f} + {sizes[1] / 1024:.0f} KiB", flush=True)
+
+
 def cfg3_training_layers(layers):
     """The same weights with the recipes' <MaxGrad> on every trainable layer."""
     out = []
@@ -195,6 +336,8 @@ def cfg3_training_layers(layers):
 
 
 def main():
+    if "--backward-leg" in sys.argv[1:]:
+        return backward_leg_main([a for a in sys.argv[1:] if a != "--backward-leg"])
     from oracle import refbind
     assert refbind.build_if_possible(), "oracle/_ref could not be built (needs /root/reference)"
     import time

@@ -140,15 +140,23 @@ def test_cfg5_width_and_batch_against_oracle_on_the_persistent_kernels(gpu):
         assert rel_err(a, b) < 1e-4, f"layer {li} {nm}"
 
 
+# the od leg of the next test: persistent against per-step kernels, 3x the worst measured on an MI355X, rounded up to two digits
+# (in_diff per sequence 1.22e-6, gradient tensors 5.2e-7: no CTC in front of it, so no 6e-3 either)
+OD_LAYER_BAR = dict(in_diff_seq=3.7e-6, grads=1.6e-6)
+
+
 def test_cfg5_full_length_layer_persistent_equals_per_step_kernels(gpu, monkeypatch):
     """One 1024-cell BiLSTM layer at the FULL cfg5 size (S = 64, T = 3000): the gate-gradient buffer is 6.3 GB, beyond 32-bit
     buffer offsets (the backward kernel re-bases its resource per chunk of steps), and the batch takes two sequence windows.
     The persistent path must reproduce the one-launch-per-step kernels (forward bit for bit, backward to the last bits)."""
     from eesen_amd.api import Net, Ctc, CuMatrix
+    from oracle import fullsize
     cfg = synth.config("cfg5"); cfg.update(layers=1)
     layers = synth.make_model(**cfg)
     batch = synth.make_batch(**cfg)
-    res = {}
+    # the backward pass alone, on a fixed top gradient (per-sequence powers 1 .. 2^-24, some sequences zero): no CTC round-off in it
+    od = fullsize.fixed_top_gradient("cfg5_full_length_layer", batch.lens, batch.T, batch.S, cfg["K"])
+    res, res_od = {}, {}
     for mode in ("1", "0"):
         monkeypatch.setenv("EESEN_PERSISTENT", mode)
         net = Net.from_layers(layers); net.SetTrainOptions(1.0, 0.0); ctc = Ctc()
@@ -160,6 +168,8 @@ def test_cfg5_full_length_layer_persistent_equals_per_step_kernels(gpu, monkeypa
         info = net.RecurrenceInfo()
         assert info["fwd_persistent"] == info["bwd_persistent"] == (1 if mode == "1" else 0), info
         res[mode] = (out.numpy(), ctc.pzx.copy(), idf.numpy(), net.GetGrads())
+        net.BackpropagateNoUpdate(CuMatrix.from_numpy(od), idf)
+        res_od[mode] = (idf.numpy(), net.GetGrads())
         del net, ctc, out, diff, idf
     # (round 6: the wide forward tile runs on two fp16 planes per operand -- fp32-class, another summation order: 2e-6 like the narrow
     # tile's; EESEN_FWD_SPLIT=0 keeps the fp32-input kernel, which is bit-identical to the per-step one)
@@ -169,6 +179,22 @@ def test_cfg5_full_length_layer_persistent_equals_per_step_kernels(gpu, monkeypa
     assert e[0] < 2e-6 and e[1] < 1e-6 and e[2] < 6e-3 and e[3] < 1e-4, e
     vm = valid_mask(batch.lens, batch.T, batch.S)
     assert np.all(np.isfinite(res["1"][3])) and np.all(res["1"][2][~vm] == 0)
+    # the od leg: per sequence for in_diff (each over its valid rows, against its own max), per tensor for the gradients
+    T, S = batch.T, batch.S
+    vm2 = vm.reshape(T, S)
+    i1, i0 = res_od["1"][0].reshape(T, S, -1), res_od["0"][0].reshape(T, S, -1)
+    zero = fullsize.od_zero_sequences(S)
+    e_seq = {s: rel_err(i1[vm2[:, s], s], i0[vm2[:, s], s]) for s in range(S) if s not in zero}
+    e_grad = {f"L{li}.{nm}": rel_err(a, b) for (li, nm, a), (_, _, b) in zip(split_params(layers, res_od["1"][1]),
+                                                                             split_params(layers, res_od["0"][1]))}
+    print(f"od leg, persistent vs per-step: in_diff per sequence up to {max(e_seq.values()):.3g} (sequence {max(e_seq, key=e_seq.get)}), "
+          f"gradient tensors up to {max(e_grad.values()):.3g} ({max(e_grad, key=e_grad.get)})")
+    for m in ("1", "0"):
+        assert not np.any(res_od[m][0][~vm]) and not np.any(res_od[m][0].reshape(T, S, -1)[:, zero]), m
+    bad = {s: v for s, v in e_seq.items() if not v < OD_LAYER_BAR["in_diff_seq"]}
+    assert not bad, f"in_diff per sequence (od powers {fullsize.od_exponents(S)[list(bad)].tolist()}): {bad}"
+    bad = {k: v for k, v in e_grad.items() if not v < OD_LAYER_BAR["grads"]}
+    assert not bad, bad
     # EESEN_FWD_SPLIT=0: the persistent forward on the fp32-input MFMA must give the per-step kernels' output and ln p bit for bit
     monkeypatch.setenv("EESEN_PERSISTENT", "1"); monkeypatch.setenv("EESEN_FWD_SPLIT", "0")
     net = Net.from_layers(layers); ctc = Ctc()
