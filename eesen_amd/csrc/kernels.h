@@ -85,7 +85,7 @@ struct LstmLayerDev {
   // whole batch needs more workgroups than can be co-resident (S = 64 at H = 1024: BASELINE config 5) run as several
   // launches, one window each -- the sequences are independent chains.  s_count = 0 means all S.
   int s_begin = 0, s_count = 0;
-  // partial-sum exchange space of the K-split backward kernel for wide layers (lstm_bwd_ksplit_px_floats; null: not offered)
+  // partial-sum exchange space of the K-split backward kernel for wide layers (what the backward plan asks for: RecPlan::need_px)
   float* PX = nullptr;
   size_t px_floats = 0;
   // first-poll delay of the persistent kernels' hand-off waits in wall-clock ticks of 10 ns; set by the host from the measured
@@ -116,13 +116,11 @@ struct LstmLayerDev {
   const float* wm_amax = nullptr;
   // the K-split backward tile of wide layers on two fp16 planes per operand (round 6; tuning.h: EESEN_BWD_F16): DGH = the gate gradients a
   // second time, as planes with a per-(producer, sequence) power of two ([T*S x ndir*4H] words of 4 bytes: the fp32 rows' bytes), EX = the
-  // inverse powers ([T][ndir][ceil(S/16)][H/16][4 groups of 4 sequences] words of 16 bytes); both null: not offered (lstm_bwd_planes_floats)
+  // inverse powers ([T][ndir][ceil(S/16)][H/16][4 groups of 4 sequences] words of 16 bytes); handed over when the backward plan asks (RecPlan::need_dgh, need_ex)
   int bwd_f16 = 0;
   unsigned char* DGH = nullptr;
   float* EX = nullptr;
 };
-// floats of LstmLayerDev::EX this layer shape needs when its backward pass may take the fp16-plane K-split tile (0: it will not)
-size_t lstm_bwd_planes_ex_floats(const LstmLayerDev& L);
 float handoff_flight_ns();
 // The share of the device's CUs this PROCESS sizes its persistent grids against: 1/n (EESEN_GPU_SHARE, or set by a communicator
 // that found n of its ranks on this device: comm.cpp).  Process-wide.
@@ -136,38 +134,26 @@ void lstm_fwd_step(hipStream_t st, const LstmLayerDev& L, int step);
 // One step of the backward recurrence: fw direction handles t = T-1-step, bw direction t = step.
 // dY: [T*S x ndir*H] gradient w.r.t. the layer output, DG: [T*S x ndir*4H] (out), DCF: [S x ndir*H] carry.
 void lstm_bwd_step(hipStream_t st, const LstmLayerDev& L, int step, const float* dY, int lddy, float* DG, float* DCF);
-// The whole recurrence of one layer in ONE cooperative launch with W_m resident in registers (lstm_persistent.hip).
-// cnt: >= ndir * ceil(S/16) zero-initialisable counters, err: one word raised when a bounded spin gives up.
-// Return false (nothing launched) when the shape does not fit the resident-workgroup budget: use the step kernels then.
-bool lstm_fwd_persistent(hipStream_t st, const LstmLayerDev& L, unsigned* cnt, unsigned* err, int spin_limit,
-                         unsigned long long* trace = nullptr, hipEvent_t after_reset = nullptr);
-// counter geometry of the forward persistent kernel (for gated consumers): workgroups per group, sequence tiles
 // out[r][c] = (u(r,c) > p) ? 1/(1-p) : 0 with u ~ U[0,1) from a counter-based hash of (seed, element) -- the mask recipe of
 // bilstm-parallel-layer.h:54-61 (SetRandUniform / SetRandUniformCol, Add(-p), ApplyHeaviside, Scale(1/(1-p))); per_column
 // draws one value per column and repeats it down the rows (SetRandUniformCol, cpucompute/matrix.cc:952-965).
 void dropout_mask(hipStream_t st, float* out, long rows, int cols, int ld, float p, unsigned long long seed, bool per_column);
-// out[r][c] = a[r][c] * m[r][c]   (MulElements, :416 / :895)
 // <Sigmoid> / <Tanh> layers: y = f(x) (cuda-kernels.cu:687-697, 713-727) and d *= f'(y) in place (:699-709, :730-740)
 void activation_rows(hipStream_t st, bool tanh_, const float* x, int ldx, float* y, int ldy, long rows, int cols);
 void activation_diff_rows(hipStream_t st, bool tanh_, const float* y, int ldy, float* d, int ldd, long rows, int cols);
+// out[r][c] = a[r][c] * m[r][c]   (MulElements, :416 / :895)
 void mul_elements(hipStream_t st, const float* a, int lda, const float* m, int ldm, float* out, int ldo, long rows, int cols);
-void lstm_fwd_persistent_geometry(const LstmLayerDev& L, int* nblk, int* nz, int* units_per_wg = nullptr);
-// sequence windows (= cooperative launches) the persistent forward pass of this layer takes: 1 for every shape whose
-// workgroups are co-resident at once, 2+ for S = 64 at H = 1024, 0 when no persistent tile fits (per-step kernels then)
-int lstm_fwd_persistent_windows(const LstmLayerDev& L);
-// true when lstm_fwd_persistent would run this layer's recurrence on the bf16 kernel (L.fwd_bf16 set and the shape allows)
-bool lstm_fwd_persistent_is_bf16(const LstmLayerDev& L);
-// the forward tile this layer takes leaves room on a CU for a 128 x 128 GEMM workgroup (net.cpp: "the middle first")
-bool lstm_fwd_persistent_leaves_room(const LstmLayerDev& L);
-size_t lstm_bwd_ksplit_px_floats(const LstmLayerDev& L);
-// What runs a layer's time recurrence.  ONE selection function per pass (lstm_fwd_plan / lstm_bwd_plan, lstm_persistent.hip) decides
-// the instantiation; the launchers execute the plan, and everything else that has to know -- the per-minibatch side-stream rule of
-// Net::backpropagate, the exchange-schedule rule of the data-parallel path (comm.cpp), eesen_net_plan_string, the tests -- reads the
-// SAME plan, so a rule can no longer drift away from what the launcher picks.
+// What runs a layer's time recurrence: the whole recurrence in ONE launch per sequence window, with W_m resident in registers
+// (lstm_persistent.hip).  ONE selection function per pass (lstm_fwd_plan / lstm_bwd_plan, rec_plan.cpp) decides the instantiation and
+// answers every question about it; the launchers execute the plan they are given, and everything else that has to know -- the gating
+// and early-middle rules of Net::forward_pass, the buffers and the per-minibatch side-stream rule of Net::backpropagate, the
+// exchange-schedule rule of the data-parallel path (comm.cpp), eesen_net_plan_string, the tests -- reads the SAME plan, computed once
+// per layer and pass, so a rule cannot drift away from what the launcher runs.  Plans are not kept across minibatches:
+// they depend on the minibatch shape, the layer's dropout mode and the buffers reserved so far.
 enum { kRecNone = 0, kRecFwdBf = 1, kRecFwdMux = 2, kRecFwdF32 = 3, kRecBwdQ4 = 4, kRecBwdKsplit = 5, kRecBwdKsplitMux = 6, kRecBwdGeneric = 7 };
 struct RecPlan {
   int kind = kRecNone;        // kRecNone: no persistent tile fits this shape -- the one-launch-per-step kernels of lstm.hip
-  char kernel[80] = "";       // the instantiation, e.g. "lstm_bwd_persistent_q4_kernel<8,4>"
+  const char* kernel = "";    // the instantiation, e.g. "lstm_bwd_persistent_q4_kernel<8,4>"
   int seq_tile = 0;           // sequences per workgroup
   int units = 0;              // hidden units per workgroup
   int windows = 0;            // launches per layer pass (sequence windows, one after the other)
@@ -177,17 +163,31 @@ struct RecPlan {
   int vgprs = 0, lds = 0;     // registers per lane / static LDS bytes of the instantiation (hipFuncGetAttributes = the code object's
                               // .vgpr_count / .group_segment_fixed_size: pinned by tests/test_kernel_resources.py); 0: not known
   int free_vgprs = -1;        // registers per SIMD lane this grid leaves on a CU it occupies: 512 - waves per SIMD x allocated (-1: not known)
-  bool light = false;         // backward: the 4- / 8-sequence tiles, beside which a side-stream GEMM workgroup keeps a third of its rate
+  // forward, for consumers of the pass's rows while it runs (net.cpp).  The arrival counters of a gated consumer: grid[0] workgroups
+  // per (direction, sequence tile) group of `units` cells each, `seq_tiles` sequence tiles over the whole batch
+  int seq_tiles = 1;
+  bool one_window = false;    // the whole batch steps together in one launch (not so: sequence windows; the time-multiplexed kernel, whose
+                              // one launch steps two sequence tiles in turn; no persistent tile)
+  bool leaves_room = false;   // the grid leaves register and LDS room for a 128 x 128 GEMM workgroup on the same CU ("the middle first")
+  bool bf16 = false;          // the recurrent product on bf16 operands (eesen_net_set_forward_precision(1) and the shape allows)
+  // backward
+  bool light = false;         // the 4- / 8-sequence tiles, beside which a side-stream GEMM workgroup keeps a third of its rate
+  size_t need_px = 0, need_ex = 0;   // floats of LstmLayerDev::PX (px_floats) and EX the launch must be handed (0: none)
+  bool need_dgh = false;             // ... and LstmLayerDev::DGH, [T*S x ndir*4H] words
   // for the launcher
-  int cpw = 0, stq = 0, chunk = 0, xchg = 0;
+  size_t ctl_words = 0;       // arrival-counter words one launch clears (at most kCtlHalf)
+  int chunk = 0;
   const void* fn = nullptr;
 };
 RecPlan lstm_fwd_plan(const LstmLayerDev& L);
-// assume_px: plan as if the caller will hand over the K-split kernels' exchange buffer (LstmLayerDev::PX) -- Net::backpropagate does
-// whenever lstm_bwd_ksplit_px_floats asks for one; the launcher itself plans with the buffer it was really given
-RecPlan lstm_bwd_plan(const LstmLayerDev& L, bool assume_px);
-bool lstm_bwd_persistent(hipStream_t st, const LstmLayerDev& L, const float* dY, int lddy, float* DG, unsigned* cnt,
-                         unsigned* err, int spin_limit, unsigned long long* trace = nullptr);
+RecPlan lstm_bwd_plan(const LstmLayerDev& L);
+// Execute a plan whose kind is not kRecNone (those shapes take the step kernels above).  cnt: kCtlHalf zero-initialisable counter
+// words, err: one word raised when a bounded spin gives up.  after_reset: recorded once the counters are cleared, where the plan is
+// one_window (a gated consumer may poll from there on).
+void lstm_fwd_launch(hipStream_t st, const RecPlan& plan, const LstmLayerDev& L, unsigned* cnt, unsigned* err, int spin_limit,
+                     unsigned long long* trace = nullptr, hipEvent_t after_reset = nullptr);
+void lstm_bwd_launch(hipStream_t st, const RecPlan& plan, const LstmLayerDev& L, const float* dY, int lddy, float* DG, unsigned* cnt,
+                     unsigned* err, int spin_limit, unsigned long long* trace = nullptr);
 // bias_grad[ndir*4H] = column sums of DG; peep_grad[ndir][3][H] = the diag(D^T C) products of
 // bilstm-parallel-layer.h:507-510 / :598-601.  ws: >= red_rows_ws(...) floats.
 void lstm_bias_peep_grads(hipStream_t st, const LstmLayerDev& L, const float* DG, float* bias_grad, float* peep_grad,

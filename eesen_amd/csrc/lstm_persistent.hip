@@ -22,7 +22,7 @@
 // shares its first line with the previous block, which caches it one step early.
 // A workgroup can run at most one step ahead of the slowest one of its (direction, sequence-tile) group, and step t
 // writes row block t while laggards still read row block t-1, so there is no write-after-read hazard.
-// All workgroups must be co-resident: the host launches only after an occupancy check with margin (see coop_launch for why the
+// All workgroups must be co-resident: the host launches only after an occupancy check with margin (see plan_launch, rec_plan.cpp, for why the
 // launch itself is an ordinary one) and otherwise falls back to the per-step kernels; a spin that exceeds its bound raises an
 // error word instead of hanging.
 //
@@ -31,11 +31,7 @@
 // lstm_fwd_persistent_bf_kernel<.,2,3,3> (the exact 3-way bf16 split, EESEN_FWD_SPLIT=1), is fp32-class but not bit-identical; the
 // backward pass differs in the last bits (FMA contraction, and the full-line operand fetch consumes each 32-float chunk as two
 // 16-float halves); tests assert exactly that.
-#include "kernels.h"
-
-#include <atomic>
-#include <map>
-#include <mutex>
+#include "rec_kernels.h"
 
 namespace eesen {
 namespace {
@@ -2033,608 +2029,61 @@ __global__ __launch_bounds__(NW * 64) void lstm_bwd_persistent_ksplit_mux_kernel
   }
 }
 
-// EESEN_GPU_SHARE=n (tuning.h): this process may count on 1/n of the device's CUs -- n trainer processes on one GPU (the reference's
-// own two-jobs-one-GPU test mode; tests/test_gpu_multirank.py) each size their persistent grids against their share, so that all
-// of them are co-resident TOGETHER instead of relying on the spin time-outs to find out that they are not.
-// (round 6: a communicator that finds several of its ranks on ONE device sets the share itself -- set_gpu_share, comm.cpp -- so that
-// co-located trainer jobs need no environment variable; an explicit EESEN_GPU_SHARE wins)
-static std::atomic<int> g_share_override{0};
-static int gpu_share() {
-  static const int env = [] { const char* e = getenv("EESEN_GPU_SHARE"); const int v = e && *e ? atoi(e) : 0; return v < 1 ? 0 : v; }();
-  if (env) return env;
-  const int o = g_share_override.load(std::memory_order_relaxed);
-  return o > 0 ? o : 1;
-}
-// the CUs this process sizes its tiles and grids against: the device's, divided by EESEN_GPU_SHARE
-static int share_of_cus() {
-  int ncu = 256, dev = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  return std::max(1, ncu / gpu_share());
-}
-// census: optional -- `bool(int wgs)`: have `wgs` workgroups of this very kernel been SEEN co-resident on this device (run once, cached)?
-template <class K, class C = bool (*)(int)>
-bool fits(K kernel, dim3 grid, int threads, C census = nullptr) {  // grid: the workgroups of ONE launch (one sequence window)
-  int dev = 0, ncu = 0, nb = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-  {  // the occupancy of an instantiation does not change: asked once per (device, kernel) -- this runs several times per layer pass
-    static std::mutex mu;
-    static std::map<std::pair<int, const void*>, int> cache;   // (instantiations of one template share a function TYPE: keyed by address)
-    std::lock_guard<std::mutex> lock(mu);
-    const auto key = std::make_pair(dev, reinterpret_cast<const void*>(kernel));
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, 0) != hipSuccess) return false;
-      it = cache.emplace(key, nb).first;
-    }
-    nb = it->second;
-  }
-  // the occupancy query can over-report by one workgroup per CU (MI355X guide: SGPR-heavy kernels): keep a margin of one -- unless the
-  // caller has a residency CENSUS for this instantiation (below), which settles whether the query's own number is real
-  const long wgs = (long)grid.x * grid.y * grid.z;
-  if (wgs <= (long)ncu * std::max(1, nb - 1) / gpu_share()) return true;
-  return census && wgs <= (long)ncu * nb / gpu_share() && census((int)wgs);
-}
+static_assert(NW == kRecWaves && sizeof(Role) == sizeof(RecRole), "rec_kernels.h states the workgroup size and the role argument");
 
-// The persistent grids are launched as ORDINARY kernels: hipLaunchCooperativeKernel costs ~40 us more per launch (its dedicated
-// queue; 0.3 ms per cfg2 step over eight launches, measured) and guarantees nothing that fits() has not checked already -- the
-// runtime does not gang-schedule a cooperative grid either (the side-stream GEMMs co-run with it), it only refuses grids above the
-// occupancy limit, which is the check fits() makes with a workgroup per CU of margin.  Workgroups that are not resident at once
-// are waited for by the others' bounded spins, and a spin that gives up is recovered from (net.cpp).  (plan_launch below.)
+// ---- the instantiations (rec_kernels.h): every one this file compiles, a row each; the planner (rec_plan.cpp) looks them up here
+#define EESEN_ROW(family, kind, kernel, ...) {family, kind, {__VA_ARGS__}, reinterpret_cast<const void*>(&kernel<__VA_ARGS__>), #kernel "<" #__VA_ARGS__ ">"}
+#define EESEN_FWD_F32(...) EESEN_ROW(kFwdF32, kRecFwdF32, lstm_fwd_persistent_kernel, __VA_ARGS__)
+#define EESEN_FWD_BF(...) EESEN_ROW(kFwdBf, kRecFwdBf, lstm_fwd_persistent_bf_kernel, __VA_ARGS__)
+#define EESEN_BWD_GEN(...) EESEN_ROW(kBwdGeneric, kRecBwdGeneric, lstm_bwd_persistent_kernel, __VA_ARGS__)
+#define EESEN_BWD_Q4(...) EESEN_ROW(kBwdQ4, kRecBwdQ4, lstm_bwd_persistent_q4_kernel, __VA_ARGS__)
+const RecKernel kRecKernels[] = {
+    // <CPW, MT, NT, DROP, XCHG>: 16 x 16, 16 x 8 and 32 x 4 tiles; the exchange-layout fetch exists on the 16-sequence tiles, without dropout
+    EESEN_FWD_F32(1,1,4,true,false), EESEN_FWD_F32(1,1,4,false,false), EESEN_FWD_F32(1,1,4,false,true),
+    EESEN_FWD_F32(2,1,4,true,false), EESEN_FWD_F32(2,1,4,false,false), EESEN_FWD_F32(2,1,4,false,true),
+    EESEN_FWD_F32(4,1,4,true,false), EESEN_FWD_F32(4,1,4,false,false), EESEN_FWD_F32(4,1,4,false,true),
+    EESEN_FWD_F32(1,1,2,true,false), EESEN_FWD_F32(1,1,2,false,false), EESEN_FWD_F32(1,1,2,false,true),
+    EESEN_FWD_F32(2,1,2,true,false), EESEN_FWD_F32(2,1,2,false,false), EESEN_FWD_F32(2,1,2,false,true),
+    EESEN_FWD_F32(1,2,1,true,false), EESEN_FWD_F32(1,2,1,false,false),
+    EESEN_FWD_F32(2,2,1,true,false), EESEN_FWD_F32(2,2,1,false,false),
+    EESEN_FWD_F32(4,2,1,true,false), EESEN_FWD_F32(4,2,1,false,false),
+    // <CPW, NT, AP, WP, F16>: two fp16 planes (narrow, wide), the 3-way bf16 split (narrow), config 4's bf16 forward (wide)
+    EESEN_FWD_BF(1,2,2,2,true), EESEN_FWD_BF(2,2,2,2,true),
+    EESEN_FWD_BF(1,4,2,2,true), EESEN_FWD_BF(2,4,2,2,true), EESEN_FWD_BF(3,4,2,2,true), EESEN_FWD_BF(4,4,2,2,true),
+    EESEN_FWD_BF(1,2,3,3,false), EESEN_FWD_BF(2,2,3,3,false),
+    EESEN_FWD_BF(1,4,1,2,false), EESEN_FWD_BF(2,4,1,2,false), EESEN_FWD_BF(3,4,1,2,false), EESEN_FWD_BF(4,4,1,2,false),
+    // <CPW, NT, XCHG>
+    EESEN_ROW(kFwdMux, kRecFwdMux, lstm_fwd_persistent_mux_kernel, 4,4,true), EESEN_ROW(kFwdMux, kRecFwdMux, lstm_fwd_persistent_mux_kernel, 4,4,false),
+    // <CPW, sequences per workgroup, DROP>
+    EESEN_BWD_GEN(1,8,true), EESEN_BWD_GEN(1,8,false), EESEN_BWD_GEN(1,16,true), EESEN_BWD_GEN(1,16,false),
+    EESEN_BWD_GEN(2,8,true), EESEN_BWD_GEN(2,8,false), EESEN_BWD_GEN(2,16,true), EESEN_BWD_GEN(2,16,false),
+    EESEN_BWD_GEN(4,8,true), EESEN_BWD_GEN(4,8,false), EESEN_BWD_GEN(4,16,true), EESEN_BWD_GEN(4,16,false),
+    EESEN_BWD_GEN(8,8,true), EESEN_BWD_GEN(8,8,false), EESEN_BWD_GEN(8,16,true), EESEN_BWD_GEN(8,16,false),
+    EESEN_BWD_GEN(16,8,true), EESEN_BWD_GEN(16,8,false), EESEN_BWD_GEN(16,16,true), EESEN_BWD_GEN(16,16,false),
+    // <CPW, sequences per workgroup: one or two 4-sequence tiles>
+    EESEN_BWD_Q4(2,4), EESEN_BWD_Q4(2,8), EESEN_BWD_Q4(4,4), EESEN_BWD_Q4(4,8), EESEN_BWD_Q4(6,4), EESEN_BWD_Q4(6,8), EESEN_BWD_Q4(8,4), EESEN_BWD_Q4(8,8),
+    // <CPW>
+    EESEN_ROW(kBwdKsplit, kRecBwdKsplit, lstm_bwd_persistent_ksplit_kernel, 2), EESEN_ROW(kBwdKsplit, kRecBwdKsplit, lstm_bwd_persistent_ksplit_kernel, 3),
+    EESEN_ROW(kBwdKsplit, kRecBwdKsplit, lstm_bwd_persistent_ksplit_kernel, 4),
+    EESEN_ROW(kBwdKsplitH, kRecBwdKsplit, lstm_bwd_persistent_ksplit_h_kernel, 2), EESEN_ROW(kBwdKsplitH, kRecBwdKsplit, lstm_bwd_persistent_ksplit_h_kernel, 4),
+    EESEN_ROW(kBwdKsplitMux, kRecBwdKsplitMux, lstm_bwd_persistent_ksplit_mux_kernel, 2), EESEN_ROW(kBwdKsplitMux, kRecBwdKsplitMux, lstm_bwd_persistent_ksplit_mux_kernel, 3),
+    EESEN_ROW(kBwdKsplitMux, kRecBwdKsplitMux, lstm_bwd_persistent_ksplit_mux_kernel, 4),
+};
+#undef EESEN_BWD_Q4
+#undef EESEN_BWD_GEN
+#undef EESEN_FWD_BF
+#undef EESEN_FWD_F32
+#undef EESEN_ROW
+
 }  // namespace
 
-void set_gpu_share(int n) { g_share_override.store(n < 1 ? 1 : n, std::memory_order_relaxed); }
-int gpu_share_value() { return gpu_share(); }
-
-// One-way flight of an agent-scope increment between two CUs of the current device, in nanoseconds (measured once per device and
-// process, ~3 ms: 2000 round trips, the median of five runs).  The first-poll delays of the recurrence kernels are multiples of it.
-float handoff_flight_ns() {
-  static float cache[64] = {0};
-  static std::mutex mu;                       // Nets may be created from several host threads
-  std::lock_guard<std::mutex> lock(mu);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0.f;
-  if (cache[dev] > 0.f) return cache[dev];
-  unsigned* flags = nullptr;
-  unsigned long long* out = nullptr;
-  EESEN_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&flags), 64 * sizeof(unsigned)));
-  EESEN_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&out), sizeof(unsigned long long)));
-  const int rounds = 2000;
-  double ns[5];
-  for (int rep = 0; rep < 5; ++rep) {
-    EESEN_HIP_CHECK(hipMemset(flags, 0, 64 * sizeof(unsigned)));
-    hipLaunchKernelGGL(handoff_pingpong_kernel, dim3(2), dim3(64), 0, nullptr, flags, out, rounds);
-    unsigned long long ticks = 0;
-    EESEN_HIP_CHECK(hipMemcpy(&ticks, out, sizeof(ticks), hipMemcpyDeviceToHost));
-    // 0 ticks: the two workgroups never saw each other (not co-resident on a busy device): no measurement, the default flight
-    ns[rep] = ticks ? 10.0 * (double)ticks / (2.0 * rounds) : 500.0;
-  }
-  std::sort(ns, ns + 5);
-  (void)hipFree(flags);
-  (void)hipFree(out);
-  // (the median of five.  The measurement has two modes on an MI355X -- 370-420 ns and 550-620 ns, by where the dispatcher puts the two
-  // workgroups; some boxes read the far one every time -- and a step's time does not depend on which one its process measured: net.cpp
-  // uses the delays tuned on this part whenever the reading is in that range, and the reading itself only as a plausibility check)
-  cache[dev] = (float)std::min(2000.0, std::max(100.0, ns[2]));
-  return cache[dev];
-}
-
-// ctl: [0 .. 2*ndir*nz) arrival counters (fwd then bwd use disjoint halves via `ctl_off`), last word = error flag
-// Forward tile (sequences x hidden units per workgroup), chosen so that every CU gets ONE workgroup where the shape allows:
-//   32 x 4  <MT=2, NT=1>: the decomposition of lstm_fwd_step_kernel (any H)
-//   16 x 8  <MT=1, NT=2>: half the m_{t-1} fetch per CU; 256 workgroups at H = 512, S = 32
-//   16 x 16 <MT=1, NT=4>: for wide layers (H = 1024: 16 x 8 would need 512 co-resident workgroups); 64 gate rows of W_m
-//                         (256 KB at H = 1024) live in the registers of one workgroup
-struct FwdTile { int mt, nt; };
-static bool narrow2_ok(const LstmLayerDev& L, int need);
-static FwdTile fwd_tile(const LstmLayerDev& L) {
-  const int need = ((L.H + 31) / 32 + NW - 1) / NW;
-  const int ncu = share_of_cus();
-  // (wide layers take the 16-sequence tile at ANY batch size: their 32 x 4 tile would need H/4 x ndir workgroups -- 512 at H = 1024 --
-  // and a batch of <= 16 sequences fell back to the per-step kernels: seen at S = 16, T = 3000 with the six-layer cfg5 stack, round 4)
-  // (S <= 16 on narrow layers: the 32 x 4 tile has twice the workgroups of the 16 x 8 tile -- but only the latter has the bf16-pipe
-  // kernel; LstmLayerDev::fwd_t16_small takes it there too where that kernel applies)
-  const bool t16_ok = L.H % 8 == 0 && (L.S > 16 || need > 2 || (L.fwd_t16_small && L.fwd_split && !L.drop_mode && L.X && L.H % 32 == 0));
-  // The narrow 16 x 8 tile needs H/8 x ndir x S/16 workgroups: one per CU up to S = 32 at H = 512.  Beyond that, up to TWO per CU
-  // (round 5; S = 64 at H = 512: 512 workgroups of the bf16-pipe kernel, 108 registers) where a residency census has SEEN that many
-  // co-resident (narrow2_ok) -- two chains per CU interleaved by the hardware: 3.5 us per step for 64 sequences against 4.2 on the
-  // wide tile; otherwise the wide 16 x 16 tile.
-  const long narrow_wgs = (long)(L.H / 8) * L.ndir * cdiv(L.S, 16);
-  const bool narrow_full = narrow_wgs > ncu && !(narrow_wgs <= 2L * ncu && need <= 2 && narrow2_ok(L, need));
-  if (t16_ok && L.H % 16 == 0 && need <= 4 && (need > 2 || narrow_full)) return {1, 4};
-  if (t16_ok && need <= 2) return {1, 2};
-  return {2, 1};
-}
-
-// Sequence windows: the smallest number of equal windows (each a multiple of the sequence tile) whose workgroups can all be
-// co-resident.  1 for every configuration but the largest (S = 64 at H = 1024 needs 512 workgroups of the wide tiles: two
-// windows of 32 sequences, run one after the other -- the sequences are independent chains).
-template <class F>
-static int pick_windows(int S, int seq_tile, F fits_with) {
-  for (int nwin = 1; nwin <= 8; nwin *= 2) {
-    if (S % nwin != 0 || (S / nwin) % seq_tile != 0) { if (nwin == 1 && fits_with(S)) return 1; continue; }
-    if (fits_with(S / nwin)) return nwin;
-  }
-  return 0;
-}
-
-// Which instantiation of lstm_fwd_persistent_bf_kernel, if any, this layer's forward recurrence takes:
-//   * BASELINE config 4's bf16 forward (L.fwd_bf16: W_m as hi + lo planes, m_t one plane): the wide tile's
-//     geometry (16 sequences x 16 units), whole 256-unit multiples (each of the 8 waves owns CPW = H / 256 chunks of 32 units);
-//   * the fp32-class 3-way split (L.fwd_split; three planes each): wherever the narrow 16 x 8 fp32 tile would be taken.
-// Both: exchange buffer present, no recurrent dropout, block offsets within 32 bits -- and the instantiation's workgroups co-resident in
-// SOME number of sequence windows: a shape or device on which only the bf16-pipe tile does not fit falls through to the fp32 tiles
-// (which ran in this slot before round 4) instead of dropping to the one-launch-per-step kernels.
-//   * round 6, fp32-class on two fp16 planes per operand (L.fwd_f16 and the layer's W_m bound on hand): the narrow tile like the
-//     3-way split, AND the wide 16 x 16 tile (whole 256-unit multiples) that had only the fp32-input kernel.
-struct BfPlan { bool on; int cpw, nt, ap, wp; bool f16; };
-static BfPlan bf_plan_shape(const LstmLayerDev& L) {
-  const BfPlan off{false, 0, 0, 0, 0, false};
-  if (L.X == nullptr || L.drop_mode || L.T < 2 || L.H % 32 != 0) return off;
-  auto small = [&](int ap) { return (size_t)L.T * L.ndir * cdiv(L.S, 16) * (size_t)(L.H / 32) * 1024 * ap < ((size_t)1 << 31); };
-  if (L.fwd_bf16) {
-    if (L.H % 256 != 0 || L.H / 256 > 4 || !small(1)) return off;
-    return {true, L.H / 256, 4, 1, 2, false};
-  }
-  const bool f16 = L.fwd_f16 && L.wm_amax != nullptr;
-  if (L.fwd_split || f16) {
-    const FwdTile ft = fwd_tile(L);
-    const int need = (L.H / 32 + NW - 1) / NW;
-    if (f16 && ft.mt == 1 && ft.nt == 4 && L.H % 256 == 0 && L.H / 256 <= 4 && small(2)) return {true, L.H / 256, 4, 2, 2, true};
-    if (ft.mt != 1 || ft.nt != 2 || need > 2 || L.H % 8 != 0 || !small(3)) return off;
-    if (f16) return {true, need, 2, 2, 2, true};
-    if (L.fwd_split) return {true, need, 2, 3, 3, false};
-  }
-  return off;
-}
-// calls F<CPW, NT, AP, WP, F16>() for the instantiation of the plan (the combinations bf_plan can return)
-#define EESEN_BF_DISPATCH(P, F)                                                                           \
-  do {                                                                                                    \
-    if ((P).f16 && (P).nt == 2) { if ((P).cpw <= 1) F(1, 2, 2, 2, true); else F(2, 2, 2, 2, true); }       \
-    else if ((P).f16) { switch ((P).cpw) { case 1: F(1, 4, 2, 2, true); break; case 2: F(2, 4, 2, 2, true); break; case 3: F(3, 4, 2, 2, true); break; default: F(4, 4, 2, 2, true); } } \
-    else if ((P).nt == 2) { if ((P).cpw <= 1) F(1, 2, 3, 3, false); else F(2, 2, 3, 3, false); }           \
-    else { switch ((P).cpw) { case 1: F(1, 4, 1, 2, false); break; case 2: F(2, 4, 1, 2, false); break; case 3: F(3, 4, 1, 2, false); break; default: F(4, 4, 1, 2, false); } } \
-  } while (0)
-// Residency census of one instantiation of the bf16-pipe kernel: `wgs` workgroups launched in its census mode (T < 0) on the idle
-// device must all check in within 5 ms.  Once per (device, workgroup count) and process, ~1 ms; the occupancy query's own number is
-// only trusted where this has seen it (the MI355X guide: the query over-reports by one block per CU for SGPR-heavy kernels).
-template <int C, int N, int A, int W, bool F>
-static bool bf_census(int wgs) {
-  static std::mutex mu;
-  static std::map<std::pair<int, int>, bool> seen;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  // A device this process SHARES (EESEN_GPU_SHARE > 1: peers' grids come and go) has no idle moment to take a census in, and its
-  // answer would differ from rank to rank and run to run -- and with it the forward tile, whose two candidates are not bit-identical
-  // (ADVICE r5): there the occupancy query's margin decides alone, the same way in every process.
-  if (gpu_share() > 1) return false;
-  std::lock_guard<std::mutex> lock(mu);
-  const auto key = std::make_pair(dev, wgs);
-  if (auto it = seen.find(key); it != seen.end()) return it->second;
-  bool ok = false;
-  unsigned* w = nullptr;
-  if (hipDeviceSynchronize() == hipSuccess && hipMalloc(reinterpret_cast<void**>(&w), 2 * sizeof(unsigned)) == hipSuccess) {
-    // up to three takes: a grid that fits an idle device is seen at once; one transient occupant (another stream's kernel retiring)
-    // must not decide the tile for the life of the process
-    for (int take = 0; take < 3 && !ok; ++take) {
-      if (hipMemset(w, 0, 2 * sizeof(unsigned)) != hipSuccess) break;
-      LstmLayerDev L{};
-      L.T = -1;
-      hipLaunchKernelGGL((lstm_fwd_persistent_bf_kernel<C, N, A, W, F>), dim3(wgs), dim3(NW * 64), 0, nullptr, L, w, w + 1, 0,
-                         static_cast<unsigned long long*>(nullptr), Role{1, 1, 1, 0});
-      unsigned e = 1;
-      ok = hipMemcpy(&e, w + 1, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess && e == 0;
-    }
-    (void)hipFree(w);
-  }
-  seen[key] = ok;
-  if (getenv("EESEN_PRINT_PLAN")) fprintf(stderr, "LOG (eesen_hip) residency census: %d workgroups of lstm_fwd_persistent_bf_kernel<%d,%d,%d,%d,%s> on device %d: %s\n", wgs, C, N, A, W, F ? "true" : "false", dev, ok ? "seen co-resident" : "NOT seen");
-  return ok;
-}
-static bool bf_fits(const LstmLayerDev& L, const BfPlan& P, int Sw) {
-  dim3 grid(L.H / (4 * P.nt), L.ndir, cdiv(Sw, 16));
-#define EESEN_BF_FITS(C, N, A, W, F) return fits(lstm_fwd_persistent_bf_kernel<C, N, A, W, F>, grid, NW * 64, &bf_census<C, N, A, W, F>)
-  EESEN_BF_DISPATCH(P, EESEN_BF_FITS);
-#undef EESEN_BF_FITS
-  return false;
-}
-// the narrow bf16-pipe tile as up to two workgroups per CU (fwd_tile): the plan's own shape conditions, and the grid seen co-resident
-static bool narrow2_ok(const LstmLayerDev& L, int need) {
-  const bool f16 = L.fwd_f16 && L.wm_amax != nullptr;
-  if (!L.fwd_narrow2 || !(L.fwd_split || f16) || L.fwd_bf16 || L.X == nullptr || L.drop_mode || L.T < 2 || L.H % 32 != 0) return false;
-  if ((size_t)L.T * L.ndir * cdiv(L.S, 16) * (size_t)(L.H / 32) * 1024 * 3 >= ((size_t)1 << 31)) return false;
-  return bf_fits(L, f16 ? BfPlan{true, need, 2, 2, 2, true} : BfPlan{true, need, 2, 3, 3, false}, L.S);
-}
-static BfPlan bf_plan(const LstmLayerDev& L) {
-  BfPlan P = bf_plan_shape(L);
-  if (P.on && pick_windows(L.S, 16, [&](int Sw) { return bf_fits(L, P, Sw); }) == 0) P.on = false;
-  return P;
-}
-
-void lstm_fwd_persistent_geometry(const LstmLayerDev& L, int* nblk, int* nz, int* units_per_wg) {
-  if (const BfPlan P = bf_plan(L); P.on) {
-    *nblk = L.H / (4 * P.nt); *nz = cdiv(L.S, 16);
-    if (units_per_wg) *units_per_wg = 4 * P.nt;
-    return;
-  }
-  const FwdTile ft = fwd_tile(L);
-  *nblk = L.H / (4 * ft.nt);
-  *nz = cdiv(L.S, 16 * ft.mt);
-  if (units_per_wg) *units_per_wg = 4 * ft.nt;
-}
-
-// true when the forward tile this layer takes leaves register and LDS room for a 128 x 128 GEMM workgroup on the same CU (the
-// early middle part of the next layer's input GEMM, net.cpp): the narrow tiles (<= 8 units, <= 131 VGPRs); the wide fp32 tile
-// (206 VGPRs) does not
-bool lstm_fwd_persistent_leaves_room(const LstmLayerDev& L) {
-  // (the bf16 forward's successor in BASELINE config 4 is a projection, not an LSTM layer; two narrow workgroups per CU leave no room)
-  if (const BfPlan P = bf_plan(L); P.on) return P.nt <= 2 && (long)(L.H / (4 * P.nt)) * L.ndir * cdiv(L.S, 16) <= share_of_cus();
-  const FwdTile ft = fwd_tile(L);
-  return 4 * ft.nt <= 8;
-}
-
-// ---- the instantiations, by address: a plan carries the host stub of the kernel it chose; occupancy query, resource query and
-// launch all go through that one pointer (hipOccupancyMaxActiveBlocksPerMultiprocessor / hipFuncGetAttributes / hipLaunchKernel)
-template <int CPW, int MT, int NT>
-static const void* fwd_f32_fn(bool drop, bool xchg) {
-  if (drop) return reinterpret_cast<const void*>(&lstm_fwd_persistent_kernel<CPW, MT, NT, true>);
-  if constexpr (MT == 1) {
-    if (xchg) return reinterpret_cast<const void*>(&lstm_fwd_persistent_kernel<CPW, 1, NT, false, true>);
-  }
-  return reinterpret_cast<const void*>(&lstm_fwd_persistent_kernel<CPW, MT, NT, false>);
-}
-static const void* fwd_f32_fn(const FwdTile& ft, int need, bool drop, bool xchg) {
-  if (ft.nt == 4) return need <= 1 ? fwd_f32_fn<1, 1, 4>(drop, xchg) : need <= 2 ? fwd_f32_fn<2, 1, 4>(drop, xchg) : fwd_f32_fn<4, 1, 4>(drop, xchg);
-  if (ft.nt == 2) return need <= 1 ? fwd_f32_fn<1, 1, 2>(drop, xchg) : fwd_f32_fn<2, 1, 2>(drop, xchg);
-  return need <= 1 ? fwd_f32_fn<1, 2, 1>(drop, false) : need <= 2 ? fwd_f32_fn<2, 2, 1>(drop, false) : fwd_f32_fn<4, 2, 1>(drop, false);
-}
-static int fwd_f32_cpw(const FwdTile& ft, int need) { return ft.nt == 2 ? (need <= 1 ? 1 : 2) : (need <= 1 ? 1 : need <= 2 ? 2 : 4); }
-static const void* fwd_bf_fn(const BfPlan& B) {
-#define EESEN_BF_FN(C, N, A, W, F) return reinterpret_cast<const void*>(&lstm_fwd_persistent_bf_kernel<C, N, A, W, F>)
-  EESEN_BF_DISPATCH(B, EESEN_BF_FN);
-#undef EESEN_BF_FN
+const RecKernel* rec_kernel(int family, int a0, int a1, int a2, int a3, int a4) {
+  const int want[5] = {a0, a1, a2, a3, a4};
+  for (const RecKernel& k : kRecKernels)
+    if (k.family == family && std::equal(want, want + 5, k.arg)) return &k;
   return nullptr;
 }
-static const void* bwd_q4_fn(int cpw, int stq) {
-#define EESEN_Q4_FN(CPW) (stq == 8 ? reinterpret_cast<const void*>(&lstm_bwd_persistent_q4_kernel<CPW, 8>) : reinterpret_cast<const void*>(&lstm_bwd_persistent_q4_kernel<CPW, 4>))
-  switch (cpw) { case 8: return EESEN_Q4_FN(8); case 6: return EESEN_Q4_FN(6); case 4: return EESEN_Q4_FN(4); default: return EESEN_Q4_FN(2); }
-#undef EESEN_Q4_FN
-}
-static const void* bwd_ksplit_h_fn(int cpw) {
-  switch (cpw) {
-    case 4: return reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_h_kernel<4>);
-    case 2: return reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_h_kernel<2>);
-    default: return nullptr;
-  }
-}
-static const void* bwd_ksplit_fn(int cpw, bool mux) {
-  switch (cpw) {
-    case 4: return mux ? reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_mux_kernel<4>) : reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_kernel<4>);
-    case 3: return mux ? reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_mux_kernel<3>) : reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_kernel<3>);
-    case 2: return mux ? reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_mux_kernel<2>) : reinterpret_cast<const void*>(&lstm_bwd_persistent_ksplit_kernel<2>);
-    default: return nullptr;
-  }
-}
-template <int CPW>
-static const void* bwd_generic_fn(int stile, bool drop) {
-  if (stile == 8) return drop ? reinterpret_cast<const void*>(&lstm_bwd_persistent_kernel<CPW, 8, true>) : reinterpret_cast<const void*>(&lstm_bwd_persistent_kernel<CPW, 8, false>);
-  return drop ? reinterpret_cast<const void*>(&lstm_bwd_persistent_kernel<CPW, 16, true>) : reinterpret_cast<const void*>(&lstm_bwd_persistent_kernel<CPW, 16, false>);
-}
-static int bwd_generic_cpw(int need) { return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : need <= 8 ? 8 : 16; }
-static const void* bwd_generic_fn(int need, int stile, bool drop) {
-  switch (bwd_generic_cpw(need)) {
-    case 1: return bwd_generic_fn<1>(stile, drop);
-    case 2: return bwd_generic_fn<2>(stile, drop);
-    case 4: return bwd_generic_fn<4>(stile, drop);
-    case 8: return bwd_generic_fn<8>(stile, drop);
-    default: return bwd_generic_fn<16>(stile, drop);
-  }
-}
-
-// registers and LDS of the chosen instantiation, and what its grid leaves free on a CU (RecPlan::free_vgprs): a SIMD has 512
-// registers per lane, allocated in blocks of 8; a 512-thread workgroup is two waves per SIMD
-static void plan_resources(RecPlan& P, const dim3& grid) {
-  P.grid[0] = (int)grid.x; P.grid[1] = (int)grid.y; P.grid[2] = (int)grid.z;
-  P.wgs = (int)(grid.x * grid.y * grid.z);
-  P.wgs_per_cu = std::max(1, cdiv(P.wgs, share_of_cus()));
-  if (!P.fn) return;
-  static std::mutex mu;
-  static std::map<const void*, std::pair<int, int>> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(P.fn);
-  if (it == cache.end()) {
-    hipFuncAttributes a{};
-    if (hipFuncGetAttributes(&a, P.fn) != hipSuccess) { (void)hipGetLastError(); return; }
-    it = cache.emplace(P.fn, std::make_pair((int)a.numRegs, (int)a.sharedSizeBytes)).first;
-  }
-  P.vgprs = it->second.first;
-  P.lds = it->second.second;
-  if (P.vgprs > 0) P.free_vgprs = 512 - P.wgs_per_cu * (NW / 4) * ((P.vgprs + 7) & ~7);
-}
-
-// (see "The persistent grids are launched as ORDINARY kernels" above)
-template <class... Args>
-static void plan_launch(hipStream_t st, const RecPlan& P, const dim3& grid, Args... args) {
-  void* argv[] = {static_cast<void*>(&args)...};
-  EESEN_HIP_CHECK(hipLaunchKernel(P.fn, dim3(grid.x * grid.y * grid.z), dim3(NW * 64), argv, 0, st));
-}
-
-// number of sequence windows the forward pass of this layer takes (0: no persistent tile fits; 1: the whole batch at once)
-int lstm_fwd_persistent_windows(const LstmLayerDev& L) {
-  if (const BfPlan P = bf_plan(L); P.on) return pick_windows(L.S, 16, [&](int Sw) { return bf_fits(L, P, Sw); });
-  const int nch = (L.H + 31) / 32;
-  const int need = (nch + NW - 1) / NW;
-  const FwdTile ft = fwd_tile(L);
-  auto fits_with = [&](int Sw) {
-    dim3 grid(L.H / (4 * ft.nt), L.ndir, cdiv(Sw, 16 * ft.mt));
-    return fits(fwd_f32_fn(ft, need, L.drop_mode != 0, false), grid, NW * 64);
-  };
-  return pick_windows(L.S, 16 * ft.mt, fits_with);
-}
-
-// ---- forward ----------------------------------------------------------------------------------------------------------------
-RecPlan lstm_fwd_plan(const LstmLayerDev& L0) {
-  RecPlan P;
-  const int nch = (L0.H + 31) / 32;
-  const int need = (nch + NW - 1) / NW;
-  const FwdTile ft = fwd_tile(L0);
-  if (need > 4 || (ft.nt == 2 && need > 2) || L0.H % (4 * ft.nt) != 0 || L0.T < 2) return P;
-  // The hand-off relies on every step reading cache lines nobody has touched before in this launch.  That holds only if
-  // a time step's row block [S x ndir*H] of Y starts on a 128-byte line: otherwise the last line of block t also carries
-  // the first bytes of block t+1, gets cached (L1 and the XCD's non-coherent L2) while block t+1 is still unwritten,
-  // and is read back stale one step later (seen at S = 17, H = 20).  Such shapes use the per-step kernels.
-  if (((size_t)L0.S * L0.ndir * L0.H * sizeof(float)) % 128 != 0) return P;
-  if ((size_t)(L0.T + 2) * L0.S * L0.ndir * L0.H * sizeof(float) >= ((size_t)1 << 31)) return P;  // 32-bit buffer offsets over all of Y
-  const int nwin = lstm_fwd_persistent_windows(L0);
-  if (nwin == 0) return P;
-  if (nwin > 1 && ((size_t)(L0.S / nwin) * L0.ndir * L0.H * sizeof(float)) % 128 != 0) return P;  // a window's rows start on a line too
-  if (const BfPlan B = bf_plan(L0); B.on) {   // on the bf16 matrix pipe: config 4's bf16 forward, or the fp32-class 3-way split (lstm_fwd_persistent_bf_kernel)
-    const dim3 grid(L0.H / (4 * B.nt), L0.ndir, cdiv(L0.S / nwin, 16));
-    if ((size_t)grid.y * grid.z * kShards * kShardStride > (size_t)kCtlHalf) return P;
-    P.kind = kRecFwdBf; P.fn = fwd_bf_fn(B); P.cpw = B.cpw; P.seq_tile = 16; P.units = 4 * B.nt; P.windows = nwin;
-    snprintf(P.kernel, sizeof(P.kernel), "lstm_fwd_persistent_bf_kernel<%d,%d,%d,%d,%s>", B.nt == 2 ? (B.cpw <= 1 ? 1 : 2) : std::min(4, std::max(1, B.cpw)), B.nt, B.ap, B.wp, B.f16 ? "true" : "false");
-    plan_resources(P, grid);
-    return P;
-  }
-  // Two windows of the wide tile: one launch that time-multiplexes the two sequence tiles of every workgroup instead
-  // (lstm_fwd_persistent_mux_kernel).  LstmLayerDev::fwd_mux = 0 (EESEN_FWD_MUX=0): the two launches, one after the other.
-  if (L0.fwd_mux && nwin == 2 && ft.mt == 1 && ft.nt == 4 && need > 2 && need <= 4 && !L0.drop_mode && L0.H % 32 == 0) {
-    const int nz = cdiv(L0.S, 16), ng = cdiv(nz, 2);
-    const bool xchg = L0.X != nullptr && (size_t)L0.T * L0.ndir * nz * (size_t)(L0.H / 32) * 2048 < ((size_t)1 << 31);
-    const dim3 grid(L0.H / 16, L0.ndir, ng);
-    const void* fn = xchg ? reinterpret_cast<const void*>(&lstm_fwd_persistent_mux_kernel<4, 4, true>) : reinterpret_cast<const void*>(&lstm_fwd_persistent_mux_kernel<4, 4, false>);
-    if (fits(fn, grid, NW * 64) && (size_t)L0.ndir * nz * kShards * kShardStride <= (size_t)kCtlHalf) {
-      P.kind = kRecFwdMux; P.fn = fn; P.cpw = 4; P.seq_tile = 32; P.units = 16; P.windows = 1; P.xchg = xchg;
-      snprintf(P.kernel, sizeof(P.kernel), "lstm_fwd_persistent_mux_kernel<4,4,%s>", xchg ? "true" : "false");
-      plan_resources(P, grid);
-      return P;
-    }
-  }
-  const dim3 grid(L0.H / (4 * ft.nt), L0.ndir, cdiv(L0.S / nwin, 16 * ft.mt));
-  if ((size_t)grid.y * grid.z * kShards * kShardStride > (size_t)kCtlHalf) return P;
-  // exchange-layout operand fetch: 16-sequence tiles, whole 32-unit chunks, block offsets within 32 bits
-  const bool xchg = L0.X != nullptr && ft.mt == 1 && L0.H % 32 == 0 && !L0.drop_mode &&
-                    (size_t)L0.T * L0.ndir * cdiv(L0.S, 16) * (size_t)(L0.H / 32) * 2048 < ((size_t)1 << 31);
-  P.kind = kRecFwdF32; P.fn = fwd_f32_fn(ft, need, L0.drop_mode != 0, xchg); P.cpw = fwd_f32_cpw(ft, need);
-  P.seq_tile = 16 * ft.mt; P.units = 4 * ft.nt; P.windows = nwin; P.xchg = xchg;
-  snprintf(P.kernel, sizeof(P.kernel), "lstm_fwd_persistent_kernel<%d,%d,%d,%s,%s>", P.cpw, ft.mt, ft.nt, L0.drop_mode ? "true" : "false", xchg && !L0.drop_mode ? "true" : "false");
-  plan_resources(P, grid);
-  return P;
-}
-
-bool lstm_fwd_persistent_is_bf16(const LstmLayerDev& L) { return L.fwd_bf16 && lstm_fwd_plan(L).kind == kRecFwdBf; }
-
-bool lstm_fwd_persistent(hipStream_t st, const LstmLayerDev& L0, unsigned* cnt, unsigned* err, int spin_limit,
-                         unsigned long long* trace, hipEvent_t after_reset) {
-  const RecPlan P = lstm_fwd_plan(L0);
-  if (P.kind == kRecNone) return false;
-  const dim3 grid(P.grid[0], P.grid[1], P.grid[2]);
-  const Role role{P.grid[0], P.grid[1], P.grid[2], L0.xcd_map};
-  if (P.kind == kRecFwdMux) {
-    LstmLayerDev L = L0;
-    L.s_begin = 0; L.s_count = 0;
-    EESEN_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * L0.ndir * cdiv(L0.S, 16) * kShards * kShardStride, st));
-    plan_launch(st, P, grid, L, cnt, err, spin_limit, role);
-    return true;
-  }
-  for (int w = 0; w < P.windows; ++w) {
-    LstmLayerDev L = L0;
-    L.s_count = L0.S / P.windows;
-    L.s_begin = w * L.s_count;
-    // Two workgroups per CU (the narrow tile at --num-sequence 64): a step takes a quarter longer and its increments land later -- the
-    // first poll 700 ns after the publish instead of 400.  Swept on the final kernels (round 6, cfg2 at S = 64, ms per step at a first
-    // poll after 300 / 400 / 500 / 600 / 700 / 850 ns: 52.8 / 52.0 / 51.0-51.7 / 51.4 / 51.0 / 51.4; profiles/r06_poll_sweep.log).
-    if (P.wgs_per_cu >= 2 && !L0.poll_raw) L.poll_delay = L0.poll_delay * 7 / 4;
-    EESEN_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * grid.y * grid.z * kShards * kShardStride, st));
-    if (after_reset && P.windows == 1) EESEN_HIP_CHECK(hipEventRecord(after_reset, st));  // a gated consumer may start polling from here on
-    plan_launch(st, P, grid, L, cnt, err, spin_limit, trace, role);
-  }
-  return true;
-}
-
-void wait_for_word(hipStream_t st, const unsigned* word, unsigned target, unsigned* err, double limit_s) {
-  const unsigned long long ticks = (unsigned long long)(std::max(0.05, limit_s) * 1e8);   // wall_clock64: 100 MHz
-  hipLaunchKernelGGL(wait_for_word_kernel, dim3(1), dim3(64), 0, st, word, target, err, ticks);
-  check_launch("wait_for_word");
-}
-
-// ---- backward ---------------------------------------------------------------------------------------------------------------
-// Floats of partial-sum exchange space the K-split backward kernels need for this layer shape: per (direction, 16-sequence tile)
-// group and 64-unit block 16 blocks of 16 x 16 words of 8 bytes (value, step), two slots by step parity (px_put / px_take);
-// 0 = the kernel does not apply (narrow layers take the 4 x 32
-// tile, dropout layers and odd shapes the generic one).  LstmLayerDev::bwd_ksplit = 0 (EESEN_BWD_KSPLIT=0) switches it off.
-size_t lstm_bwd_ksplit_px_floats(const LstmLayerDev& L) {
-  if (!L.bwd_ksplit) return 0;
-  if (L.drop_mode || L.H % 256 != 0 || L.H < 768 || L.H > 1024 || L.T < 2) return 0;
-  const int ncu = share_of_cus();
-  const long blocks16 = (long)cdiv(L.H, 16) * L.ndir * cdiv(L.S, 16);
-  if (2 * blocks16 <= ncu && L.S > 8) return 0;   // the 8-sequence / 4 x 32 tiles are taken there
-  // the largest window the launcher may pick is the whole batch
-  return (size_t)2 * L.ndir * cdiv(L.S, 16) * (size_t)(L.H / 64) * 4096 * 2;
-}
-
-// the fp16-plane K-split tile applies (shape and switches; the buffers are the caller's to hand over)
-static bool bwd_planes_shape(const LstmLayerDev& L) {
-  if (!L.bwd_f16 || !L.bwd_ksplit || L.wm_amax == nullptr) return false;
-  const int cpw = (4 * L.H / 4) / (32 * NW);
-  return lstm_bwd_ksplit_px_floats(L) != 0 && (cpw == 2 || cpw == 4) && (4 * L.H / 4) % (32 * NW) == 0;
-}
-size_t lstm_bwd_planes_ex_floats(const LstmLayerDev& L) {
-  return bwd_planes_shape(L) ? (size_t)L.T * L.ndir * cdiv(L.S, 16) * (size_t)(L.H / 16) * 16 : 0;   // 64 bytes per (t, dir, tile, producer)
-}
-
-RecPlan lstm_bwd_plan(const LstmLayerDev& L0, bool assume_px) {
-  RecPlan P;
-  const int nch = (4 * L0.H + 31) / 32;
-  const int need = (nch + NW - 1) / NW;
-  // Sequences per workgroup: 16 fills the MFMA rows; 8 wastes half of them but halves the 128 KB of DG_next each workgroup
-  // must fetch per step, which is what bounds the step (measured: 3.75 us of fetch at ~34 GB/s per CU vs 1.8 us of MFMA).
-  // Take 8 whenever 16 would leave half of the chip's CUs without a workgroup.
-  const int ncu = share_of_cus();
-  const long blocks16 = (long)cdiv(L0.H, 16) * L0.ndir * cdiv(L0.S, 16);
-  const int stile = 2 * blocks16 <= ncu && L0.S > 8 ? 8 : 16;
-  P.light = stile == 8;   // (a property of the SHAPE: it also holds for the per-step kernels a shape without a persistent tile takes)
-  if (need > 16 || L0.T < 2) return P;
-  if (((size_t)L0.S * L0.ndir * 4 * L0.H * sizeof(float)) % 128 != 0) return P;      // line-aligned DG row blocks (see forward)
-  // 32-bit buffer offsets: the kernel re-bases its DG resource every `chunk` steps; a chunk touches chunk + 1 row blocks
-  const size_t blk_bytes = (size_t)L0.S * L0.ndir * 4 * L0.H * sizeof(float);
-  const long max_blocks = (long)((((size_t)1 << 31) - 1) / blk_bytes);
-  if (max_blocks < 3) return P;
-  int chunk = (int)std::min<long>(L0.T, max_blocks - 1);
-  if (chunk < L0.T) { int p2 = 1; while (p2 * 2 <= chunk) p2 *= 2; chunk = p2; }   // a power of two keeps `step % chunk` cheap
-  P.chunk = chunk;
-  // The 4-sequence x 32-unit tile (lstm_bwd_persistent_q4_kernel<., 4>): wherever the 8-sequence tile would be taken and the shape
-  // allows; with TWO 4-sequence tiles per workgroup (<., 8>, round 5) where that grid does not fit but half as many workgroups do
-  // (S = 64 at H = 512) -- LstmLayerDev::bwd_q4_st8: 0 = never (the 16 x 16 tile there, as before round 5), 2 = wherever it applies,
-  // before the one-tile form (the tests' A/B arm: same gate gradients bit for bit)
-  for (int pass = 0; pass < 2; ++pass) {
-    const int stq = (L0.bwd_q4_st8 == 2) == (pass == 0) ? 8 : 4;
-    // (round 5: any whole number of 32-unit workgroups up to 512 cells -- the recipes' 320 among them: the waves' k chunks beyond 4H read
-    // as zero and their weights ARE zero, so K = 4H need not fill the 8 waves x CPW / 2 pairs exactly)
-    if (!L0.bwd_q4 || L0.drop_mode || L0.H % 32 != 0 || L0.H > 512 || chunk < L0.T) break;
-    // (a ragged last tile is masked in the kernel -- operand rows and cells beyond S -- so S need not be a multiple of the tile: the
-    // recipes' default --num-sequence 10 takes this tile too)
-    if (stq == 4 && stile != 8) continue;
-    if (stq == 8 && !(L0.bwd_q4_st8 && L0.S > 8)) continue;
-    const int cpw = 2 * ((L0.H + 127) / 128);   // 2, 4, 6 or 8 chunks of 32 floats per wave: K = 4H in 8 waves x (cpw / 2) pairs of 64
-    const dim3 grid(L0.H / 32, L0.ndir, cdiv(L0.S, stq));
-    const size_t cwords = (size_t)grid.y * grid.z * kShards * kShardStride;
-    const void* fn = bwd_q4_fn(cpw, stq);
-    if (fits(fn, grid, NW * 64) && cwords <= (size_t)kCtlHalf) {
-      P.kind = kRecBwdQ4; P.fn = fn; P.cpw = cpw; P.stq = stq; P.seq_tile = stq; P.units = 32; P.windows = 1;
-      snprintf(P.kernel, sizeof(P.kernel), "lstm_bwd_persistent_q4_kernel<%d,%d>", cpw, stq);
-      plan_resources(P, grid);
-      return P;
-    }
-  }
-  // Wide layers: K split four ways (lstm_bwd_persistent_ksplit_kernel) wherever the 16-sequence tile would be taken and the caller
-  // handed over the partial-sum exchange buffer (lstm_bwd_ksplit_px_floats)
-  const size_t px_need = stile == 16 && (L0.PX || assume_px) ? lstm_bwd_ksplit_px_floats(L0) : 0;
-  if (px_need && (L0.PX ? L0.px_floats >= px_need : assume_px)) {
-    const int cpw = (4 * L0.H / 4) / (32 * NW);
-    auto kfits = [&](int Sw) {
-      dim3 grid(L0.H / 64 * 4, L0.ndir, cdiv(Sw, 16));
-      const size_t c1 = (size_t)grid.y * grid.z * 4 * kShards * kShardStride;
-      if (c1 > (size_t)kCtlHalf) return false;
-      const void* fn = bwd_ksplit_fn(cpw, false);
-      return fn != nullptr && fits(fn, grid, NW * 64);
-    };
-    // Round 6: the same tile on two fp16 planes per operand (lstm_bwd_persistent_ksplit_h_kernel) where the caller handed over the
-    // plane and exponent buffers; batches that need two windows take two launches of it (faster than one multiplexed fp32 launch)
-    if (bwd_planes_shape(L0) && (assume_px || (L0.DGH && L0.EX))) {
-      const void* fnh = bwd_ksplit_h_fn(cpw);
-      auto hfits = [&](int Sw) {
-        dim3 grid(L0.H / 64 * 4, L0.ndir, cdiv(Sw, 16));
-        const size_t c1 = (size_t)grid.y * grid.z * 4 * kShards * kShardStride;
-        return c1 <= (size_t)kCtlHalf && fnh != nullptr && fits(fnh, grid, NW * 64);
-      };
-      const int nwh = pick_windows(L0.S, 16, hfits);
-      if (nwh > 0 && (nwh == 1 || ((size_t)(L0.S / nwh) * L0.ndir * 4 * L0.H * sizeof(float)) % 128 == 0)) {
-        const dim3 grid(L0.H / 64 * 4, L0.ndir, cdiv(L0.S / nwh, 16));
-        P.kind = kRecBwdKsplit; P.fn = fnh; P.cpw = cpw; P.seq_tile = 16; P.units = 64; P.windows = nwh;
-        snprintf(P.kernel, sizeof(P.kernel), "lstm_bwd_persistent_ksplit_h_kernel<%d>", cpw);
-        plan_resources(P, grid);
-        return P;
-      }
-    }
-    const int nwin = pick_windows(L0.S, 16, kfits);
-    // Two windows: one launch that time-multiplexes two sequence tiles per workgroup instead (lstm_bwd_persistent_ksplit_mux_kernel;
-    // LstmLayerDev::bwd_mux = 0 / EESEN_BWD_MUX=0: the two launches, one after the other)
-    if (nwin == 2 && L0.bwd_mux && cpw >= 2 && cpw <= 4) {
-      const int nz = cdiv(L0.S, 16), ng = cdiv(nz, 2);
-      const dim3 grid(L0.H / 64 * 4, L0.ndir, ng);
-      const size_t c1 = (size_t)L0.ndir * nz * 4 * kShards * kShardStride;
-      const void* fn = bwd_ksplit_fn(cpw, true);
-      if (c1 <= (size_t)kCtlHalf && fits(fn, grid, NW * 64)) {
-        P.kind = kRecBwdKsplitMux; P.fn = fn; P.cpw = cpw; P.seq_tile = 32; P.units = 64; P.windows = 1;
-        snprintf(P.kernel, sizeof(P.kernel), "lstm_bwd_persistent_ksplit_mux_kernel<%d>", cpw);
-        plan_resources(P, grid);
-        return P;
-      }
-    }
-    if (nwin > 0 && (nwin == 1 || ((size_t)(L0.S / nwin) * L0.ndir * 4 * L0.H * sizeof(float)) % 128 == 0)) {
-      const dim3 grid(L0.H / 64 * 4, L0.ndir, cdiv(L0.S / nwin, 16));
-      P.kind = kRecBwdKsplit; P.fn = bwd_ksplit_fn(cpw, false); P.cpw = cpw; P.seq_tile = 16; P.units = 64; P.windows = nwin;
-      snprintf(P.kernel, sizeof(P.kernel), "lstm_bwd_persistent_ksplit_kernel<%d>", cpw);
-      plan_resources(P, grid);
-      return P;
-    }
-  }
-  const void* fn = bwd_generic_fn(need, stile, L0.drop_mode != 0);
-  auto gfits = [&](int Sw) {
-    dim3 grid(cdiv(L0.H, 16), L0.ndir, cdiv(Sw, stile));
-    if ((size_t)grid.y * grid.z * kShards * kShardStride > (size_t)kCtlHalf) return false;
-    return fits(fn, grid, NW * 64);
-  };
-  const int nwin = pick_windows(L0.S, stile, gfits);
-  if (nwin == 0) return P;
-  if (nwin > 1 && ((size_t)(L0.S / nwin) * L0.ndir * 4 * L0.H * sizeof(float)) % 128 != 0) return P;
-  const dim3 grid(cdiv(L0.H, 16), L0.ndir, cdiv(L0.S / nwin, stile));
-  P.kind = kRecBwdGeneric; P.fn = fn; P.cpw = bwd_generic_cpw(need); P.seq_tile = stile; P.units = 16; P.windows = nwin;
-  snprintf(P.kernel, sizeof(P.kernel), "lstm_bwd_persistent_kernel<%d,%d,%s>", P.cpw, stile, L0.drop_mode ? "true" : "false");
-  plan_resources(P, grid);
-  return P;
-}
-
-bool lstm_bwd_persistent(hipStream_t st, const LstmLayerDev& L0, const float* dY, int lddy, float* DG, unsigned* cnt,
-                         unsigned* err, int spin_limit, unsigned long long* trace) {
-  const RecPlan P = lstm_bwd_plan(L0, false);
-  if (P.kind == kRecNone) return false;
-  const dim3 grid(P.grid[0], P.grid[1], P.grid[2]);
-  const Role role{P.grid[0], P.grid[1], P.grid[2], L0.xcd_map};
-  int chunk = P.chunk;
-  if (P.kind == kRecBwdQ4) {
-    LstmLayerDev L = L0;
-    L.s_begin = 0; L.s_count = 0;
-    EESEN_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * grid.y * grid.z * kShards * kShardStride, st));
-    plan_launch(st, P, grid, L, dY, lddy, DG, cnt, err, spin_limit, trace, role);
-    return true;
-  }
-  if (P.kind == kRecBwdKsplitMux || P.kind == kRecBwdKsplit) {
-    const size_t px_need = lstm_bwd_ksplit_px_floats(L0);
-    unsigned long long* px = reinterpret_cast<unsigned long long*>(L0.PX);
-    for (int w = 0; w < P.windows; ++w) {
-      LstmLayerDev L = L0;
-      if (P.kind == kRecBwdKsplitMux) { L.s_begin = 0; L.s_count = 0; }
-      else { L.s_count = L0.S / P.windows; L.s_begin = w * L.s_count; }
-      // counters: one set per (direction, 16-sequence tile) and K quarter -- the multiplexed launch covers every tile of the batch
-      const size_t c1 = (size_t)L0.ndir * (P.kind == kRecBwdKsplitMux ? cdiv(L0.S, 16) : (int)grid.z) * 4 * kShards * kShardStride;
-      EESEN_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * c1, st));
-      EESEN_HIP_CHECK(hipMemsetAsync(L.PX, 0, sizeof(float) * px_need, st));
-      if (P.kind == kRecBwdKsplitMux) plan_launch(st, P, grid, L, dY, lddy, DG, px, cnt, err, spin_limit, role, chunk);
-      else plan_launch(st, P, grid, L, dY, lddy, DG, px, cnt, err, spin_limit, role, chunk, trace);
-    }
-    return true;
-  }
-  for (int w = 0; w < P.windows; ++w) {
-    LstmLayerDev L = L0;
-    L.s_count = L0.S / P.windows;
-    L.s_begin = w * L.s_count;
-    EESEN_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * (grid.y * grid.z * kShards * kShardStride), st));
-    plan_launch(st, P, grid, L, dY, lddy, DG, cnt, err, spin_limit, trace, role, chunk);
-  }
-  return true;
-}
+const void* handoff_pingpong_fn() { return reinterpret_cast<const void*>(&handoff_pingpong_kernel); }
+const void* wait_for_word_fn() { return reinterpret_cast<const void*>(&wait_for_word_kernel); }
 
 }  // namespace eesen

@@ -537,9 +537,9 @@ void Net::set_seq_lengths(const int* l, int s) {
   propagated = false;
 }
 
-static LstmLayerDev lstm_view(const Net& net, const Layer& L) {
+static LstmLayerDev lstm_view(const Net& net, const Layer& L, int T) {
   LstmLayerDev d;
-  d.T = net.T; d.S = net.S; d.H = L.H; d.ndir = L.ndir;
+  d.T = T; d.S = net.S; d.H = L.H; d.ndir = L.ndir;
   d.G = L.G.p; d.C = L.C.p; d.Y = L.Y.p;
   d.X = L.X.p;
   d.Wm = net.params.p + L.p_off + L.off_wm;
@@ -782,14 +782,17 @@ void Net::forward_pass() {
       // The NEXT LSTM layer's input GEMM can run on the side stream WHILE this layer's persistent kernel is running:
       // its row tiles wait on the kernel's arrival counters and are visited middle-out in time (gemm_f32_nt_gated).
       Layer* nxt = (&L - layers.data()) + 1 < (long)layers.size() ? &layers[(&L - layers.data()) + 1] : nullptr;
-      int gate_nblk = 0, nz = 1, gate_units = 0;
-      lstm_fwd_persistent_geometry(lstm_view(*this, L), &gate_nblk, &nz, &gate_units);
+      // The ONE forward plan of this layer pass: what runs the recurrence, and what may run beside it.  (A shape without a persistent
+      // tile -- kRecNone, the per-step kernels -- gets neither early form of the next layer's input GEMM.)
+      LstmLayerDev v = lstm_view(*this, L, T);
+      const RecPlan fp = persistent ? lstm_fwd_plan(v) : RecPlan{};
+      const bool pers = fp.kind != kRecNone;
       // (with forward dropout the next layer reads the MASKED output, which exists only after the recurrence: no gating)
       // (the 16-unit tile of wide layers fills the register file -- 2 x 206 VGPRs per SIMD -- so spinning GEMM workgroups
       // could keep its cooperative kernel from becoming resident: no gating there)
-      const bool plan_gate = persistent && overlap && gate_fwd && !fwd_bf16 && !L.cur_fwd_drop && gate_units <= 8 && nxt && nxt->is_lstm() && T >= 2 && rows >= 128 &&
-                             lstm_fwd_persistent_windows(lstm_view(*this, L)) == 1 &&
-                             (nxt->ndir * 4 * nxt->H) % 128 == 0 && ldY % 16 == 0 && nd * nz * kShards <= 64;
+      const bool plan_gate = pers && overlap && gate_fwd && !fwd_bf16 && !L.cur_fwd_drop && fp.units <= 8 && nxt && nxt->is_lstm() && T >= 2 && rows >= 128 &&
+                             fp.one_window &&
+                             (nxt->ndir * 4 * nxt->H) % 128 == 0 && ldY % 16 == 0 && nd * fp.seq_tiles * kShards <= 64;
       // The MIDDLE of the next layer's input GEMM under the END of this layer's recurrence.  A bidirectional layer has finished frame
       // t when its forward chain has passed step t and its backward chain step T-1-t: once both have published step m = 3T/4, the
       // frames [T-1-m, m] -- half of them -- are final, and the next layer's input GEMM for those rows runs on the side stream
@@ -800,15 +803,14 @@ void Net::forward_pass() {
       // no GEMM workgroup fits on a CU (section 9), the early part would only queue.  Same GEMM, same rows: results are
       // bit-identical to the one-launch GEMM (every output row is its own dot products).
       const int mile_step = (3 * T) / 4;   // measured at cfg2, same box: 60 % 39.4, 67 % 38.7, 75 % 38.2, 82 % 38.85, 88 % 38.8, off 39.0 ms
-      const bool plan_mid = persistent && overlap && tn.fwd_mid && !plan_gate && !L.cur_fwd_drop && lstm_fwd_persistent_leaves_room(lstm_view(*this, L)) && nd == 2 && nxt && nxt->is_lstm() &&
-                            T >= 32 && mile_step + 1 < T && lstm_fwd_persistent_windows(lstm_view(*this, L)) == 1;
+      const bool plan_mid = pers && overlap && tn.fwd_mid && !plan_gate && !L.cur_fwd_drop && fp.leaves_room && nd == 2 && nxt && nxt->is_lstm() &&
+                            T >= 32 && mile_step + 1 < T && fp.one_window;
       // (Round 3 built, and round 4 re-tried as a profiling arm, a COMMAND-PROCESSOR wait instead of the spinning waiter --
       // hipStreamWaitValue64 on signal memory.  It costs 2.2 ms per cfg2 step, and it is NOT immune to kernel-serialising tools, as
       // had been assumed: under `rocprofv3 --pmc` the run dead-locked for the whole 40 minutes of a GPU call (the tool holds the
       // recurrence's dispatch back behind the side queue's pending wait packet), with no bound to give up at.  The spinning waiter
       // below gives up after a wall-clock bound and the run continues; counter passes set EESEN_FWD_MID=0.)
       { const int ti_ = timer.begin(st, 1);
-      LstmLayerDev v = lstm_view(*this, L);
       v.poll_delay = delay_fwd;
       v.poll_raw = poll_raw;
       if (plan_mid) {
@@ -818,12 +820,11 @@ void Net::forward_pass() {
         v.milestone = mile.p;
         v.milestone_step = mile_step;
       }
-      const bool pers = persistent && lstm_fwd_persistent(st, v, ctl.p, ctl.p + kCtlWords - 1, spin_limit, trace.p,
-                                                          plan_gate ? ev_gate_reset : nullptr);
-      if (!pers)
+      if (pers) lstm_fwd_launch(st, fp, v, ctl.p, ctl.p + kCtlWords - 1, spin_limit, trace.p, plan_gate ? ev_gate_reset : nullptr);
+      else
         for (int step = 0; step < T; ++step) lstm_fwd_step(st, v, step);
       info_fwd_persistent += pers ? 1 : 0;
-      info_fwd_bf16 += pers && lstm_fwd_persistent_is_bf16(v) ? 1 : 0;
+      info_fwd_bf16 += fp.bf16 ? 1 : 0;
       ++info_lstm_layers;
       check_launch("lstm_fwd");
       timer.end(st, ti_);
@@ -832,7 +833,7 @@ void Net::forward_pass() {
         nxt->G.reserve((size_t)rows * ldG2);
         EESEN_HIP_CHECK(hipStreamWaitEvent(st2, ev_gate_reset, 0));
         const int tj_ = timer.begin(st2, 0);
-        GemmGate gate{ctl.p, ctl.p + kCtlWords - 1, nd, nz, gate_nblk, T, S, spin_limit};
+        GemmGate gate{ctl.p, ctl.p + kCtlWords - 1, nd, fp.seq_tiles, fp.grid[0], T, S, spin_limit};
         gated_rows = rows / 128 * 128;
         // (this layer's output is the operand: no forward dropout here, so it is bounded by 1; the weights' word was written on `st`
         // before ev_gate_reset, which the side stream has just waited for)
@@ -958,8 +959,9 @@ void Net::backpropagate_impl(const float* out_diff, int ldd, float* in_diff, int
   // layer: 79.8 ms per step overlapped, 71.4 not (with the two-tile 4 x 32 kernel there: 77.2 / 67.2).  At the recipes' 320 cells the
   // gradient GEMMs are 0.39 x the work and overlapping still pays at S = 64 (47.7 against 49.8 ms per minibatch): the rule stops at
   // H > 320.  EESEN_OVERLAP=1 forces it.
-  const bool overlap = overlap_for_minibatch();
-  exchange_deferred = comm && exchange_deferred_for_minibatch();
+  const std::vector<RecPlan> bwd = bwd_plans(T);   // the ONE backward plan of every LSTM layer for this pass
+  const bool overlap = overlap_for_minibatch(bwd);
+  exchange_deferred = comm && exchange_deferred_for_minibatch(bwd);
   bucket_log.clear();
   info_bwd_persistent = 0;
   live_valid = comm != nullptr;
@@ -1025,18 +1027,17 @@ void Net::backpropagate_impl(const float* out_diff, int ldd, float* in_diff, int
       bucket_allreduce(li, st);
     } else {
       const int H = L.H, nd = L.ndir, ldG = nd * 4 * H, ldY = nd * H;
-      LstmLayerDev v = lstm_view(*this, L);
+      LstmLayerDev v = lstm_view(*this, L, T);
       v.poll_delay = overlap ? delay_bwd_side : delay_bwd;   // (beside side-stream GEMMs the hand-off's increments land later: see the constructor)
       v.poll_raw = poll_raw;
-      if (persistent) {  // wide layers: partial-sum exchange space of the K-split backward kernel (shared by the layers: their passes are serial)
-        const size_t need = lstm_bwd_ksplit_px_floats(v);
-        if (need) { bwd_px.reserve(need); v.PX = bwd_px.p; v.px_floats = bwd_px.cap; }
-        if (const size_t ex = lstm_bwd_planes_ex_floats(v)) {   // the fp16-plane form: planes of the gate gradients + inverse powers (shared by the layers)
-          bwd_dgh.reserve((size_t)rows * ldG);
-          bwd_ex.reserve(ex);
-          v.DGH = reinterpret_cast<unsigned char*>(bwd_dgh.p);
-          v.EX = bwd_ex.p;
-        }
+      const RecPlan& bp = bwd[li];
+      // what the plan asks for (shared by the layers: their passes are serial).  Wide layers: partial-sum exchange space of the K-split kernel
+      if (bp.need_px) { bwd_px.reserve(bp.need_px); v.PX = bwd_px.p; v.px_floats = bwd_px.cap; }
+      if (bp.need_dgh) {   // its fp16-plane form: planes of the gate gradients + inverse powers
+        bwd_dgh.reserve((size_t)rows * ldG);
+        bwd_ex.reserve(bp.need_ex);
+        v.DGH = reinterpret_cast<unsigned char*>(bwd_dgh.p);
+        v.EX = bwd_ex.p;
       }
       EESEN_REQUIRE(in_train || !L.has_dropout(), EESEN_ERR_STATE, "Can't backpropagate a dropout layer in test mode (bilstm-parallel-layer.h:425)");
       if (L.cur_fwd_drop) mul_elements(st, d, ld_d, L.fmask.p, ldY, d, ld_d, rows, ldY);  // out_diff_drop, :892-896
@@ -1051,9 +1052,10 @@ void Net::backpropagate_impl(const float* out_diff, int ldd, float* in_diff, int
       // step 3T/4 of this recurrence, beside the weight-gradient GEMMs already co-running on the side stream, the cfg2 step went
       // 38.4 -> 39.4-39.5 ms on the same box -- the recurrence loses more to the third contender than the GEMM's head start gains.)
       { const int ti_ = timer.begin(st, 3);
-      if (persistent && lstm_bwd_persistent(st, v, d, ld_d, DGl, ctl.p + kCtlHalf, ctl.p + kCtlWords - 1, spin_limit, trace.p ? trace.p + 640 : nullptr))
+      if (bp.kind != kRecNone) {
+        lstm_bwd_launch(st, bp, v, d, ld_d, DGl, ctl.p + kCtlHalf, ctl.p + kCtlWords - 1, spin_limit, trace.p ? trace.p + 640 : nullptr);
         ++info_bwd_persistent;
-      else
+      } else
         for (int step = 0; step < T; ++step) lstm_bwd_step(st, v, step, d, ld_d, DGl, DCF.p);
       check_launch("lstm_bwd");
       timer.end(st, ti_); }
@@ -1115,8 +1117,9 @@ void Net::backpropagate_impl(const float* out_diff, int ldd, float* in_diff, int
     if (side_pending[k]) EESEN_HIP_CHECK(hipStreamWaitEvent(st, ev_grad[k], 0));
 }
 
-// The two per-minibatch schedule decisions of the backward pass, both read from the plan the launcher itself will execute
-// (lstm_bwd_plan: one selection function).
+// The backward plan of every LSTM layer at the current minibatch shape and T frames (other layers, and every layer without persistent
+// kernels: kRecNone), and the two per-minibatch schedule decisions of the backward pass, both read from those plans -- the ones the
+// launcher itself executes (lstm_bwd_plan: one selection function).
 //   * side stream: the weight-gradient GEMMs under the next-lower recurrence, unless a narrow layer (320 < H <= 512) at more than 32
 //     sequences takes a tile that is not "light" (see the measurements at the call site);
 //   * exchange (comm.cpp): deferred behind the last recurrence whenever some layer's persistent backward grid leaves fewer than 256
@@ -1124,21 +1127,24 @@ void Net::backpropagate_impl(const float* out_diff, int ldd, float* in_diff, int
 //     248-256 registers per lane, profiles/r05_rccl_kernel_descriptors.md) then cannot become resident beside it, would run in the
 //     gaps between recurrences and, while it waits for a late peer, hold CUs the next recurrence needs.  Every BASELINE shape is in
 //     that class; narrow layers of <= 256 cells are not.  EESEN_COMM_DEFER=0|1 overrides.
-bool Net::overlap_for_minibatch() const {
+std::vector<RecPlan> Net::bwd_plans(int T) const {
+  std::vector<RecPlan> plans(layers.size());
+  for (size_t li = 0; li < layers.size(); ++li)
+    if (persistent && layers[li].is_lstm()) plans[li] = lstm_bwd_plan(lstm_view(*this, layers[li], T));
+  return plans;
+}
+bool Net::overlap_for_minibatch(const std::vector<RecPlan>& bwd) const {
   bool ov = overlap;
   if (ov && tn.overlap < 0 && persistent)
-    for (const Layer& L : layers)
-      if (L.is_lstm() && L.H > 320 && L.H <= 512 && S > 32 && !lstm_bwd_plan(lstm_view(*this, L), true).light) ov = false;
+    for (size_t li = 0; li < layers.size(); ++li)
+      if (const Layer& L = layers[li]; L.is_lstm() && L.H > 320 && L.H <= 512 && S > 32 && !bwd[li].light) ov = false;
   return ov;
 }
-bool Net::exchange_deferred_for_minibatch() const {
+bool Net::exchange_deferred_for_minibatch(const std::vector<RecPlan>& bwd) const {
   if (tn.comm_defer >= 0) return tn.comm_defer != 0;
   if (!persistent) return false;    // no persistent grid: an all-reduce kernel only ever meets finite kernels
-  for (const Layer& L : layers)
-    if (L.is_lstm()) {
-      const RecPlan bp = lstm_bwd_plan(lstm_view(*this, L), true);
-      if (bp.kind != kRecNone && bp.free_vgprs < kRcclVgprsPerSimdLane) return true;   // (unknown register count: -1, deferred)
-    }
+  for (const RecPlan& bp : bwd)
+    if (bp.kind != kRecNone && bp.free_vgprs < kRcclVgprsPerSimdLane) return true;   // (unknown register count: -1, deferred)
   return false;
 }
 
@@ -1149,9 +1155,8 @@ std::string Net::plan_string() const {
   EESEN_REQUIRE(finalized, EESEN_ERR_STATE, "net not finalized");
   EESEN_REQUIRE(S > 0, EESEN_ERR_STATE, "call eesen_net_set_seq_lengths first: the plan depends on the minibatch shape");
   EESEN_HIP_CHECK(hipSetDevice(device));
-  Net& self = const_cast<Net&>(*this);   // lstm_view reads T: plan for the shape the next Propagate will see
-  const int T_saved = T;
-  if (!propagated) { int tm = 0; for (int v : lens) tm = std::max(tm, v); self.T = tm; }
+  int T = this->T;   // plan for the shape the next Propagate will see
+  if (!propagated) { T = 0; for (int v : lens) T = std::max(T, v); }
   auto one = [](const RecPlan& P) {
     char b[512];
     if (P.kind == kRecNone) { snprintf(b, sizeof(b), "{\"kernel\": \"per-step kernels (lstm.hip)\", \"persistent\": false}"); return std::string(b); }
@@ -1160,25 +1165,24 @@ std::string Net::plan_string() const {
              P.kernel, P.seq_tile, P.units, P.grid[0], P.grid[1], P.grid[2], P.wgs, P.wgs_per_cu, P.windows, P.vgprs, P.lds, P.free_vgprs);
     return std::string(b);
   };
+  const std::vector<RecPlan> bwd = bwd_plans(T);
   std::string o = "{\"T\": " + std::to_string(T) + ", \"S\": " + std::to_string(S) + ", \"persistent\": " + (persistent ? "true" : "false") + ", \"layers\": [";
   bool first = true;
   for (size_t li = 0; li < layers.size(); ++li) {
     const Layer& L = layers[li];
     if (!L.is_lstm()) continue;
-    LstmLayerDev v = lstm_view(*this, L);
-    const RecPlan fp = persistent && T >= 1 ? lstm_fwd_plan(v) : RecPlan{}, bp = persistent && T >= 1 ? lstm_bwd_plan(v, true) : RecPlan{};
+    const RecPlan fp = persistent && T >= 1 ? lstm_fwd_plan(lstm_view(*this, L, T)) : RecPlan{}, &bp = bwd[li];
     o += std::string(first ? "" : ", ") + "{\"layer\": " + std::to_string(li) + ", \"cells\": " + std::to_string(L.H) + ", \"directions\": " + std::to_string(L.ndir) +
          ", \"forward\": " + one(fp) + ", \"backward\": " + one(bp) + "}";
     first = false;
   }
-  const bool ov = overlap_for_minibatch();
+  const bool ov = overlap_for_minibatch(bwd);
   o += std::string("], \"weight_gradient_gemms\": \"") + (ov ? "side stream, under the next-lower recurrence" : "main stream, serial") + "\"";
   o += std::string(", \"gemm_arithmetic\": \"") + (gemm_mode() == 2 ? "two fp16 planes, three products (fp32-class)" : gemm_mode() == 1 ? "3-way bf16 split (fp32-class)" : "f32-input MFMA") + "\"";
-  o += std::string(", \"exchange\": ") + (comm ? (exchange_deferred_for_minibatch() ? "\"deferred: every bucket behind the backward pass's last recurrence\""
+  o += std::string(", \"exchange\": ") + (comm ? (exchange_deferred_for_minibatch(bwd) ? "\"deferred: every bucket behind the backward pass's last recurrence\""
                                                                                       : "\"overlapped: each bucket as soon as its layer's gradients are enqueued\"") : "null");
   o += std::string(", \"exchange_rule\": \"") + (tn.comm_defer >= 0 ? "EESEN_COMM_DEFER" : "auto: deferred when a persistent backward grid leaves < 256 registers per SIMD lane") + "\"";
   o += ", \"gpu_share\": " + std::to_string(gpu_share_value()) + "}";
-  self.T = T_saved;
   return o;
 }
 

@@ -189,8 +189,9 @@ struct Net {
   // layer's gradients are enqueued -- no all-reduce kernel then competes with a persistent grid for CUs (comm.cpp)
   std::vector<int> deferred_buckets;
   bool exchange_deferred = false;             // this backward pass's schedule (decided per minibatch: exchange_deferred_for_minibatch)
-  bool overlap_for_minibatch() const;         // weight-gradient GEMMs on the side stream for the current shape (net.cpp)
-  bool exchange_deferred_for_minibatch() const;
+  std::vector<RecPlan> bwd_plans(int T) const;   // per layer: the backward recurrence plan at the current shape and T frames (net.cpp)
+  bool overlap_for_minibatch(const std::vector<RecPlan>& bwd) const;   // weight-gradient GEMMs on the side stream for the current shape
+  bool exchange_deferred_for_minibatch(const std::vector<RecPlan>& bwd) const;
   std::string plan_string() const;            // eesen_net_plan_string
   hipEvent_t ev_bwd_done = nullptr;
   void issue_bucket(int li);

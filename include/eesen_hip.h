@@ -183,7 +183,7 @@ int eesen_net_recurrence_info(eesen_net_t* net, int* out4);
  * and backward recurrence plans -- kernel instantiation, sequences / units per workgroup, grid, launches per pass, registers per
  * lane and LDS bytes of the instantiation, registers per SIMD lane its grid leaves free on a CU -- and the schedule decisions that
  * follow from them: weight-gradient GEMMs on the side stream or not, the exchange schedule with a communicator attached.  The
- * launchers execute exactly these plans (one selection function per pass, lstm_persistent.hip: lstm_fwd_plan / lstm_bwd_plan).
+ * launchers execute exactly these plans (one selection function per pass, rec_plan.cpp: lstm_fwd_plan / lstm_bwd_plan).
  * Diagnostic; the reference has no counterpart (its kernels are chosen at compile time, src/gpucompute/cuda-kernels.cu). */
 int eesen_net_plan_string(eesen_net_t* net, char* json, int cap);
 /* Test hook: stores `value` into that device word on the handle's stream, as a kernel that gave up would (1: a recurrence
