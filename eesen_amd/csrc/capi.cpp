@@ -278,21 +278,11 @@ int eesen_ctc_set_guard(eesen_ctc_t* ctc, eesen_net_t* net) {
   return guard([&] {
     REQ_PTR(ctc);
     ctc->flush();
-    // the guard word is read with copies enqueued on the Ctc's stream: only in the Net's own stream are they ordered behind the
-    // kernels that raise it (a Net and a Ctc created without a stream share the device's default stream, like the reference's
-    // single-stream CuDevice)
-    if (net) EESEN_REQUIRE(net->device == ctc->device && net->st == ctc->st, EESEN_ERR_INVALID, "eesen_ctc_set_guard: the Ctc and the Net must live on the same device and stream");
-    if (ctc->guard_net) {   // unhook from the Net guarded so far
-      auto& g = ctc->guard_net->guards;
-      g.erase(std::remove(g.begin(), g.end(), static_cast<Ctc*>(ctc)), g.end());
-    }
-    ctc->guard = net && net->ctl.p ? net->ctl.p + kCtlWords - 1 : nullptr;
-    ctc->guard_net = ctc->guard ? net : nullptr;
-    if (ctc->guard_net) net->guards.push_back(ctc);
+    ctc->guard.hook(net, ctc->device, ctc->st, "eesen_ctc_set_guard");
   });
 }
 int eesen_ctc_dropped(eesen_ctc_t* ctc, long* minibatches) {
-  return guard([&] { REQ_PTR(ctc); REQ_PTR(minibatches); ctc->flush(); *minibatches = ctc->dropped; });
+  return guard([&] { REQ_PTR(ctc); REQ_PTR(minibatches); ctc->flush(); *minibatches = ctc->guard.dropped; });
 }
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode) {
   return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); });
@@ -351,18 +341,11 @@ int eesen_ce_set_guard(eesen_ce_t* ce, eesen_net_t* net) {
   return guard([&] {
     REQ_PTR(ce);
     ce->flush();
-    if (net) EESEN_REQUIRE(net->device == ce->device && net->st == ce->st, EESEN_ERR_INVALID, "eesen_ce_set_guard: the CE and the Net must live on the same device and stream");
-    if (ce->guard_net) {   // unhook from the Net guarded so far
-      auto& g = ce->guard_net->ce_guards;
-      g.erase(std::remove(g.begin(), g.end(), static_cast<CeLoss*>(ce)), g.end());
-    }
-    ce->guard = net && net->ctl.p ? net->ctl.p + kCtlWords - 1 : nullptr;
-    ce->guard_net = ce->guard ? net : nullptr;
-    if (ce->guard_net) net->ce_guards.push_back(ce);
+    ce->guard.hook(net, ce->device, ce->st, "eesen_ce_set_guard");
   });
 }
 int eesen_ce_dropped(eesen_ce_t* ce, long* minibatches) {
-  return guard([&] { REQ_PTR(ce); REQ_PTR(minibatches); ce->flush(); *minibatches = ce->dropped; });
+  return guard([&] { REQ_PTR(ce); REQ_PTR(minibatches); ce->flush(); *minibatches = ce->guard.dropped; });
 }
 int eesen_ce_set_profiling(eesen_ce_t* ce, int mode) {
   return guard([&] { REQ_PTR(ce); ce->timer.enable(mode == 2); ce->timer.set_accumulate(mode == 2); });
@@ -439,9 +422,7 @@ int eesen_op_gemm_bench(int device, int a_kc, int b_kc, int M, int N, int K, con
     EESEN_HIP_CHECK(hipSetDevice(device));
     DevBuf<float> ws;
     ws.reserve((size_t)16 << 20);
-    hipEvent_t e0, e1;
-    EESEN_HIP_CHECK(hipEventCreate(&e0));
-    EESEN_HIP_CHECK(hipEventCreate(&e1));
+    DevEvent e0(true), e1(true);
     // the operand bounds of the two-plane mode are measured once, outside the timed loop (the Net keeps them per tensor)
     DevBuf<float> am;
     am.reserve((size_t)M + N + (size_t)kAmaxBlocks * 16384);
@@ -450,15 +431,13 @@ int eesen_op_gemm_bench(int device, int a_kc, int b_kc, int M, int N, int K, con
     if (a_kc) amax_rows_cols(nullptr, A, M, K, lda, am.p, nullptr, nullptr); else amax_rows_cols(nullptr, A, K, M, lda, nullptr, am.p, aws);
     if (b_kc) amax_rows_cols(nullptr, B, N, K, ldb, am.p + M, nullptr, nullptr); else amax_rows_cols(nullptr, B, K, N, ldb, nullptr, am.p + M, aws);
     for (int i = 0; i < 2; ++i) gemm_f32(nullptr, a_kc != 0, b_kc != 0, M, N, K, 1.f, A, lda, B, ldb, 0.f, C, ldc, nullptr, ws.p, ws.cap, 0, false, ba, bb);
-    EESEN_HIP_CHECK(hipEventRecord(e0, nullptr));
+    e0.record(nullptr);
     for (int i = 0; i < iters; ++i) gemm_f32(nullptr, a_kc != 0, b_kc != 0, M, N, K, 1.f, A, lda, B, ldb, 0.f, C, ldc, nullptr, ws.p, ws.cap, 0, false, ba, bb);
-    EESEN_HIP_CHECK(hipEventRecord(e1, nullptr));
-    EESEN_HIP_CHECK(hipEventSynchronize(e1));
+    e1.record(nullptr);
+    e1.wait();
     float ms = 0.f;
     EESEN_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     *avg_ms = ms / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
   });
 }
 

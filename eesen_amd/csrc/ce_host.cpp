@@ -10,44 +10,24 @@
 namespace eesen {
 
 CeLoss::CeLoss(int dev, void* stream) : device(dev) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    throw Error(EESEN_ERR_HIP, "no HIP device available: this library has no CPU fallback");
-  EESEN_REQUIRE(dev >= 0 && dev < n, EESEN_ERR_INVALID, "device index out of range");
-  EESEN_HIP_CHECK(hipSetDevice(dev));
+  require_device(dev);
   st = reinterpret_cast<hipStream_t>(stream);  // NULL = the device's default stream (shared with the Net)
-  for (auto& x : ev) EESEN_HIP_CHECK(hipEventCreate(&x));
 }
 
-CeLoss::~CeLoss() {
+CeLoss::~CeLoss() {   // drained here; the guard hook, the pinned slots and the events go with the members
   (void)hipSetDevice(device);
   (void)hipStreamSynchronize(st);
-  if (guard_net) {
-    auto& g = guard_net->ce_guards;
-    g.erase(std::remove(g.begin(), g.end(), this), g.end());
-  }
-  for (auto& x : ev)
-    if (x) (void)hipEventDestroy(x);
-  auto drop = [](Ctc::Pin& pin) {
-    if (pin.p) (void)hipHostFree(pin.p);
-    if (pin.ev) (void)hipEventDestroy(pin.ev);
-  };
-  for (auto& x : stage) drop(x);
-  for (auto& x : pend) drop(x.pin);
 }
 
 // The totals and the progressive report of ce-loss.cc:144-167, in call order.  obj_out (may be null): this call's objective.
 void CeLoss::fold(Pending& q, double* obj_out) {
   if (!q.active) return;
-  EESEN_HIP_CHECK(hipEventSynchronize(q.pin.ev));
-  q.pin.busy = false;
+  q.pin.wait();
   q.active = false;
-  const CeSums* r = static_cast<const CeSums*>(q.pin.p);
-  if (*reinterpret_cast<const unsigned*>(r + 1) != 0) {  // computed from a timed-out forward pass (Ctc::guard): not a statistic
+  const CeSums* r = q.pin.as<CeSums>();
+  if (*reinterpret_cast<const unsigned*>(r + 1) != 0) {  // computed from a timed-out forward pass (StatGuard): not a statistic
     if (obj_out) *obj_out = std::numeric_limits<double>::quiet_NaN();
-    if (dropped++ == 0 || dropped % 100 == 0)
-      fprintf(stderr, "WARNING (eesen_hip) CE statistics of a minibatch computed from a timed-out forward pass were dropped (%ld so far)\n", dropped);
+    guard.note_dropped("CE");
     return;
   }
   const double ce = r->obj;
@@ -109,29 +89,28 @@ void CeLoss::eval_parallel(const int* frame_num_utt, int S, const float* net_out
   tg.reserve(n);
   part.reserve(nb);
   res.reserve(1);
-  Ctc::Pin& sp = stage[stage_idx++ & 1];
-  int* pinned = static_cast<int*>(Ctc::pin_reserve(sp, n * sizeof(int)));
+  PinBuf& sp = stage[stage_idx++ & 1];
+  int* pinned = static_cast<int*>(loss_slot(sp, n * sizeof(int)));
   std::copy(frame_num_utt, frame_num_utt + S, pinned);
   std::copy(targets, targets + rows, pinned + S);
   EESEN_HIP_CHECK(hipMemcpyAsync(tg.p, pinned, n * sizeof(int), hipMemcpyHostToDevice, st));
-  EESEN_HIP_CHECK(hipEventRecord(sp.ev, st));
-  sp.busy = true;
+  sp.used(st);
 
   const bool acc = timer.enabled();
   int sp0 = -1;
-  if (acc) sp0 = timer.begin(st, 0); else EESEN_HIP_CHECK(hipEventRecord(ev[0], st));
+  if (acc) sp0 = timer.begin(st, 0); else ev[0].record(st);
   ce_eval(st, net_out, ld, rows, K, S, tg.p, tg.p + S, diff, ldd, part.p, res.p);
-  if (acc) timer.end(st, sp0); else EESEN_HIP_CHECK(hipEventRecord(ev[1], st));
+  if (acc) timer.end(st, sp0); else ev[1].record(st);
 
   // the sums (and the guard word's value when they were computed) back through a pinned slot
   Pending& q = pend[pend_idx++ & 1];
   fold(q, nullptr);
-  CeSums* r = static_cast<CeSums*>(Ctc::pin_reserve(q.pin, sizeof(CeSums) + sizeof(unsigned)));
+  CeSums* r = static_cast<CeSums*>(loss_slot(q.pin, sizeof(CeSums) + sizeof(unsigned)));
   EESEN_HIP_CHECK(hipMemcpyAsync(r, res.p, sizeof(CeSums), hipMemcpyDeviceToHost, st));
   *reinterpret_cast<unsigned*>(r + 1) = 0;
-  if (guard) EESEN_HIP_CHECK(hipMemcpyAsync(r + 1, guard, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  EESEN_HIP_CHECK(hipEventRecord(q.pin.ev, st));
-  q.pin.busy = true; q.S = S; q.rows = rows; q.active = true;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(r + 1, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  q.pin.used(st);
+  q.S = S; q.rows = rows; q.active = true;
   if (obj_host) {
     fold(pend[pend_idx & 1], nullptr);   // the older one first: totals accumulate in call order
     fold(q, obj_host);
@@ -149,7 +128,7 @@ std::string CeLoss::report() {
 
 void CeLoss::phase_times(float* out1) {
   if (timer.enabled()) { timer.collect(out1, 1); return; }   // sums since the last read
-  EESEN_HIP_CHECK(hipEventSynchronize(ev[1]));
+  ev[1].wait();
   float ms = 0.f;
   EESEN_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
   out1[0] = ms * 1e-3f;

@@ -234,18 +234,18 @@ void comm_exchange(const char* addr, int port, int rank, int world, char* buf, i
 struct Comm {
   int device = 0, rank = 0, world = 1;
   ncclComm_t comm = nullptr;
-  hipStream_t st = nullptr;  // the exchange runs here, beside the compute stream(s)
-  double* scratch_d = nullptr;
-  double* scratch_h = nullptr;  // pinned
+  DevStream st;              // the exchange runs here, beside the compute stream(s)
+  DevBuf<double> scratch_d;
+  PinBuf scratch_h;          // owned only: allreduce_host is synchronous
   static constexpr int kScratch = 64;
 
   // watchdog (see the head of this file)
-  struct Pending { hipEvent_t ev; double t0; };
+  struct Pending { DevEvent ev; double t0; };
   std::thread wd;
   std::mutex mu;
   std::condition_variable cv;
   std::deque<Pending> pending;
-  std::vector<hipEvent_t> free_ev;
+  std::vector<DevEvent> free_ev;
   bool stop = false;
   std::atomic<bool> dead{false};
   std::string dead_msg;
@@ -253,18 +253,15 @@ struct Comm {
 
   Comm(int dev, const char* id128, int rank_, int world_) : device(dev), rank(rank_), world(world_) {
     EESEN_REQUIRE(world >= 1 && rank >= 0 && rank < world, EESEN_ERR_INVALID, "communicator: bad rank / world size");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(EESEN_ERR_HIP, "no HIP device available for the communicator");
-    EESEN_REQUIRE(dev >= 0 && dev < n, EESEN_ERR_INVALID, "device index out of range");
-    EESEN_HIP_CHECK(hipSetDevice(dev));
+    require_device(dev);
     ncclUniqueId id;
     std::memcpy(id.internal, id128, NCCL_UNIQUE_ID_BYTES);
     EESEN_NCCL_CHECK(rccl().CommInitRank(&comm, world, id, rank));
     int lo = 0, hi = 0;
     EESEN_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    EESEN_HIP_CHECK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi));
-    EESEN_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&scratch_d), kScratch * sizeof(double)));
-    EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&scratch_h), kScratch * sizeof(double), hipHostMallocDefault));
+    EESEN_HIP_CHECK(hipStreamCreateWithPriority(&st.s, hipStreamNonBlocking, hi));
+    scratch_d.reserve(kScratch);
+    scratch_h.reserve(kScratch * sizeof(double));
     if (const char* e = getenv("EESEN_COMM_TIMEOUT_S")) timeout_s = std::max(0.05, atof(e));
     wd = std::thread([this] { watch(); });
     share_colocated_device();
@@ -315,27 +312,21 @@ struct Comm {
     (void)hipSetDevice(device);
     if (st) (void)hipStreamSynchronize(st);
     if (comm) (void)rccl().CommDestroy(comm);
-    for (auto& p : pending) (void)hipEventDestroy(p.ev);
-    for (auto e : free_ev) (void)hipEventDestroy(e);
-    if (scratch_d) (void)hipFree(scratch_d);
-    if (scratch_h) (void)hipHostFree(scratch_h);
-    if (st) (void)hipStreamDestroy(st);
   }
   void check_alive() const {
     if (dead.load(std::memory_order_acquire)) throw Error(EESEN_ERR_COMM, dead_msg);
   }
   // an event behind the collective just enqueued on `on`: the watchdog sees when it completes
   void track(hipStream_t on) {
-    hipEvent_t ev = nullptr;
+    DevEvent ev;
     {
       std::lock_guard<std::mutex> g(mu);
-      if (!free_ev.empty()) { ev = free_ev.back(); free_ev.pop_back(); }
+      if (!free_ev.empty()) { ev = std::move(free_ev.back()); free_ev.pop_back(); }
     }
-    if (!ev) EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    EESEN_HIP_CHECK(hipEventRecord(ev, on));
+    ev.record(on);
     {
       std::lock_guard<std::mutex> g(mu);
-      pending.push_back({ev, now_s()});
+      pending.push_back({std::move(ev), now_s()});
     }
   }
   void watch() {
@@ -344,17 +335,18 @@ struct Comm {
     while (!stop) {
       cv.wait_for(lk, std::chrono::milliseconds(timeout_s < 5 ? 10 : 100));
       while (!pending.empty()) {
-        const Pending p = pending.front();
+        const hipEvent_t front = pending.front().ev.e;   // (only this thread pops)
+        const double t0 = pending.front().t0;
         lk.unlock();
-        const hipError_t e = hipEventQuery(p.ev);
+        const hipError_t e = hipEventQuery(front);
         lk.lock();
         if (e == hipSuccess) {
+          free_ev.push_back(std::move(pending.front().ev));
           pending.pop_front();
-          free_ev.push_back(p.ev);
           continue;
         }
-        if (now_s() - p.t0 > timeout_s && !dead.load()) {
-          dead_msg = "data-parallel exchange: a collective issued " + std::to_string((int)(now_s() - p.t0)) + " s ago has not completed on rank " +
+        if (now_s() - t0 > timeout_s && !dead.load()) {
+          dead_msg = "data-parallel exchange: a collective issued " + std::to_string((int)(now_s() - t0)) + " s ago has not completed on rank " +
                      std::to_string(rank) + " of " + std::to_string(world) + " (a peer died or stalled; EESEN_COMM_TIMEOUT_S = " +
                      std::to_string((int)timeout_s) + "): communicator aborted";
           fprintf(stderr, "ERROR (eesen_hip) %s\n", dead_msg.c_str());
@@ -386,14 +378,14 @@ struct Comm {
     if (n == 0) return;
     check_alive();
     EESEN_HIP_CHECK(hipSetDevice(device));
-    std::memcpy(scratch_h, v, n * sizeof(double));
-    EESEN_HIP_CHECK(hipMemcpyAsync(scratch_d, scratch_h, n * sizeof(double), hipMemcpyHostToDevice, st));
-    EESEN_NCCL_CHECK(rccl().AllReduce(scratch_d, scratch_d, (size_t)n, ncclFloat64, op == 1 ? ncclMax : ncclSum, comm, st));
+    std::memcpy(scratch_h.p, v, n * sizeof(double));
+    EESEN_HIP_CHECK(hipMemcpyAsync(scratch_d.p, scratch_h.p, n * sizeof(double), hipMemcpyHostToDevice, st));
+    EESEN_NCCL_CHECK(rccl().AllReduce(scratch_d.p, scratch_d.p, (size_t)n, ncclFloat64, op == 1 ? ncclMax : ncclSum, comm, st));
     track(st);
-    EESEN_HIP_CHECK(hipMemcpyAsync(scratch_h, scratch_d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    EESEN_HIP_CHECK(hipMemcpyAsync(scratch_h.p, scratch_d.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
     EESEN_HIP_CHECK(hipStreamSynchronize(st));  // returns when the collective has run -- or when the watchdog has aborted it
     check_alive();
-    std::memcpy(v, scratch_h, n * sizeof(double));
+    std::memcpy(v, scratch_h.p, n * sizeof(double));
   }
   // What this communicator really is, as JSON -- COLLECTIVE (every rank calls it; it gathers one word per rank): the library the
   // dynamic linker resolved and its version, whether it is the tests' stand-in, the ranks the library itself counts, and the
@@ -461,14 +453,8 @@ void Net::set_comm(Comm* c) {
   // so give the bounded spins ten times the room instead of treating it as a lost peer.
   if (c && !tn.spin_limit_set) spin_limit = std::max(spin_limit, 4000000);
   if (c && ev_ready.size() < layers.size()) {
-    EESEN_HIP_CHECK(hipSetDevice(device));
-    const size_t old = ev_ready.size();
-    ev_ready.resize(layers.size(), nullptr);
-    ev_bucket.resize(layers.size(), nullptr);
-    for (size_t i = old; i < layers.size(); ++i) {
-      EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev_ready[i], hipEventDisableTiming));
-      EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev_bucket[i], hipEventDisableTiming));
-    }
+    ev_ready.resize(layers.size());
+    ev_bucket.resize(layers.size());
   }
   bucket_pending.assign(layers.size(), 0);
 }
@@ -496,7 +482,6 @@ void Net::bucket_allreduce(int li, hipStream_t producer) {
 // a persistent grid that needs every CU.  Same buckets, same order, same sums as the overlapped mode; update() waits bucket by bucket.
 void Net::flush_deferred_buckets() {
   if (!comm || deferred_buckets.empty()) return;
-  if (!ev_bwd_done) EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev_bwd_done, hipEventDisableTiming));
   EESEN_HIP_CHECK(hipEventRecord(ev_bwd_done, st));
   EESEN_HIP_CHECK(hipStreamWaitEvent(comm->st, ev_bwd_done, 0));
   for (int li : deferred_buckets) issue_bucket(li);
@@ -534,8 +519,7 @@ void Net::fail_step_buckets() noexcept {
     std::vector<char> logged(layers.size(), 0);
     for (int li : bucket_log) logged[li] = 1;
     flush_deferred_buckets();                    // complete gradients, recorded but not yet issued
-    if (!ev_bwd_done) EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev_bwd_done, hipEventDisableTiming));
-    for (hipStream_t s : {st, st2}) {            // whatever was enqueued before the failure may still write the gradient buffer
+    for (hipStream_t s : {st, st2.s}) {            // whatever was enqueued before the failure may still write the gradient buffer
       if (!s) continue;
       EESEN_HIP_CHECK(hipEventRecord(ev_bwd_done, s));
       EESEN_HIP_CHECK(hipStreamWaitEvent(comm->st, ev_bwd_done, 0));
@@ -587,11 +571,11 @@ int Net::live_ranks() {
   const int top = top_trainable();
   EESEN_REQUIRE(top >= 0, EESEN_ERR_STATE, "the net has no trainable layer");
   if (bucket_pending[top]) EESEN_HIP_CHECK(hipStreamWaitEvent(st, ev_bucket[top], 0));  // update() has not waited for it yet
-  if (!live_pin) EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&live_pin), sizeof(float), hipHostMallocDefault));
-  EESEN_HIP_CHECK(hipMemcpyAsync(live_pin, fresh.p + P, sizeof(float), hipMemcpyDeviceToHost, st));
+  float* live = static_cast<float*>(live_pin.reserve(sizeof(float)));   // (owned only: the copy is waited for right here)
+  EESEN_HIP_CHECK(hipMemcpyAsync(live, fresh.p + P, sizeof(float), hipMemcpyDeviceToHost, st));
   EESEN_HIP_CHECK(hipStreamSynchronize(st));
   comm->check_alive();
-  return (int)(*live_pin + 0.5f);
+  return (int)(*live + 0.5f);
 }
 
 void Net::allreduce_grads(Comm* c) {

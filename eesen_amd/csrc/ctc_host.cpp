@@ -1,11 +1,9 @@
 // ctc_host.cpp -- host side of the Ctc object: label expansion, launch sequence, statistics, greedy
-// decoding.  Replaces eesen::Ctc::EvalParallel / ErrorRateMSeq (/root/reference/src/net/ctc-loss.cc:101-194,
+// decoding.  Replaces eesen::Ctc::EvalParallel / ErrorRateMSeq (the reference's src/net/ctc-loss.cc:101-194,
 // :235-298).  The lattice arithmetic itself is in ctc.hip.
 #include <algorithm>
 #include <cmath>
 #include <fstream>
-
-#include <algorithm>
 #include <limits>
 
 #include "net.h"
@@ -13,59 +11,25 @@
 namespace eesen {
 
 Ctc::Ctc(int dev, void* stream) : device(dev) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    throw Error(EESEN_ERR_HIP, "no HIP device available: this library has no CPU fallback");
-  EESEN_REQUIRE(dev >= 0 && dev < n, EESEN_ERR_INVALID, "device index out of range");
-  EESEN_HIP_CHECK(hipSetDevice(dev));
+  require_device(dev);
   st = reinterpret_cast<hipStream_t>(stream);  // NULL = the device's default stream (shared with the Net)
   if (const char* e = getenv("EESEN_CTC_WAVES"); e && *e) sweep_waves = atoi(e);
-  for (auto& x : ev) EESEN_HIP_CHECK(hipEventCreate(&x));
 }
 
-Ctc::~Ctc() {
+Ctc::~Ctc() {   // drained here; the guard hook, the pinned slots and the events go with the members
   (void)hipSetDevice(device);
   (void)hipStreamSynchronize(st);
-  if (guard_net) {
-    auto& g = guard_net->guards;
-    g.erase(std::remove(g.begin(), g.end(), this), g.end());
-  }
-  for (auto& x : ev)
-    if (x) (void)hipEventDestroy(x);
-  auto drop = [](Pin& pin) {
-    if (pin.p) (void)hipHostFree(pin.p);
-    if (pin.ev) (void)hipEventDestroy(pin.ev);
-  };
-  for (auto& x : stage) drop(x);
-  for (auto& x : ppzx) drop(x.pin);
-  for (auto& x : perr) { drop(x.pin); drop(x.probs); }
-  if (own_stream) (void)hipStreamDestroy(st);
-}
-
-void* Ctc::pin_reserve(Pin& pin, size_t bytes) {
-  if (!pin.ev) EESEN_HIP_CHECK(hipEventCreateWithFlags(&pin.ev, hipEventDisableTiming));
-  if (pin.busy) { EESEN_HIP_CHECK(hipEventSynchronize(pin.ev)); pin.busy = false; }  // two calls ago: long done
-  if (bytes > pin.cap) {
-    if (pin.p) EESEN_HIP_CHECK(hipHostFree(pin.p));
-    pin.p = nullptr;
-    pin.cap = std::max<size_t>(bytes * 2, 4096);
-    EESEN_HIP_CHECK(hipHostMalloc(&pin.p, pin.cap, hipHostMallocDefault));
-  }
-  return pin.p;
 }
 
 void Ctc::flush_pzx(PendingPzx& q) {
   if (!q.active) return;
-  EESEN_HIP_CHECK(hipEventSynchronize(q.pin.ev));
-  q.pin.busy = false;
-  const float* pz = static_cast<const float*>(q.pin.p);
+  q.pin.wait();
+  const float* pz = q.pin.as<float>();
   q.active = false;
-  if (reinterpret_cast<const unsigned*>(pz)[q.S] != 0) {  // computed from a timed-out forward pass (see Ctc::guard): not a statistic
+  if (reinterpret_cast<const unsigned*>(pz)[q.S] != 0) {  // computed from a timed-out forward pass (see StatGuard): not a statistic
     sequences -= q.S;
     frames -= q.nframes;
-    if (dropped++ == 0 || dropped % 100 == 0)
-      fprintf(stderr, "WARNING (eesen_hip) CTC statistics of a minibatch computed from a timed-out forward pass were dropped (%ld so far)\n", dropped);
+    guard.note_dropped("CTC");
     return;
   }
   double sum = 0;
@@ -130,12 +94,11 @@ void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, i
   // the stream, and the slot written here was last read by the copy of two calls ago -- nothing drains the stream.
   if (labx.cap < h.size()) EESEN_HIP_CHECK(hipStreamSynchronize(st));  // reallocation frees what queued kernels may still read
   labx.reserve(h.size());
-  Pin& sp = stage[stage_idx++ & 1];
-  int* pinned = static_cast<int*>(pin_reserve(sp, h.size() * sizeof(int)));
+  PinBuf& sp = stage[stage_idx++ & 1];
+  int* pinned = static_cast<int*>(loss_slot(sp, h.size() * sizeof(int)));
   std::copy(h.begin(), h.end(), pinned);
   EESEN_HIP_CHECK(hipMemcpyAsync(labx.p, pinned, h.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  EESEN_HIP_CHECK(hipEventRecord(sp.ev, st));
-  sp.busy = true;
+  sp.used(st);
   const int* labx_d = labx.p;
   const int* lens_dd = labx_d + n_labx;
   const int* ll_d = lens_dd + S;
@@ -148,24 +111,24 @@ void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, i
 
   const bool acc = timer.enabled();
   int sp0 = -1, sp1 = -1, sp2 = -1;
-  if (acc) sp0 = timer.begin(st, 0); else EESEN_HIP_CHECK(hipEventRecord(ev[0], st));
+  if (acc) sp0 = timer.begin(st, 0); else ev[0].record(st);
   log_rows(st, net_out, ld, logp.p, K, rows, K);                                               // ctc-loss.cc:132-133
-  if (acc) { timer.end(st, sp0); sp1 = timer.begin(st, 1); } else EESEN_HIP_CHECK(hipEventRecord(ev[1], st));
+  if (acc) { timer.end(st, sp0); sp1 = timer.begin(st, 1); } else ev[1].record(st);
   ctc_alpha_beta(st, logp.p, K, T, S, Lpad, labx_d, lens_dd, ll_d, alpha.p, beta.p, pzx_d.p, sweep_waves);  // :136-153
-  if (acc) { timer.end(st, sp1); sp2 = timer.begin(st, 2); } else EESEN_HIP_CHECK(hipEventRecord(ev[2], st));
+  if (acc) { timer.end(st, sp1); sp2 = timer.begin(st, 2); } else ev[2].record(st);
   ctc_error_diff(st, net_out, ld, T, S, K, Lpad, Lprime, lens_dd, ll_d, labx_d, alpha.p, beta.p, pzx_d.p, diff, ldd);  // :156-168
-  if (acc) timer.end(st, sp2); else EESEN_HIP_CHECK(hipEventRecord(ev[3], st));
+  if (acc) timer.end(st, sp2); else ev[3].record(st);
 
   // ln p(z|x) per sequence (ctc-loss.cc:146-153 reads it element by element): back through a pinned slot.  A caller that wants
   // the values now waits for them; otherwise they join the objective sum when the next call needs the slot or the statistics.
   PendingPzx& q = ppzx[ppzx_idx++ & 1];
   flush_pzx(q);
-  float* pz = static_cast<float*>(pin_reserve(q.pin, (size_t)(S + 1) * sizeof(float)));
+  float* pz = static_cast<float*>(loss_slot(q.pin, (size_t)(S + 1) * sizeof(float)));
   EESEN_HIP_CHECK(hipMemcpyAsync(pz, pzx_d.p, S * sizeof(float), hipMemcpyDeviceToHost, st));
   reinterpret_cast<unsigned*>(pz)[S] = 0;   // the guard word's value when these ln p were computed
-  if (guard) EESEN_HIP_CHECK(hipMemcpyAsync(pz + S, guard, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  EESEN_HIP_CHECK(hipEventRecord(q.pin.ev, st));
-  q.pin.busy = true; q.S = S; q.active = true;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(pz + S, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  q.pin.used(st);
+  q.S = S; q.active = true;
   q.nframes = 0;
   for (int s = 0; s < S; ++s) q.nframes += frame_num_utt[s];
   frames += q.nframes;
@@ -182,7 +145,7 @@ void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, i
 
 void Ctc::phase_times(float* out3) {
   if (timer.enabled()) { timer.collect(out3, 3); return; }   // sums since the last read
-  EESEN_HIP_CHECK(hipEventSynchronize(ev[3]));
+  ev[3].wait();
   for (int i = 0; i < 3; ++i) {
     float ms = 0.f;
     EESEN_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
@@ -232,13 +195,12 @@ static int levenshtein(const int* ref, int nr, const std::vector<int>& hyp) {
 
 void Ctc::flush_err(PendingErr& q, int* num_err, int* num_ref) {
   if (!q.active) return;
-  EESEN_HIP_CHECK(hipEventSynchronize(q.pin.ev));
-  q.pin.busy = false;
-  const int* ids = static_cast<const int*>(q.pin.p);
+  q.pin.wait();
+  const int* ids = q.pin.as<int>();
   const int S = q.S;
   int err = 0, ref = 0;
-  if (q.guarded && ids[(size_t)q.rows] != 0) {  // decoded from a timed-out forward pass (see Ctc::guard): not a statistic
-    if (q.with_probs) { EESEN_HIP_CHECK(hipEventSynchronize(q.probs.ev)); q.probs.busy = false; }
+  if (q.guarded && ids[(size_t)q.rows] != 0) {  // decoded from a timed-out forward pass (see StatGuard): not a statistic
+    if (q.with_probs) q.probs.wait();
     if (num_err) *num_err = 0;
     if (num_ref) *num_ref = 0;
     q.active = false;
@@ -247,11 +209,10 @@ void Ctc::flush_err(PendingErr& q, int* num_err, int* num_ref) {
   std::vector<int> hyp, frm;
   std::ofstream output;
   if (q.with_probs) {
-    EESEN_HIP_CHECK(hipEventSynchronize(q.probs.ev));
-    q.probs.busy = false;
+    q.probs.wait();
     output.open(seq_out, std::ofstream::out | std::ofstream::app);  // ctc-loss.cc:247-250
   }
-  const float* probs = static_cast<const float*>(q.probs.p);
+  const float* probs = q.probs.as<float>();
   for (int s = 0; s < S; ++s) {
     hyp.clear(); frm.clear();
     int last = -1;
@@ -291,20 +252,19 @@ void Ctc::error_rate_mseq(const int* frame_num_utt, int S, const float* net_out,
   PendingErr& q = perr[perr_idx++ & 1];
   flush_err(q, nullptr, nullptr);
   row_argmax(st, net_out, ld, rows, K, ids_d.p);  // FindRowMaxId, ctc-loss.cc:238-239
-  int* pinned = static_cast<int*>(pin_reserve(q.pin, ((size_t)rows + 1) * sizeof(int)));
+  int* pinned = static_cast<int*>(loss_slot(q.pin, ((size_t)rows + 1) * sizeof(int)));
   EESEN_HIP_CHECK(hipMemcpyAsync(pinned, ids_d.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, st));
   pinned[rows] = 0;
-  q.rows = rows; q.guarded = guard != nullptr;
-  if (guard) EESEN_HIP_CHECK(hipMemcpyAsync(pinned + rows, guard, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  EESEN_HIP_CHECK(hipEventRecord(q.pin.ev, st));
-  q.pin.busy = true; q.S = S; q.K = K; q.active = true;
+  q.rows = rows; q.guarded = guard.word != nullptr;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(pinned + rows, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  q.pin.used(st);
+  q.S = S; q.K = K; q.active = true;
   q.with_probs = !seq_out.empty();
   if (q.with_probs) {  // "This is inefficient, but ok for now" (ctc-loss.cc:283): the whole posterior matrix comes back
-    float* pp = static_cast<float*>(pin_reserve(q.probs, (size_t)rows * K * sizeof(float)));
+    float* pp = static_cast<float*>(loss_slot(q.probs, (size_t)rows * K * sizeof(float)));
     EESEN_HIP_CHECK(hipMemcpy2DAsync(pp, (size_t)K * sizeof(float), net_out, (size_t)ld * sizeof(float), (size_t)K * sizeof(float), rows,
                                      hipMemcpyDeviceToHost, st));
-    EESEN_HIP_CHECK(hipEventRecord(q.probs.ev, st));
-    q.probs.busy = true;
+    q.probs.used(st);
   }
   q.frames.assign(frame_num_utt, frame_num_utt + S);
   q.off.assign(label_off, label_off + S + 1);

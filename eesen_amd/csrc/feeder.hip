@@ -128,22 +128,19 @@ std::vector<float> delta_scales(int order, int window) {
 
 struct Feeder {
   struct Slot {
-    float* host = nullptr;  // pinned
-    size_t host_cap = 0;    // floats
-    long* off_h = nullptr;  // pinned: S offsets (floats) + S frame counts packed behind them as ints
-    size_t meta_cap = 0;    // sequences
+    // Pinned staging, owned only: its reuse is ordered by `ready` (the slot's copies and kernels have run), not by a use of its own.
+    PinBuf host;            // the utterance matrices back to back
+    PinBuf off_h;           // S offsets (floats) + S frame counts packed behind them as ints
     DevBuf<float> packed, out;
     DevBuf<long> off_d;
     DevBuf<int> frames_d;
-    hipEvent_t ready = nullptr, consumed = nullptr;
+    DevEvent ready, consumed;
     bool in_flight = false, has_consumer = false;
     int T = 0, S = 0, D = 0, ld = 0;
     // feature front end: the second packed buffer of the stage ping-pong, per-boundary offsets / frame counts, CMVN vectors
     DevBuf<float> packed2, cmvn_d;
-    long* meta_h = nullptr;   // pinned: (n_stages + 1) x S offsets, then as many frame counts (ints)
-    size_t meta2_cap = 0;     // (n_stages + 1) * S
-    float* cmvn_h = nullptr;  // pinned
-    size_t cmvn_cap = 0;
+    PinBuf meta_h;            // (n_stages + 1) x S offsets, then as many frame counts (ints)
+    PinBuf cmvn_h;
     DevBuf<long> offs_d;
     DevBuf<int> frs_d;
   };
@@ -151,35 +148,41 @@ struct Feeder {
   std::vector<Stage> pipe;
   DevBuf<float> scales_d;
   int device;
-  hipStream_t compute, copy = nullptr;
+  hipStream_t compute;
+  DevStream copy;
   std::vector<Slot> slots;
   int next = 0;
 
   Feeder(int dev, void* compute_stream, int nslots) : device(dev), compute(static_cast<hipStream_t>(compute_stream)) {
     EESEN_REQUIRE(nslots >= 1 && nslots <= 8, EESEN_ERR_INVALID, "1..8 staging slots");
-    int n = 0;
-    EESEN_REQUIRE(hipGetDeviceCount(&n) == hipSuccess && n > 0, EESEN_ERR_HIP, "no HIP device visible: the feeder has no CPU fallback");
-    EESEN_REQUIRE(dev >= 0 && dev < n, EESEN_ERR_INVALID, "device index out of range");
-    EESEN_HIP_CHECK(hipSetDevice(device));
-    EESEN_HIP_CHECK(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+    require_device(dev);
+    EESEN_HIP_CHECK(hipStreamCreateWithFlags(&copy.s, hipStreamNonBlocking));
     slots.resize(nslots);
-    for (auto& s : slots) {
-      EESEN_HIP_CHECK(hipEventCreateWithFlags(&s.ready, hipEventDisableTiming));
-      EESEN_HIP_CHECK(hipEventCreateWithFlags(&s.consumed, hipEventDisableTiming));
-    }
   }
-  ~Feeder() {
+  ~Feeder() {   // drained here; the slots and the copy stream go with the members
     (void)hipSetDevice(device);
     if (copy) (void)hipStreamSynchronize(copy);
-    for (auto& s : slots) {
-      if (s.host) (void)hipHostFree(s.host);
-      if (s.off_h) (void)hipHostFree(s.off_h);
-      if (s.meta_h) (void)hipHostFree(s.meta_h);
-      if (s.cmvn_h) (void)hipHostFree(s.cmvn_h);
-      if (s.ready) (void)hipEventDestroy(s.ready);
-      if (s.consumed) (void)hipEventDestroy(s.consumed);
+  }
+  // the slot's previous batch: its copy + kernels must have run (the pinned staging is overwritten) and its consumer must have
+  // finished reading the assembled matrix (`out` is overwritten)
+  Slot& next_slot(int* id) {
+    *id = next;
+    next = (next + 1) % (int)slots.size();
+    Slot& sl = slots[*id];
+    if (sl.in_flight) sl.ready.wait();
+    if (sl.has_consumer) sl.consumed.wait();
+    sl.in_flight = sl.has_consumer = false;
+    return sl;
+  }
+  // the raw matrices back to back in the slot's pinned staging (a quarter more when it has to grow), rows made contiguous
+  static float* pack(Slot& sl, const float* const* utts, const int* frames, const int* strides, const long* off, int S, int D, long total) {
+    float* host = static_cast<float*>(sl.host.reserve((size_t)total * sizeof(float), ((size_t)total + (size_t)total / 4) * sizeof(float)));
+    for (int s = 0; s < S; ++s) {
+      const int st = strides ? strides[s] : D;
+      if (st == D) std::memcpy(host + off[s], utts[s], (size_t)frames[s] * D * sizeof(float));
+      else for (int t = 0; t < frames[s]; ++t) std::memcpy(host + off[s] + (long)t * D, utts[s] + (long)t * st, (size_t)D * sizeof(float));
     }
-    if (copy) (void)hipStreamDestroy(copy);
+    return host;
   }
 
   int submit(const float* const* utts, const int* frames, const int* strides, int S, int D) {
@@ -195,39 +198,17 @@ struct Feeder {
       T = std::max(T, frames[s]);
     }
     EESEN_REQUIRE(T > 0, EESEN_ERR_INVALID, "every utterance is empty");
-    const int id = next;
-    next = (next + 1) % (int)slots.size();
-    Slot& sl = slots[id];
-    // the slot's previous batch: its copy + kernel must have run (we overwrite the pinned staging) and its consumer must
-    // have finished reading the assembled matrix (we overwrite `out`)
-    if (sl.in_flight) EESEN_HIP_CHECK(hipEventSynchronize(sl.ready));
-    if (sl.has_consumer) EESEN_HIP_CHECK(hipEventSynchronize(sl.consumed));
-    sl.in_flight = sl.has_consumer = false;
-    if ((size_t)total > sl.host_cap) {
-      if (sl.host) EESEN_HIP_CHECK(hipHostFree(sl.host));
-      sl.host = nullptr;
-      sl.host_cap = (size_t)total + (size_t)total / 4;
-      EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.host), sl.host_cap * sizeof(float), hipHostMallocDefault));
-    }
-    if ((size_t)S > sl.meta_cap) {
-      if (sl.off_h) EESEN_HIP_CHECK(hipHostFree(sl.off_h));
-      sl.off_h = nullptr;
-      sl.meta_cap = (size_t)S;
-      EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.off_h), sl.meta_cap * (sizeof(long) + sizeof(int)), hipHostMallocDefault));
-    }
-    int* frames_h = reinterpret_cast<int*>(sl.off_h + sl.meta_cap);
+    int id = 0;
+    Slot& sl = next_slot(&id);
+    long* off_h = static_cast<long*>(sl.off_h.reserve((size_t)S * (sizeof(long) + sizeof(int))));
+    int* frames_h = reinterpret_cast<int*>(off_h + S);
     long o = 0;
-    for (int s = 0; s < S; ++s) {  // pack: utterance matrices back to back, rows made contiguous
-      sl.off_h[s] = o;
+    for (int s = 0; s < S; ++s) {
+      off_h[s] = o;
       frames_h[s] = frames[s];
-      const int st = strides ? strides[s] : D;
-      if (st == D) {
-        std::memcpy(sl.host + o, utts[s], (size_t)frames[s] * D * sizeof(float));
-      } else {
-        for (int t = 0; t < frames[s]; ++t) std::memcpy(sl.host + o + (long)t * D, utts[s] + (long)t * st, (size_t)D * sizeof(float));
-      }
       o += (long)frames[s] * D;
     }
+    const float* host = pack(sl, utts, frames, strides, off_h, S, D, total);
     const int ld = (D + 3) / 4 * 4;  // rows of the assembled matrix start on 16 bytes (GEMM operand alignment)
     sl.packed.reserve((size_t)total);
     sl.off_d.reserve((size_t)S);
@@ -235,8 +216,8 @@ struct Feeder {
     const bool fresh = sl.out.reserve((size_t)T * S * ld);
     if (ld != D && fresh) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, sl.out.cap * sizeof(float), copy));  // pad columns stay zero
     else if (ld != D) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, (size_t)T * S * ld * sizeof(float), copy));
-    if (total) EESEN_HIP_CHECK(hipMemcpyAsync(sl.packed.p, sl.host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, copy));
-    EESEN_HIP_CHECK(hipMemcpyAsync(sl.off_d.p, sl.off_h, (size_t)S * sizeof(long), hipMemcpyHostToDevice, copy));
+    if (total) EESEN_HIP_CHECK(hipMemcpyAsync(sl.packed.p, host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, copy));
+    EESEN_HIP_CHECK(hipMemcpyAsync(sl.off_d.p, off_h, (size_t)S * sizeof(long), hipMemcpyHostToDevice, copy));
     EESEN_HIP_CHECK(hipMemcpyAsync(sl.frames_d.p, frames_h, (size_t)S * sizeof(int), hipMemcpyHostToDevice, copy));
     const bool vec = D % 4 == 0;  // then every packed frame and every output row is 16-byte aligned
     const long n = (long)T * S * (vec ? D / 4 : D);
@@ -244,7 +225,7 @@ struct Feeder {
     if (vec) interleave_kernel<4><<<blocks, 256, 0, copy>>>(sl.packed.p, sl.off_d.p, sl.frames_d.p, sl.out.p, T, S, D, ld);
     else interleave_kernel<1><<<blocks, 256, 0, copy>>>(sl.packed.p, sl.off_d.p, sl.frames_d.p, sl.out.p, T, S, D, ld);
     check_launch("interleave_kernel");
-    EESEN_HIP_CHECK(hipEventRecord(sl.ready, copy));
+    sl.ready.record(copy);
     sl.in_flight = true;
     sl.T = T; sl.S = S; sl.D = D; sl.ld = ld;
     return id;
@@ -281,7 +262,7 @@ struct Feeder {
     }
     EESEN_REQUIRE(n_cmvn <= 1, EESEN_ERR_INVALID, "at most one CMVN stage");
     for (auto& s : slots)  // batches in flight still read the old scale table
-      if (s.in_flight) EESEN_HIP_CHECK(hipEventSynchronize(s.ready));
+      if (s.in_flight) s.ready.wait();
     if (!scales.empty()) {
       scales_d.reserve(scales.size());
       EESEN_HIP_CHECK(hipMemcpy(scales_d.p, scales.data(), scales.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -316,20 +297,10 @@ struct Feeder {
     std::vector<int> dims(nb);
     dims[0] = D;
     for (int k = 0; k < nst; ++k) dims[k + 1] = stage_dim(pipe[k], dims[k]);
-    const int id = next;
-    next = (next + 1) % (int)slots.size();
-    Slot& sl = slots[id];
-    if (sl.in_flight) EESEN_HIP_CHECK(hipEventSynchronize(sl.ready));
-    if (sl.has_consumer) EESEN_HIP_CHECK(hipEventSynchronize(sl.consumed));
-    sl.in_flight = sl.has_consumer = false;
-    if ((size_t)nb * S > sl.meta2_cap) {
-      if (sl.meta_h) EESEN_HIP_CHECK(hipHostFree(sl.meta_h));
-      sl.meta_h = nullptr;
-      sl.meta2_cap = (size_t)nb * S;
-      EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.meta_h), sl.meta2_cap * (sizeof(long) + sizeof(int)), hipHostMallocDefault));
-    }
-    long* off_h = sl.meta_h;
-    int* fr_h = reinterpret_cast<int*>(sl.meta_h + sl.meta2_cap);
+    int id = 0;
+    Slot& sl = next_slot(&id);
+    long* off_h = static_cast<long*>(sl.meta_h.reserve((size_t)nb * S * (sizeof(long) + sizeof(int))));
+    int* fr_h = reinterpret_cast<int*>(off_h + (size_t)nb * S);
     std::vector<long> total(nb, 0);
     int T = 0;
     for (int s = 0; s < S; ++s) {
@@ -347,31 +318,15 @@ struct Feeder {
       T = std::max(T, f);
     }
     EESEN_REQUIRE(T > 0, EESEN_ERR_INVALID, "every utterance is empty after the front end");
-    if ((size_t)total[0] > sl.host_cap) {
-      if (sl.host) EESEN_HIP_CHECK(hipHostFree(sl.host));
-      sl.host = nullptr;
-      sl.host_cap = (size_t)total[0] + (size_t)total[0] / 4;
-      EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.host), sl.host_cap * sizeof(float), hipHostMallocDefault));
-    }
-    for (int s = 0; s < S; ++s) {  // pack the RAW matrices back to back
-      const long o = off_h[s];
-      const int st = strides ? strides[s] : D;
-      if (st == D) std::memcpy(sl.host + o, utts[s], (size_t)frames[s] * D * sizeof(float));
-      else for (int t = 0; t < frames[s]; ++t) std::memcpy(sl.host + o + (long)t * D, utts[s] + (long)t * st, (size_t)D * sizeof(float));
-    }
+    const float* host = pack(sl, utts, frames, strides, off_h, S, D, total[0]);   // (off_h[s]: the offsets at boundary 0)
     if (Dc) {
-      if ((size_t)S * 2 * Dc > sl.cmvn_cap) {
-        if (sl.cmvn_h) EESEN_HIP_CHECK(hipHostFree(sl.cmvn_h));
-        sl.cmvn_h = nullptr;
-        sl.cmvn_cap = (size_t)S * 2 * Dc;
-        EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&sl.cmvn_h), sl.cmvn_cap * sizeof(float), hipHostMallocDefault));
-      }
+      float* cmvn_h = static_cast<float*>(sl.cmvn_h.reserve((size_t)S * 2 * Dc * sizeof(float)));
       for (int s = 0; s < S; ++s) {
-        if (frames[s]) std::memcpy(sl.cmvn_h + (size_t)s * 2 * Dc, cmvn[s], (size_t)2 * Dc * sizeof(float));
-        else std::memset(sl.cmvn_h + (size_t)s * 2 * Dc, 0, (size_t)2 * Dc * sizeof(float));
+        if (frames[s]) std::memcpy(cmvn_h + (size_t)s * 2 * Dc, cmvn[s], (size_t)2 * Dc * sizeof(float));
+        else std::memset(cmvn_h + (size_t)s * 2 * Dc, 0, (size_t)2 * Dc * sizeof(float));
       }
       sl.cmvn_d.reserve((size_t)S * 2 * Dc);
-      EESEN_HIP_CHECK(hipMemcpyAsync(sl.cmvn_d.p, sl.cmvn_h, (size_t)S * 2 * Dc * sizeof(float), hipMemcpyHostToDevice, copy));
+      EESEN_HIP_CHECK(hipMemcpyAsync(sl.cmvn_d.p, cmvn_h, (size_t)S * 2 * Dc * sizeof(float), hipMemcpyHostToDevice, copy));
     }
     // even boundaries live in `packed`, odd ones in `packed2`
     size_t cap_even = 0, cap_odd = 0;
@@ -384,7 +339,7 @@ struct Feeder {
     const bool fresh = sl.out.reserve((size_t)T * S * ld);
     if (ld != Dout && fresh) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, sl.out.cap * sizeof(float), copy));
     else if (ld != Dout) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, (size_t)T * S * ld * sizeof(float), copy));
-    if (total[0]) EESEN_HIP_CHECK(hipMemcpyAsync(sl.packed.p, sl.host, (size_t)total[0] * sizeof(float), hipMemcpyHostToDevice, copy));
+    if (total[0]) EESEN_HIP_CHECK(hipMemcpyAsync(sl.packed.p, host, (size_t)total[0] * sizeof(float), hipMemcpyHostToDevice, copy));
     EESEN_HIP_CHECK(hipMemcpyAsync(sl.offs_d.p, off_h, (size_t)nb * S * sizeof(long), hipMemcpyHostToDevice, copy));
     EESEN_HIP_CHECK(hipMemcpyAsync(sl.frs_d.p, fr_h, (size_t)nb * S * sizeof(int), hipMemcpyHostToDevice, copy));
     for (int k = 0; k < nst; ++k) {
@@ -407,7 +362,7 @@ struct Feeder {
     if (vec) interleave_kernel<4><<<blocks, 256, 0, copy>>>(last, sl.offs_d.p + (size_t)nst * S, sl.frs_d.p + (size_t)nst * S, sl.out.p, T, S, Dout, ld);
     else interleave_kernel<1><<<blocks, 256, 0, copy>>>(last, sl.offs_d.p + (size_t)nst * S, sl.frs_d.p + (size_t)nst * S, sl.out.p, T, S, Dout, ld);
     check_launch("interleave_kernel");
-    EESEN_HIP_CHECK(hipEventRecord(sl.ready, copy));
+    sl.ready.record(copy);
     sl.in_flight = true;
     sl.T = T; sl.S = S; sl.D = Dout; sl.ld = ld;
     return id;
@@ -427,7 +382,7 @@ struct Feeder {
   void release(int id) {  // everything enqueued on the compute stream so far may read the slot; later work may not
     Slot& sl = checked(id);
     EESEN_HIP_CHECK(hipSetDevice(device));
-    EESEN_HIP_CHECK(hipEventRecord(sl.consumed, compute));
+    sl.consumed.record(compute);
     sl.has_consumer = true;
   }
 };
@@ -476,7 +431,7 @@ int eesen_feeder_submit_raw(eesen_feeder_t* f, const float* const* utts, const i
     *slot = f->submit_raw(utts, frames, strides, cmvn, S, D_in);
   });
 }
-// the arithmetic of ApplyCmvn, /root/reference/src/feat/cmvn.cc:78-108: host-only (a few dozen doubles per speaker)
+// the arithmetic of ApplyCmvn, the reference's src/feat/cmvn.cc:78-108: host-only (a few dozen doubles per speaker)
 int eesen_cmvn_norm(const double* stats, int rows, int cols, int norm_vars, float* offset_scale) {
   return guard([&] {
     REQ_PTR(stats); REQ_PTR(offset_scale);

@@ -1,5 +1,5 @@
 // net.cpp -- host orchestration of the hot path: the replacement of eesen::Net
-// (/root/reference/src/net/net.{h,cc}) for the layer kinds on the path.
+// (the reference's src/net/net.{h,cc}) for the layer kinds on the path.
 //
 //   Net::Propagate      net.cc:67-86     -> Net::propagate
 //   Net::Backpropagate  net.cc:88-108    -> Net::backpropagate (+ Net::update for the Update calls :101-104)
@@ -20,32 +20,21 @@ namespace eesen {
 
 
 // ------------------------------------------------------------------------------------------ PhaseTimer
-PhaseTimer::~PhaseTimer() {
-  for (auto& s : spans_) {
-    (void)hipEventDestroy(s.a);
-    (void)hipEventDestroy(s.b);
-  }
-}
 int PhaseTimer::begin(hipStream_t st, int phase) {
   if (!on_) return -1;
-  if (used_ == spans_.size()) {
-    Span s;
-    EESEN_HIP_CHECK(hipEventCreate(&s.a));
-    EESEN_HIP_CHECK(hipEventCreate(&s.b));
-    spans_.push_back(s);
-  }
+  if (used_ == spans_.size()) spans_.emplace_back();
   spans_[used_].phase = phase;
-  EESEN_HIP_CHECK(hipEventRecord(spans_[used_].a, st));
+  spans_[used_].a.record(st);
   return (int)used_++;
 }
 void PhaseTimer::end(hipStream_t st, int idx) {
   if (!on_ || idx < 0) return;
-  EESEN_HIP_CHECK(hipEventRecord(spans_[idx].b, st));
+  spans_[idx].b.record(st);
 }
 void PhaseTimer::collect(float* out, int nphase) {
   for (int i = 0; i < nphase; ++i) out[i] = 0.f;
   for (size_t i = 0; i < used_; ++i) {
-    EESEN_HIP_CHECK(hipEventSynchronize(spans_[i].b));
+    spans_[i].b.wait();
     float ms = 0.f;
     EESEN_HIP_CHECK(hipEventElapsedTime(&ms, spans_[i].a, spans_[i].b));
     if (spans_[i].phase >= 0 && spans_[i].phase < nphase) out[spans_[i].phase] += ms * 1e-3f;
@@ -55,7 +44,7 @@ void PhaseTimer::collect(float* out, int nphase) {
 
 int PhaseTimer::spans(int* phases, float* secs, int cap) {
   for (size_t i = 0; i < used_ && (int)i < cap; ++i) {
-    EESEN_HIP_CHECK(hipEventSynchronize(spans_[i].b));
+    spans_[i].b.wait();
     float ms = 0.f;
     EESEN_HIP_CHECK(hipEventElapsedTime(&ms, spans_[i].a, spans_[i].b));
     if (phases) phases[i] = spans_[i].phase;
@@ -115,13 +104,7 @@ static void for_each_param(const Layer& L, F f) {
 
 // ------------------------------------------------------------------------------------------ Net
 Net::Net(int dev, void* stream) : device(dev) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    throw Error(EESEN_ERR_HIP, "no HIP device available: this library has no CPU fallback (hipGetDeviceCount: " +
-                                   std::string(e == hipSuccess ? "0 devices" : hipGetErrorString(e)) + ")");
-  EESEN_REQUIRE(dev >= 0 && dev < n, EESEN_ERR_INVALID, "device index out of range");
-  EESEN_HIP_CHECK(hipSetDevice(dev));
+  require_device(dev);
   // NULL selects the device's default stream, so a Net and a Ctc created without a stream are ordered
   // against each other exactly like the reference's single-stream CuDevice.
   st = reinterpret_cast<hipStream_t>(stream);
@@ -129,11 +112,7 @@ Net::Net(int dev, void* stream) : device(dev) {
   // recurrence kernels of the main stream are dispatched first
   int lo = 0, hi = 0;
   EESEN_HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-  EESEN_HIP_CHECK(hipStreamCreateWithPriority(&st2, hipStreamNonBlocking, lo));
-  EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev_rec, hipEventDisableTiming));
-  for (auto& e : ev_grad) EESEN_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev_gate_reset, hipEventDisableTiming));
-  EESEN_HIP_CHECK(hipEventCreateWithFlags(&ev_gate_done, hipEventDisableTiming));
+  EESEN_HIP_CHECK(hipStreamCreateWithPriority(&st2.s, hipStreamNonBlocking, lo));
   tn = Tuning::from_env();   // every switch: tuning.h
   persistent = tn.persistent;
   // The next layer's input GEMM can run UNDER this layer's forward recurrence, gated tile by tile on the recurrence's arrival
@@ -183,15 +162,10 @@ Net::Net(int dev, void* stream) : device(dev) {
 Net::~Net() {
   (void)hipSetDevice(device);
   (void)hipStreamSynchronize(st);
-  for (Ctc* c : guards) {   // a Ctc that outlives this Net must not keep reading its (about to be freed) error word
-    (void)hipStreamSynchronize(c->st);
-    c->guard = nullptr;
-    c->guard_net = nullptr;
-  }
-  for (CeLoss* c : ce_guards) {
-    (void)hipStreamSynchronize(c->st);
-    c->guard = nullptr;
-    c->guard_net = nullptr;
+  for (StatGuard* g : guards) {   // a loss object that outlives this Net must not keep reading its (about to be freed) error word
+    (void)hipStreamSynchronize(g->st);
+    g->word = nullptr;
+    g->net = nullptr;
   }
   if (trace.p) {  // EESEN_TRACE=1: timeline of workgroup 0 of the last persistent launches (shader-clock ticks)
     std::vector<unsigned long long> h(1280);
@@ -210,21 +184,33 @@ Net::~Net() {
                        pass ? "bwd" : "fwd", seg[0] / n, seg[1] / n, seg[2] / n, seg[3] / n, seg[4] / n, n);
       }
   }
-  if (lens_pin) (void)hipHostFree(lens_pin);
-  if (err_pin) (void)hipHostFree(err_pin);
-  if (live_pin) (void)hipHostFree(live_pin);
-  for (auto& h : in_stage) { if (h.p) (void)hipHostFree(h.p); if (h.ev) (void)hipEventDestroy(h.ev); }
-  if (lens_ev) (void)hipEventDestroy(lens_ev);
-  if (err_ev) (void)hipEventDestroy(err_ev);
-  if (st2) { (void)hipStreamSynchronize(st2); (void)hipStreamDestroy(st2); }
-  if (ev_rec) (void)hipEventDestroy(ev_rec);
-  for (auto& e : ev_grad) if (e) (void)hipEventDestroy(e);
-  if (ev_gate_reset) (void)hipEventDestroy(ev_gate_reset);
-  if (ev_gate_done) (void)hipEventDestroy(ev_gate_done);
-  for (auto& e : ev_ready) if (e) (void)hipEventDestroy(e);
-  for (auto& e : ev_bucket) if (e) (void)hipEventDestroy(e);
-  if (ev_bwd_done) (void)hipEventDestroy(ev_bwd_done);
-  if (own_stream) (void)hipStreamDestroy(st);
+  if (st2) (void)hipStreamSynchronize(st2);   // drained here; the pinned buffers, events and the side stream go with the members
+}
+
+// ------------------------------------------------------------------------------------------ StatGuard
+// The guard word is read with copies enqueued on the loss object's stream: only in the Net's own stream are they ordered behind the
+// kernels that raise it (a Net and a loss object created without a stream share the device's default stream, like the reference's
+// single-stream CuDevice).
+void StatGuard::hook(Net* n, int device, hipStream_t stream, const char* entry_point) {
+  if (n && !(n->device == device && n->st == stream))
+    throw Error(EESEN_ERR_INVALID, std::string(entry_point) + ": the loss object and the Net must live on the same device and stream");
+  unhook();   // from the Net guarded so far
+  if (!n || !n->ctl.p) return;
+  word = n->ctl.p + kCtlWords - 1;
+  net = n;
+  st = stream;
+  n->guards.push_back(this);
+}
+
+void StatGuard::unhook() {
+  if (net) net->guards.erase(std::remove(net->guards.begin(), net->guards.end(), this), net->guards.end());
+  word = nullptr;
+  net = nullptr;
+}
+
+void StatGuard::note_dropped(const char* what) {
+  if (dropped++ == 0 || dropped % 100 == 0)
+    fprintf(stderr, "WARNING (eesen_hip) %s statistics of a minibatch computed from a timed-out forward pass were dropped (%ld so far)\n", what, dropped);
 }
 
 void Net::sync() {
@@ -282,20 +268,17 @@ void Net::check_device_error(bool consumer) {
 
 void Net::arm_device_error_poll() {
   if (!ctl.p) return;
-  if (!err_pin) {
-    EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&err_pin), sizeof(unsigned), hipHostMallocDefault));
-    *err_pin = 0;
-    EESEN_HIP_CHECK(hipEventCreateWithFlags(&err_ev, hipEventDisableTiming));
-  }
-  EESEN_HIP_CHECK(hipMemcpyAsync(err_pin, ctl.p + kCtlWords - 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  EESEN_HIP_CHECK(hipEventRecord(err_ev, st));
+  // (the slot is only ever overwritten by the next poll's copy, in stream order: nothing waits here)
+  if (!err_pin.p) *static_cast<unsigned*>(err_pin.reserve(sizeof(unsigned))) = 0;
+  EESEN_HIP_CHECK(hipMemcpyAsync(err_pin.p, ctl.p + kCtlWords - 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  err_pin.used(st);
   err_armed = true;
 }
 
 void Net::poll_device_error() {
-  if (!err_armed || hipEventQuery(err_ev) != hipSuccess) return;  // not there yet: the next poll or sync() will see it
+  if (!err_armed || !err_pin.ev.query()) return;  // not there yet: the next poll or sync() will see it
   err_armed = false;
-  if (*err_pin) check_device_error(/*consumer=*/false);  // re-reads the word, resets it and falls back
+  if (*err_pin.as<unsigned>()) check_device_error(/*consumer=*/false);  // re-reads the word, resets it and falls back
   else steps_since_clean = 0;
 }
 
@@ -522,17 +505,11 @@ void Net::set_seq_lengths(const int* l, int s) {
   lens_d.reserve(s);
   // Stream-ordered upload: kernels of the previous step that still read the old lengths are ahead of this copy on the
   // stream (the side stream was joined at the end of Backpropagate), so nothing has to be drained.
-  if ((size_t)s > lens_pin_cap) {
-    if (lens_pin) { EESEN_HIP_CHECK(hipStreamSynchronize(st)); EESEN_HIP_CHECK(hipHostFree(lens_pin)); }
-    lens_pin = nullptr;
-    lens_pin_cap = std::max<size_t>(64, (size_t)s * 2);
-    EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&lens_pin), lens_pin_cap * sizeof(int), hipHostMallocDefault));
-  }
-  if (!lens_ev) EESEN_HIP_CHECK(hipEventCreateWithFlags(&lens_ev, hipEventDisableTiming));
-  else EESEN_HIP_CHECK(hipEventSynchronize(lens_ev));  // the previous upload has left the staging buffer
-  std::copy(lens.begin(), lens.end(), lens_pin);
-  EESEN_HIP_CHECK(hipMemcpyAsync(lens_d.p, lens_pin, s * sizeof(int), hipMemcpyHostToDevice, st));
-  EESEN_HIP_CHECK(hipEventRecord(lens_ev, st));
+  // (the staging buffer's only device reader is the previous upload: once that has left it, it may be refilled -- or freed to grow)
+  int* pinned = static_cast<int*>(lens_pin.reserve(s * sizeof(int), std::max<size_t>(64, (size_t)s * 2) * sizeof(int)));
+  std::copy(lens.begin(), lens.end(), pinned);
+  EESEN_HIP_CHECK(hipMemcpyAsync(lens_d.p, pinned, s * sizeof(int), hipMemcpyHostToDevice, st));
+  lens_pin.used(st);
   S = s;
   propagated = false;
 }
@@ -697,21 +674,13 @@ void Net::propagate(const float* in, int nrows, int ld, bool is_device) {
     // synchronously, train-ctc-parallel.cc:198, and its trainer rebuilds feat_mat_host every minibatch): it is copied into one of
     // two pinned staging slots here and now, and travels from there on the stream.  (An asynchronous copy straight from pageable
     // memory may still be in flight when the caller reuses the buffer -- seen as run-to-run differences when two jobs share a GPU.)
-    HostStage& hs = in_stage[in_stage_idx++ & 1];
+    PinBuf& hs = in_stage[in_stage_idx++ & 1];
     const size_t bytes = (size_t)rows * D * sizeof(float);
-    if (!hs.ev) EESEN_HIP_CHECK(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
-    if (hs.busy) { EESEN_HIP_CHECK(hipEventSynchronize(hs.ev)); hs.busy = false; }   // two Propagates ago
-    if (bytes > hs.cap) {
-      if (hs.p) EESEN_HIP_CHECK(hipHostFree(hs.p));
-      hs.p = nullptr;
-      hs.cap = bytes + bytes / 4;
-      EESEN_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hs.p), hs.cap, hipHostMallocDefault));
-    }
-    for (int r = 0; r < rows; ++r) std::memcpy(hs.p + (size_t)r * D, in + (size_t)r * ld, (size_t)D * sizeof(float));
-    EESEN_HIP_CHECK(hipMemcpy2DAsync(input.p, (size_t)D4 * sizeof(float), hs.p, (size_t)D * sizeof(float), (size_t)D * sizeof(float), rows,
+    float* staged = static_cast<float*>(hs.reserve(bytes, bytes + bytes / 4));   // (its last use: two Propagates ago)
+    for (int r = 0; r < rows; ++r) std::memcpy(staged + (size_t)r * D, in + (size_t)r * ld, (size_t)D * sizeof(float));
+    EESEN_HIP_CHECK(hipMemcpy2DAsync(input.p, (size_t)D4 * sizeof(float), staged, (size_t)D * sizeof(float), (size_t)D * sizeof(float), rows,
                                      hipMemcpyHostToDevice, st));
-    EESEN_HIP_CHECK(hipEventRecord(hs.ev, st));
-    hs.busy = true;
+    hs.used(st);
   }
   forward_pass();
 }
@@ -820,7 +789,7 @@ void Net::forward_pass() {
         v.milestone = mile.p;
         v.milestone_step = mile_step;
       }
-      if (pers) lstm_fwd_launch(st, fp, v, ctl.p, ctl.p + kCtlWords - 1, spin_limit, trace.p, plan_gate ? ev_gate_reset : nullptr);
+      if (pers) lstm_fwd_launch(st, fp, v, ctl.p, ctl.p + kCtlWords - 1, spin_limit, trace.p, plan_gate ? ev_gate_reset.get() : nullptr);
       else
         for (int step = 0; step < T; ++step) lstm_fwd_step(st, v, step);
       info_fwd_persistent += pers ? 1 : 0;

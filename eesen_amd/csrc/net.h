@@ -65,7 +65,6 @@ struct Layer {
 
 class PhaseTimer {
  public:
-  ~PhaseTimer();
   void enable(bool on) { on_ = on; }
   bool enabled() const { return on_; }
   // accumulate: spans pile up over several steps and are summed (and cleared) by one collect() -- no host
@@ -77,7 +76,7 @@ class PhaseTimer {
   void collect(float* out, int nphase);  // seconds per phase; synchronises on the recorded events
   int spans(int* phases, float* secs, int cap);  // every recorded span in record order (phase, seconds); does not clear
  private:
-  struct Span { hipEvent_t a, b; int phase; };
+  struct Span { DevEvent a{true}, b{true}; int phase = 0; };
   std::vector<Span> spans_;
   size_t used_ = 0;
   bool on_ = false, accumulate_ = false;
@@ -91,10 +90,27 @@ constexpr size_t kLiveWords = 4;       // floats behind the gradient buffer: [0]
 // (profiles/r05_rccl_kernel_descriptors.md, read from librccl's gfx950 code object)
 constexpr int kRcclVgprsPerSimdLane = 256;
 
+// The hook of a loss object (Ctc, CeLoss) onto the error word of the Net whose outputs it evaluates (eesen_ctc_set_guard /
+// eesen_ce_set_guard).  The word's value travels back with every minibatch's results; a minibatch computed while it was set (a
+// timed-out persistent forward pass: garbage activations) is DROPPED from the statistics instead of being folded into them.
+// Whichever of the two objects dies first undoes the hook.
+struct StatGuard {
+  const unsigned* word = nullptr;
+  struct Net* net = nullptr;   // whose error word `word` points at
+  long dropped = 0;
+  hipStream_t st = nullptr;    // the loss object's stream: ~Net drains it before the word is freed
+  StatGuard() = default;
+  StatGuard(const StatGuard&) = delete;
+  StatGuard& operator=(const StatGuard&) = delete;
+  ~StatGuard() { unhook(); }
+  void hook(struct Net* n, int device, hipStream_t stream, const char* entry_point);   // n == nullptr: only unhooks
+  void unhook();
+  void note_dropped(const char* what);   // counts, and warns at the first and every hundredth
+};
+
 struct Net {
   int device = 0;
-  hipStream_t st = nullptr;
-  bool own_stream = false;
+  hipStream_t st = nullptr;   // the caller's (NULL: the device's default stream); not owned
   std::vector<Layer> layers;
   bool finalized = false;
   size_t P = 0;  // floats in the flat buffers (with alignment padding)
@@ -113,7 +129,7 @@ struct Net {
   int T = 0, S = 0, rows = 0;
   bool propagated = false;
   DevBuf<float> input;  // [rows x pad4(din0)]
-  struct HostStage { float* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool busy = false; } in_stage[2];  // pinned staging of HOST inputs
+  PinBuf in_stage[2];   // pinned staging of HOST inputs
   unsigned in_stage_idx = 0;
   const float* out_ptr = nullptr;
   int out_cols = 0, out_ld = 0;
@@ -122,10 +138,10 @@ struct Net {
   DevBuf<float> DGb[2], DCF, dA, dB, ws, ws2;
   DevBuf<float> bwd_px;       // partial-sum exchange space of the K-split backward kernel (wide layers)
   DevBuf<float> bwd_dgh, bwd_ex;   // ... of its fp16-plane form: the gate gradients as planes, the inverse powers (LstmLayerDev::DGH / EX)
-  hipStream_t st2 = nullptr;  // side stream: weight-gradient GEMMs under the next layer's recurrence
-  hipEvent_t ev_rec = nullptr, ev_grad[2] = {nullptr, nullptr};
+  DevStream st2;              // side stream: weight-gradient GEMMs under the next layer's recurrence
+  DevEvent ev_rec, ev_grad[2];
   bool overlap = true;
-  hipEvent_t ev_gate_reset = nullptr, ev_gate_done = nullptr;  // gated / early input GEMM of the next layer (forward)
+  DevEvent ev_gate_reset, ev_gate_done;  // gated / early input GEMM of the next layer (forward)
   DevBuf<unsigned> mile;      // progress milestone of the running forward recurrence (LstmLayerDev::milestone)
   bool gate_fwd = true;
   bool fwd_bf16 = false;      // eesen_net_set_forward_precision(1 | 2): forward GEMMs on bf16-rounded operands (BASELINE config 4)
@@ -142,13 +158,10 @@ struct Net {
   DevBuf<unsigned long long> trace;  // EESEN_TRACE=1 debug timeline
   void check_device_error(bool consumer);
   int steps_since_clean = 0;  // Propagates enqueued since the error word was last seen clear
-  // set_seq_lengths does not drain the stream: the lengths go through a pinned staging word-array (the previous copy has
-  // long completed; waiting for it bounds the host's run-ahead to one step), and the persistent kernels' error word is
-  // polled through an asynchronous copy enqueued behind every Propagate / Update (full check in sync()).
-  int* lens_pin = nullptr;
-  size_t lens_pin_cap = 0;
-  hipEvent_t lens_ev = nullptr, err_ev = nullptr;
-  unsigned* err_pin = nullptr;
+  // set_seq_lengths does not drain the stream: the lengths go through a PinBuf (the previous copy has long completed; waiting
+  // for it bounds the host's run-ahead to one step), and the persistent kernels' error word is polled through an asynchronous
+  // copy into another, enqueued behind every Propagate / Update (full check in sync()).
+  PinBuf lens_pin, err_pin;
   bool err_armed = false;
   void poll_device_error();      // non-blocking
   void arm_device_error_poll();  // enqueue the copy of the error word
@@ -183,7 +196,7 @@ struct Net {
   // over the ranks on the communicator's stream as soon as that layer's weight-gradient kernels are enqueued (the point
   // of the reference's per-layer Update, net.cc:98-104), and Update waits bucket by bucket
   Comm* comm = nullptr;                       // not owned
-  std::vector<hipEvent_t> ev_ready, ev_bucket;
+  std::vector<DevEvent> ev_ready, ev_bucket;
   std::vector<char> bucket_pending;
   // EESEN_COMM_DEFER=1 (tuning.h): the buckets of a backward pass are issued when its last recurrence has run instead of as each
   // layer's gradients are enqueued -- no all-reduce kernel then competes with a persistent grid for CUs (comm.cpp)
@@ -193,16 +206,15 @@ struct Net {
   bool overlap_for_minibatch(const std::vector<RecPlan>& bwd) const;   // weight-gradient GEMMs on the side stream for the current shape
   bool exchange_deferred_for_minibatch(const std::vector<RecPlan>& bwd) const;
   std::string plan_string() const;            // eesen_net_plan_string
-  hipEvent_t ev_bwd_done = nullptr;
+  DevEvent ev_bwd_done;
   void issue_bucket(int li);
   void fail_step_buckets() noexcept;          // Backpropagate threw with peers waiting: complete the step's collective sequence (comm.cpp)
   void flush_deferred_buckets();
-  std::vector<struct Ctc*> guards;   // the Ctc objects guarding on this Net's error word (eesen_ctc_set_guard): unhooked in ~Net
-  std::vector<struct CeLoss*> ce_guards;   // the same for the CE objects (eesen_ce_set_guard)
+  std::vector<StatGuard*> guards;   // the loss objects guarding on this Net's error word (eesen_ctc_set_guard / eesen_ce_set_guard): unhooked in ~Net
   bool grads_sanitized = false;   // this step's gradients went through an all-reduce that zeroed them on a raised error word: update() must apply
   bool live_valid = false;        // the liveness word behind the gradient buffer was written for THIS step (backpropagate / backpropagate_zero)
   std::vector<int> bucket_log;                // layer order of the last Backpropagate's buckets (tests)
-  float* live_pin = nullptr;                  // pinned landing slot of the liveness word
+  PinBuf live_pin;                            // landing slot of the liveness word
   void set_comm(Comm* c);
   int top_trainable() const;
   int live_ranks();
@@ -234,41 +246,31 @@ struct Net {
   void sync();
 };
 
+// a staging / result slot of the loss objects: twice what is asked for when it has to grow, at least a page
+inline void* loss_slot(PinBuf& pin, size_t bytes) { return pin.reserve(bytes, std::max<size_t>(bytes * 2, 4096)); }
+
 struct Ctc {
   int device = 0;
   hipStream_t st = nullptr;
-  bool own_stream = false;
   DevBuf<float> logp, alpha, beta, pzx_d;
-  DevBuf<int> labx, lens_d, lablens_d, cls_off, cls_pos, ids_d;
+  DevBuf<int> labx, ids_d;
   std::vector<int> last_lens;
   int last_T = 0, last_S = 0, last_Lpad = 0, last_Lprime = 0;
   int sweep_waves = 0;   // EESEN_CTC_WAVES when this object was created (tuning.h): 0 = the default number of waves per lattice
   double obj_sum = 0;
   long sequences = 0, frames = 0, err_tokens = 0, ref_tokens = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  DevEvent ev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};   // phase_times without the timer
   PhaseTimer timer;  // eesen_ctc_set_profiling(2): spans accumulate over many calls, read once (no per-call synchronisation)
-  // Nothing in a training step has to stall the host: label staging goes through two alternating pinned slots, and the
+  // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
-  // back through pinned slots that are folded into the statistics at the next call that needs them ("deferred").
-  struct Pin {
-    void* p = nullptr;
-    size_t cap = 0;            // bytes
-    hipEvent_t ev = nullptr;   // last use of the slot by the device
-    bool busy = false;
-  };
-  Pin stage[2];                // label expansion + class position lists (H2D)
+  // back through PinBufs that are folded into the statistics at the next call that needs them ("deferred").
+  PinBuf stage[2];             // label expansion + class position lists (H2D)
   unsigned stage_idx = 0;
-  struct PendingPzx { Pin pin; int S = 0; long nframes = 0; bool active = false; } ppzx[2];
-  struct PendingErr { Pin pin, probs; int S = 0, K = 0, rows = 0; bool active = false, with_probs = false, guarded = false; std::vector<int> frames, ids, off; } perr[2];
-  // eesen_ctc_set_guard: the error word of the Net whose outputs this Ctc evaluates.  Its value travels back with every
-  // minibatch's ln p / decoded ids; a minibatch computed while it was set (a timed-out persistent forward pass: garbage
-  // activations) is DROPPED from the statistics instead of being folded into the objective and TOKEN_ACCURACY.
-  const unsigned* guard = nullptr;
-  struct Net* guard_net = nullptr;   // whose error word `guard` points at: that Net unhooks the guard when it is destroyed first (eesen_ctc_set_guard)
-  long dropped = 0;
+  struct PendingPzx { PinBuf pin; int S = 0; long nframes = 0; bool active = false; } ppzx[2];
+  struct PendingErr { PinBuf pin, probs; int S = 0, K = 0, rows = 0; bool active = false, with_probs = false, guarded = false; std::vector<int> frames, ids, off; } perr[2];
+  StatGuard guard;             // eesen_ctc_set_guard
   std::string seq_out;         // --sequence-out-file of the trainer (ctc-loss.cc:247-250,282-291): decoded sequences are appended here
   unsigned ppzx_idx = 0, perr_idx = 0;
-  static void* pin_reserve(Pin& pin, size_t bytes);  // waits for the slot's last use, grows it, returns the host pointer
   void flush_pzx(PendingPzx& q);
   void flush_err(PendingErr& q, int* num_err, int* num_ref);
   void flush();                // fold every deferred result into the statistics (blocks until they have arrived)
@@ -284,26 +286,24 @@ struct Ctc {
 };
 
 // eesen::CE (src/net/ce-loss.h:32-77): frame-level cross-entropy (ce_host.cpp, ce.hip).  As with the Ctc nothing in a training
-// step stalls the host: targets travel through two alternating pinned slots, and each call's sums come back through a pinned
-// slot that is folded into the running totals -- in call order -- when the next-but-one call needs the slot or the totals are read.
+// step stalls the host: targets travel through two alternating PinBufs, and each call's sums come back through a PinBuf
+// that is folded into the running totals -- in call order -- when the next-but-one call needs the slot or the totals are read.
 struct CeLoss {
   int device = 0;
   hipStream_t st = nullptr;
   DevBuf<int> tg;              // lens[S] then targets[rows] of the current call
   DevBuf<CeSums> part, res;    // workgroup partials, the call's sums
-  Ctc::Pin stage[2];
+  PinBuf stage[2];
   unsigned stage_idx = 0;
-  struct Pending { Ctc::Pin pin; int S = 0; long rows = 0; bool active = false; } pend[2];
+  struct Pending { PinBuf pin; int S = 0; long rows = 0; bool active = false; } pend[2];
   unsigned pend_idx = 0;
   // running totals and the *_progress_ counters of ce-loss.cc:144-167 (the reference's are int32; these are wide)
   double obj = 0, obj_progress = 0;
   long correct = 0, frames = 0, sequences = 0, correct_progress = 0, frames_progress = 0, sequences_progress = 0;
   int report_step = 100;       // the trainer's default (train-ce-parallel.cc:52); the reference's CE leaves it uninitialised
   std::vector<std::string> progress;   // progress lines not yet handed out (eesen_ce_progress), oldest first
-  const unsigned* guard = nullptr;     // eesen_ce_set_guard: as Ctc::guard
-  struct Net* guard_net = nullptr;
-  long dropped = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  StatGuard guard;             // eesen_ce_set_guard
+  DevEvent ev[2] = {DevEvent(true), DevEvent(true)};
   PhaseTimer timer;
 
   CeLoss(int device, void* stream);

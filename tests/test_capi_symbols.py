@@ -36,13 +36,17 @@ def test_version_and_device_count_do_not_need_a_gpu():
 
 def test_no_silent_cpu_fallback():
     from eesen_amd import _lib
-    from eesen_amd.api import Net, Ctc, EesenError
+    from eesen_amd.api import Net, Ctc, CE, Feeder, EesenError
     if _lib.device_count() > 0:
         pytest.skip("a GPU is visible")
     with pytest.raises(EesenError, match="no HIP device"):
         Net()
     with pytest.raises(EesenError, match="no HIP device"):
         Ctc()
+    with pytest.raises(EesenError, match="no HIP device"):
+        CE()
+    with pytest.raises(EesenError, match="no HIP device"):
+        Feeder()
 
 
 def test_product_package_does_not_import_the_oracle():
