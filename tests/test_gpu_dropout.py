@@ -1,7 +1,10 @@
 """Dropout variants of BiLstm(Parallel) (/root/reference/src/net/bilstm-parallel-layer.h:46-94, 209-377,
 604-879) on the HIP path.  The oracle's restatement is pinned against the reference run with its own masks
 (tests/test_oracle_vs_reference.py::test_dropout_restatement_matches_the_reference); here the HIP library and the oracle get
-IDENTICAL masks (injected), so parity is the usual 1e-4; the device-side mask generator is checked on its own."""
+IDENTICAL masks (injected), so parity is the usual 1e-4; the device-side mask generator is checked on its own.
+The shapes here are narrow (32 cells and below: three instantiations of the dropout recurrences, behind a whole net and its CTC).  The
+wide shapes -- every DROP = true row of the recurrence kernel table, one layer per case, per sequence against an fp64 layer -- are
+in tests/test_gpu_recurrence_dropout.py (cases: tests/dropout_cases.py)."""
 import numpy as np
 import pytest
 
