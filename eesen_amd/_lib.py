@@ -89,6 +89,8 @@ SIGNATURES = {
     "eesen_ctc_set_profiling": (_i, [_vp, _i]),
     "eesen_ctc_set_sequence_out_file": (_i, [_vp, C.c_char_p]),
     "eesen_ctc_get_phase_times": (_i, [_vp, _vp]),
+    "eesen_ctc_align_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "eesen_ctc_get_align_times": (_i, [_vp, _vp]),
     "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "eesen_ce_destroy": (_i, [_vp]),
     "eesen_ce_eval_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -510,6 +510,26 @@ class Ctc:
         self.pzx = pzx
         return diff
 
+    def AlignParallel(self, frame_num_utt: Sequence[int], net_out: CuMatrix, label: Sequence[Sequence[int]], is_log: bool = False):
+        """Best-path (Viterbi) CTC alignment (eesen_ctc_align_parallel; no counterpart in the reference's src/net).  net_out: posteriors,
+        or log-domain scores with is_log=True.  Returns (ali [T, S] int32 class id per frame, pos [T, S] int32 lattice position,
+        score [S] float32).  Ties: the smallest move wins (stay, j-1, j-2), the final blank wins over the last label.  Rows past an
+        utterance's length are -1; an utterance without a feasible path has score -1e30 and -1 everywhere.  Statistics untouched."""
+        fn = np.ascontiguousarray(frame_num_utt, np.int32)
+        ids, off = self._csr(label)
+        S = fn.size
+        ali = np.empty(net_out.rows, np.int32)
+        pos = np.empty(net_out.rows, np.int32)
+        score = np.empty(S, np.float32)
+        check(self.lib.eesen_ctc_align_parallel(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
+                                                int(bool(is_log)), _np_ptr(ids), _np_ptr(off), _np_ptr(ali), _np_ptr(pos), _np_ptr(score)))
+        return ali.reshape(-1, S), pos.reshape(-1, S), score
+
+    def AlignTimes(self) -> dict:
+        out = np.zeros(3, np.float32)
+        check(self.lib.eesen_ctc_get_align_times(self.h, _np_ptr(out)))
+        return dict(zip(["log", "sweep", "traceback"], out.tolist()))
+
     def ErrorRateMSeq(self, frame_num_utt: Sequence[int], net_out: CuMatrix, label: Sequence[Sequence[int]], deferred: bool = False):
         """Ctc::ErrorRateMSeq (ctc-loss.cc:235-298): accumulates the error / reference token counts.  Returns this call's
         (errors, refs); with deferred=True only the argmax and the copy of the ids are enqueued and the host part (collapse +

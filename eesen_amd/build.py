@@ -20,7 +20,7 @@ FLAGS = (os.environ.get("EESEN_BUILD_DEFS", "").split()) + ["--offload-arch=gfx9
 
 
 BINDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin")
-TOOLS = {"train-ctc-parallel": "train_ctc_parallel.cc", "train-ce-parallel": "train_ce_parallel.cc", "net-output-extract": "net_output_extract.cc"}
+TOOLS = {"train-ctc-parallel": "train_ctc_parallel.cc", "train-ce-parallel": "train_ce_parallel.cc", "net-output-extract": "net_output_extract.cc", "ctc-align": "ctc_align.cc"}
 
 
 def csrc_digest() -> str:
@@ -87,7 +87,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     for name, src in TOOLS.items():
         exe = os.path.join(BINDIR, name)
         srcp = os.path.join(CSRC, "tools", src)
-        if force or _stale(exe, [srcp, LIB, os.path.join(CSRC, "tools", "kaldi_tables.h"), os.path.join(CSRC, "tools", "feat_pipeline.h"), os.path.join(CSRC, "tools", "parse_options.h"),
+        if force or _stale(exe, [srcp, LIB, os.path.join(CSRC, "tools", "kaldi_tables.h"), os.path.join(CSRC, "tools", "feat_pipeline.h"), os.path.join(CSRC, "tools", "parse_options.h"), os.path.join(CSRC, "tools", "class_prior.h"),
                                  os.path.join(CSRC, "..", "..", "include", "eesen_hip.h"), os.path.join(CSRC, "..", "..", "include", "eesen_hip_info.h")]):
             run([cxx, "-O2", "-std=c++17", "-Wall", srcp, "-o", exe, "-L" + LIBDIR, "-leesen_hip", "-Wl,-rpath," + LIBDIR,
                  "-Wl,-rpath,$ORIGIN/../lib", "-Wl,--allow-shlib-undefined"])

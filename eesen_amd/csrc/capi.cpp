@@ -245,6 +245,16 @@ int eesen_ctc_eval_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, c
     ctc->eval_parallel(frame_num_utt, S, net_out_dev, rows, K, ld, label_ids, label_off, diff_dev, diff_ld, pzx_host);
   });
 }
+int eesen_ctc_align_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                             int is_log, const int* label_ids, const int* label_off, int* ali_host, int* pos_host, float* score_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev); REQ_PTR(label_ids); REQ_PTR(label_off); REQ_PTR(ali_host); REQ_PTR(score_host);
+    ctc->align_parallel(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, label_ids, label_off, ali_host, pos_host, score_host);
+  });
+}
+int eesen_ctc_get_align_times(eesen_ctc_t* ctc, float* out3) {
+  return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->align_times(out3); });
+}
 int eesen_ctc_error_rate_mseq(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* net_out_dev, int rows, int K,
                               int ld, const int* label_ids, const int* label_off, int* num_err, int* num_ref) {
   return guard([&] {
@@ -285,7 +295,7 @@ int eesen_ctc_dropped(eesen_ctc_t* ctc, long* minibatches) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(minibatches); ctc->flush(); *minibatches = ctc->guard.dropped; });
 }
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode) {
-  return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); });
+  return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); ctc->align_timer.enable(mode == 2); ctc->align_timer.set_accumulate(mode == 2); });
 }
 int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->phase_times(out3); });

@@ -21,6 +21,8 @@
 // The per-frame gradient is then a bulk pass (one wavefront per frame) that stages alpha+beta in LDS, reduces the
 // blank's ~L'/2 positions across the wave and lets lane k >= 1 fold class k's few lattice positions (precomputed per
 // utterance), emitting d(-ln p)/d(logits) directly.
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace eesen {
@@ -108,7 +110,9 @@ __device__ __forceinline__ void store_row(float* __restrict__ dst, const float (
 }
 
 // ---- alpha / beta sweeps: grid (S, 2), one wavefront each -------------------------------------------
-template <int PL, int NW, bool is_beta>
+// best_path: the same sweep in the max-plus semiring (delta rows of the Viterbi alignment, ctc_best_path_kernel below): the
+// two log-adds of a step become two maxima, and a cell none of whose predecessors is reachable stays at exactly -1e30.
+template <int PL, int NW, bool is_beta, bool best_path = false>
 __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld, int T, int S, const int* __restrict__ labx,
                                           const int* __restrict__ lens, const int* __restrict__ lablens,
                                           float* __restrict__ alpha, float* __restrict__ beta, float* __restrict__ pzx,
@@ -153,7 +157,7 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
     }
   }
   if (len <= 0) {   // (uniform over the workgroup: len belongs to the lattice)
-    if (!is_beta && threadIdx.x == 0) pzx[s] = kLogZero;
+    if (!is_beta && !best_path && threadIdx.x == 0) pzx[s] = kLogZero;
     return;
   }
   float* out = (is_beta ? beta : alpha) + (size_t)s * T * Lpad + j0;
@@ -214,9 +218,16 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
           float n2 = in2 ? cur[in2 ? i2 : 0] : ((is_beta ? i2 == PL : i2 == -1) ? e1 : e2);
           n1 = use1[i] ? n1 : kLogZero;
           n2 = use2[i] ? n2 : kLogZero;
-          float acc = LogAPlusB_fast(n1, cur[i]);                               // :1397,:1399,:1403 / :1533,:1535,:1539
-          if (PL % 2 != 0 || (i & 1)) acc = LogAPlusB_fast(n2, acc);           // :1400 / :1536 (odd positions only: labels)
-          const float v = AddAB_fast(P[u][i], acc);                             // :1397-1405 / :1533-1541
+          float acc, v;
+          if constexpr (best_path) {
+            acc = fmaxf(n1, cur[i]);
+            if (PL % 2 != 0 || (i & 1)) acc = fmaxf(n2, acc);
+            v = acc > kLogZero ? P[u][i] + acc : kLogZero;                      // one addition per step, in path order
+          } else {
+            acc = LogAPlusB_fast(n1, cur[i]);                                   // :1397,:1399,:1403 / :1533,:1535,:1539
+            if (PL % 2 != 0 || (i & 1)) acc = LogAPlusB_fast(n2, acc);         // :1400 / :1536 (odd positions only: labels)
+            v = AddAB_fast(P[u][i], acc);                                       // :1397-1405 / :1533-1541
+          }
           nxt[i] = valid[i] ? v : kLogZero;                                      // :1380-1383 / :1495-1498
         }
 #pragma unroll
@@ -230,7 +241,7 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
 #pragma unroll
       for (int i = 0; i < PL; ++i) P[u][i] = Q[u][i];
   }
-  if (!is_beta) {
+  if constexpr (!is_beta && !best_path) {
     // ln p(z|x) = logadd(alpha[T_s-1][L'_s-1], alpha[T_s-1][L'_s-2])  (ctc-loss.cc:147-153)
 #pragma unroll
     for (int i = 0; i < PL; ++i) last[j0 + i] = cur[i];
@@ -252,6 +263,62 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_beta_kernel(const float* __
   // the sweep direction is a template parameter so that every register-array index in the step is a compile-time constant
   if (blockIdx.y == 1) ctc_sweep<PL, NW, true>(logp, ld, T, S, labx, lens, lablens, alpha, beta, pzx, last, edge);
   else ctc_sweep<PL, NW, false>(logp, ld, T, S, labx, lens, lablens, alpha, beta, pzx, last, edge);
+}
+
+// ---- best-path (Viterbi) alignment: no counterpart in the reference, which aligns through a per-utterance TLG graph and its
+// WFST decoder (asr_egs/wsj/steps/align_ctc_single_utt.sh:67-85).  delta_t(j) = s_t(l'_j) + max(delta_{t-1}(j), delta_{t-1}(j-1),
+// [delta_{t-1}(j-2)]) over the topology of the alpha sweep; grid (S), the delta rows land where alpha rows would.
+template <int PL, int NW>
+__global__ __launch_bounds__(64 * NW) void ctc_best_path_kernel(const float* __restrict__ logp, int ld, int T, int S,
+                                                                const int* __restrict__ labx, const int* __restrict__ lens,
+                                                                const int* __restrict__ lablens, float* __restrict__ delta) {
+  __shared__ float edge[2][NW][2];
+  ctc_sweep<PL, NW, false, true>(logp, ld, T, S, labx, lens, lablens, delta, nullptr, nullptr, nullptr, edge);
+}
+
+// Traceback: the move into (t, j) is re-derived from the stored delta row t-1 with the sweep's own comparisons on the sweep's own
+// floats, so it is the move the sweep took.  Ties go to the smallest move (stay, j-1, j-2), and the final blank L'-1 wins over the
+// last label L'-2.  One workgroup per utterance: lane 0 walks the n dependent steps (the three candidates and the two labels of a
+// step are independent loads), all lanes write -1 into the rows the path does not cover.  An utterance whose best final delta is
+// <= -1e29 (too few frames for its labels, no frames, or a zero-probability frame on every path) has no alignment: score -1e30,
+// every entry -1.
+__global__ __launch_bounds__(64) void ctc_traceback_kernel(const float* __restrict__ delta, int T, int S, int Lpad,
+                                                           const int* __restrict__ labx, const int* __restrict__ lens,
+                                                           const int* __restrict__ lablens, int* __restrict__ ali,
+                                                           int* __restrict__ pos, float* __restrict__ score) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int n = min(lens[s], T), ll = lablens[s];
+  const int* lab = labx + (size_t)s * Lpad;
+  const float* d = delta + (size_t)s * T * Lpad;
+  float best = kLogZero;
+  int j = -1;
+  if (n > 0 && ll >= 2 && ll <= Lpad) {
+    const float a = d[(size_t)(n - 1) * Lpad + ll - 1], b = d[(size_t)(n - 1) * Lpad + ll - 2];
+    best = a >= b ? a : b;
+    j = a >= b ? ll - 1 : ll - 2;
+    if (!(best > -1e29f)) { best = kLogZero; j = -1; }
+  }
+  for (int t = (j < 0 ? 0 : n) + lane; t < T; t += 64) {
+    ali[(size_t)t * S + s] = -1;
+    pos[(size_t)t * S + s] = -1;
+  }
+  if (lane != 0) return;
+  score[s] = best;
+  if (j < 0) return;
+  for (int t = n - 1;; --t) {
+    const int c = lab[j];
+    pos[(size_t)t * S + s] = j;
+    ali[(size_t)t * S + s] = c;
+    if (t == 0) break;
+    const float* row = d + (size_t)(t - 1) * Lpad;
+    const int c2 = lab[max(j - 2, 0)];
+    const float a0 = row[j];
+    const float r1 = row[max(j - 1, 0)], r2 = row[max(j - 2, 0)];
+    const float a1 = j >= 1 ? r1 : kLogZero;
+    const float a2 = (j > 1 && (j & 1) && c2 != c) ? r2 : kLogZero;
+    const int move = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
+    j = max(j - move, 0);   // (a NaN score must not walk off the row)
+  }
 }
 
 // ---- error kernel (:1603-1627) + softmax Jacobian (ctc-loss.cc:160-168): one wavefront per 8 frames of an utterance -----
@@ -455,17 +522,13 @@ int ctc_sweep_waves(int Lpad, int waves) {
   return Lpad <= 256 ? 1 : Lpad == 512 ? 4 : Lpad == 1024 ? 8 : 16;
 }
 
-void ctc_alpha_beta(hipStream_t st, const float* logp, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
-                    const int* lablens, float* alpha, float* beta, float* pzx, int waves) {
-  const int nw = ctc_sweep_waves(Lpad, waves);
-  const int pl = Lpad / (64 * nw);
-  dim3 grid(S, 2), block(64 * nw);
-  bool launched = false;
-#define EESEN_AB(PL, NW)                                                                                                 \
-  if (!launched && pl == PL && nw == NW) {                                                                               \
-    hipLaunchKernelGGL((ctc_alpha_beta_kernel<PL, NW>), grid, block, 0, st, logp, ld, T, S, labx, lens, lablens, alpha, \
-                       beta, pzx);                                                                                       \
-    launched = true;                                                                                                     \
+// calls f(PL, NW) as compile-time constants for the instantiated (positions per lane, waves) pair; false where there is none
+template <class F>
+static bool with_sweep_shape(int pl, int nw, F&& f) {
+#define EESEN_AB(PL, NW)                                                              \
+  if (pl == PL && nw == NW) {                                                         \
+    f(std::integral_constant<int, PL>(), std::integral_constant<int, NW>());          \
+    return true;                                                                      \
   }
   EESEN_AB(1, 1) EESEN_AB(2, 1) EESEN_AB(4, 1) EESEN_AB(8, 1) EESEN_AB(16, 1)          // <= 1024 positions, one wave
   EESEN_AB(2, 2)                                                                       // 256 positions as 2 waves
@@ -474,8 +537,38 @@ void ctc_alpha_beta(hipStream_t st, const float* logp, int ld, int T, int S, int
   EESEN_AB(16, 2) EESEN_AB(8, 4) EESEN_AB(4, 8) EESEN_AB(2, 16)                        // 2048 positions
   EESEN_AB(16, 4) EESEN_AB(8, 8) EESEN_AB(4, 16)                                       // 4096 positions
 #undef EESEN_AB
+  return false;
+}
+
+void ctc_alpha_beta(hipStream_t st, const float* logp, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
+                    const int* lablens, float* alpha, float* beta, float* pzx, int waves) {
+  const int nw = ctc_sweep_waves(Lpad, waves);
+  const int pl = Lpad / (64 * nw);
+  dim3 grid(S, 2), block(64 * nw);
+  const bool launched = with_sweep_shape(pl, nw, [&](auto PL, auto NW) {
+    hipLaunchKernelGGL((ctc_alpha_beta_kernel<decltype(PL)::value, decltype(NW)::value>), grid, block, 0, st, logp, ld, T, S, labx, lens, lablens,
+                       alpha, beta, pzx);
+  });
   if (!launched) throw Error(EESEN_ERR_INVALID, "ctc: no lattice kernel for this padded label length / wave count (at most 4096 positions)");
   check_launch("ctc_alpha_beta");
+}
+
+void ctc_best_path(hipStream_t st, const float* logp, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
+                   const int* lablens, float* delta, int waves) {
+  const int nw = ctc_sweep_waves(Lpad, waves);
+  const int pl = Lpad / (64 * nw);
+  const bool launched = with_sweep_shape(pl, nw, [&](auto PL, auto NW) {
+    hipLaunchKernelGGL((ctc_best_path_kernel<decltype(PL)::value, decltype(NW)::value>), dim3(S), dim3(64 * nw), 0, st, logp, ld, T, S, labx, lens,
+                       lablens, delta);
+  });
+  if (!launched) throw Error(EESEN_ERR_INVALID, "ctc: no lattice kernel for this padded label length / wave count (at most 4096 positions)");
+  check_launch("ctc_best_path");
+}
+
+void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, const int* labx, const int* lens, const int* lablens,
+                   int* ali, int* pos, float* score) {
+  hipLaunchKernelGGL(ctc_traceback_kernel, dim3(S), dim3(64), 0, st, delta, T, S, Lpad, labx, lens, lablens, ali, pos, score);
+  check_launch("ctc_traceback");
 }
 
 void ctc_error_diff(hipStream_t st, const float* probs, int ld, int T, int S, int K, int Lpad, int Lmax, const int* lens,

@@ -55,12 +55,9 @@ static void check_batch(const int* frame_num_utt, int S, int rows, int K, const 
     EESEN_REQUIRE(label_ids[i] >= 0 && label_ids[i] < K, EESEN_ERR_INVALID, "label id outside [0, K)");
 }
 
-void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld, const int* label_ids,
-                        const int* label_off, float* diff, int ldd, float* pzx_host) {
-  check_batch(frame_num_utt, S, rows, K, label_ids, label_off);
-  EESEN_REQUIRE(ld >= K && ldd >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
-  EESEN_HIP_CHECK(hipSetDevice(device));
-  const int T = rows / S;
+// Label expansion (ctc-loss.cc:116-129) with the sequence and expanded-label lengths, uploaded in stream order; the device
+// pointers stay valid until the next call.
+Ctc::Lattices Ctc::upload_lattices(const int* frame_num_utt, int S, const int* label_ids, const int* label_off) {
   int maxU = 0;
   for (int s = 0; s < S; ++s) {
     const int U = label_off[s + 1] - label_off[s];
@@ -99,9 +96,20 @@ void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, i
   std::copy(h.begin(), h.end(), pinned);
   EESEN_HIP_CHECK(hipMemcpyAsync(labx.p, pinned, h.size() * sizeof(int), hipMemcpyHostToDevice, st));
   sp.used(st);
-  const int* labx_d = labx.p;
-  const int* lens_dd = labx_d + n_labx;
-  const int* ll_d = lens_dd + S;
+  return Lattices{labx.p, labx.p + n_labx, labx.p + n_labx + S, Lpad, Lprime};
+}
+
+void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld, const int* label_ids,
+                        const int* label_off, float* diff, int ldd, float* pzx_host) {
+  check_batch(frame_num_utt, S, rows, K, label_ids, label_off);
+  EESEN_REQUIRE(ld >= K && ldd >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  const int T = rows / S;
+  const Lattices lat = upload_lattices(frame_num_utt, S, label_ids, label_off);
+  const int Lpad = lat.Lpad, Lprime = lat.Lprime;
+  const int* labx_d = lat.labx;
+  const int* lens_dd = lat.lens;
+  const int* ll_d = lat.lablens;
 
   if (logp.cap < (size_t)rows * K || alpha.cap < (size_t)S * T * Lpad || pzx_d.cap < (size_t)S) EESEN_HIP_CHECK(hipStreamSynchronize(st));
   logp.reserve((size_t)rows * K);
@@ -149,6 +157,61 @@ void Ctc::phase_times(float* out3) {
   for (int i = 0; i < 3; ++i) {
     float ms = 0.f;
     EESEN_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+    out3[i] = ms * 1e-3f;
+  }
+}
+
+// Best-path alignment of every utterance against its labels.  The delta rows borrow `alpha`, the logarithms `logp`; the statistics
+// and the accessors of the last EvalParallel (last_*) are left alone.
+void Ctc::align_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* label_ids,
+                         const int* label_off, int* ali_host, int* pos_host, float* score_host) {
+  check_batch(frame_num_utt, S, rows, K, label_ids, label_off);
+  EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  const int T = rows / S;
+  const Lattices lat = upload_lattices(frame_num_utt, S, label_ids, label_off);
+  const size_t n_out = 2 * (size_t)rows + S;   // class ids, positions, scores
+  if ((!is_log && logp.cap < (size_t)rows * K) || alpha.cap < (size_t)S * T * lat.Lpad || ali_d.cap < n_out) EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  if (!is_log) logp.reserve((size_t)rows * K);
+  alpha.reserve((size_t)S * T * lat.Lpad);
+  ali_d.reserve(n_out);
+  int* ali_dev = ali_d.p;
+  int* pos_dev = ali_dev + rows;
+  float* score_dev = reinterpret_cast<float*>(pos_dev + rows);
+
+  const bool acc = align_timer.enabled();
+  int sp0 = -1, sp1 = -1, sp2 = -1;
+  if (acc) sp0 = align_timer.begin(st, 0); else aev[0].record(st);
+  if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
+  if (acc) { align_timer.end(st, sp0); sp1 = align_timer.begin(st, 1); } else aev[1].record(st);
+  ctc_best_path(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, lat.Lpad, lat.labx, lat.lens, lat.lablens, alpha.p, sweep_waves);
+  if (acc) { align_timer.end(st, sp1); sp2 = align_timer.begin(st, 2); } else aev[2].record(st);
+  ctc_traceback(st, alpha.p, T, S, lat.Lpad, lat.labx, lat.lens, lat.lablens, ali_dev, pos_dev, score_dev);
+  if (acc) align_timer.end(st, sp2); else aev[3].record(st);
+
+  // results and the guard word's value when they were computed, through one pinned slot
+  int* out = static_cast<int*>(loss_slot(align_pin, (n_out + 1) * sizeof(int)));
+  EESEN_HIP_CHECK(hipMemcpyAsync(out, ali_dev, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
+  out[n_out] = 0;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_out, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  align_pin.used(st);
+  align_pin.wait();
+  // computed from a timed-out forward pass (guard word set): no alignment -- NaN and -1, never garbage with status OK
+  const bool bad = out[n_out] != 0;
+  for (int r = 0; r < rows; ++r) {
+    ali_host[r] = bad ? -1 : out[r];
+    if (pos_host) pos_host[r] = bad ? -1 : out[rows + r];
+  }
+  const float* sc = reinterpret_cast<const float*>(out + 2 * (size_t)rows);
+  for (int s = 0; s < S; ++s) score_host[s] = bad ? std::numeric_limits<float>::quiet_NaN() : sc[s];
+}
+
+void Ctc::align_times(float* out3) {
+  if (align_timer.enabled()) { align_timer.collect(out3, 3); return; }
+  aev[3].wait();
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.f;
+    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, aev[i], aev[i + 1]));
     out3[i] = ms * 1e-3f;
   }
 }

@@ -209,6 +209,15 @@ void log_rows(hipStream_t st, const float* in, int ldi, float* out, int ldo, int
 void ctc_alpha_beta(hipStream_t st, const float* logp, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
                     const int* lablens, float* alpha, float* beta, float* pzx, int waves = 0);
 int ctc_sweep_waves(int Lpad, int waves = 0);
+// Best-path (Viterbi) alignment over the same lattices.  ctc_best_path: the alpha sweep in the max-plus semiring, S workgroups; the
+// delta rows are written in alpha's layout [S][T][Lpad] (rows t >= lens[s] are not written).  scores: [T*S x K] (ld) log-domain.
+void ctc_best_path(hipStream_t st, const float* scores, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
+                   const int* lablens, float* delta, int waves = 0);
+// ctc_traceback: from argmax(delta[n-1][L'-1], delta[n-1][L'-2]) (the final blank wins a tie) back to t = 0, the smallest move winning
+// among equal predecessors.  ali / pos [T*S] (row t*S + s): class id / lattice position per frame, -1 on rows t >= lens[s] and on
+// every row of an utterance without a feasible path; score [S]: the path's log-score, -1e30 without one.
+void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, const int* labx, const int* lens, const int* lablens,
+                   int* ali, int* pos, float* score);
 // diff[t*S+s][k] = y*rowsum(e) - gamma ... (error kernel + softmax Jacobian, ctc-loss.cc:156-168)
 // labx [S x Lpad]: the expanded labels (blank 0 at even positions), lablens [S] = 2 U_s + 1
 void ctc_error_diff(hipStream_t st, const float* probs, int ld, int T, int S, int K, int Lpad, int Lmax, const int* lens,

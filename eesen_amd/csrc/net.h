@@ -253,7 +253,7 @@ struct Ctc {
   int device = 0;
   hipStream_t st = nullptr;
   DevBuf<float> logp, alpha, beta, pzx_d;
-  DevBuf<int> labx, ids_d;
+  DevBuf<int> labx, ids_d, ali_d;   // ali_d: class ids [rows], lattice positions [rows], then the scores [S] of align_parallel
   std::vector<int> last_lens;
   int last_T = 0, last_S = 0, last_Lpad = 0, last_Lprime = 0;
   int sweep_waves = 0;   // EESEN_CTC_WAVES when this object was created (tuning.h): 0 = the default number of waves per lattice
@@ -261,6 +261,9 @@ struct Ctc {
   long sequences = 0, frames = 0, err_tokens = 0, ref_tokens = 0;
   DevEvent ev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};   // phase_times without the timer
   PhaseTimer timer;  // eesen_ctc_set_profiling(2): spans accumulate over many calls, read once (no per-call synchronisation)
+  DevEvent aev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};  // align_times without the timer
+  PhaseTimer align_timer;      // the same for align_parallel (phases: log, sweep, traceback)
+  PinBuf align_pin;            // results of align_parallel (D2H)
   // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
   // back through PinBufs that are folded into the statistics at the next call that needs them ("deferred").
@@ -283,6 +286,13 @@ struct Ctc {
                        const int* label_ids, const int* label_off, int* num_err, int* num_ref);
   void get_alpha_beta(float* alpha_host, float* beta_host, int* Lprime);
   void phase_times(float* out3);
+  // Best-path alignment (ctc_best_path + ctc_traceback in ctc.hip); touches neither the objective nor the error statistics.
+  void align_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* label_ids,
+                      const int* label_off, int* ali_host, int* pos_host, float* score_host);
+  void align_times(float* out3);
+ private:
+  struct Lattices { const int *labx, *lens, *lablens; int Lpad, Lprime; };
+  Lattices upload_lattices(const int* frame_num_utt, int S, const int* label_ids, const int* label_off);
 };
 
 // eesen::CE (src/net/ce-loss.h:32-77): frame-level cross-entropy (ce_host.cpp, ce.hip).  As with the Ctc nothing in a training

@@ -332,4 +332,35 @@ class MatrixWriter {
   bool text_ = false;
 };
 
+// Int32VectorWriter to `ark:file` (binary) or `ark,t:file` (text): what read_int_vector above and the trainers' target readers take
+class IntVectorWriter {
+ public:
+  explicit IntVectorWriter(const std::string& wspecifier) {
+    const Spec sp = parse_spec(wspecifier);
+    if (sp.kind != "ark") throw std::runtime_error("only ark: output is supported");
+    text_ = wspecifier.substr(0, wspecifier.find(':')).find(",t") != std::string::npos;
+    out_.reset(new OutStream(sp.path));
+  }
+  void Write(const std::string& key, const int32_t* v, int n, int stride = 1) {
+    std::ostream& f_ = out_->get();
+    f_ << key << ' ';
+    if (text_) {
+      for (int i = 0; i < n; ++i) f_ << v[(size_t)i * stride] << ' ';
+      f_ << '\n';
+    } else {
+      const char four = 4;
+      const int32_t size = n;
+      f_.write("\0B", 2);
+      f_.write(&four, 1);
+      f_.write(reinterpret_cast<const char*>(&size), 4);
+      for (int i = 0; i < n; ++i) { f_.write(&four, 1); f_.write(reinterpret_cast<const char*>(v + (size_t)i * stride), 4); }
+    }
+    f_.flush();
+    if (!f_) throw std::runtime_error("write error");
+  }
+ private:
+  std::unique_ptr<OutStream> out_;
+  bool text_ = false;
+};
+
 }  // namespace ktab

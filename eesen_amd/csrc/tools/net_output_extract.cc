@@ -5,7 +5,6 @@
 // --num-sequence utterances padded together (an extension: padding is masked in both directions, so valid frames do not
 // change by a bit).
 #include <algorithm>
-#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <iostream>
@@ -14,6 +13,7 @@
 #include "../../../include/eesen_hip.h"
 #include "kaldi_tables.h"
 #include "feat_pipeline.h"
+#include "class_prior.h"
 #include "parse_options.h"
 
 namespace {
@@ -22,27 +22,6 @@ using namespace ktab;
 void ck(int rc) {
   if (rc != EESEN_OK) throw std::runtime_error(eesen_last_error());
 }
-// ClassPrior::ClassPrior (class-prior.cc:30-77): counts -> floor -> blank scaling -> normalise -> log, with FLT_MAX/2 added
-// for the classes below the cutoff so that they get zero likelihood
-std::vector<float> class_log_priors(const std::string& path, double prior_cutoff, double blank_scale) {
-  std::ifstream f(path);
-  if (!f) throw std::runtime_error("cannot open " + path);
-  std::string txt((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-  for (char& c : txt) if (c == '[' || c == ']') c = ' ';
-  std::istringstream ss(txt);
-  std::vector<double> pri;
-  for (double v; ss >> v;) pri.push_back(v);
-  std::vector<float> mask(pri.size(), 0.f);
-  for (size_t i = 0; i < pri.size(); ++i)
-    if (pri[i] < prior_cutoff) { pri[i] = prior_cutoff; mask[i] = FLT_MAX / 2; }
-  if (blank_scale != 1.0 && !pri.empty()) pri[0] *= blank_scale;
-  double sum = 0;
-  for (double v : pri) sum += v;
-  std::vector<float> out(pri.size());
-  for (size_t i = 0; i < pri.size(); ++i) out[i] = (float)std::log(pri[i] / sum) + mask[i];
-  return out;
-}
-
 }  // namespace
 
 int main(int argc, char** argv) {

@@ -314,6 +314,33 @@ int eesen_ctc_get_alpha_beta(eesen_ctc_t* ctc, float* alpha_host, float* beta_ho
  * multi-step region needs no host synchronisation per step (0 = back to last-call timing). */
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode);
 int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3);
+/* Best-path (Viterbi) alignment of every utterance against its labels: which lattice position, hence which class, each frame
+ * belongs to on the single most likely path.  The reference has no such call: it aligns one utterance at a time through a TLG
+ * graph and the WFST decoder (asr_egs/wsj/steps/align_ctc_single_utt.sh:67-85).  Arguments as eesen_ctc_eval_parallel;
+ * scores_dev [T*S x K] (device, ld >= K) holds posteriors (is_log == 0: the call takes the logarithm itself) or log-domain scores
+ * (is_log != 0: e.g. what eesen_op_log_sub_prior left, prior-scaled log-likelihoods).  With l' the labels interleaved with blanks
+ * (L' = 2U+1 positions, blank = 0) and s_t(k) the log-score of class k at frame t:
+ *   delta_0(0) = s_0(l'_0), delta_0(1) = s_0(l'_1), delta_0(j >= 2) = -1e30
+ *   delta_t(j) = s_t(l'_j) + max(delta_{t-1}(j), delta_{t-1}(j-1), [delta_{t-1}(j-2) iff j odd and l'_j != l'_{j-2}])
+ *   j_end = argmax(delta_{n-1}(L'-1), delta_{n-1}(L'-2)), score = delta_{n-1}(j_end), traced back to t = 0.
+ * Tie rule (part of the interface): among equal predecessors the smallest move wins -- stay, then j-1, then j-2 -- and at the end
+ * the final blank L'-1 wins over L'-2.  The additions run in path order in fp32, so two paths that emit the same classes have
+ * bit-identical scores and the rule decides between them.
+ * Host outputs: ali_host [rows] the class id l'_{j_t} at row t*S + s (the row order of the scores and of eesen_ce_eval_parallel's
+ * targets), pos_host [rows] (may be NULL) the lattice position j_t, score_host [S].  Rows t >= frame_num_utt[s] read -1.
+ * An utterance without a feasible path -- fewer frames than labels + adjacent repeats, no frames, best final delta <= -1e29 --
+ * is a result, not an error: score -1e30 and -1 in every row; the other utterances are not affected.  The shortest feasible
+ * length (labels + adjacent repeats frames: one path, ending on the last label) is an ordinary case.
+ * Restrictions as eesen_ctc_eval_parallel (EESEN_ERR_INVALID): >= 1 label per utterance, L' <= 4096, labels in [0, K), ld >= K.
+ * The objective / error statistics are not touched; the lattice buffers of the last eesen_ctc_eval_parallel are borrowed
+ * (eesen_ctc_get_alpha_beta afterwards reads this call's delta rows).  With a guard (eesen_ctc_set_guard) a minibatch computed
+ * while the Net's recurrence error word was set returns score = NaN and ali = pos = -1.  The call waits for its results. */
+int eesen_ctc_align_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                             int is_log, const int* label_ids, const int* label_off,
+                             int* ali_host /*rows*/, int* pos_host /*rows or NULL*/, float* score_host /*S*/);
+/* seconds of the last eesen_ctc_align_parallel's device work: out[0]=log (is_log == 0), [1]=max-plus sweep, [2]=traceback;
+ * summed over all calls since the last read under eesen_ctc_set_profiling(ctc, 2). */
+int eesen_ctc_get_align_times(eesen_ctc_t* ctc, float* out3);
 
 /* ---- CE (src/net/ce-loss.h:32-77): frame-level cross-entropy ----------------------------------- */
 int eesen_ce_create(int device, void* stream, eesen_ce_t** out);

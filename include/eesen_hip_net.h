@@ -264,6 +264,21 @@ class Ctc {
     HipCheck(eesen_ctc_error_rate_mseq(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
                                        ids_.data(), off_.data(), NULL, NULL));
   }
+  /* Best-path (Viterbi) alignment, eesen_ctc_align_parallel: no counterpart in src/net (the reference aligns through a TLG graph and
+   * its decoder, align_ctc_single_utt.sh:67-85).  net_out: posteriors, or log-domain scores with is_log.  ali / pos (pos may be NULL):
+   * class id / lattice position of row t*S + s, -1 beyond an utterance's length; score: the path's log-score per utterance, -1e30 (and
+   * -1 in every row) where no path exists.  Ties: the smallest move wins, the final blank wins over the last label. */
+  void AlignParallel(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out, std::vector<std::vector<int32> >& label,
+                     std::vector<int32>* ali, std::vector<int32>* pos, std::vector<BaseFloat>* score, bool is_log = false) {
+    const int S = (int)frame_num_utt.size();
+    Csr(label, S);
+    if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
+    ali->resize(net_out.NumRows());
+    if (pos) pos->resize(net_out.NumRows());
+    score->resize(S);
+    HipCheck(eesen_ctc_align_parallel(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                      is_log ? 1 : 0, ids_.data(), off_.data(), ali->data(), pos ? pos->data() : NULL, score->data()));
+  }
   void SetReportStep(int32 s) { report_step_ = s; }
   void SetFramesPerSec(float f) { frames_per_sec_ = f; }
   float NumErrorTokens() const { long e = 0; HipCheck(eesen_ctc_stats(h_, NULL, NULL, NULL, &e, NULL)); return (float)e; }   /* ctc-loss.h:62 */
