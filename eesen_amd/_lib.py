@@ -91,6 +91,10 @@ SIGNATURES = {
     "eesen_ctc_get_phase_times": (_i, [_vp, _vp]),
     "eesen_ctc_align_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "eesen_ctc_get_align_times": (_i, [_vp, _vp]),
+    "eesen_ctc_decode_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "eesen_ctc_get_decode_times": (_i, [_vp, _vp]),
+    "eesen_edit_distance": (_i, [_vp, _i, _vp, _i, _vp]),
+    "eesen_ctc_get_decode_candidates": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "eesen_ce_destroy": (_i, [_vp]),
     "eesen_ce_eval_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -530,6 +530,40 @@ class Ctc:
         check(self.lib.eesen_ctc_get_align_times(self.h, _np_ptr(out)))
         return dict(zip(["log", "sweep", "traceback"], out.tolist()))
 
+    def DecodeParallel(self, frame_num_utt: Sequence[int], net_out: CuMatrix, beam: int = 16, max_classes: int = 20, nbest: int = 1,
+                       is_log: bool = False):
+        """Lexicon-free CTC prefix beam search (eesen_ctc_decode_parallel; no counterpart in the reference's src/net).  net_out: posteriors,
+        or log-domain scores with is_log=True.  Returns (hyps, scores): hyps[s] is the list of the utterance's returned labellings, best
+        first, each a list of ints (at most nbest; none where the beam died); scores [S, nbest] float32, -1e30 beyond the returned
+        count (NaN under a raised guard word).  Statistics untouched."""
+        fn = np.ascontiguousarray(frame_num_utt, np.int32)
+        S = fn.size
+        T = net_out.rows // max(S, 1)
+        hyp = np.empty((S, int(nbest), max(T, 0)), np.int32)
+        hlen = np.empty((S, int(nbest)), np.int32)
+        score = np.empty((S, int(nbest)), np.float32)
+        check(self.lib.eesen_ctc_decode_parallel(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
+                                                 int(bool(is_log)), int(beam), int(max_classes), int(nbest), _np_ptr(hyp), _np_ptr(hlen),
+                                                 _np_ptr(score)))
+        self.hyp, self.hyp_len = hyp, hlen          # the raw [S, nbest, T] labels (-1 beyond each length) and [S, nbest] lengths
+        hyps = [[hyp[s, i, :hlen[s, i]].tolist() for i in range(int(nbest)) if hlen[s, i] >= 0] for s in range(S)]
+        return hyps, score
+
+    def DecodeTimes(self) -> dict:
+        out = np.zeros(3, np.float32)
+        check(self.lib.eesen_ctc_get_decode_times(self.h, _np_ptr(out)))
+        return dict(zip(["topc", "beam", "hyp"], out.tolist()))
+
+    def DecodeCandidates(self, rows: int, max_classes: int):
+        """The candidate classes the last DecodeParallel selected (tests): (ids [rows, C'], scores [rows, C'], blank [rows])."""
+        n = C.c_int(0)
+        check(self.lib.eesen_ctc_get_decode_candidates(self.h, None, None, None, C.byref(n)))
+        ids = np.empty((rows, n.value), np.int32)
+        sc = np.empty((rows, n.value), np.float32)
+        bl = np.empty(rows, np.float32)
+        check(self.lib.eesen_ctc_get_decode_candidates(self.h, _np_ptr(ids), _np_ptr(sc), _np_ptr(bl), None))
+        return ids, sc, bl
+
     def ErrorRateMSeq(self, frame_num_utt: Sequence[int], net_out: CuMatrix, label: Sequence[Sequence[int]], deferred: bool = False):
         """Ctc::ErrorRateMSeq (ctc-loss.cc:235-298): accumulates the error / reference token counts.  Returns this call's
         (errors, refs); with deferred=True only the argmax and the copy of the ids are enqueued and the host part (collapse +

@@ -14,13 +14,13 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_DIR, "csrc")
 LIBDIR = os.path.join(_DIR, "lib")
 LIB = os.path.join(LIBDIR, "libeesen_hip.so")
-SOURCES = ["gemm.hip", "lstm.hip", "lstm_persistent.hip", "rec_plan.cpp", "ctc.hip", "ce.hip", "optim.hip", "feeder.hip", "net.cpp", "ctc_host.cpp", "ce_host.cpp", "nnet_format.cpp", "capi.cpp", "comm.cpp"]
+SOURCES = ["gemm.hip", "lstm.hip", "lstm_persistent.hip", "rec_plan.cpp", "ctc.hip", "ctc_decode.hip", "ce.hip", "optim.hip", "feeder.hip", "net.cpp", "ctc_host.cpp", "ce_host.cpp", "nnet_format.cpp", "capi.cpp", "comm.cpp"]
 HEADERS = ["common.h", "guard.h", "kernels.h", "rec_kernels.h", "net.h", "handles.h", "tuning.h", os.path.join("..", "..", "include", "eesen_hip.h")]
 FLAGS = (os.environ.get("EESEN_BUILD_DEFS", "").split()) + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 
 
 BINDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin")
-TOOLS = {"train-ctc-parallel": "train_ctc_parallel.cc", "train-ce-parallel": "train_ce_parallel.cc", "net-output-extract": "net_output_extract.cc", "ctc-align": "ctc_align.cc"}
+TOOLS = {"train-ctc-parallel": "train_ctc_parallel.cc", "train-ce-parallel": "train_ce_parallel.cc", "net-output-extract": "net_output_extract.cc", "ctc-align": "ctc_align.cc", "ctc-decode": "ctc_decode.cc"}
 
 
 def csrc_digest() -> str:

@@ -255,6 +255,26 @@ int eesen_ctc_align_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, 
 int eesen_ctc_get_align_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->align_times(out3); });
 }
+int eesen_ctc_decode_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                              int is_log, int beam, int max_classes, int nbest, int* hyp_host, int* hyp_len_host, float* score_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev); REQ_PTR(hyp_host); REQ_PTR(hyp_len_host); REQ_PTR(score_host);
+    ctc->decode_parallel(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, beam, max_classes, nbest, hyp_host, hyp_len_host, score_host);
+  });
+}
+int eesen_ctc_get_decode_times(eesen_ctc_t* ctc, float* out3) {
+  return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->decode_times(out3); });
+}
+int eesen_ctc_get_decode_candidates(eesen_ctc_t* ctc, int* ids_host, float* scores_host, float* blank_host, int* num_classes) {
+  return guard([&] { REQ_PTR(ctc); ctc->get_decode_candidates(ids_host, scores_host, blank_host, num_classes); });
+}
+int eesen_edit_distance(const int* ref, int num_ref, const int* hyp, int num_hyp, int* errors) {
+  return guard([&] {
+    REQ_PTR(errors);
+    if (num_ref < 0 || num_hyp < 0 || (num_ref > 0 && !ref) || (num_hyp > 0 && !hyp)) throw Error(EESEN_ERR_INVALID, "edit distance: bad sequence");
+    *errors = edit_distance(ref, num_ref, hyp, num_hyp);
+  });
+}
 int eesen_ctc_error_rate_mseq(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* net_out_dev, int rows, int K,
                               int ld, const int* label_ids, const int* label_off, int* num_err, int* num_ref) {
   return guard([&] {
@@ -295,7 +315,8 @@ int eesen_ctc_dropped(eesen_ctc_t* ctc, long* minibatches) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(minibatches); ctc->flush(); *minibatches = ctc->guard.dropped; });
 }
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode) {
-  return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); ctc->align_timer.enable(mode == 2); ctc->align_timer.set_accumulate(mode == 2); });
+  return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); ctc->align_timer.enable(mode == 2); ctc->align_timer.set_accumulate(mode == 2);
+                     ctc->decode_timer.enable(mode == 2); ctc->decode_timer.set_accumulate(mode == 2); });
 }
 int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->phase_times(out3); });

@@ -1,0 +1,346 @@
+// ctc_decode.hip -- lexicon-free CTC prefix beam search over a padded utterance batch, for gfx950.
+//
+// No counterpart in the reference, which decodes one utterance per process through a TLG graph and its WFST decoder.  The
+// computation is stated in INTEGRATION.md "Decoding" and restated in numpy in tests/ctc_beam_restatement.py.  Three launches per
+// minibatch, none per frame:
+//   ctc_row_topc_kernel     one wavefront per row: the C' best non-blank classes (ascending id), their scores, the blank's score
+//   ctc_prefix_beam_kernel  one workgroup per utterance walks its n frames: beam state and the frame's candidate keys in LDS, the trie
+//                           of surviving prefixes written (never read) to global memory
+//   ctc_hyp_kernel          one lane per (utterance, rank) walks the trie to the root
+// Every log-mass is an fp32 value in [-1e30, +inf): sums are clamped from below at the library's finite sentinel, so the sweep's
+// branch-free log-add (ctc.hip: LogAPlusB_fast) is exact on the special cases here too.
+#include "kernels.h"
+
+namespace eesen {
+namespace {
+
+constexpr float kLogZero = -1e30f, kDead = -1e29f;
+constexpr int kMaxBeam = 64, kMaxCls = 64, kMaxKeys = 4096;
+constexpr unsigned long long kDeadKey = ~0ull;
+
+// A prefix is known by a 64-bit fingerprint of its labels and its length: h(p + c) = h(p) * M + (c + 1) mod 2^64, M odd, so the
+// parent's fingerprint is (h - (c + 1)) * M^-1 -- the merge test needs neither the sequences nor the trie.
+constexpr unsigned long long kHashMul = 0x9E3779B97F4A7C15ull;
+constexpr unsigned long long inv_mod_2_64(unsigned long long a) {
+  unsigned long long x = a;   // Newton: 3 correct bits double five times over
+  for (int i = 0; i < 6; ++i) x *= 2 - a * x;
+  return x;
+}
+constexpr unsigned long long kHashMulInv = inv_mod_2_64(kHashMul);
+static_assert(kHashMul * kHashMulInv == 1ull, "inverse of the fingerprint multiplier");
+
+__device__ __forceinline__ float clamp_score(float v) { return fmaxf(v, kLogZero); }   // (a NaN becomes the sentinel too)
+__device__ __forceinline__ float log_add(float a, float b) {
+  const float m = fmaxf(a, b), n = fminf(a, b);
+  return m + __logf(1.f + __expf(n - m));
+}
+__device__ __forceinline__ float score_add(float a, float b) { return fmaxf(a + b, kLogZero); }
+// order-preserving map of a float onto an unsigned: a < b  <=>  ord(a) < ord(b)
+__device__ __forceinline__ unsigned ord(float v) {
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// selection key: smaller is better -- the total descending, then the tie-rule index ascending
+__device__ __forceinline__ unsigned long long make_key(float total, unsigned idx) {
+  return ((unsigned long long)(~ord(total)) << 32) | idx;
+}
+
+// ---- candidate classes of every frame ------------------------------------------------------------------------------------------
+// The C'-th largest key among classes 1 .. K-1 by bisection on the 32 key bits (a count per bit), then one pass in class order that
+// keeps what lies above it and the first `need` classes that equal it: ties go to the smaller id and the output is in ascending id
+// order by construction.  REG: K <= 256, the row's keys stay in four registers per lane; otherwise the row is re-read per pass (it
+// stays in L1/L2: at most 80 KB).
+template <bool REG>
+__global__ __launch_bounds__(256) void ctc_row_topc_kernel(const float* __restrict__ sc, int ld, int rows, int K, int S,
+                                                           const int* __restrict__ lens, int Cc, int* __restrict__ cid,
+                                                           float* __restrict__ csc, float* __restrict__ sblank) {
+  constexpr int VPL = 4;
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  if (r / S >= lens[r % S]) return;   // a frame beyond its utterance: never read
+  const float* row = sc + (size_t)r * ld;
+  // key of class k; 0 (below every clamped value's key) for the blank and beyond the row
+  auto key_of = [&](int k) -> unsigned { return (k >= 1 && k < K) ? ord(clamp_score(row[k])) : 0u; };
+  unsigned u[VPL];
+  if constexpr (REG) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) u[i] = key_of(lane + 64 * i);
+  }
+  auto count = [&](auto pred) -> int {   // classes whose key satisfies pred (wave-uniform)
+    int c = 0;
+    if constexpr (REG) {
+#pragma unroll
+      for (int i = 0; i < VPL; ++i) c += __popcll(__ballot(pred(u[i])));
+    } else {
+      for (int base = 0; base < K; base += 64) c += __popcll(__ballot(pred(key_of(base + lane))));
+    }
+    return c;
+  };
+  unsigned tau = 0;
+  for (int bit = 31; bit >= 0; --bit) {
+    const unsigned cand = tau | (1u << bit);
+    if (count([&](unsigned k) { return k >= cand; }) >= Cc) tau = cand;
+  }
+  const int need = Cc - count([&](unsigned k) { return k > tau; });   // >= 1 of the classes that equal the threshold
+  const unsigned long long below = (1ull << lane) - 1;
+  int n_out = 0, n_eq = 0;
+  int* ids = cid + (size_t)r * Cc;
+  float* vals = csc + (size_t)r * Cc;
+  auto emit = [&](int k, unsigned key) {
+    const bool eq = key == tau;
+    const unsigned long long eqm = __ballot(eq);
+    const bool take = key > tau || (eq && n_eq + __popcll(eqm & below) < need);
+    const unsigned long long tm = __ballot(take);
+    const int at = n_out + __popcll(tm & below);
+    if (take && at < Cc) { ids[at] = k; vals[at] = clamp_score(row[k]); }
+    n_eq += __popcll(eqm);
+    n_out += __popcll(tm);
+  };
+  if constexpr (REG) {
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) emit(lane + 64 * i, u[i]);
+  } else {
+    for (int base = 0; base < K; base += 64) emit(base + lane, key_of(base + lane));
+  }
+  if (lane == 0) sblank[r] = clamp_score(row[0]);
+}
+
+// ---- the beam ------------------------------------------------------------------------------------------------------------------
+struct BeamState {
+  float lb[kMaxBeam], lnb[kMaxBeam];   // log-mass ending in blank / in the last label
+  float se[kMaxBeam];                  // this frame's score of the entry's own last label
+  int node[kMaxBeam], last[kMaxBeam], len[kMaxBeam];   // trie node, last label (-1: the empty prefix), length
+  unsigned long long hash[kMaxBeam];   // fingerprint of the labels
+};
+
+// Between two sort stages whose strides are both <= 64 a wave re-reads only what it wrote itself (pair q of a stage touches the
+// 128-element block q / 64, and a wave keeps its pairs from stage to stage): LDS operations of one wave execute in order, so
+// only the compiler's schedule has to be pinned.
+__device__ __forceinline__ void sort_sync(bool wave_local) {
+  if (wave_local) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    __syncthreads();
+  }
+}
+
+// Grid (S), 64 .. 512 threads.  Frame t of an utterance, between workgroup barriers:
+//   1  entry q < nb: its stay candidate; the extension that spells q (found by fingerprint) is log-added into it and marked merged
+//   2  the nb * C' extensions write their keys behind the stays; the key array is padded with dead keys to a power of two
+//   3  bitonic sort of the keys (workgroup barriers only around strides >= 128)
+//   4  rank r < B takes key r: a stay copies its entry, an extension becomes trie node 1 + t * B + r
+// The next frame's candidates and the scores of the labels an entry can end in next (its own last label or one of this frame's
+// candidates) are fetched at the top of the frame and land in LDS just before step 4, off the dependent chain.
+__global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __restrict__ sc, int ld, int T, int S,
+                                                              const int* __restrict__ lens, int B, int Cc,
+                                                              const int* __restrict__ cid_g, const float* __restrict__ csc_g,
+                                                              const float* __restrict__ sblank_g, int* __restrict__ tparent,
+                                                              int* __restrict__ tlabel, int* __restrict__ fnode,
+                                                              int* __restrict__ flen, float* __restrict__ fscore,
+                                                              int* __restrict__ count) {
+  __shared__ unsigned long long keys[kMaxKeys];
+  __shared__ BeamState st[2];
+  __shared__ float stay_lb[kMaxBeam], stay_lnb[kMaxBeam], nx_stay[kMaxBeam], nx_ext[kMaxCls];
+  __shared__ int c_id[2][kMaxCls];
+  __shared__ float c_sc[2][kMaxCls], c_bl[2];
+  __shared__ unsigned long long merged[kMaxBeam];   // per entry: which of its extensions went into another entry's stay
+  __shared__ int nb_sh;
+  const int s = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+  const int n = min(lens[s], T);
+  const size_t cap = 1 + (size_t)T * B;
+  int* tp = tparent + (size_t)s * cap;
+  int* tl = tlabel + (size_t)s * cap;
+  if (tid == 0) {
+    st[0].lb[0] = 0.f; st[0].lnb[0] = kLogZero; st[0].se[0] = kLogZero;
+    st[0].node[0] = 0; st[0].last[0] = -1; st[0].len[0] = 0; st[0].hash[0] = 0;
+    nb_sh = 1;
+    tp[0] = -1; tl[0] = -1;
+    if (n > 0) c_bl[0] = sblank_g[s];
+  }
+  if (tid < kMaxBeam) merged[tid] = 0;
+  if (n > 0 && tid < Cc) {
+    c_id[0][tid] = cid_g[(size_t)s * Cc + tid];
+    c_sc[0][tid] = csc_g[(size_t)s * Cc + tid];
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < n; ++t) {
+    const int nb = nb_sh;
+    if (nb == 0) break;   // the beam died (uniform): possible only with is_log input
+    const BeamState& a = st[cur];
+    BeamState& nx = st[cur ^ 1];
+    const int* ci_ = c_id[t & 1];
+    const float* cs_ = c_sc[t & 1];
+    const float bl = c_bl[t & 1];
+    // extension of entry p by candidate ci
+    auto ext_value = [&](int p, int ci) -> float {
+      const float lb = a.lb[p], lnb = a.lnb[p];
+      return score_add(cs_[ci], ci_[ci] == a.last[p] ? lb : log_add(lb, lnb));
+    };
+    // in flight over the whole frame: frame t + 1 (the last frame re-reads itself, unused)
+    const size_t row1 = (size_t)min(t + 1, n - 1) * S + s;
+    int pf_id = 0;
+    float pf_sc = 0.f, pf_ext = 0.f, pf_stay = kLogZero, pf_bl = 0.f;
+    if (tid < Cc) {
+      pf_id = cid_g[row1 * Cc + tid];
+      pf_sc = csc_g[row1 * Cc + tid];
+      pf_ext = sc[row1 * ld + ci_[tid]];
+    }
+    if (tid < nb && a.last[tid] >= 0) pf_stay = sc[row1 * ld + a.last[tid]];
+    if (tid == 0) pf_bl = sblank_g[row1];
+
+    if (tid < nb) {   // ---- 1
+      const int q = tid, e = a.last[q];
+      const float lb = a.lb[q], lnb = a.lnb[q];
+      const float slb = score_add(bl, log_add(lb, lnb));
+      float slnb = e >= 0 ? score_add(a.se[q], lnb) : kLogZero;
+      if (e >= 0) {
+        const unsigned long long ph = (a.hash[q] - (unsigned long long)(e + 1)) * kHashMulInv;
+        const int plen = a.len[q] - 1;
+        int p = -1;
+        for (int i = 0; i < nb; ++i)
+          if (a.hash[i] == ph && a.len[i] == plen) p = i;
+        if (p >= 0) {
+          int lo = 0, hi = Cc;   // first candidate id >= e
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (ci_[mid] < e) lo = mid + 1; else hi = mid;
+          }
+          if (lo < Cc && ci_[lo] == e) {
+            slnb = log_add(slnb, ext_value(p, lo));
+            atomicOr(&merged[p], 1ull << lo);
+          }
+        }
+      }
+      stay_lb[q] = slb;
+      stay_lnb[q] = slnb;
+      const float total = log_add(slb, slnb) + 0.f;   // (+ 0: a -0 orders as +0)
+      keys[q] = total > kDead ? make_key(total, q) : kDeadKey;
+    }
+    __syncthreads();
+    const int n_ext = nb * Cc;   // ---- 2
+    int npad = 2;
+    while (npad < nb + n_ext) npad <<= 1;   // <= 64 + 2048 -> <= 4096
+    for (int x = tid; x < npad - nb; x += NT) {
+      unsigned long long key = kDeadKey;
+      if (x < n_ext) {
+        const int p = x / Cc, ci = x - p * Cc;
+        const float v = ext_value(p, ci) + 0.f;
+        if (!((merged[p] >> ci) & 1) && v > kDead) key = make_key(v, kMaxBeam + x);
+      }
+      keys[nb + x] = key;
+    }
+    __syncthreads();
+    bool first = true;   // ---- 3
+    for (int k = 2; k <= npad; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        if (!first) sort_sync(j <= 32);   // the stage before had stride 2 j (<= 64) or 1
+        first = false;
+        for (int q = tid; q < (npad >> 1); q += NT) {
+          const int i = 2 * q - (q & (j - 1)), l = i | j;
+          const unsigned long long x = keys[i], y = keys[l];
+          if ((x > y) == ((i & k) == 0)) { keys[i] = y; keys[l] = x; }
+        }
+      }
+    // the prefetched frame lands (nothing of it is read before the barrier below; what it replaces was last read before the
+    // barrier that ended frame t - 1)
+    if (tid < Cc) {
+      c_id[(t + 1) & 1][tid] = pf_id;
+      c_sc[(t + 1) & 1][tid] = pf_sc;
+      nx_ext[tid] = clamp_score(pf_ext);
+    }
+    if (tid < nb) nx_stay[tid] = clamp_score(pf_stay);
+    if (tid == 0) c_bl[(t + 1) & 1] = pf_bl;
+    __syncthreads();
+    if (tid < 64) {   // ---- 4 (wave 0)
+      const unsigned long long key = (tid < B && tid < npad) ? keys[tid] : kDeadKey;
+      const bool live = key != kDeadKey;
+      if (live) {
+        const int idx = (int)(unsigned)key;
+        if (idx < kMaxBeam) {
+          nx.lb[tid] = stay_lb[idx]; nx.lnb[tid] = stay_lnb[idx]; nx.se[tid] = nx_stay[idx];
+          nx.node[tid] = a.node[idx]; nx.last[tid] = a.last[idx]; nx.len[tid] = a.len[idx]; nx.hash[tid] = a.hash[idx];
+        } else {
+          const int x = idx - kMaxBeam, p = x / Cc, ci = x - p * Cc, c = ci_[ci];
+          const int node = 1 + t * B + tid;   // < cap: t < n <= T, tid < B
+          nx.lb[tid] = kLogZero; nx.lnb[tid] = ext_value(p, ci); nx.se[tid] = nx_ext[ci];
+          nx.node[tid] = node; nx.last[tid] = c; nx.len[tid] = a.len[p] + 1;
+          nx.hash[tid] = a.hash[p] * kHashMul + (unsigned long long)(c + 1);
+          tp[node] = a.node[p];
+          tl[node] = c;
+        }
+      }
+      const int alive = __popcll(__ballot(live));   // the live keys are a prefix of the sorted array
+      if (tid == 0) nb_sh = alive;
+      merged[tid] = 0;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  const int nb = nb_sh;
+  if (tid < B) {
+    const BeamState& a = st[cur];
+    const bool live = tid < nb;
+    fnode[(size_t)s * B + tid] = live ? a.node[tid] : -1;
+    flen[(size_t)s * B + tid] = live ? a.len[tid] : -1;
+    fscore[(size_t)s * B + tid] = live ? log_add(a.lb[tid], a.lnb[tid]) + 0.f : kLogZero;
+  }
+  if (tid == 0) count[s] = nb;
+}
+
+// ---- hypotheses: one lane per (utterance, rank) -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void ctc_hyp_kernel(const int* __restrict__ tparent, const int* __restrict__ tlabel,
+                                                     const int* __restrict__ fnode, const int* __restrict__ flen,
+                                                     const float* __restrict__ fscore, const int* __restrict__ count, int T, int S,
+                                                     int B, int N, int* __restrict__ hyp, int* __restrict__ hyp_len,
+                                                     float* __restrict__ score) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S * N) return;
+  const int s = i / N, r = i - s * N;
+  const int cap = 1 + T * B;
+  const int* tp = tparent + (size_t)s * cap;
+  const int* tl = tlabel + (size_t)s * cap;
+  int* h = hyp + (size_t)i * T;
+  const bool have = r < count[s];
+  int node = have ? fnode[(size_t)s * B + r] : 0;
+  const int L = have ? min(flen[(size_t)s * B + r], T) : 0;
+  for (int j = L; j < T; ++j) h[j] = -1;
+  for (int j = L - 1; j >= 0 && node > 0 && node < cap; --j) {   // the root is node 0
+    h[j] = tl[node];
+    node = tp[node];
+  }
+  hyp_len[i] = have ? L : -1;
+  score[i] = have ? fscore[(size_t)s * B + r] : kLogZero;
+}
+
+}  // namespace
+
+void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, int S, const int* lens, int Cc, int* cid, float* csc,
+                  float* sblank) {
+  if (rows <= 0) return;
+  if (K <= 256) hipLaunchKernelGGL(ctc_row_topc_kernel<true>, dim3(cdiv(rows, 4)), dim3(256), 0, st, scores, ld, rows, K, S, lens, Cc, cid, csc, sblank);
+  else hipLaunchKernelGGL(ctc_row_topc_kernel<false>, dim3(cdiv(rows, 4)), dim3(256), 0, st, scores, ld, rows, K, S, lens, Cc, cid, csc, sblank);
+  check_launch("ctc_row_topc");
+}
+
+void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
+                     const float* csc, const float* sblank, int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, int* count) {
+  EESEN_REQUIRE(B >= 1 && B <= kMaxBeam && Cc >= 1 && Cc <= kMaxCls && B * Cc <= kMaxKeys / 2, EESEN_ERR_INVALID, "ctc_prefix_beam: beam or class count outside the key array");
+  // one thread per pair of the widest sort stage, 64 .. 512
+  int keys = 2;
+  while (keys < B + B * Cc) keys <<= 1;
+  const int threads = std::min(512, std::max(64, keys / 2));
+  hipLaunchKernelGGL(ctc_prefix_beam_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank, tparent, tlabel,
+                     fnode, flen, fscore, count);
+  check_launch("ctc_prefix_beam");
+}
+
+void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const int* count,
+             int T, int S, int B, int N, int* hyp, int* hyp_len, float* score) {
+  hipLaunchKernelGGL(ctc_hyp_kernel, dim3(cdiv(S * N, 64)), dim3(64), 0, st, tparent, tlabel, fnode, flen, fscore, count, T, S, B, N, hyp, hyp_len, score);
+  check_launch("ctc_hyp");
+}
+
+}  // namespace eesen

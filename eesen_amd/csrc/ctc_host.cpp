@@ -216,6 +216,111 @@ void Ctc::align_times(float* out3) {
   }
 }
 
+// Prefix beam search of every utterance (INTEGRATION.md "Decoding").  The logarithms borrow `logp`; everything else is this call's own.
+void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                          int nbest, int* hyp_host, int* hyp_len_host, float* score_host) {
+  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
+  EESEN_REQUIRE(K >= 2, EESEN_ERR_INVALID, "decoding needs the blank and at least one other class (K >= 2)");
+  EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  EESEN_REQUIRE(beam >= 1 && beam <= 64, EESEN_ERR_INVALID, "beam outside [1, 64]");
+  EESEN_REQUIRE(max_classes >= 1 && max_classes <= 64, EESEN_ERR_INVALID, "max_classes outside [1, 64]");
+  EESEN_REQUIRE(beam * max_classes <= 2048, EESEN_ERR_INVALID, "beam * max_classes above 2048 (the candidate keys of a frame live in LDS)");
+  EESEN_REQUIRE(nbest >= 1 && nbest <= beam, EESEN_ERR_INVALID, "nbest outside [1, beam]");
+  const int T = rows / S;
+  for (int s = 0; s < S; ++s)
+    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  const int B = beam, N = nbest, Cc = std::min(max_classes, K - 1);
+  const size_t n_cand = (size_t)rows * Cc, n_beam = (size_t)S * B, n_trie = (size_t)S * (1 + (size_t)T * B);
+  const size_t n_f = n_cand + rows + n_beam, n_i = n_cand + S + 2 * n_beam + S;
+  const size_t n_hyp = (size_t)S * N * T, n_out = n_hyp + 2 * (size_t)S * N;   // labels, lengths, scores
+  EESEN_REQUIRE(n_trie <= ((size_t)1 << 30), EESEN_ERR_INVALID, "decoding: more than 2^30 trie nodes (S * (1 + T * beam)): decode fewer utterances together");
+  if ((!is_log && logp.cap < (size_t)rows * K) || dec_f.cap < n_f || dec_i.cap < n_i || dec_trie.cap < 2 * n_trie || dec_out.cap < n_out)
+    EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  if (!is_log) logp.reserve((size_t)rows * K);
+  dec_f.reserve(n_f);
+  dec_i.reserve(n_i);
+  dec_trie.reserve(2 * n_trie);
+  dec_out.reserve(n_out);
+  float* csc = dec_f.p;
+  float* sblank = csc + n_cand;
+  float* fscore = sblank + rows;
+  int* cid = dec_i.p;
+  int* lens_d = cid + n_cand;
+  int* fnode = lens_d + S;
+  int* flen = fnode + n_beam;
+  int* count = flen + n_beam;
+  int* hyp_d = dec_out.p;
+  int* len_d = hyp_d + n_hyp;
+  float* score_d = reinterpret_cast<float*>(len_d + (size_t)S * N);
+
+  PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
+  int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
+  std::copy(frame_num_utt, frame_num_utt + S, pinned);
+  EESEN_HIP_CHECK(hipMemcpyAsync(lens_d, pinned, S * sizeof(int), hipMemcpyHostToDevice, st));
+  sp.used(st);
+
+  const float* sc = is_log ? scores : logp.p;
+  const int sld = is_log ? ld : K;
+  const bool acc = decode_timer.enabled();
+  int sp0 = -1, sp1 = -1, sp2 = -1;
+  if (acc) sp0 = decode_timer.begin(st, 0); else dev[0].record(st);
+  if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
+  ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
+  if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
+  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, count);
+  if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
+  ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, count, T, S, B, N, hyp_d, len_d, score_d);
+  if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
+  dec_rows = rows; dec_S = S; dec_C = Cc;
+  dec_lens.assign(frame_num_utt, frame_num_utt + S);
+
+  // results and the guard word's value when they were computed, through one pinned slot
+  int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
+  EESEN_HIP_CHECK(hipMemcpyAsync(out, hyp_d, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
+  out[n_out] = 0;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_out, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  decode_pin.used(st);
+  decode_pin.wait();
+  // computed from a timed-out forward pass (guard word set): no hypotheses -- NaN and -1, never garbage with status OK
+  const bool bad = out[n_out] != 0;
+  for (size_t i = 0; i < n_hyp; ++i) hyp_host[i] = bad ? -1 : out[i];
+  const float* scr = reinterpret_cast<const float*>(out + n_hyp + (size_t)S * N);
+  for (size_t i = 0; i < (size_t)S * N; ++i) {
+    hyp_len_host[i] = bad ? -1 : out[n_hyp + i];
+    score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
+  }
+}
+
+void Ctc::decode_times(float* out3) {
+  if (decode_timer.enabled()) { decode_timer.collect(out3, 3); return; }
+  dev[3].wait();
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.f;
+    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, dev[i], dev[i + 1]));
+    out3[i] = ms * 1e-3f;
+  }
+}
+
+void Ctc::get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc) {
+  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "no DecodeParallel yet");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  const size_t n_cand = (size_t)dec_rows * dec_C;
+  if (Cc) *Cc = dec_C;
+  if (ids_host) EESEN_HIP_CHECK(hipMemcpy(ids_host, dec_i.p, n_cand * sizeof(int), hipMemcpyDeviceToHost));
+  if (scores_host) EESEN_HIP_CHECK(hipMemcpy(scores_host, dec_f.p, n_cand * sizeof(float), hipMemcpyDeviceToHost));
+  if (blank_host) EESEN_HIP_CHECK(hipMemcpy(blank_host, dec_f.p + n_cand, (size_t)dec_rows * sizeof(float), hipMemcpyDeviceToHost));
+  for (int r = 0; r < dec_rows; ++r) {   // rows the selection never visits
+    if (r / dec_S < dec_lens[r % dec_S]) continue;
+    for (int c = 0; c < dec_C; ++c) {
+      if (ids_host) ids_host[(size_t)r * dec_C + c] = -1;
+      if (scores_host) scores_host[(size_t)r * dec_C + c] = -1e30f;
+    }
+    if (blank_host) blank_host[r] = -1e30f;
+  }
+}
+
 void Ctc::get_alpha_beta(float* alpha_host, float* beta_host, int* Lprime) {
   EESEN_REQUIRE(last_T > 0, EESEN_ERR_STATE, "no EvalParallel yet");
   EESEN_HIP_CHECK(hipSetDevice(device));
@@ -255,6 +360,8 @@ static int levenshtein(const int* ref, int nr, const std::vector<int>& hyp) {
   }
   return prev[nh];
 }
+
+int edit_distance(const int* ref, int nr, const int* hyp, int nh) { return levenshtein(ref, nr, std::vector<int>(hyp, hyp + nh)); }
 
 void Ctc::flush_err(PendingErr& q, int* num_err, int* num_ref) {
   if (!q.active) return;

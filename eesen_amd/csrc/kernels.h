@@ -218,6 +218,20 @@ void ctc_best_path(hipStream_t st, const float* scores, int ld, int T, int S, in
 // every row of an utterance without a feasible path; score [S]: the path's log-score, -1e30 without one.
 void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, const int* labx, const int* lens, const int* lablens,
                    int* ali, int* pos, float* score);
+// Lexicon-free prefix beam search (ctc_decode.hip; the computation: INTEGRATION.md "Decoding").  scores: [T*S x K] (ld) log-domain.
+// ctc_row_topc: per row t*S + s with t < lens[s] the Cc = min(max_classes, K - 1) best non-blank classes -- ids ascending in
+// cid [rows][Cc], their scores in csc [rows][Cc], the blank's in sblank [rows]; every score clamped from below at -1e30.
+void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, int S, const int* lens, int Cc, int* cid, float* csc,
+                  float* sblank);
+// ctc_prefix_beam: S workgroups, each walks its utterance's frames.  tparent / tlabel [S][1 + T*B]: the trie (node 0 = the empty
+// prefix), written only; fnode / flen / fscore [S][B]: node, length and total of the final beam, best first (-1, -1, -1e30 beyond
+// count[s] live entries).  1 <= B <= 64, 1 <= Cc <= 64, B * Cc <= 2048.
+void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
+                     const float* csc, const float* sblank, int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, int* count);
+// ctc_hyp: hyp [S][N][T] the labels of the N best entries front to back (-1 beyond the length), hyp_len / score [S][N] (-1 / -1e30
+// beyond count[s]).
+void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const int* count,
+             int T, int S, int B, int N, int* hyp, int* hyp_len, float* score);
 // diff[t*S+s][k] = y*rowsum(e) - gamma ... (error kernel + softmax Jacobian, ctc-loss.cc:156-168)
 // labx [S x Lpad]: the expanded labels (blank 0 at even positions), lablens [S] = 2 U_s + 1
 void ctc_error_diff(hipStream_t st, const float* probs, int ld, int T, int S, int K, int Lpad, int Lmax, const int* lens,

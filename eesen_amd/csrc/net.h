@@ -264,6 +264,14 @@ struct Ctc {
   DevEvent aev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};  // align_times without the timer
   PhaseTimer align_timer;      // the same for align_parallel (phases: log, sweep, traceback)
   PinBuf align_pin;            // results of align_parallel (D2H)
+  // decode_parallel (ctc_decode.hip): candidates of every frame and the final beam (floats, ints), the trie, the hypotheses
+  DevBuf<float> dec_f;
+  DevBuf<int> dec_i, dec_trie, dec_out;
+  DevEvent dev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};  // decode_times without the timer
+  PhaseTimer decode_timer;     // phases: top-C (with the logarithm), beam, hypotheses
+  PinBuf decode_pin;           // results of decode_parallel (D2H)
+  int dec_rows = 0, dec_S = 0, dec_C = 0;   // shape of the candidates the last decode_parallel left (get_decode_candidates)
+  std::vector<int> dec_lens;
   // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
   // back through PinBufs that are folded into the statistics at the next call that needs them ("deferred").
@@ -290,10 +298,20 @@ struct Ctc {
   void align_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* label_ids,
                       const int* label_off, int* ali_host, int* pos_host, float* score_host);
   void align_times(float* out3);
+  // Prefix beam search over the posteriors (ctc_row_topc + ctc_prefix_beam + ctc_hyp in ctc_decode.hip); touches neither the
+  // objective nor the error statistics, and none of the buffers of eval_parallel / align_parallel but `logp`.
+  void decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                       int nbest, int* hyp_host, int* hyp_len_host, float* score_host);
+  void decode_times(float* out3);
+  // the candidate classes the last decode_parallel selected: ids / scores [rows][C'], blank [rows]; rows beyond an utterance: -1 / -1e30
+  void get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc);
  private:
   struct Lattices { const int *labx, *lens, *lablens; int Lpad, Lprime; };
   Lattices upload_lattices(const int* frame_num_utt, int S, const int* label_ids, const int* label_off);
 };
+
+// LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: what Ctc::error_rate_mseq counts with (ctc_host.cpp)
+int edit_distance(const int* ref, int nr, const int* hyp, int nh);
 
 // eesen::CE (src/net/ce-loss.h:32-77): frame-level cross-entropy (ce_host.cpp, ce.hip).  As with the Ctc nothing in a training
 // step stalls the host: targets travel through two alternating PinBufs, and each call's sums come back through a PinBuf

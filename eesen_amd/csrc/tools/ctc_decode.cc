@@ -1,0 +1,207 @@
+// ctc_decode.cc -- lexicon-free CTC prefix beam search of utterances, over the C-ABI of include/eesen_hip.h, host C++ only.  The
+// reference has no such binary: it decodes ONE utterance per process through a TLG graph and its WFST decoder over
+// net-output-extract's output.  Here, per group of --num-sequence utterances: Net::Feedforward as net-output-extract does it ->
+// optional ClassPrior::SubtractOnLogpost (the options of net-output-extract) -> eesen_ctc_decode_parallel.  Written: one int32 vector
+// per hypothesis, the labels (blank-free); with --nbest > 1 under the keys utt-1, utt-2, ... (as lattice-to-nbest names them).
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <fstream>
+#include <iostream>
+#include <sstream>
+
+#include "../../../include/eesen_hip.h"
+#include "kaldi_tables.h"
+#include "feat_pipeline.h"
+#include "class_prior.h"
+#include "parse_options.h"
+
+namespace {
+using namespace ktab;
+
+void ck(int rc) {
+  if (rc != EESEN_OK) throw std::runtime_error(eesen_last_error());
+}
+std::string fmt9(double v) {
+  std::ostringstream o;
+  o.precision(9);
+  o << v;
+  return o.str();
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+  try {
+    std::string class_frame_counts, scores_out, ref_rspecifier;
+    float prior_scale = 1.f;
+    double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
+    int num_sequence = 1, device = 0, beam = 16, max_classes = 20, nbest = 1;
+    std::string use_gpu = "yes";
+    eesen_tools::ParseOptions po(
+        "Decode utterances without a lexicon: CTC prefix beam search over the network's outputs.\n"
+        "Writes the most probable label sequences (blank-free int32 vectors); with --nbest > 1 under the keys utt-1, utt-2, ...\n"
+        "\n"
+        "Usage:  ctc-decode [options] <model-in> <feature-rspecifier> <hyp-wspecifier>\n"
+        "e.g.: \n"
+        "ctc-decode --beam=16 net ark:features.ark ark:hyp.ark\n");
+    po.Register("class-frame-counts", &class_frame_counts, "Vector with frame-counts of classes to compute log-priors; the search then runs on "
+                                                           "log-posteriors minus the scaled log-priors");
+    po.Register("prior-scale", &prior_scale, "Scaling factor to be applied on class-log-priors");
+    po.Register("prior-cutoff", &prior_cutoff, "Classes with priors lower than cutoff will have 0 likelihood");
+    po.Register("blank-scale", &blank_scale, "Scale probability of class 0 (blank) by this factor");
+    po.Register("beam", &beam, "Prefixes kept per frame (1 .. 64)");
+    po.Register("max-classes", &max_classes, "Non-blank classes a prefix is extended by per frame: the best of the frame (1 .. 64; beam * max-classes <= 2048)");
+    po.Register("nbest", &nbest, "Hypotheses written per utterance (1 .. beam)");
+    po.Register("scores-out", &scores_out, "Also write `key log-probability` text lines, one per hypothesis, to this file");
+    po.Register("ref-rspecifier", &ref_rspecifier, "Reference label sequences: the token errors of the best hypotheses against them are counted");
+    po.Register("use-gpu", &use_gpu, "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)");
+    po.Register("num-sequence", &num_sequence, "Utterances forwarded and decoded together");
+    po.Register("frame-limit", &frame_limit, "Max number of frames forwarded together");
+    po.Register("device", &device, "GPU index");
+    po.Read(argc, argv);
+    std::vector<std::string> args;
+    for (int i = 1; i <= po.NumArgs(); ++i) args.push_back(po.GetArg(i));
+    if (args.size() != 3) {
+      po.PrintUsage();
+      return 1;
+    }
+    eesen_net_t* net = nullptr;
+    eesen_feeder_t* feeder = nullptr;
+    eesen_ctc_t* ctc = nullptr;
+    ck(eesen_net_create(device, nullptr, &net));
+    ck(eesen_net_read(net, args[0].c_str()));
+    ck(eesen_net_set_train_mode(net, 0));
+    ck(eesen_feeder_create(device, nullptr, 1, &feeder));
+    ck(eesen_ctc_create(device, nullptr, &ctc));
+    ck(eesen_ctc_set_guard(ctc, net));       // hypotheses of a timed-out forward pass come back as NaN, never as table entries
+    int D = 0, K = 0;
+    ck(eesen_net_input_dim(net, &D));
+    ck(eesen_net_output_dim(net, &K));
+    std::vector<float> log_pri;
+    if (!class_frame_counts.empty()) {
+      log_pri = class_log_priors(class_frame_counts, prior_cutoff, blank_scale);
+      if ((int)log_pri.size() != K)
+        throw std::runtime_error("Dimensionality mismatch, class_frame_counts " + std::to_string(log_pri.size()) + " class_output_llk " + std::to_string(K));
+    }
+    // feature pipes (`apply-cmvn ... | splice-feats ... |`) as net-output-extract recognises them: the raw table is read here and the
+    // filters run on the device (feat_pipeline.h)
+    Pipeline pipe;
+    const bool piped = !getenv("EESEN_HOST_FEATURE_PIPES") && parse_feature_pipeline(args[1], &pipe);
+    std::unique_ptr<CmvnTable> cmvn_table;
+    if (piped) {
+      ck(eesen_feeder_set_pipeline(feeder, pipe.stages.data(), (int)pipe.stages.size()));
+      if (!pipe.cmvn.empty()) cmvn_table.reset(new CmvnTable(pipe.cmvn, pipe.utt2spk, pipe.norm_vars));
+    }
+    std::map<std::string, std::vector<int32_t>> refs;
+    if (!ref_rspecifier.empty()) refs = read_targets(ref_rspecifier);
+    FeatureReader reader(piped ? pipe.source : args[1]);
+    IntVectorWriter writer(args[2]);
+    std::ofstream scores;
+    if (!scores_out.empty()) {
+      scores.open(scores_out);
+      if (!scores) throw std::runtime_error("cannot open " + scores_out);
+    }
+    long num_done = 0, num_empty = 0, num_dead = 0, tok_err = 0, tok_ref = 0, num_scored = 0;
+    double tot_t = 0, tot_score = 0;
+    std::vector<std::pair<std::string, Mat>> group;
+    std::vector<int> out_frames;            // per utterance of the group: frames behind the pipeline
+    std::vector<const float*> cmvn;
+    std::vector<int> hyp, hyp_len;
+    std::vector<float> score;
+    auto flush = [&]() {
+      const int S = (int)group.size();
+      std::vector<const float*> ptr(S);
+      std::vector<int> frames(out_frames), raw_frames(S);
+      for (int s = 0; s < S; ++s) { ptr[s] = group[s].second.v.data(); raw_frames[s] = group[s].second.rows; }
+      int slot = 0, T = 0, S2 = 0, ld = 0;
+      float* feats = nullptr;
+      if (piped) ck(eesen_feeder_submit_raw(feeder, ptr.data(), raw_frames.data(), nullptr, cmvn_table ? cmvn.data() : nullptr, S, group[0].second.cols, &slot));
+      else ck(eesen_feeder_submit(feeder, ptr.data(), frames.data(), nullptr, S, D, &slot));
+      ck(eesen_feeder_acquire(feeder, slot, &feats, &T, &S2, &ld));
+      ck(eesen_net_set_seq_lengths(net, frames.data(), S));
+      const float* out = nullptr;
+      int oc = 0, old = 0;
+      ck(eesen_net_propagate(net, feats, T * S, ld, 1, &out, &oc, &old));
+      ck(eesen_feeder_release(feeder, slot));
+      if (!log_pri.empty())
+        ck(eesen_op_log_sub_prior(device, nullptr, const_cast<float*>(out), T * S, K, old, 1, log_pri.data(), prior_scale));
+      hyp.resize((size_t)S * nbest * T); hyp_len.resize((size_t)S * nbest); score.resize((size_t)S * nbest);
+      ck(eesen_ctc_decode_parallel(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, hyp.data(),
+                                   hyp_len.data(), score.data()));
+      for (int s = 0; s < S; ++s) {
+        const std::string& utt = group[s].first;
+        const size_t e0 = (size_t)s * nbest;
+        if (std::isnan(score[e0])) throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no hypotheses");
+        if (hyp_len[e0] < 0) {
+          std::cerr << "WARNING (ctc-decode:main()) " << utt << ", every prefix has probability zero on " << frames[s]
+                    << " frames, producing no output for this utterance" << std::endl;
+          ++num_dead;
+          continue;
+        }
+        for (int i = 0; i < nbest && hyp_len[e0 + i] >= 0; ++i) {
+          const std::string key = nbest > 1 ? utt + "-" + std::to_string(i + 1) : utt;
+          writer.Write(key, hyp.data() + (e0 + i) * T, hyp_len[e0 + i]);
+          if (scores.is_open()) scores << key << ' ' << fmt9(score[e0 + i]) << '\n';
+        }
+        const auto ref = refs.find(utt);
+        if (ref != refs.end()) {
+          int err = 0;
+          ck(eesen_edit_distance(ref->second.data(), (int)ref->second.size(), hyp.data() + e0 * T, hyp_len[e0], &err));
+          tok_err += err; tok_ref += (long)ref->second.size(); ++num_scored;
+        }
+        ++num_done;
+        if (hyp_len[e0] == 0) ++num_empty;
+        tot_t += frames[s];
+        tot_score += score[e0];
+      }
+      group.clear(); out_frames.clear(); cmvn.clear();
+    };
+    int max_len = 0;
+    for (; !reader.Done(); reader.Next()) {
+      Mat& m = reader.Value();
+      int rows = m.rows, cols = m.cols;
+      const float* cm = nullptr;
+      const std::string& utt = reader.Key();
+      if (piped) {  // what the filters would have dropped (apply-cmvn.cc:87-92, add-deltas.cc:55-58, subsample-feats.cc:87-92)
+        if (cmvn_table) {
+          const std::vector<float>* n = cmvn_table->lookup(utt);
+          if (!n) { std::cerr << "WARNING (ctc-decode:main()) No normalization statistics available for key " << utt << ", producing no output for this utterance" << std::endl; continue; }
+          if (CmvnTable::dim(*n) != m.cols)
+            throw std::runtime_error("Dim mismatch in ApplyCmvn: cmvn 2x" + std::to_string(CmvnTable::dim(*n) + 1) + ", feats " + std::to_string(m.rows) + "x" + std::to_string(m.cols));
+          cm = n->data();
+        }
+        if (m.rows == 0) { std::cerr << "WARNING (ctc-decode:main()) Empty feature matrix for key " << utt << std::endl; continue; }
+        ck(eesen_feeder_pipeline_shape(feeder, m.cols, m.rows, &cols, &rows));
+        if (rows == 0) { std::cerr << "WARNING (ctc-decode:main()) For utterance " << utt << ", output would have no rows, producing no output." << std::endl; continue; }
+      }
+      if (cols != D) throw std::runtime_error("feature dimension " + std::to_string(cols) + " does not match the net's InputDim " + std::to_string(D));
+      if (!group.empty() && ((int)group.size() == num_sequence || (double)std::max(max_len, rows) * (group.size() + 1) > frame_limit)) {
+        flush();
+        max_len = 0;
+      }
+      max_len = std::max(max_len, rows);
+      out_frames.push_back(rows);
+      cmvn.push_back(cm);
+      group.emplace_back(utt, std::move(m));
+    }
+    if (!group.empty()) flush();
+    if (scores.is_open()) {
+      scores.close();
+      if (!scores) throw std::runtime_error("write error: " + scores_out);
+    }
+    if (!ref_rspecifier.empty()) {
+      std::cerr << "LOG (ctc-decode:main()) " << tok_err << " token errors on " << tok_ref << " reference tokens of " << num_scored << " utterances" << std::endl;
+      std::cerr << "LOG (ctc-decode:main()) \nTOKEN_ACCURACY >> " << 100.0 * (1.0 - (double)tok_err / (double)std::max(tok_ref, 1L)) << "% <<" << std::endl;
+    }
+    if (num_dead) std::cerr << "LOG (ctc-decode:main()) " << num_dead << " utterances without a hypothesis" << std::endl;
+    std::cerr << "LOG (ctc-decode:main()) Done " << num_done << " utterances, " << num_empty << " empty hypotheses; average log-probability per frame "
+              << (tot_t > 0 ? tot_score / tot_t : 0.0) << std::endl;
+    eesen_ctc_destroy(ctc);
+    eesen_feeder_destroy(feeder);
+    eesen_net_destroy(net);
+    return num_done ? 0 : 255;
+  } catch (const std::exception& e) {
+    std::cerr << "ERROR (ctc-decode:main()) " << e.what() << std::endl;
+    return 255;
+  }
+}

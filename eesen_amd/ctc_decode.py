@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""ctc-decode on MI355X: lexicon-free CTC prefix beam search of utterances (the Python mirror of eesen_amd/csrc/tools/ctc_decode.cc:
+the same library calls in the same order, byte-identical tables).
+
+Usage: python -m eesen_amd.ctc_decode [options] <model-in> <feature-rspecifier> <hyp-wspecifier>
+e.g.:  python -m eesen_amd.ctc_decode --num-sequence=20 --beam=16 final.nnet scp:feats.scp ark:hyp.ark
+
+The reference has no such tool: it decodes ONE utterance per process through a TLG graph and its WFST decoder.  Per group of
+--num-sequence utterances: forward pass as net-output-extract -> optional log + prior subtraction (net-output-extract's options) ->
+Ctc.DecodeParallel.  Written: one int32 vector per hypothesis, the labels (blank-free); with --nbest > 1 under the keys utt-1, utt-2, ...
+"""
+from __future__ import annotations
+
+import math
+import os
+import sys
+
+
+def main(argv=None) -> int:
+    from eesen_amd.parse_options import ParseOptions, ParseError
+    ap = ParseOptions("Decode utterances without a lexicon: CTC prefix beam search over the network's outputs.\n"
+                      "Writes the most probable label sequences (blank-free int32 vectors); with --nbest > 1 under the keys utt-1, utt-2, ...\n"
+                      "\n"
+                      "Usage:  ctc-decode [options] <model-in> <feature-rspecifier> <hyp-wspecifier>\n"
+                      "e.g.: \n"
+                      "ctc-decode --beam=16 net ark:features.ark ark:hyp.ark\n", prog="ctc-decode")
+    ap.register("class-frame-counts", "", "Vector with frame-counts of classes to compute log-priors; the search then runs on log-posteriors "
+                                          "minus the scaled log-priors")
+    ap.register("prior-scale", 1.0, "Scaling factor to be applied on class-log-priors")
+    ap.register("prior-cutoff", 1e-10, "Classes with priors lower than cutoff will have 0 likelihood")
+    ap.register("blank-scale", 1.0, "Scale probability of class 0 (blank) by this factor")
+    ap.register("beam", 16, "Prefixes kept per frame (1 .. 64)")
+    ap.register("max-classes", 20, "Non-blank classes a prefix is extended by per frame: the best of the frame (1 .. 64; beam * max-classes <= 2048)")
+    ap.register("nbest", 1, "Hypotheses written per utterance (1 .. beam)")
+    ap.register("scores-out", "", "Also write `key log-probability` text lines, one per hypothesis, to this file")
+    ap.register("ref-rspecifier", "", "Reference label sequences: the token errors of the best hypotheses against them are counted")
+    ap.register("use-gpu", "yes", "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)")
+    ap.register("num-sequence", 1, "Utterances forwarded and decoded together")
+    ap.register("frame-limit", 1e5, "Max number of frames forwarded together", kind="double")
+    ap.register("device", 0, "GPU index")
+    try:
+        o = ap.read(argv)
+    except ParseError as e:
+        print(str(e), file=sys.stderr)
+        return 255
+    if len(o.args) != 3:
+        ap.print_usage()
+        return 1
+    model_filename, feature_rspecifier, hyp_wspecifier = o.args
+
+    def warn(msg):
+        print(f"WARNING (ctc-decode:main()) {msg}", file=sys.stderr)
+
+    def log(msg):
+        print(f"LOG (ctc-decode:main()) {msg}", file=sys.stderr)
+
+    try:
+        import ctypes as C
+        import numpy as np
+        from eesen_amd import kaldi_io, _lib, frontend
+        from eesen_amd.api import Net, Ctc
+        from eesen_amd.batching import interleave
+        from eesen_amd.net_output_extract import class_log_priors
+
+        kind, out_path, out_text = kaldi_io._parse_specifier(hyp_wspecifier)
+        if kind != "ark":
+            raise kaldi_io.KaldiIOError("only ark: output is supported")
+        net = Net(o.device).Read(model_filename)
+        net.SetTestMode()
+        ctc = Ctc(o.device)
+        ctc.SetGuard(net)           # hypotheses of a timed-out forward pass come back as NaN, never as table entries
+        log_pri = class_log_priors(o.class_frame_counts, o.prior_cutoff, o.blank_scale) if o.class_frame_counts else None
+        K = net.OutputDim()
+        if log_pri is not None and log_pri.size != K:
+            raise kaldi_io.KaldiIOError(f"Dimensionality mismatch, class_frame_counts {log_pri.size} class_output_llk {K}")
+        refs = kaldi_io.read_vec_int_table(o.ref_rspecifier) if o.ref_rspecifier else {}
+        pipe = frontend.parse_feature_pipeline(feature_rspecifier) if not os.environ.get("EESEN_HOST_FEATURE_PIPES") else None
+        feeder = None
+        if pipe is not None:
+            from eesen_amd.api import Feeder
+            feeder = Feeder(o.device, slots=1)
+            feeder.set_pipeline(pipe.stages)
+        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0)
+        scores = open(o.scores_out, "w") if o.scores_out else None
+        lib = _lib.load()
+
+        def flush(group):
+            for _, m in group:
+                if m.shape[1] != net.InputDim():
+                    raise kaldi_io.KaldiIOError(f"feature dimension {m.shape[1]} does not match the net's InputDim {net.InputDim()}")
+            if pipe is not None:    # raw matrices: the filters of the rspecifier pipe run on the device (eesen_amd.frontend)
+                lens = np.array([m.shape[0] for _, m in group], np.int32)
+                slot = feeder.submit([m for _, m in group])
+                net.SetSeqLengths(lens)
+                out = net.Propagate(feeder.acquire(slot))
+                feeder.release(slot)
+            else:
+                feats, lens, _ = interleave([m for _, m in group], net.InputDim())
+                net.SetSeqLengths(lens)
+                out = net.Propagate(feats)
+            if log_pri is not None:
+                _lib.check(lib.eesen_op_log_sub_prior(o.device, None, C.c_void_p(out.ptr), out.rows, out.cols, out.stride, 1,
+                                                      log_pri.ctypes.data_as(C.c_void_p), o.prior_scale))
+            hyps, score = ctc.DecodeParallel(lens, out, beam=o.beam, max_classes=o.max_classes, nbest=o.nbest, is_log=log_pri is not None)
+            for s, (key, m) in enumerate(group):
+                frames = int(lens[s])
+                if math.isnan(score[s, 0]):
+                    raise RuntimeError(f"the forward pass of {key} timed out on the device: no hypotheses")
+                if not hyps[s]:
+                    warn(f"{key}, every prefix has probability zero on {frames} frames, producing no output for this utterance")
+                    n["dead"] += 1
+                    continue
+                for i, h in enumerate(hyps[s]):
+                    k = f"{key}-{i + 1}" if o.nbest > 1 else key
+                    if scores:
+                        scores.write(f"{k} {float(score[s, i]):.9g}\n")
+                    yield k, np.asarray(h, np.int32)
+                if key in refs:
+                    ref, best, err = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][0], np.int32), C.c_int(0)
+                    _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
+                    n["tok_err"] += err.value; n["tok_ref"] += int(ref.size); n["scored"] += 1
+                n["done"] += 1; n["frames"] += frames; n["score"] += float(score[s, 0])
+                n["empty"] += len(hyps[s][0]) == 0
+
+        def produce():
+            group, max_len = [], 0
+            table = frontend.read_raw(pipe, warn=warn) if pipe is not None else kaldi_io.read_mat_table(feature_rspecifier)
+            for key, mat in table:
+                if group and (len(group) == o.num_sequence or max(max_len, mat.shape[0]) * (len(group) + 1) > o.frame_limit):
+                    yield from flush(group)
+                    group, max_len = [], 0
+                group.append((key, mat)); max_len = max(max_len, mat.shape[0])
+            if group:
+                yield from flush(group)
+
+        kaldi_io.write_vec_int_ark(out_path, produce(), text=out_text)
+        if scores:
+            scores.close()
+        if o.ref_rspecifier:
+            log(f"{n['tok_err']} token errors on {n['tok_ref']} reference tokens of {n['scored']} utterances")
+            log(f"\nTOKEN_ACCURACY >> {100.0 * (1.0 - n['tok_err'] / max(n['tok_ref'], 1)):g}% <<")
+        if n["dead"]:
+            log(f"{n['dead']} utterances without a hypothesis")
+        avg = n["score"] / n["frames"] if n["frames"] else 0.0
+        log(f"Done {n['done']} utterances, {n['empty']} empty hypotheses; average log-probability per frame {avg:g}")
+        return 0 if n["done"] else 255
+    except Exception as e:
+        print(f"ERROR (ctc-decode:main()) {e}", file=sys.stderr)
+        return 255
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -352,7 +352,7 @@ def write_vec_int_ark(path: str, items, text: bool = False):
             v = np.ascontiguousarray(v, np.int32)
             f.write(key.encode() + b" ")
             if text:
-                f.write((" ".join(str(int(x)) for x in v) + " \n").encode())
+                f.write(("".join(f"{int(x)} " for x in v) + "\n").encode())
             else:
                 f.write(b"\x00B\x04" + struct.pack("<i", v.size))
                 out = np.empty((v.size, 5), np.uint8)

@@ -341,6 +341,42 @@ int eesen_ctc_align_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, 
 /* seconds of the last eesen_ctc_align_parallel's device work: out[0]=log (is_log == 0), [1]=max-plus sweep, [2]=traceback;
  * summed over all calls since the last read under eesen_ctc_set_profiling(ctc, 2). */
 int eesen_ctc_get_align_times(eesen_ctc_t* ctc, float* out3);
+/* Lexicon-free CTC prefix beam search of every utterance: the most probable LABELLING (a sum over paths, where the greedy collapse of
+ * eesen_ctc_error_rate_mseq keeps one path), its log-probability, and an N-best list.  The reference has no such call: it decodes one
+ * utterance per process through a TLG graph and its WFST decoder.  frame_num_utt, S, scores_dev, rows, K, ld, is_log as
+ * eesen_ctc_align_parallel (is_log != 0: e.g. what eesen_op_log_sub_prior left).  Blank = class 0; every log-score is clamped from
+ * below at -1e30 on load.  The computation, per utterance of n frames, with beam = B, max_classes = C, nbest = N:
+ *   candidates of a frame: the C' = min(C, K-1) non-blank classes with the largest s_t(k), ties to the smaller class id;
+ *   an entry is (prefix, lb, lnb): the log-mass of the paths that spell the prefix and end in blank / in its last label e; the beam
+ *   starts as the empty prefix with lb = 0, lnb = -1e30; with tot = logadd(lb, lnb), at frame t
+ *     stay of p:        lb' = s_t(0) + tot,  lnb' = s_t(e) + lnb  (-1e30 for the empty prefix)
+ *     extension p + c:  lb' = -1e30,         lnb' = s_t(c) + (c == e ? lb : tot)      for every candidate class c
+ *     merge:            if p + c is itself in the beam as q, its lnb' is log-added into q's stay and it is no candidate of its own;
+ *   candidates whose total logadd(lb', lnb') is <= -1e29 are dead; the B largest totals survive.
+ * The order is total and part of the interface: higher total first; on equal totals stays before extensions, stays by previous
+ * rank, extensions by the parent's rank, then by class id.  logadd(a, b) = max + log(1 + exp(min - max)) in fp32.
+ * Host outputs, with T = rows / S: hyp_host [S][nbest][T] int32, the labels (blank-free) of the min(nbest, live entries) best
+ * entries after frame n-1, best first, -1 beyond each length; hyp_len_host [S][nbest], -1 beyond the returned count; score_host
+ * [S][nbest] the totals, -1e30 beyond it.  n == 0 returns the empty labelling with score 0.  A beam that dies entirely (possible only
+ * with is_log input, e.g. an all -inf row) returns count 0 for that utterance and leaves the others untouched.
+ * Limits (EESEN_ERR_INVALID): 1 <= beam <= 64, 1 <= max_classes <= 64, beam * max_classes <= 2048, 1 <= nbest <= beam, K >= 2,
+ * ld >= K, S * (1 + T * beam) <= 2^30.
+ * The objective / error statistics and the lattices of the last eesen_ctc_eval_parallel are not touched.  With a guard
+ * (eesen_ctc_set_guard) a minibatch computed while the Net's recurrence error word was set returns score = NaN and hyp_len = -1.
+ * The call waits for its results. */
+int eesen_ctc_decode_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                              int is_log, int beam, int max_classes, int nbest,
+                              int* hyp_host /*S*nbest*T*/, int* hyp_len_host /*S*nbest*/, float* score_host /*S*nbest*/);
+/* seconds of the last eesen_ctc_decode_parallel's device work: out[0]=candidate classes (with the logarithm when is_log == 0),
+ * [1]=beam, [2]=hypotheses; summed over all calls since the last read under eesen_ctc_set_profiling(ctc, 2). */
+int eesen_ctc_get_decode_times(eesen_ctc_t* ctc, float* out3);
+/* The candidate classes the last eesen_ctc_decode_parallel selected (tests): ids_host / scores_host [rows][C'] in ascending id order,
+ * blank_host [rows], *num_classes = C'; any pointer may be NULL.  Rows beyond an utterance's length read -1 / -1e30. */
+int eesen_ctc_get_decode_candidates(eesen_ctc_t* ctc, int* ids_host, float* scores_host, float* blank_host, int* num_classes);
+
+/* LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: the count eesen_ctc_error_rate_mseq accumulates, for a
+ * host that scores hypotheses of its own (ctc-decode --ref-rspecifier).  No device work. */
+int eesen_edit_distance(const int* ref, int num_ref, const int* hyp, int num_hyp, int* errors);
 
 /* ---- CE (src/net/ce-loss.h:32-77): frame-level cross-entropy ----------------------------------- */
 int eesen_ce_create(int device, void* stream, eesen_ce_t** out);

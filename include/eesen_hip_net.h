@@ -279,6 +279,28 @@ class Ctc {
     HipCheck(eesen_ctc_align_parallel(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
                                       is_log ? 1 : 0, ids_.data(), off_.data(), ali->data(), pos ? pos->data() : NULL, score->data()));
   }
+  /* Lexicon-free prefix beam search, eesen_ctc_decode_parallel: no counterpart in src/net (the reference decodes through a TLG graph and
+   * its WFST decoder).  net_out: posteriors, or log-domain scores with is_log.  hyps[s]: the utterance's labellings, best first (at most
+   * nbest; none where the beam died); scores[s]: their log-probabilities. */
+  void DecodeParallel(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out,
+                      std::vector<std::vector<std::vector<int32> > >* hyps, std::vector<std::vector<BaseFloat> >* scores, int32 beam = 16,
+                      int32 max_classes = 20, int32 nbest = 1, bool is_log = false) {
+    const int S = (int)frame_num_utt.size();
+    const int T = S > 0 ? net_out.NumRows() / S : 0;
+    if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
+    std::vector<int32> hyp((size_t)S * nbest * T + 1), len((size_t)S * nbest + 1);
+    std::vector<BaseFloat> sc((size_t)S * nbest + 1);
+    HipCheck(eesen_ctc_decode_parallel(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                       is_log ? 1 : 0, beam, max_classes, nbest, hyp.data(), len.data(), sc.data()));
+    hyps->assign(S, std::vector<std::vector<int32> >());
+    scores->assign(S, std::vector<BaseFloat>());
+    for (int s = 0; s < S; ++s)
+      for (int i = 0; i < nbest && len[(size_t)s * nbest + i] >= 0; ++i) {
+        const int32* h = hyp.data() + ((size_t)s * nbest + i) * T;
+        (*hyps)[s].push_back(std::vector<int32>(h, h + len[(size_t)s * nbest + i]));
+        (*scores)[s].push_back(sc[(size_t)s * nbest + i]);
+      }
+  }
   void SetReportStep(int32 s) { report_step_ = s; }
   void SetFramesPerSec(float f) { frames_per_sec_ = f; }
   float NumErrorTokens() const { long e = 0; HipCheck(eesen_ctc_stats(h_, NULL, NULL, NULL, &e, NULL)); return (float)e; }   /* ctc-loss.h:62 */
