@@ -95,6 +95,14 @@ SIGNATURES = {
     "eesen_ctc_get_decode_times": (_i, [_vp, _vp]),
     "eesen_edit_distance": (_i, [_vp, _i, _vp, _i, _vp]),
     "eesen_ctc_get_decode_candidates": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "eesen_lm_create_from_arpa": (_i, [C.c_char_p, C.c_char_p, _i, C.POINTER(_vp)]),
+    "eesen_lm_destroy": (_i, [_vp]),
+    "eesen_lm_info": (_i, [_vp, _pi, _pi, _pi, _pi]),
+    "eesen_lm_step": (_i, [_vp, _i, _i, _pf, _pi]),
+    "eesen_lm_start": (_i, [_vp, _pi]),
+    "eesen_lm_final": (_i, [_vp, _i, _pf]),
+    "eesen_lm_score": (_i, [_vp, _vp, _i, _i, _pd, _pd]),
+    "eesen_ctc_decode_parallel_lm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "eesen_ce_destroy": (_i, [_vp]),
     "eesen_ce_eval_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),

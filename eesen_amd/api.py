@@ -469,6 +469,54 @@ def _net_info(net: "Net", which: int) -> str:
     return "\n".join(out) + "\n"
 
 
+class TokenLm:
+    """A token n-gram LM for Ctc.DecodeParallel(lm=...): an ARPA file over the net's own tokens compiled into a deterministic backoff
+    automaton (eesen_lm_create_from_arpa; INTEGRATION.md "LM fusion").  units: the recipes' units.txt (`symbol id` per line); without
+    it the ARPA's words are decimal class ids.  K: the net's class count, blank included.  Host only: needs no device."""
+
+    def __init__(self, arpa: str, units: Optional[str] = None, K: int = 0):
+        self.lib = _lib.load()
+        self.h = C.c_void_p()
+        self.K = int(K)
+        check(self.lib.eesen_lm_create_from_arpa(str(arpa).encode(), str(units).encode() if units else None, int(K), C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h:
+            try:
+                self.lib.eesen_lm_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def Info(self) -> dict:
+        o, st, ar, eos = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.eesen_lm_info(self.h, C.byref(o), C.byref(st), C.byref(ar), C.byref(eos)))
+        return dict(order=o.value, states=st.value, arcs=ar.value, has_eos=bool(eos.value))
+
+    def Start(self) -> int:
+        st = C.c_int()
+        check(self.lib.eesen_lm_start(self.h, C.byref(st)))
+        return st.value
+
+    def Step(self, state: int, c: int) -> Tuple[float, int]:
+        """lm_step: (ln P(c | state) as the fp32 sum the device forms, the next state)."""
+        w, nx = C.c_float(), C.c_int()
+        check(self.lib.eesen_lm_step(self.h, int(state), int(c), C.byref(w), C.byref(nx)))
+        return w.value, nx.value
+
+    def Final(self, state: int) -> float:
+        w = C.c_float()
+        check(self.lib.eesen_lm_final(self.h, int(state), C.byref(w)))
+        return w.value
+
+    def Score(self, labels: Sequence[int], eos: bool = False, with_abs: bool = False):
+        """ln P_lm(labels [, </s>]) in fp64 on the stored fp32 weights; with_abs: (that, the sum of the weights' magnitudes)."""
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        v, a = C.c_double(), C.c_double()
+        check(self.lib.eesen_lm_score(self.h, _np_ptr(lab) if lab.size else None, int(lab.size), int(bool(eos)), C.byref(v), C.byref(a)))
+        return (v.value, a.value) if with_abs else v.value
+
+
 class Ctc:
     """eesen::Ctc (ctc-loss.h:31-90) for the multi-sequence path."""
 
@@ -531,21 +579,34 @@ class Ctc:
         return dict(zip(["log", "sweep", "traceback"], out.tolist()))
 
     def DecodeParallel(self, frame_num_utt: Sequence[int], net_out: CuMatrix, beam: int = 16, max_classes: int = 20, nbest: int = 1,
-                       is_log: bool = False):
+                       is_log: bool = False, lm: Optional["TokenLm"] = None, lm_weight: float = 1.0, insertion_bonus: float = 0.0,
+                       lm_eos: bool = False):
         """Lexicon-free CTC prefix beam search (eesen_ctc_decode_parallel; no counterpart in the reference's src/net).  net_out: posteriors,
         or log-domain scores with is_log=True.  Returns (hyps, scores): hyps[s] is the list of the utterance's returned labellings, best
         first, each a list of ints (at most nbest; none where the beam died); scores [S, nbest] float32, -1e30 beyond the returned
-        count (NaN under a raised guard word).  Statistics untouched."""
+        count (NaN under a raised guard word).  Statistics untouched.
+        lm: a TokenLm fused into the search (eesen_ctc_decode_parallel_lm): every label adds lm_weight * ln P_lm(label | prefix) +
+        insertion_bonus, with lm_eos lm_weight * ln P_lm(</s> | labels) joins at the end; self.lm_score [S, nbest] is then each
+        entry's unweighted ln P_lm (None without an LM).  lm=None is the plain call."""
         fn = np.ascontiguousarray(frame_num_utt, np.int32)
         S = fn.size
         T = net_out.rows // max(S, 1)
         hyp = np.empty((S, int(nbest), max(T, 0)), np.int32)
         hlen = np.empty((S, int(nbest)), np.int32)
         score = np.empty((S, int(nbest)), np.float32)
-        check(self.lib.eesen_ctc_decode_parallel(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
-                                                 int(bool(is_log)), int(beam), int(max_classes), int(nbest), _np_ptr(hyp), _np_ptr(hlen),
-                                                 _np_ptr(score)))
+        if lm is None:
+            lm_score = None
+            check(self.lib.eesen_ctc_decode_parallel(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
+                                                     int(bool(is_log)), int(beam), int(max_classes), int(nbest), _np_ptr(hyp), _np_ptr(hlen),
+                                                     _np_ptr(score)))
+        else:
+            lm_score = np.empty((S, int(nbest)), np.float32)
+            check(self.lib.eesen_ctc_decode_parallel_lm(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols,
+                                                        net_out.stride, int(bool(is_log)), int(beam), int(max_classes), int(nbest), lm.h,
+                                                        float(lm_weight), float(insertion_bonus), int(bool(lm_eos)), _np_ptr(hyp),
+                                                        _np_ptr(hlen), _np_ptr(score), _np_ptr(lm_score)))
         self.hyp, self.hyp_len = hyp, hlen          # the raw [S, nbest, T] labels (-1 beyond each length) and [S, nbest] lengths
+        self.lm_score = lm_score
         hyps = [[hyp[s, i, :hlen[s, i]].tolist() for i in range(int(nbest)) if hlen[s, i] >= 0] for s in range(S)]
         return hyps, score
 

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include <algorithm>
+#include <memory>
 
 #include "guard.h"
 #include "net.h"
@@ -267,6 +268,55 @@ int eesen_ctc_get_decode_times(eesen_ctc_t* ctc, float* out3) {
 }
 int eesen_ctc_get_decode_candidates(eesen_ctc_t* ctc, int* ids_host, float* scores_host, float* blank_host, int* num_classes) {
   return guard([&] { REQ_PTR(ctc); ctc->get_decode_candidates(ids_host, scores_host, blank_host, num_classes); });
+}
+int eesen_lm_create_from_arpa(const char* arpa_path, const char* units_path, int K, eesen_lm_t** lm) {
+  return guard([&] {
+    REQ_PTR(arpa_path); REQ_PTR(lm);
+    std::unique_ptr<eesen_lm> made(new eesen_lm);
+    made->from_arpa(arpa_path, units_path, K);
+    *lm = made.release();
+  });
+}
+int eesen_lm_destroy(eesen_lm_t* lm) {
+  return guard([&] { delete lm; });
+}
+int eesen_lm_info(eesen_lm_t* lm, int* order, int* states, int* arcs, int* has_eos) {
+  return guard([&] {
+    REQ_PTR(lm);
+    if (order) *order = lm->order;
+    if (states) *states = lm->states();
+    if (arcs) *arcs = lm->arcs();
+    if (has_eos) *has_eos = lm->has_eos ? 1 : 0;
+  });
+}
+int eesen_lm_step(eesen_lm_t* lm, int state, int c, float* w, int* next) {
+  return guard([&] { REQ_PTR(lm); REQ_PTR(w); REQ_PTR(next); lm->step(state, c, w, next); });
+}
+int eesen_lm_start(eesen_lm_t* lm, int* state) {
+  return guard([&] { REQ_PTR(lm); REQ_PTR(state); *state = lm->start; });
+}
+int eesen_lm_final(eesen_lm_t* lm, int state, float* w) {
+  return guard([&] {
+    REQ_PTR(lm); REQ_PTR(w);
+    EESEN_REQUIRE(state >= 0 && state < lm->states(), EESEN_ERR_INVALID, "LM state out of range");
+    *w = lm->fin[state];
+  });
+}
+int eesen_lm_score(eesen_lm_t* lm, const int* labels, int n, int use_eos, double* logprob_f64, double* abs_sum_f64) {
+  return guard([&] {
+    REQ_PTR(lm); REQ_PTR(logprob_f64);
+    EESEN_REQUIRE(n >= 0 && (n == 0 || labels != nullptr), EESEN_ERR_INVALID, "labels: null pointer or negative count");
+    *logprob_f64 = lm->score(labels, n, use_eos != 0, abs_sum_f64);
+  });
+}
+int eesen_ctc_decode_parallel_lm(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                                 int is_log, int beam, int max_classes, int nbest, eesen_lm_t* lm, float lm_weight, float insertion_bonus,
+                                 int use_eos, int* hyp_host, int* hyp_len_host, float* score_host, float* lm_score_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev); REQ_PTR(hyp_host); REQ_PTR(hyp_len_host); REQ_PTR(score_host);
+    ctc->decode_parallel_lm(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, beam, max_classes, nbest, lm, lm_weight, insertion_bonus,
+                            use_eos != 0, hyp_host, hyp_len_host, score_host, lm_score_host);
+  });
 }
 int eesen_edit_distance(const int* ref, int num_ref, const int* hyp, int num_hyp, int* errors) {
   return guard([&] {

@@ -3,6 +3,7 @@
 // :235-298).  The lattice arithmetic itself is in ctc.hip.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <limits>
 
@@ -219,6 +220,48 @@ void Ctc::align_times(float* out3) {
 // Prefix beam search of every utterance (INTEGRATION.md "Decoding").  The logarithms borrow `logp`; everything else is this call's own.
 void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                           int nbest, int* hyp_host, int* hyp_len_host, float* score_host) {
+  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, 0.f, 0.f, false, hyp_host, hyp_len_host, score_host, nullptr);
+}
+
+// With a token LM fused into the beam (INTEGRATION.md "LM fusion"): ctc_prefix_beam_lm in place of ctc_prefix_beam, inside the same
+// phase.  The tables are uploaded when this Ctc meets the model for the first time.
+void Ctc::decode_parallel_lm(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                             int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
+                             float* score_host, float* lm_score_host) {
+  EESEN_REQUIRE(lm != nullptr, EESEN_ERR_INVALID, "decoding with an LM: the LM handle is null");
+  EESEN_REQUIRE(lm->K == K, EESEN_ERR_INVALID, "the LM was built for another class count K than the scores have");
+  EESEN_REQUIRE(!use_eos || lm->has_eos, EESEN_ERR_INVALID, "use_eos on an LM whose file has no </s>");
+  EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(insertion_bonus), EESEN_ERR_INVALID, "lm_weight and insertion_bonus must be finite");
+  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, lm, lm_weight, insertion_bonus, use_eos, hyp_host, hyp_len_host,
+               score_host, lm_score_host);
+}
+
+void Ctc::upload_lm(const TokenLm& lm) {
+  if (lm_serial == lm.serial) return;
+  EESEN_HIP_CHECK(hipStreamSynchronize(st));   // (a launch in flight may still read the tables this replaces)
+  const size_t ns = lm.bo_w.size(), na = lm.arc_cls.size();
+  std::vector<int> packed(4 * ns + 3 * na);
+  auto bits = [](float v) { int b; std::memcpy(&b, &v, sizeof b); return b; };
+  for (size_t i = 0; i < ns; ++i) {
+    int* r = packed.data() + 4 * i;
+    r[0] = lm.arc_off[i]; r[1] = lm.arc_off[i + 1] - lm.arc_off[i]; r[2] = lm.bo_next[i]; r[3] = bits(lm.bo_w[i]);
+  }
+  for (size_t i = 0; i < na; ++i) {
+    packed[4 * ns + 2 * i] = bits(lm.arc_w[i]);
+    packed[4 * ns + 2 * i + 1] = lm.arc_next[i];
+    packed[4 * ns + 2 * na + i] = lm.arc_cls[i];
+  }
+  lm_i.reserve(packed.size());
+  lm_f.reserve(ns);
+  EESEN_HIP_CHECK(hipMemcpy(lm_i.p, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
+  EESEN_HIP_CHECK(hipMemcpy(lm_f.p, lm.fin.data(), ns * sizeof(float), hipMemcpyHostToDevice));
+  lm_tab = LmTables{lm_i.p, lm_i.p + 4 * ns, lm_i.p + 4 * ns + 2 * na, lm_f.p, lm.start};
+  lm_serial = lm.serial;
+}
+
+void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                       int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
+                       float* score_host, float* lm_score_host) {
   EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
   EESEN_REQUIRE(K >= 2, EESEN_ERR_INVALID, "decoding needs the blank and at least one other class (K >= 2)");
   EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
@@ -232,8 +275,8 @@ void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, 
   EESEN_HIP_CHECK(hipSetDevice(device));
   const int B = beam, N = nbest, Cc = std::min(max_classes, K - 1);
   const size_t n_cand = (size_t)rows * Cc, n_beam = (size_t)S * B, n_trie = (size_t)S * (1 + (size_t)T * B);
-  const size_t n_f = n_cand + rows + n_beam, n_i = n_cand + S + 2 * n_beam + S;
-  const size_t n_hyp = (size_t)S * N * T, n_out = n_hyp + 2 * (size_t)S * N;   // labels, lengths, scores
+  const size_t n_f = n_cand + rows + n_beam + (lm ? n_beam : 0), n_i = n_cand + S + 2 * n_beam + S;
+  const size_t n_hyp = (size_t)S * N * T, n_out = n_hyp + (lm ? 3 : 2) * (size_t)S * N;   // labels, lengths, scores (, LM sums)
   EESEN_REQUIRE(n_trie <= ((size_t)1 << 30), EESEN_ERR_INVALID, "decoding: more than 2^30 trie nodes (S * (1 + T * beam)): decode fewer utterances together");
   if ((!is_log && logp.cap < (size_t)rows * K) || dec_f.cap < n_f || dec_i.cap < n_i || dec_trie.cap < 2 * n_trie || dec_out.cap < n_out)
     EESEN_HIP_CHECK(hipStreamSynchronize(st));
@@ -253,6 +296,9 @@ void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, 
   int* hyp_d = dec_out.p;
   int* len_d = hyp_d + n_hyp;
   float* score_d = reinterpret_cast<float*>(len_d + (size_t)S * N);
+  float* flm = fscore + n_beam;             // (with an LM only)
+  float* lmsum_d = score_d + (size_t)S * N;
+  if (lm) upload_lm(*lm);
 
   PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
   int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
@@ -268,9 +314,11 @@ void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, 
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
   ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
   if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
-  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, count);
+  if (lm) ctc_prefix_beam_lm(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm_tab, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, flm, count);
+  else ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, count);
   if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
   ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, count, T, S, B, N, hyp_d, len_d, score_d);
+  if (lm) ctc_rank_gather(st, flm, count, S, B, N, lmsum_d);
   if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
   dec_rows = rows; dec_S = S; dec_C = Cc;
   dec_lens.assign(frame_num_utt, frame_num_utt + S);
@@ -289,6 +337,7 @@ void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, 
   for (size_t i = 0; i < (size_t)S * N; ++i) {
     hyp_len_host[i] = bad ? -1 : out[n_hyp + i];
     score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
+    if (lm && lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[(size_t)S * N + i];
   }
 }
 

@@ -228,6 +228,15 @@ void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, 
 // count[s] live entries).  1 <= B <= 64, 1 <= Cc <= 64, B * Cc <= 2048.
 void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
                      const float* csc, const float* sblank, int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, int* count);
+struct LmTables;
+// ctc_prefix_beam_lm: the same search with a token n-gram LM fused in (INTEGRATION.md "LM fusion"; the tables: lm.h).  An extension
+// by class c adds g = alpha * w + beta, (w, next) = lm_step(the entry's LM state, c); with use_eos, alpha * fin[state] joins every
+// total after the last frame and the final beam is re-ranked.  flm [S][B]: the unweighted LM sum of each final entry.
+void ctc_prefix_beam_lm(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
+                        const float* csc, const float* sblank, const LmTables& lm, float alpha, float beta, bool use_eos, int* tparent,
+                        int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count);
+// out [S][N] = flm [S][B] of the N best entries, -1e30 beyond count[s]
+void ctc_rank_gather(hipStream_t st, const float* flm, const int* count, int S, int B, int N, float* out);
 // ctc_hyp: hyp [S][N][T] the labels of the N best entries front to back (-1 beyond the length), hyp_len / score [S][N] (-1 / -1e30
 // beyond count[s]).
 void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const int* count,

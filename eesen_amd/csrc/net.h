@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "lm.h"
 #include "tuning.h"
 
 namespace eesen {
@@ -272,6 +273,11 @@ struct Ctc {
   PinBuf decode_pin;           // results of decode_parallel (D2H)
   int dec_rows = 0, dec_S = 0, dec_C = 0;   // shape of the candidates the last decode_parallel left (get_decode_candidates)
   std::vector<int> dec_lens;
+  // the tables of the token LM the last decode_parallel_lm used (lm.h), keyed by the model's serial
+  DevBuf<int> lm_i;
+  DevBuf<float> lm_f;
+  LmTables lm_tab{};
+  unsigned long long lm_serial = 0;
   // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
   // back through PinBufs that are folded into the statistics at the next call that needs them ("deferred").
@@ -302,12 +308,20 @@ struct Ctc {
   // objective nor the error statistics, and none of the buffers of eval_parallel / align_parallel but `logp`.
   void decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                        int nbest, int* hyp_host, int* hyp_len_host, float* score_host);
+  // the same with a token n-gram LM fused into the beam (ctc_prefix_beam_lm); lm_score_host [S][nbest] may be null
+  void decode_parallel_lm(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                          int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
+                          float* score_host, float* lm_score_host);
   void decode_times(float* out3);
   // the candidate classes the last decode_parallel selected: ids / scores [rows][C'], blank [rows]; rows beyond an utterance: -1 / -1e30
   void get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc);
  private:
   struct Lattices { const int *labx, *lens, *lablens; int Lpad, Lprime; };
   Lattices upload_lattices(const int* frame_num_utt, int S, const int* label_ids, const int* label_off);
+  void decode_batch(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                    int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
+                    float* score_host, float* lm_score_host);
+  void upload_lm(const TokenLm& lm);
 };
 
 // LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: what Ctc::error_rate_mseq counts with (ctc_host.cpp)

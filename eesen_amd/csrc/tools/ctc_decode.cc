@@ -3,6 +3,7 @@
 // net-output-extract's output.  Here, per group of --num-sequence utterances: Net::Feedforward as net-output-extract does it ->
 // optional ClassPrior::SubtractOnLogpost (the options of net-output-extract) -> eesen_ctc_decode_parallel.  Written: one int32 vector
 // per hypothesis, the labels (blank-free); with --nbest > 1 under the keys utt-1, utt-2, ... (as lattice-to-nbest names them).
+// With --lm a token n-gram LM (an ARPA file over the net's tokens) is fused into the search: eesen_ctc_decode_parallel_lm.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -32,8 +33,9 @@ std::string fmt9(double v) {
 
 int main(int argc, char** argv) {
   try {
-    std::string class_frame_counts, scores_out, ref_rspecifier;
-    float prior_scale = 1.f;
+    std::string class_frame_counts, scores_out, ref_rspecifier, lm_arpa, lm_units;
+    float prior_scale = 1.f, lm_weight = 1.f, insertion_bonus = 0.f;
+    bool lm_eos = false;
     double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
     int num_sequence = 1, device = 0, beam = 16, max_classes = 20, nbest = 1;
     std::string use_gpu = "yes";
@@ -54,6 +56,11 @@ int main(int argc, char** argv) {
     po.Register("nbest", &nbest, "Hypotheses written per utterance (1 .. beam)");
     po.Register("scores-out", &scores_out, "Also write `key log-probability` text lines, one per hypothesis, to this file");
     po.Register("ref-rspecifier", &ref_rspecifier, "Reference label sequences: the token errors of the best hypotheses against them are counted");
+    po.Register("lm", &lm_arpa, "ARPA file of a token n-gram LM (its words: the symbols of --lm-units, or class ids) fused into the search");
+    po.Register("lm-units", &lm_units, "units.txt of the LM's words: `symbol id` per line; without it the ARPA's words are decimal class ids");
+    po.Register("lm-weight", &lm_weight, "Weight of the LM's log-probability of every label");
+    po.Register("insertion-bonus", &insertion_bonus, "Added per label, in nats");
+    po.Register("lm-eos", &lm_eos, "Add the weighted log-probability of </s> at the end of every hypothesis");
     po.Register("use-gpu", &use_gpu, "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)");
     po.Register("num-sequence", &num_sequence, "Utterances forwarded and decoded together");
     po.Register("frame-limit", &frame_limit, "Max number of frames forwarded together");
@@ -77,6 +84,9 @@ int main(int argc, char** argv) {
     int D = 0, K = 0;
     ck(eesen_net_input_dim(net, &D));
     ck(eesen_net_output_dim(net, &K));
+    eesen_lm_t* lm = nullptr;
+    if (!lm_arpa.empty()) ck(eesen_lm_create_from_arpa(lm_arpa.c_str(), lm_units.empty() ? nullptr : lm_units.c_str(), K, &lm));
+    else if (!lm_units.empty()) throw std::runtime_error("--lm-units without --lm");
     std::vector<float> log_pri;
     if (!class_frame_counts.empty()) {
       log_pri = class_log_priors(class_frame_counts, prior_cutoff, blank_scale);
@@ -102,12 +112,13 @@ int main(int argc, char** argv) {
       if (!scores) throw std::runtime_error("cannot open " + scores_out);
     }
     long num_done = 0, num_empty = 0, num_dead = 0, tok_err = 0, tok_ref = 0, num_scored = 0;
-    double tot_t = 0, tot_score = 0;
+    double tot_t = 0, tot_score = 0, tot_lm = 0;
+    long tot_labels = 0;
     std::vector<std::pair<std::string, Mat>> group;
     std::vector<int> out_frames;            // per utterance of the group: frames behind the pipeline
     std::vector<const float*> cmvn;
     std::vector<int> hyp, hyp_len;
-    std::vector<float> score;
+    std::vector<float> score, lm_score;
     auto flush = [&]() {
       const int S = (int)group.size();
       std::vector<const float*> ptr(S);
@@ -126,8 +137,14 @@ int main(int argc, char** argv) {
       if (!log_pri.empty())
         ck(eesen_op_log_sub_prior(device, nullptr, const_cast<float*>(out), T * S, K, old, 1, log_pri.data(), prior_scale));
       hyp.resize((size_t)S * nbest * T); hyp_len.resize((size_t)S * nbest); score.resize((size_t)S * nbest);
-      ck(eesen_ctc_decode_parallel(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, hyp.data(),
-                                   hyp_len.data(), score.data()));
+      if (lm) {
+        lm_score.resize((size_t)S * nbest);
+        ck(eesen_ctc_decode_parallel_lm(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, lm, lm_weight,
+                                        insertion_bonus, lm_eos ? 1 : 0, hyp.data(), hyp_len.data(), score.data(), lm_score.data()));
+      } else {
+        ck(eesen_ctc_decode_parallel(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, hyp.data(),
+                                     hyp_len.data(), score.data()));
+      }
       for (int s = 0; s < S; ++s) {
         const std::string& utt = group[s].first;
         const size_t e0 = (size_t)s * nbest;
@@ -141,7 +158,11 @@ int main(int argc, char** argv) {
         for (int i = 0; i < nbest && hyp_len[e0 + i] >= 0; ++i) {
           const std::string key = nbest > 1 ? utt + "-" + std::to_string(i + 1) : utt;
           writer.Write(key, hyp.data() + (e0 + i) * T, hyp_len[e0 + i]);
-          if (scores.is_open()) scores << key << ' ' << fmt9(score[e0 + i]) << '\n';
+          if (scores.is_open()) {
+            scores << key << ' ' << fmt9(score[e0 + i]);
+            if (lm) scores << ' ' << fmt9(lm_score[e0 + i]);
+            scores << '\n';
+          }
         }
         const auto ref = refs.find(utt);
         if (ref != refs.end()) {
@@ -153,6 +174,7 @@ int main(int argc, char** argv) {
         if (hyp_len[e0] == 0) ++num_empty;
         tot_t += frames[s];
         tot_score += score[e0];
+        if (lm) { tot_lm += lm_score[e0]; tot_labels += hyp_len[e0]; }
       }
       group.clear(); out_frames.clear(); cmvn.clear();
     };
@@ -195,7 +217,10 @@ int main(int argc, char** argv) {
     }
     if (num_dead) std::cerr << "LOG (ctc-decode:main()) " << num_dead << " utterances without a hypothesis" << std::endl;
     std::cerr << "LOG (ctc-decode:main()) Done " << num_done << " utterances, " << num_empty << " empty hypotheses; average log-probability per frame "
-              << (tot_t > 0 ? tot_score / tot_t : 0.0) << std::endl;
+              << (tot_t > 0 ? tot_score / tot_t : 0.0);
+    if (lm) std::cerr << "; average LM log-probability per label " << (tot_labels > 0 ? tot_lm / tot_labels : 0.0);
+    std::cerr << std::endl;
+    if (lm) eesen_lm_destroy(lm);
     eesen_ctc_destroy(ctc);
     eesen_feeder_destroy(feeder);
     eesen_net_destroy(net);

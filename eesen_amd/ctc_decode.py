@@ -8,6 +8,7 @@ e.g.:  python -m eesen_amd.ctc_decode --num-sequence=20 --beam=16 final.nnet scp
 The reference has no such tool: it decodes ONE utterance per process through a TLG graph and its WFST decoder.  Per group of
 --num-sequence utterances: forward pass as net-output-extract -> optional log + prior subtraction (net-output-extract's options) ->
 Ctc.DecodeParallel.  Written: one int32 vector per hypothesis, the labels (blank-free); with --nbest > 1 under the keys utt-1, utt-2, ...
+With --lm a token n-gram LM (an ARPA file over the net's tokens) is fused into the search (api.TokenLm).
 """
 from __future__ import annotations
 
@@ -34,6 +35,11 @@ def main(argv=None) -> int:
     ap.register("nbest", 1, "Hypotheses written per utterance (1 .. beam)")
     ap.register("scores-out", "", "Also write `key log-probability` text lines, one per hypothesis, to this file")
     ap.register("ref-rspecifier", "", "Reference label sequences: the token errors of the best hypotheses against them are counted")
+    ap.register("lm", "", "ARPA file of a token n-gram LM (its words: the symbols of --lm-units, or class ids) fused into the search")
+    ap.register("lm-units", "", "units.txt of the LM's words: `symbol id` per line; without it the ARPA's words are decimal class ids")
+    ap.register("lm-weight", 1.0, "Weight of the LM's log-probability of every label")
+    ap.register("insertion-bonus", 0.0, "Added per label, in nats")
+    ap.register("lm-eos", False, "Add the weighted log-probability of </s> at the end of every hypothesis")
     ap.register("use-gpu", "yes", "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)")
     ap.register("num-sequence", 1, "Utterances forwarded and decoded together")
     ap.register("frame-limit", 1e5, "Max number of frames forwarded together", kind="double")
@@ -58,7 +64,7 @@ def main(argv=None) -> int:
         import ctypes as C
         import numpy as np
         from eesen_amd import kaldi_io, _lib, frontend
-        from eesen_amd.api import Net, Ctc
+        from eesen_amd.api import Net, Ctc, TokenLm
         from eesen_amd.batching import interleave
         from eesen_amd.net_output_extract import class_log_priors
 
@@ -71,6 +77,11 @@ def main(argv=None) -> int:
         ctc.SetGuard(net)           # hypotheses of a timed-out forward pass come back as NaN, never as table entries
         log_pri = class_log_priors(o.class_frame_counts, o.prior_cutoff, o.blank_scale) if o.class_frame_counts else None
         K = net.OutputDim()
+        lm = None
+        if o.lm:
+            lm = TokenLm(o.lm, o.lm_units or None, K=K)
+        elif o.lm_units:
+            raise kaldi_io.KaldiIOError("--lm-units without --lm")
         if log_pri is not None and log_pri.size != K:
             raise kaldi_io.KaldiIOError(f"Dimensionality mismatch, class_frame_counts {log_pri.size} class_output_llk {K}")
         refs = kaldi_io.read_vec_int_table(o.ref_rspecifier) if o.ref_rspecifier else {}
@@ -80,7 +91,7 @@ def main(argv=None) -> int:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
             feeder.set_pipeline(pipe.stages)
-        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0)
+        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0)
         scores = open(o.scores_out, "w") if o.scores_out else None
         lib = _lib.load()
 
@@ -101,7 +112,9 @@ def main(argv=None) -> int:
             if log_pri is not None:
                 _lib.check(lib.eesen_op_log_sub_prior(o.device, None, C.c_void_p(out.ptr), out.rows, out.cols, out.stride, 1,
                                                       log_pri.ctypes.data_as(C.c_void_p), o.prior_scale))
-            hyps, score = ctc.DecodeParallel(lens, out, beam=o.beam, max_classes=o.max_classes, nbest=o.nbest, is_log=log_pri is not None)
+            hyps, score = ctc.DecodeParallel(lens, out, beam=o.beam, max_classes=o.max_classes, nbest=o.nbest, is_log=log_pri is not None,
+                                             lm=lm, lm_weight=o.lm_weight, insertion_bonus=o.insertion_bonus, lm_eos=o.lm_eos)
+            lm_score = ctc.lm_score
             for s, (key, m) in enumerate(group):
                 frames = int(lens[s])
                 if math.isnan(score[s, 0]):
@@ -113,7 +126,7 @@ def main(argv=None) -> int:
                 for i, h in enumerate(hyps[s]):
                     k = f"{key}-{i + 1}" if o.nbest > 1 else key
                     if scores:
-                        scores.write(f"{k} {float(score[s, i]):.9g}\n")
+                        scores.write(f"{k} {float(score[s, i]):.9g}" + (f" {float(lm_score[s, i]):.9g}" if lm is not None else "") + "\n")
                     yield k, np.asarray(h, np.int32)
                 if key in refs:
                     ref, best, err = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][0], np.int32), C.c_int(0)
@@ -121,6 +134,8 @@ def main(argv=None) -> int:
                     n["tok_err"] += err.value; n["tok_ref"] += int(ref.size); n["scored"] += 1
                 n["done"] += 1; n["frames"] += frames; n["score"] += float(score[s, 0])
                 n["empty"] += len(hyps[s][0]) == 0
+                if lm is not None:
+                    n["lm"] += float(lm_score[s, 0]); n["labels"] += len(hyps[s][0])
 
         def produce():
             group, max_len = [], 0
@@ -142,7 +157,8 @@ def main(argv=None) -> int:
         if n["dead"]:
             log(f"{n['dead']} utterances without a hypothesis")
         avg = n["score"] / n["frames"] if n["frames"] else 0.0
-        log(f"Done {n['done']} utterances, {n['empty']} empty hypotheses; average log-probability per frame {avg:g}")
+        tail = f"; average LM log-probability per label {(n['lm'] / n['labels'] if n['labels'] else 0.0):g}" if lm is not None else ""
+        log(f"Done {n['done']} utterances, {n['empty']} empty hypotheses; average log-probability per frame {avg:g}{tail}")
         return 0 if n["done"] else 255
     except Exception as e:
         print(f"ERROR (ctc-decode:main()) {e}", file=sys.stderr)

@@ -42,6 +42,7 @@ extern "C" {
 typedef struct eesen_net eesen_net_t; /* replaces eesen::Net, src/net/net.h:37-175           */
 typedef struct eesen_ctc eesen_ctc_t; /* replaces eesen::Ctc, src/net/ctc-loss.h:31-90       */
 typedef struct eesen_ce eesen_ce_t;   /* replaces eesen::CE, src/net/ce-loss.h:32-77          */
+typedef struct eesen_lm eesen_lm_t;   /* a token n-gram LM for eesen_ctc_decode_parallel_lm (no counterpart) */
 
 /* ---- library / device ------------------------------------------------------------------------ */
 const char* eesen_last_error(void);
@@ -373,6 +374,49 @@ int eesen_ctc_get_decode_times(eesen_ctc_t* ctc, float* out3);
 /* The candidate classes the last eesen_ctc_decode_parallel selected (tests): ids_host / scores_host [rows][C'] in ascending id order,
  * blank_host [rows], *num_classes = C'; any pointer may be NULL.  Rows beyond an utterance's length read -1 / -1e30. */
 int eesen_ctc_get_decode_candidates(eesen_ctc_t* ctc, int* ids_host, float* scores_host, float* blank_host, int* num_classes);
+
+/* ---- token n-gram LM, fused into the prefix beam search (INTEGRATION.md "Decoding", "LM fusion") ---------------------------------
+ * An ARPA file whose words are the net's own tokens, compiled on the host into a deterministic backoff automaton.  units_path: the
+ * recipes' units.txt (`symbol id` per line, ids in [1, K), blank 0 implied), or NULL: the ARPA's words are decimal class ids then.
+ * A word is looked up in the units table first (the recipes have a unit spelled <UNK>), then as <s>, </s> and the LM's unknown word
+ * <unk>; any other word is an error that names it.  N-grams that predict <s> are ignored.  Values are log10 in the file and are
+ * stored as fp32 natural logarithms, float(v * ln 10).  Every class 1 .. K-1 needs a unigram; one without takes <unk>'s, and without
+ * <unk> creation fails and names the class.  The file need not be suffix-closed.
+ * The automaton: state 0 is the empty context with exactly K-1 arcs; one state per listed n-gram of order < N that does not end in
+ * </s> or <unk>; the start state is <s>'s (0 without <s>).  An arc of state h for class c carries (w, next), next = the longest
+ * suffix of h c that is a state; a state carries (bo_w, bo_next) (bo_w = 0 where the file gives none) and final = ln P(</s> | state)
+ * with the backoffs resolved (0 when the file has no </s>).
+ *   lm_step(state, c): acc = 0; while the state has no arc for c: acc += bo_w, state = bo_next; return (acc + w, next)   -- in fp32
+ * Limits (EESEN_ERR_INVALID, the message names the limit): order 1..8, states and arcs below 2^31.  A malformed file (no \data\
+ * section, a section whose count disagrees with the header, a line whose word count does not fit its section, a non-numeric value,
+ * an n-gram whose (n-1)-word prefix is not listed, an n-gram listed twice) is EESEN_ERR_INVALID with the file and line.  No device work here: the tables
+ * are uploaded by the first eesen_ctc_decode_parallel_lm of a Ctc that uses the model. */
+int eesen_lm_create_from_arpa(const char* arpa_path, const char* units_path /*or NULL*/, int K, eesen_lm_t** lm);
+int eesen_lm_destroy(eesen_lm_t* lm);
+int eesen_lm_info(eesen_lm_t* lm, int* order, int* states, int* arcs, int* has_eos);   /* any pointer may be NULL */
+int eesen_lm_step(eesen_lm_t* lm, int state, int c, float* w, int* next);
+int eesen_lm_start(eesen_lm_t* lm, int* state);
+int eesen_lm_final(eesen_lm_t* lm, int state, float* w);
+/* ln P_lm(labels [, </s>]) from the start state: the automaton walked in fp64 on the stored fp32 weights; *abs_sum_f64 (may be
+ * NULL) the sum of the magnitudes of the weights on the walk.  use_eos on a model without </s> is EESEN_ERR_INVALID. */
+int eesen_lm_score(eesen_lm_t* lm, const int* labels, int n, int use_eos, double* logprob_f64, double* abs_sum_f64);
+/* eesen_ctc_decode_parallel with the LM fused in (shallow fusion): lm_weight = alpha, insertion_bonus = beta in nats per label.
+ * Only this changes in the computation stated there: an entry also carries its LM state and lmsum, the unweighted ln P_lm of its
+ * prefix (the empty prefix: the start state, 0).  For the extension p + c: (w, next) = lm_step(state_p, c), g = alpha * w + beta,
+ * lnb' = (s_t(c) + g) + (c == e ? lb : tot) with both sums clamped at -1e30 -- alpha = beta = 0 reproduces the unfused bits --,
+ * the new entry has state next and lmsum_p + w.  A merged extension brings the same lnb' into q's stay; q keeps its own state and
+ * sum.  Selection order and tie rule are unchanged.  After frame n-1 with use_eos: total += alpha * final[state] (clamped at
+ * -1e30), lmsum += final[state], and the live entries are re-ranked by the new total, ties by the previous rank.  n == 0 returns
+ * the empty labelling with score alpha * final[start] (0 without use_eos).  The score of a result is
+ *   ln(sum over its paths of P_ac) + alpha * ln P_lm(labels [, </s>]) + beta * |labels|.
+ * Outputs as eesen_ctc_decode_parallel; lm_score_host [S][nbest] (may be NULL): each entry's lmsum, -1e30 beyond the returned
+ * count (NaN under a raised guard word).  EESEN_ERR_INVALID besides that call's limits: lm == NULL, an LM built for another K,
+ * use_eos on an LM without </s>, a non-finite lm_weight or insertion_bonus.  eesen_ctc_get_decode_times (the LM lookups are part
+ * of the beam phase) and eesen_ctc_get_decode_candidates work after either call. */
+int eesen_ctc_decode_parallel_lm(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                                 int is_log, int beam, int max_classes, int nbest, eesen_lm_t* lm, float lm_weight,
+                                 float insertion_bonus, int use_eos, int* hyp_host /*S*nbest*T*/, int* hyp_len_host /*S*nbest*/,
+                                 float* score_host /*S*nbest*/, float* lm_score_host /*S*nbest or NULL*/);
 
 /* LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: the count eesen_ctc_error_rate_mseq accumulates, for a
  * host that scores hypotheses of its own (ctc-decode --ref-rspecifier).  No device work. */

@@ -229,6 +229,37 @@ class Net {
   bool attached_;
 };
 
+/* A token n-gram LM for Ctc::DecodeParallel (eesen_lm_*; no counterpart in the reference, whose LM lives in the G of its TLG graphs):
+ * an ARPA file whose words are the net's own tokens -- the symbols of units.txt, or decimal class ids when `units` is empty --
+ * compiled on the host into a backoff automaton.  num_classes: the net's output dimension, blank included. */
+class TokenLm {
+ public:
+  TokenLm(const std::string& arpa, const std::string& units, int32 num_classes) : h_(NULL) {
+    HipCheck(eesen_lm_create_from_arpa(arpa.c_str(), units.empty() ? NULL : units.c_str(), num_classes, &h_));
+  }
+  ~TokenLm() { if (h_) eesen_lm_destroy(h_); }
+  int32 Order() const { int v = 0; HipCheck(eesen_lm_info(h_, &v, NULL, NULL, NULL)); return v; }
+  int32 NumStates() const { int v = 0; HipCheck(eesen_lm_info(h_, NULL, &v, NULL, NULL)); return v; }
+  int32 NumArcs() const { int v = 0; HipCheck(eesen_lm_info(h_, NULL, NULL, &v, NULL)); return v; }
+  bool HasEos() const { int v = 0; HipCheck(eesen_lm_info(h_, NULL, NULL, NULL, &v)); return v != 0; }
+  int32 Start() const { int v = 0; HipCheck(eesen_lm_start(h_, &v)); return v; }
+  /* lm_step: ln P(c | state) as the fp32 sum the device forms; *next: the state after c */
+  BaseFloat Step(int32 state, int32 c, int32* next) const { float w = 0; int n = 0; HipCheck(eesen_lm_step(h_, state, c, &w, &n)); *next = n; return w; }
+  BaseFloat Final(int32 state) const { float w = 0; HipCheck(eesen_lm_final(h_, state, &w)); return w; }
+  /* ln P(labels [, </s>]) in double on the stored weights */
+  double Score(const std::vector<int32>& labels, bool eos = false) const {
+    double v = 0;
+    HipCheck(eesen_lm_score(h_, labels.empty() ? NULL : labels.data(), (int)labels.size(), eos ? 1 : 0, &v, NULL));
+    return v;
+  }
+  eesen_lm_t* Handle() const { return h_; }
+
+ private:
+  TokenLm(const TokenLm&);
+  TokenLm& operator=(const TokenLm&);
+  eesen_lm_t* h_;
+};
+
 /* eesen::Ctc (src/net/ctc-loss.h:29-90), the multi-sequence entry points */
 class Ctc {
  public:
@@ -299,6 +330,32 @@ class Ctc {
         const int32* h = hyp.data() + ((size_t)s * nbest + i) * T;
         (*hyps)[s].push_back(std::vector<int32>(h, h + len[(size_t)s * nbest + i]));
         (*scores)[s].push_back(sc[(size_t)s * nbest + i]);
+      }
+  }
+  /* The same search with a token LM fused in, eesen_ctc_decode_parallel_lm: every label adds lm_weight * ln P_lm(label | prefix) +
+   * insertion_bonus; with use_eos lm_weight * ln P_lm(</s> | labels) joins at the end.  lm_scores (may be NULL): per returned entry
+   * the unweighted ln P_lm of its labels. */
+  void DecodeParallel(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out, const TokenLm& lm, float lm_weight,
+                      float insertion_bonus, bool use_eos, std::vector<std::vector<std::vector<int32> > >* hyps,
+                      std::vector<std::vector<BaseFloat> >* scores, std::vector<std::vector<BaseFloat> >* lm_scores = NULL, int32 beam = 16,
+                      int32 max_classes = 20, int32 nbest = 1, bool is_log = false) {
+    const int S = (int)frame_num_utt.size();
+    const int T = S > 0 ? net_out.NumRows() / S : 0;
+    if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
+    std::vector<int32> hyp((size_t)S * nbest * T + 1), len((size_t)S * nbest + 1);
+    std::vector<BaseFloat> sc((size_t)S * nbest + 1), lsc((size_t)S * nbest + 1);
+    HipCheck(eesen_ctc_decode_parallel_lm(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                          is_log ? 1 : 0, beam, max_classes, nbest, lm.Handle(), lm_weight, insertion_bonus, use_eos ? 1 : 0,
+                                          hyp.data(), len.data(), sc.data(), lsc.data()));
+    hyps->assign(S, std::vector<std::vector<int32> >());
+    scores->assign(S, std::vector<BaseFloat>());
+    if (lm_scores) lm_scores->assign(S, std::vector<BaseFloat>());
+    for (int s = 0; s < S; ++s)
+      for (int i = 0; i < nbest && len[(size_t)s * nbest + i] >= 0; ++i) {
+        const int32* h = hyp.data() + ((size_t)s * nbest + i) * T;
+        (*hyps)[s].push_back(std::vector<int32>(h, h + len[(size_t)s * nbest + i]));
+        (*scores)[s].push_back(sc[(size_t)s * nbest + i]);
+        if (lm_scores) (*lm_scores)[s].push_back(lsc[(size_t)s * nbest + i]);
       }
   }
   void SetReportStep(int32 s) { report_step_ = s; }
