@@ -1,11 +1,12 @@
 // ctc_decode.hip -- lexicon-free CTC prefix beam search over a padded utterance batch, for gfx950.
 //
 // No counterpart in the reference, which decodes one utterance per process through a TLG graph and its WFST decoder.  The
-// computation is stated in INTEGRATION.md "Decoding" and restated in numpy in tests/ctc_beam_restatement.py.  Three launches per
-// minibatch, none per frame:
+// computation is stated in INTEGRATION.md "Decoding" and "LM fusion" and restated in numpy in tests/ctc_beam_restatement.py and
+// tests/ctc_lm_restatement.py.  Three launches per minibatch, with or without a token n-gram LM fused into the beam, none per frame:
 //   ctc_row_topc_kernel     one wavefront per row: the C' best non-blank classes (ascending id), their scores, the blank's score
 //   ctc_prefix_beam_kernel  one workgroup per utterance walks its n frames: beam state and the frame's candidate keys in LDS, the trie
-//                           of surviving prefixes written (never read) to global memory
+//                           of surviving prefixes written (never read) to global memory; <false> the plain search, <true> the
+//                           LM-fused one: one text, and the LM's arguments, LDS and barrier exist in <true> only
 //   ctc_hyp_kernel          one lane per (utterance, rank) walks the trie to the root
 // Every log-mass is an fp32 value in [-1e30, +inf): sums are clamped from below at the library's finite sentinel, so the sweep's
 // branch-free log-add (ctc.hip: LogAPlusB_fast) is exact on the special cases here too.
@@ -115,6 +116,42 @@ struct BeamState {
   unsigned long long hash[kMaxBeam];   // fingerprint of the labels
 };
 
+// What the fused search has and the plain one has not, as arguments (flm [S][B]: the LM sum of each final entry)
+template <bool LM> struct LmArgs {};
+template <> struct LmArgs<true> { LmTables tab; float alpha, beta; int use_eos; float* flm; };
+// first index in [lo, hi) of the ascending v whose value is >= x; hi if there is none
+__device__ __forceinline__ int lower_bound(const int* __restrict__ v, int lo, int hi, int x) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (v[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// lm_step of lm.h on the device copy of the tables (read-only global memory), as TokenLm::step does it on the host.  A level is the
+// state's record (one 16-byte load), a bisection of its sorted arc list, and on a hit the arc's (w, next) pair (one 8-byte load);
+// state 0 is an index.  Every lane walks a state and a class of its own, so each load is up to 64 scattered requests, and the pass
+// is paid by their number (profiles/ctc_decode_lm.md).  The backoff chain of a compiled model ends in state 0; the level bound only
+// keeps a walk over tables that are not a model's from running on.
+__device__ __forceinline__ void lm_step(const LmTables& L, int state, int c, float& w, int& next) {
+  const int4* __restrict__ rec = reinterpret_cast<const int4*>(L.state_rec);
+  const int2* __restrict__ wn = reinterpret_cast<const int2*>(L.arc_wn);
+  const int* __restrict__ cls = L.arc_cls;
+  float acc = 0.f;
+  int at = c - 1;   // state 0's arc of class c
+  for (int level = 0; level < 8 && state != 0; ++level) {
+    const int4 r = rec[state];
+    const int end = r.x + r.y;
+    const int lo = lower_bound(cls, r.x, end, c);
+    if (lo < end && cls[lo] == c) { at = lo; break; }
+    acc = __fadd_rn(acc, __int_as_float(r.w));
+    state = r.z;
+  }
+  const int2 a = wn[at];
+  w = __fadd_rn(acc, __int_as_float(a.x));
+  next = a.y;
+}
+
 // Between two sort stages whose strides are both <= 64 a wave re-reads only what it wrote itself (pair q of a stage touches the
 // 128-element block q / 64, and a wave keeps its pairs from stage to stage): LDS operations of one wave execute in order, so
 // only the compiler's schedule has to be pinned.
@@ -128,19 +165,27 @@ __device__ __forceinline__ void sort_sync(bool wave_local) {
 }
 
 // Grid (S), 64 .. 512 threads.  Frame t of an utterance, between workgroup barriers:
+//   0  LM only: one thread per (entry, candidate), nb * C' <= 2048 of them: (w, next) = lm_step(entry's LM state, class) into LDS --
+//      the only LM lookups of the frame; steps 1, 2 and 4 read w from there and form g = alpha * w + beta
 //   1  entry q < nb: its stay candidate; the extension that spells q (found by fingerprint) is log-added into it and marked merged
 //   2  the nb * C' extensions write their keys behind the stays; the key array is padded with dead keys to a power of two
 //   3  bitonic sort of the keys (workgroup barriers only around strides >= 128)
 //   4  rank r < B takes key r: a stay copies its entry, an extension becomes trie node 1 + t * B + r
 // The next frame's candidates and the scores of the labels an entry can end in next (its own last label or one of this frame's
 // candidates) are fetched at the top of the frame and land in LDS just before step 4, off the dependent chain.
+// LM: shallow fusion (INTEGRATION.md "LM fusion").  An extension's value is score_add(score_add(s_t(c), g), c == e ? lb : tot), the
+// plain one's score_add(s_t(c), ...): alpha = beta = 0 gives the plain bits.  An entry carries its LM state and the unweighted sum of
+// its prefix's LM weights; a stay keeps both.  After the last frame, with use_eos, alpha * fin[state] joins every total (fin into
+// the LM sum) and the live entries are re-ranked, ties by the previous rank.  Static LDS: the plain 38.5 KiB + 2 x 8 KiB (w, next)
+// + 1 KiB of LM state = 55.5 KiB of the 64.
+template <bool LM>
 __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __restrict__ sc, int ld, int T, int S,
                                                               const int* __restrict__ lens, int B, int Cc,
                                                               const int* __restrict__ cid_g, const float* __restrict__ csc_g,
-                                                              const float* __restrict__ sblank_g, int* __restrict__ tparent,
-                                                              int* __restrict__ tlabel, int* __restrict__ fnode,
-                                                              int* __restrict__ flen, float* __restrict__ fscore,
-                                                              int* __restrict__ count) {
+                                                              const float* __restrict__ sblank_g, LmArgs<LM> lm,
+                                                              int* __restrict__ tparent, int* __restrict__ tlabel,
+                                                              int* __restrict__ fnode, int* __restrict__ flen,
+                                                              float* __restrict__ fscore, int* __restrict__ count) {
   __shared__ unsigned long long keys[kMaxKeys];
   __shared__ BeamState st[2];
   __shared__ float stay_lb[kMaxBeam], stay_lnb[kMaxBeam], nx_stay[kMaxBeam], nx_ext[kMaxCls];
@@ -148,6 +193,11 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
   __shared__ float c_sc[2][kMaxCls], c_bl[2];
   __shared__ unsigned long long merged[kMaxBeam];   // per entry: which of its extensions went into another entry's stay
   __shared__ int nb_sh;
+  // the fused search's alone (17 KiB): the plain instantiation never names them, and what is not named is not allocated
+  __shared__ int lm_state[2][kMaxBeam];     // the entry's LM state
+  __shared__ float lm_sum[2][kMaxBeam];     // ln P_lm of its prefix, unweighted
+  __shared__ float ext_w[kMaxKeys / 2];     // this frame's lm_step of (entry p, candidate ci) at p * C' + ci
+  __shared__ int ext_next[kMaxKeys / 2];
   const int s = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   const int n = min(lens[s], T);
   const size_t cap = 1 + (size_t)T * B;
@@ -156,6 +206,7 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
   if (tid == 0) {
     st[0].lb[0] = 0.f; st[0].lnb[0] = kLogZero; st[0].se[0] = kLogZero;
     st[0].node[0] = 0; st[0].last[0] = -1; st[0].len[0] = 0; st[0].hash[0] = 0;
+    if constexpr (LM) { lm_state[0][0] = lm.tab.start; lm_sum[0][0] = 0.f; }
     nb_sh = 1;
     tp[0] = -1; tl[0] = -1;
     if (n > 0) c_bl[0] = sblank_g[s];
@@ -175,10 +226,14 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
     const int* ci_ = c_id[t & 1];
     const float* cs_ = c_sc[t & 1];
     const float bl = c_bl[t & 1];
-    // extension of entry p by candidate ci
+    const int n_ext = nb * Cc;
+    // extension of entry p by candidate ci (g is named before s_t(c): the compiler's schedule follows, profiles/ctc_decode_lm.md)
     auto ext_value = [&](int p, int ci) -> float {
       const float lb = a.lb[p], lnb = a.lnb[p];
-      return score_add(cs_[ci], ci_[ci] == a.last[p] ? lb : log_add(lb, lnb));
+      float g = 0.f;
+      if constexpr (LM) g = __fadd_rn(__fmul_rn(lm.alpha, ext_w[p * Cc + ci]), lm.beta);
+      const float cs = LM ? score_add(cs_[ci], g) : cs_[ci];
+      return score_add(cs, ci_[ci] == a.last[p] ? lb : log_add(lb, lnb));
     };
     // in flight over the whole frame: frame t + 1 (the last frame re-reads itself, unused)
     const size_t row1 = (size_t)min(t + 1, n - 1) * S + s;
@@ -192,6 +247,17 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
     if (tid < nb && a.last[tid] >= 0) pf_stay = sc[row1 * ld + a.last[tid]];
     if (tid == 0) pf_bl = sblank_g[row1];
 
+    if constexpr (LM) {   // ---- 0
+      for (int x = tid; x < n_ext; x += NT) {
+        const int p = x / Cc, ci = x - p * Cc;
+        float w;
+        int next;
+        lm_step(lm.tab, lm_state[cur][p], ci_[ci], w, next);
+        ext_w[x] = w;
+        ext_next[x] = next;
+      }
+      __syncthreads();
+    }
     if (tid < nb) {   // ---- 1
       const int q = tid, e = a.last[q];
       const float lb = a.lb[q], lnb = a.lnb[q];
@@ -204,11 +270,7 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
         for (int i = 0; i < nb; ++i)
           if (a.hash[i] == ph && a.len[i] == plen) p = i;
         if (p >= 0) {
-          int lo = 0, hi = Cc;   // first candidate id >= e
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ci_[mid] < e) lo = mid + 1; else hi = mid;
-          }
+          const int lo = lower_bound(ci_, 0, Cc, e);
           if (lo < Cc && ci_[lo] == e) {
             slnb = log_add(slnb, ext_value(p, lo));
             atomicOr(&merged[p], 1ull << lo);
@@ -221,8 +283,7 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
       keys[q] = total > kDead ? make_key(total, q) : kDeadKey;
     }
     __syncthreads();
-    const int n_ext = nb * Cc;   // ---- 2
-    int npad = 2;
+    int npad = 2;   // ---- 2
     while (npad < nb + n_ext) npad <<= 1;   // <= 64 + 2048 -> <= 4096
     for (int x = tid; x < npad - nb; x += NT) {
       unsigned long long key = kDeadKey;
@@ -263,12 +324,14 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
         if (idx < kMaxBeam) {
           nx.lb[tid] = stay_lb[idx]; nx.lnb[tid] = stay_lnb[idx]; nx.se[tid] = nx_stay[idx];
           nx.node[tid] = a.node[idx]; nx.last[tid] = a.last[idx]; nx.len[tid] = a.len[idx]; nx.hash[tid] = a.hash[idx];
+          if constexpr (LM) { lm_state[cur ^ 1][tid] = lm_state[cur][idx]; lm_sum[cur ^ 1][tid] = lm_sum[cur][idx]; }
         } else {
           const int x = idx - kMaxBeam, p = x / Cc, ci = x - p * Cc, c = ci_[ci];
           const int node = 1 + t * B + tid;   // < cap: t < n <= T, tid < B
           nx.lb[tid] = kLogZero; nx.lnb[tid] = ext_value(p, ci); nx.se[tid] = nx_ext[ci];
           nx.node[tid] = node; nx.last[tid] = c; nx.len[tid] = a.len[p] + 1;
           nx.hash[tid] = a.hash[p] * kHashMul + (unsigned long long)(c + 1);
+          if constexpr (LM) { lm_state[cur ^ 1][tid] = ext_next[x]; lm_sum[cur ^ 1][tid] = __fadd_rn(lm_sum[cur][p], ext_w[x]); }
           tp[node] = a.node[p];
           tl[node] = c;
         }
@@ -281,271 +344,61 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
     cur ^= 1;
   }
   const int nb = nb_sh;
-  if (tid < B) {
-    const BeamState& a = st[cur];
-    const bool live = tid < nb;
-    fnode[(size_t)s * B + tid] = live ? a.node[tid] : -1;
-    flen[(size_t)s * B + tid] = live ? a.len[tid] : -1;
-    fscore[(size_t)s * B + tid] = live ? log_add(a.lb[tid], a.lnb[tid]) + 0.f : kLogZero;
-  }
-  if (tid == 0) count[s] = nb;
-}
-
-// ---- the beam with a token n-gram LM fused in -----------------------------------------------------------------------------------
-// lm_step of lm.h on the device copy of the tables (read-only global memory), as TokenLm::step does it on the host.  A level is the
-// state's record (one 16-byte load), a bisection of its sorted arc list, and on a hit the arc's (w, next) pair (one 8-byte load);
-// state 0 is an index.  Every lane walks a state and a class of its own, so each load is up to 64 scattered requests, and the pass
-// is paid by their number (profiles/ctc_decode_lm.md).  The backoff chain of a compiled model ends in state 0; the level bound only
-// keeps a walk over tables that are not a model's from running on.
-__device__ __forceinline__ void lm_step(const LmTables& L, int state, int c, float& w, int& next) {
-  const int4* __restrict__ rec = reinterpret_cast<const int4*>(L.state_rec);
-  const int2* __restrict__ wn = reinterpret_cast<const int2*>(L.arc_wn);
-  const int* __restrict__ cls = L.arc_cls;
-  float acc = 0.f;
-  int at = c - 1;   // state 0's arc of class c
-  for (int level = 0; level < 8 && state != 0; ++level) {
-    const int4 r = rec[state];
-    const int end = r.x + r.y;
-    int lo = r.x, hi = end;   // first arc whose class is >= c
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (cls[mid] < c) lo = mid + 1; else hi = mid;
+  const BeamState& a = st[cur];
+  const size_t out = (size_t)s * B;
+  if constexpr (!LM) {
+    if (tid < B) {
+      const bool live = tid < nb;
+      fnode[out + tid] = live ? a.node[tid] : -1;
+      flen[out + tid] = live ? a.len[tid] : -1;
+      fscore[out + tid] = live ? log_add(a.lb[tid], a.lnb[tid]) + 0.f : kLogZero;
     }
-    if (lo < end && cls[lo] == c) { at = lo; break; }
-    acc = __fadd_rn(acc, __int_as_float(r.w));
-    state = r.z;
-  }
-  const int2 a = wn[at];
-  w = __fadd_rn(acc, __int_as_float(a.x));
-  next = a.y;
-}
-
-// ctc_prefix_beam_kernel with shallow fusion (INTEGRATION.md "LM fusion"); the unfused kernel above is left as it is and stays what
-// eesen_ctc_decode_parallel launches.  What differs, frame by frame:
-//   0  one thread per (entry, candidate), nb * C' <= 2048 of them: (w, next) = lm_step(entry's LM state, class) into LDS -- the
-//      only LM lookups of the frame; steps 1, 2 and 4 read w from there and form g = alpha * w + beta
-//   an extension's value is score_add(score_add(s_t(c), g), c == e ? lb : tot): alpha = beta = 0 gives the unfused bits
-//   4  an entry carries its LM state and the unweighted sum of its prefix's LM weights; a stay keeps both
-// After the last frame, with use_eos, alpha * fin[state] joins every total (fin into the LM sum) and the live entries are re-ranked,
-// ties by the previous rank.  Static LDS: the unfused 38.5 KiB + 2 x 8 KiB (w, next) + 1 KiB of LM state = 55.5 KiB of the 64.
-__global__ __launch_bounds__(512) void ctc_prefix_beam_lm_kernel(const float* __restrict__ sc, int ld, int T, int S,
-                                                                 const int* __restrict__ lens, int B, int Cc,
-                                                                 const int* __restrict__ cid_g, const float* __restrict__ csc_g,
-                                                                 const float* __restrict__ sblank_g, LmTables lm, float alpha,
-                                                                 float beta, int use_eos, int* __restrict__ tparent,
-                                                                 int* __restrict__ tlabel, int* __restrict__ fnode,
-                                                                 int* __restrict__ flen, float* __restrict__ fscore,
-                                                                 float* __restrict__ flm, int* __restrict__ count) {
-  __shared__ unsigned long long keys[kMaxKeys];
-  __shared__ BeamState st[2];
-  __shared__ int lm_state[2][kMaxBeam];     // the entry's LM state
-  __shared__ float lm_sum[2][kMaxBeam];     // ln P_lm of its prefix, unweighted
-  __shared__ float ext_w[kMaxKeys / 2];     // this frame's lm_step of (entry p, candidate ci) at p * C' + ci
-  __shared__ int ext_next[kMaxKeys / 2];
-  __shared__ float stay_lb[kMaxBeam], stay_lnb[kMaxBeam], nx_stay[kMaxBeam], nx_ext[kMaxCls];
-  __shared__ int c_id[2][kMaxCls];
-  __shared__ float c_sc[2][kMaxCls], c_bl[2];
-  __shared__ unsigned long long merged[kMaxBeam];
-  __shared__ int nb_sh;
-  const int s = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
-  const int n = min(lens[s], T);
-  const size_t cap = 1 + (size_t)T * B;
-  int* tp = tparent + (size_t)s * cap;
-  int* tl = tlabel + (size_t)s * cap;
-  if (tid == 0) {
-    st[0].lb[0] = 0.f; st[0].lnb[0] = kLogZero; st[0].se[0] = kLogZero;
-    st[0].node[0] = 0; st[0].last[0] = -1; st[0].len[0] = 0; st[0].hash[0] = 0;
-    lm_state[0][0] = lm.start; lm_sum[0][0] = 0.f;
-    nb_sh = 1;
-    tp[0] = -1; tl[0] = -1;
-    if (n > 0) c_bl[0] = sblank_g[s];
-  }
-  if (tid < kMaxBeam) merged[tid] = 0;
-  if (n > 0 && tid < Cc) {
-    c_id[0][tid] = cid_g[(size_t)s * Cc + tid];
-    c_sc[0][tid] = csc_g[(size_t)s * Cc + tid];
-  }
-  __syncthreads();
-  int cur = 0;
-  for (int t = 0; t < n; ++t) {
-    const int nb = nb_sh;
-    if (nb == 0) break;   // the beam died (uniform): possible only with is_log input
-    const BeamState& a = st[cur];
-    BeamState& nx = st[cur ^ 1];
-    const int* ci_ = c_id[t & 1];
-    const float* cs_ = c_sc[t & 1];
-    const float bl = c_bl[t & 1];
-    const int n_ext = nb * Cc;
-    // extension of entry p by candidate ci
-    auto ext_value = [&](int p, int ci) -> float {
-      const float lb = a.lb[p], lnb = a.lnb[p];
-      const float g = __fadd_rn(__fmul_rn(alpha, ext_w[p * Cc + ci]), beta);
-      return score_add(score_add(cs_[ci], g), ci_[ci] == a.last[p] ? lb : log_add(lb, lnb));
-    };
-    // in flight over the whole frame: frame t + 1 (the last frame re-reads itself, unused)
-    const size_t row1 = (size_t)min(t + 1, n - 1) * S + s;
-    int pf_id = 0;
-    float pf_sc = 0.f, pf_ext = 0.f, pf_stay = kLogZero, pf_bl = 0.f;
-    if (tid < Cc) {
-      pf_id = cid_g[row1 * Cc + tid];
-      pf_sc = csc_g[row1 * Cc + tid];
-      pf_ext = sc[row1 * ld + ci_[tid]];
-    }
-    if (tid < nb && a.last[tid] >= 0) pf_stay = sc[row1 * ld + a.last[tid]];
-    if (tid == 0) pf_bl = sblank_g[row1];
-
-    for (int x = tid; x < n_ext; x += NT) {   // ---- 0
-      const int p = x / Cc, ci = x - p * Cc;
-      float w;
-      int next;
-      lm_step(lm, lm_state[cur][p], ci_[ci], w, next);
-      ext_w[x] = w;
-      ext_next[x] = next;
-    }
-    __syncthreads();
-    if (tid < nb) {   // ---- 1
-      const int q = tid, e = a.last[q];
-      const float lb = a.lb[q], lnb = a.lnb[q];
-      const float slb = score_add(bl, log_add(lb, lnb));
-      float slnb = e >= 0 ? score_add(a.se[q], lnb) : kLogZero;
-      if (e >= 0) {
-        const unsigned long long ph = (a.hash[q] - (unsigned long long)(e + 1)) * kHashMulInv;
-        const int plen = a.len[q] - 1;
-        int p = -1;
-        for (int i = 0; i < nb; ++i)
-          if (a.hash[i] == ph && a.len[i] == plen) p = i;
-        if (p >= 0) {
-          int lo = 0, hi = Cc;   // first candidate id >= e
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (ci_[mid] < e) lo = mid + 1; else hi = mid;
-          }
-          if (lo < Cc && ci_[lo] == e) {
-            slnb = log_add(slnb, ext_value(p, lo));
-            atomicOr(&merged[p], 1ull << lo);
-          }
+  } else {
+    // the end of the utterance: fin joins, and the live entries (<= 64, best first) take the rank of their new total
+    if (tid < kMaxBeam) {
+      float total = kLogZero, lsum = kLogZero;
+      if (tid < nb) {
+        total = log_add(a.lb[tid], a.lnb[tid]) + 0.f;
+        lsum = lm_sum[cur][tid];
+        if (lm.use_eos) {
+          const float f = lm.tab.fin[lm_state[cur][tid]];
+          total = clamp_score(__fadd_rn(total, __fmul_rn(lm.alpha, f))) + 0.f;
+          lsum = __fadd_rn(lsum, f);
         }
+        keys[tid] = make_key(total, tid);
       }
-      stay_lb[q] = slb;
-      stay_lnb[q] = slnb;
-      const float total = log_add(slb, slnb) + 0.f;   // (+ 0: a -0 orders as +0)
-      keys[q] = total > kDead ? make_key(total, q) : kDeadKey;
+      stay_lb[tid] = total;
+      stay_lnb[tid] = lsum;
     }
     __syncthreads();
-    int npad = 2;   // ---- 2
-    while (npad < nb + n_ext) npad <<= 1;   // <= 64 + 2048 -> <= 4096
-    for (int x = tid; x < npad - nb; x += NT) {
-      unsigned long long key = kDeadKey;
-      if (x < n_ext) {
-        const int p = x / Cc, ci = x - p * Cc;
-        const float v = ext_value(p, ci) + 0.f;
-        if (!((merged[p] >> ci) & 1) && v > kDead) key = make_key(v, kMaxBeam + x);
-      }
-      keys[nb + x] = key;
-    }
-    __syncthreads();
-    bool first = true;   // ---- 3
-    for (int k = 2; k <= npad; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        if (!first) sort_sync(j <= 32);
-        first = false;
-        for (int q = tid; q < (npad >> 1); q += NT) {
-          const int i = 2 * q - (q & (j - 1)), l = i | j;
-          const unsigned long long x = keys[i], y = keys[l];
-          if ((x > y) == ((i & k) == 0)) { keys[i] = y; keys[l] = x; }
+    if (tid < B) {
+      if (tid < nb) {
+        int rank = tid;
+        if (lm.use_eos) {
+          rank = 0;
+          for (int i = 0; i < nb; ++i) rank += keys[i] < keys[tid];
         }
+        fnode[out + rank] = a.node[tid];
+        flen[out + rank] = a.len[tid];
+        fscore[out + rank] = stay_lb[tid];
+        lm.flm[out + rank] = stay_lnb[tid];
+      } else {
+        fnode[out + tid] = -1;
+        flen[out + tid] = -1;
+        fscore[out + tid] = kLogZero;
+        lm.flm[out + tid] = kLogZero;
       }
-    if (tid < Cc) {
-      c_id[(t + 1) & 1][tid] = pf_id;
-      c_sc[(t + 1) & 1][tid] = pf_sc;
-      nx_ext[tid] = clamp_score(pf_ext);
-    }
-    if (tid < nb) nx_stay[tid] = clamp_score(pf_stay);
-    if (tid == 0) c_bl[(t + 1) & 1] = pf_bl;
-    __syncthreads();
-    if (tid < 64) {   // ---- 4 (wave 0)
-      const unsigned long long key = (tid < B && tid < npad) ? keys[tid] : kDeadKey;
-      const bool live = key != kDeadKey;
-      if (live) {
-        const int idx = (int)(unsigned)key;
-        if (idx < kMaxBeam) {
-          nx.lb[tid] = stay_lb[idx]; nx.lnb[tid] = stay_lnb[idx]; nx.se[tid] = nx_stay[idx];
-          nx.node[tid] = a.node[idx]; nx.last[tid] = a.last[idx]; nx.len[tid] = a.len[idx]; nx.hash[tid] = a.hash[idx];
-          lm_state[cur ^ 1][tid] = lm_state[cur][idx]; lm_sum[cur ^ 1][tid] = lm_sum[cur][idx];
-        } else {
-          const int x = idx - kMaxBeam, p = x / Cc, ci = x - p * Cc, c = ci_[ci];
-          const int node = 1 + t * B + tid;   // < cap: t < n <= T, tid < B
-          nx.lb[tid] = kLogZero; nx.lnb[tid] = ext_value(p, ci); nx.se[tid] = nx_ext[ci];
-          nx.node[tid] = node; nx.last[tid] = c; nx.len[tid] = a.len[p] + 1;
-          nx.hash[tid] = a.hash[p] * kHashMul + (unsigned long long)(c + 1);
-          lm_state[cur ^ 1][tid] = ext_next[x]; lm_sum[cur ^ 1][tid] = __fadd_rn(lm_sum[cur][p], ext_w[x]);
-          tp[node] = a.node[p];
-          tl[node] = c;
-        }
-      }
-      const int alive = __popcll(__ballot(live));   // the live keys are a prefix of the sorted array
-      if (tid == 0) nb_sh = alive;
-      merged[tid] = 0;
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  const int nb = nb_sh;
-  // the end of the utterance: fin joins, and the live entries (<= 64, best first) take the rank of their new total
-  if (tid < kMaxBeam) {
-    const BeamState& a = st[cur];
-    float total = kLogZero, lsum = kLogZero;
-    if (tid < nb) {
-      total = log_add(a.lb[tid], a.lnb[tid]) + 0.f;
-      lsum = lm_sum[cur][tid];
-      if (use_eos) {
-        const float f = lm.fin[lm_state[cur][tid]];
-        total = clamp_score(__fadd_rn(total, __fmul_rn(alpha, f))) + 0.f;
-        lsum = __fadd_rn(lsum, f);
-      }
-      keys[tid] = make_key(total, tid);
-    }
-    stay_lb[tid] = total;
-    stay_lnb[tid] = lsum;
-  }
-  __syncthreads();
-  if (tid < B) {
-    const BeamState& a = st[cur];
-    if (tid < nb) {
-      int rank = tid;
-      if (use_eos) {
-        rank = 0;
-        for (int i = 0; i < nb; ++i) rank += keys[i] < keys[tid];
-      }
-      fnode[(size_t)s * B + rank] = a.node[tid];
-      flen[(size_t)s * B + rank] = a.len[tid];
-      fscore[(size_t)s * B + rank] = stay_lb[tid];
-      flm[(size_t)s * B + rank] = stay_lnb[tid];
-    } else {
-      fnode[(size_t)s * B + tid] = -1;
-      flen[(size_t)s * B + tid] = -1;
-      fscore[(size_t)s * B + tid] = kLogZero;
-      flm[(size_t)s * B + tid] = kLogZero;
     }
   }
   if (tid == 0) count[s] = nb;
 }
 
-// the LM sums of the N best entries: out [S][N], -1e30 beyond count[s]
-__global__ __launch_bounds__(64) void ctc_rank_gather_kernel(const float* __restrict__ flm, const int* __restrict__ count, int S, int B, int N,
-                                                             float* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= S * N) return;
-  const int s = i / N, r = i - s * N;
-  out[i] = r < count[s] ? flm[(size_t)s * B + r] : kLogZero;
-}
-
-// ---- hypotheses: one lane per (utterance, rank) -----------------------------------------------------------------------------------
+// ---- hypotheses: one lane per (utterance, rank); with an LM (flm, lm_out not null) the lane also hands out its entry's LM sum ------
 __global__ __launch_bounds__(64) void ctc_hyp_kernel(const int* __restrict__ tparent, const int* __restrict__ tlabel,
                                                      const int* __restrict__ fnode, const int* __restrict__ flen,
-                                                     const float* __restrict__ fscore, const int* __restrict__ count, int T, int S,
-                                                     int B, int N, int* __restrict__ hyp, int* __restrict__ hyp_len,
-                                                     float* __restrict__ score) {
+                                                     const float* __restrict__ fscore, const float* __restrict__ flm,
+                                                     const int* __restrict__ count, int T, int S, int B, int N, int* __restrict__ hyp,
+                                                     int* __restrict__ hyp_len, float* __restrict__ score, float* __restrict__ lm_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= S * N) return;
   const int s = i / N, r = i - s * N;
@@ -563,6 +416,7 @@ __global__ __launch_bounds__(64) void ctc_hyp_kernel(const int* __restrict__ tpa
   }
   hyp_len[i] = have ? L : -1;
   score[i] = have ? fscore[(size_t)s * B + r] : kLogZero;
+  if (lm_out) lm_out[i] = have ? flm[(size_t)s * B + r] : kLogZero;
 }
 
 }  // namespace
@@ -576,37 +430,24 @@ void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, 
 }
 
 void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                     const float* csc, const float* sblank, int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, int* count) {
+                     const float* csc, const float* sblank, const LmTables* lm, float alpha, float beta, bool use_eos, int* tparent,
+                     int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count) {
   EESEN_REQUIRE(B >= 1 && B <= kMaxBeam && Cc >= 1 && Cc <= kMaxCls && B * Cc <= kMaxKeys / 2, EESEN_ERR_INVALID, "ctc_prefix_beam: beam or class count outside the key array");
   // one thread per pair of the widest sort stage, 64 .. 512
   int keys = 2;
   while (keys < B + B * Cc) keys <<= 1;
   const int threads = std::min(512, std::max(64, keys / 2));
-  hipLaunchKernelGGL(ctc_prefix_beam_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank, tparent, tlabel,
-                     fnode, flen, fscore, count);
+  if (lm) hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
+                             LmArgs<true>{*lm, alpha, beta, use_eos ? 1 : 0, flm}, tparent, tlabel, fnode, flen, fscore, count);
+  else hipLaunchKernelGGL(ctc_prefix_beam_kernel<false>, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
+                          LmArgs<false>{}, tparent, tlabel, fnode, flen, fscore, count);
   check_launch("ctc_prefix_beam");
 }
 
-void ctc_prefix_beam_lm(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                        const float* csc, const float* sblank, const LmTables& lm, float alpha, float beta, bool use_eos, int* tparent,
-                        int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count) {
-  EESEN_REQUIRE(B >= 1 && B <= kMaxBeam && Cc >= 1 && Cc <= kMaxCls && B * Cc <= kMaxKeys / 2, EESEN_ERR_INVALID, "ctc_prefix_beam_lm: beam or class count outside the key array");
-  int keys = 2;
-  while (keys < B + B * Cc) keys <<= 1;
-  const int threads = std::min(512, std::max(64, keys / 2));
-  hipLaunchKernelGGL(ctc_prefix_beam_lm_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank, lm, alpha, beta,
-                     use_eos ? 1 : 0, tparent, tlabel, fnode, flen, fscore, flm, count);
-  check_launch("ctc_prefix_beam_lm");
-}
-
-void ctc_rank_gather(hipStream_t st, const float* flm, const int* count, int S, int B, int N, float* out) {
-  hipLaunchKernelGGL(ctc_rank_gather_kernel, dim3(cdiv(S * N, 64)), dim3(64), 0, st, flm, count, S, B, N, out);
-  check_launch("ctc_rank_gather");
-}
-
-void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const int* count,
-             int T, int S, int B, int N, int* hyp, int* hyp_len, float* score) {
-  hipLaunchKernelGGL(ctc_hyp_kernel, dim3(cdiv(S * N, 64)), dim3(64), 0, st, tparent, tlabel, fnode, flen, fscore, count, T, S, B, N, hyp, hyp_len, score);
+void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const float* flm,
+             const int* count, int T, int S, int B, int N, int* hyp, int* hyp_len, float* score, float* lm_out) {
+  hipLaunchKernelGGL(ctc_hyp_kernel, dim3(cdiv(S * N, 64)), dim3(64), 0, st, tparent, tlabel, fnode, flen, fscore, flm, count, T, S, B, N, hyp, hyp_len,
+                     score, lm_out);
   check_launch("ctc_hyp");
 }
 

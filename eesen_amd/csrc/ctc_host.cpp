@@ -223,8 +223,8 @@ void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, 
   decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, 0.f, 0.f, false, hyp_host, hyp_len_host, score_host, nullptr);
 }
 
-// With a token LM fused into the beam (INTEGRATION.md "LM fusion"): ctc_prefix_beam_lm in place of ctc_prefix_beam, inside the same
-// phase.  The tables are uploaded when this Ctc meets the model for the first time.
+// With a token LM fused into the beam (INTEGRATION.md "LM fusion"): ctc_prefix_beam with the tables, inside the same phase.  The
+// tables are uploaded when this Ctc meets the model for the first time.
 void Ctc::decode_parallel_lm(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                              int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
                              float* score_host, float* lm_score_host) {
@@ -314,11 +314,9 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
   ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
   if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
-  if (lm) ctc_prefix_beam_lm(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm_tab, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, flm, count);
-  else ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, count);
+  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, lm ? flm : nullptr, count);
   if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
-  ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, count, T, S, B, N, hyp_d, len_d, score_d);
-  if (lm) ctc_rank_gather(st, flm, count, S, B, N, lmsum_d);
+  ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, lm ? flm : nullptr, count, T, S, B, N, hyp_d, len_d, score_d, lm ? lmsum_d : nullptr);
   if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
   dec_rows = rows; dec_S = S; dec_C = Cc;
   dec_lens.assign(frame_num_utt, frame_num_utt + S);

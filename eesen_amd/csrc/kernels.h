@@ -223,24 +223,21 @@ void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, c
 // cid [rows][Cc], their scores in csc [rows][Cc], the blank's in sblank [rows]; every score clamped from below at -1e30.
 void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, int S, const int* lens, int Cc, int* cid, float* csc,
                   float* sblank);
+struct LmTables;
 // ctc_prefix_beam: S workgroups, each walks its utterance's frames.  tparent / tlabel [S][1 + T*B]: the trie (node 0 = the empty
 // prefix), written only; fnode / flen / fscore [S][B]: node, length and total of the final beam, best first (-1, -1, -1e30 beyond
-// count[s] live entries).  1 <= B <= 64, 1 <= Cc <= 64, B * Cc <= 2048.
+// count[s] live entries).  1 <= B <= 64, 1 <= Cc <= 64, B * Cc <= 2048.  lm == null: the plain search (ctc_prefix_beam_kernel<false>;
+// alpha, beta, use_eos and flm are not read).  Otherwise the same search with a token n-gram LM fused in (<true>; INTEGRATION.md
+// "LM fusion"; the tables: lm.h): an extension by class c adds g = alpha * w + beta, (w, next) = lm_step(the entry's LM state, c);
+// with use_eos, alpha * fin[state] joins every total after the last frame and the final beam is re-ranked.  flm [S][B]: the
+// unweighted LM sum of each final entry.
 void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                     const float* csc, const float* sblank, int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, int* count);
-struct LmTables;
-// ctc_prefix_beam_lm: the same search with a token n-gram LM fused in (INTEGRATION.md "LM fusion"; the tables: lm.h).  An extension
-// by class c adds g = alpha * w + beta, (w, next) = lm_step(the entry's LM state, c); with use_eos, alpha * fin[state] joins every
-// total after the last frame and the final beam is re-ranked.  flm [S][B]: the unweighted LM sum of each final entry.
-void ctc_prefix_beam_lm(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                        const float* csc, const float* sblank, const LmTables& lm, float alpha, float beta, bool use_eos, int* tparent,
-                        int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count);
-// out [S][N] = flm [S][B] of the N best entries, -1e30 beyond count[s]
-void ctc_rank_gather(hipStream_t st, const float* flm, const int* count, int S, int B, int N, float* out);
+                     const float* csc, const float* sblank, const LmTables* lm, float alpha, float beta, bool use_eos, int* tparent,
+                     int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count);
 // ctc_hyp: hyp [S][N][T] the labels of the N best entries front to back (-1 beyond the length), hyp_len / score [S][N] (-1 / -1e30
-// beyond count[s]).
-void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const int* count,
-             int T, int S, int B, int N, int* hyp, int* hyp_len, float* score);
+// beyond count[s]); with flm and lm_out (both null without an LM) lm_out [S][N] = flm of the same entries, -1e30 beyond count[s].
+void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const float* flm,
+             const int* count, int T, int S, int B, int N, int* hyp, int* hyp_len, float* score, float* lm_out);
 // diff[t*S+s][k] = y*rowsum(e) - gamma ... (error kernel + softmax Jacobian, ctc-loss.cc:156-168)
 // labx [S x Lpad]: the expanded labels (blank 0 at even positions), lablens [S] = 2 U_s + 1
 void ctc_error_diff(hipStream_t st, const float* probs, int ld, int T, int S, int K, int Lpad, int Lmax, const int* lens,

@@ -308,7 +308,7 @@ struct Ctc {
   // objective nor the error statistics, and none of the buffers of eval_parallel / align_parallel but `logp`.
   void decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                        int nbest, int* hyp_host, int* hyp_len_host, float* score_host);
-  // the same with a token n-gram LM fused into the beam (ctc_prefix_beam_lm); lm_score_host [S][nbest] may be null
+  // the same with a token n-gram LM fused into the beam (ctc_prefix_beam with its tables); lm_score_host [S][nbest] may be null
   void decode_parallel_lm(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                           int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
                           float* score_host, float* lm_score_host);

@@ -1,4 +1,4 @@
-"""-m gpu: the CTC prefix beam search (csrc/ctc_decode.hip: ctc_row_topc_kernel + ctc_prefix_beam_kernel + ctc_hyp_kernel, through
+"""-m gpu: the CTC prefix beam search (csrc/ctc_decode.hip: ctc_row_topc_kernel + ctc_prefix_beam_kernel<false> + ctc_hyp_kernel, through
 api.Ctc.DecodeParallel) held per utterance against the fp64 restatement of the computation (tests/ctc_beam_restatement.py) and
 against the exact ln p of every returned labelling, on the same float32 posteriors.
 

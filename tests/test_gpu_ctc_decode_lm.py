@@ -1,4 +1,4 @@
-"""-m gpu: the CTC prefix beam search with a token n-gram LM fused in (csrc/ctc_decode.hip: ctc_prefix_beam_lm_kernel, csrc/lm.cpp,
+"""-m gpu: the CTC prefix beam search with a token n-gram LM fused in (csrc/ctc_decode.hip: ctc_prefix_beam_kernel<true>, csrc/lm.cpp,
 through api.Ctc.DecodeParallel(lm=...)) held per utterance against the fp64 restatement (tests/ctc_lm_restatement.py: the textbook ARPA
 definition on dictionaries, no automaton) and against the exact fused score of every returned labelling.
 
@@ -187,6 +187,28 @@ def test_eos_rerank(ctc, tmp_path):
         assert abs(float(yes[1][0, j]) - (float(no[1][0, i]) + fin * ln10)) <= 1e-5
         assert abs(float(yes[4][0, j]) - (float(no[4][0, i]) + fin * ln10)) <= 1e-5
         assert abs(float(yes[4][0, j]) - lm.Score(h, eos=True)) <= 1e-5
+
+
+@pytest.mark.parametrize("eos", [True, False])
+def test_lm_scores_come_out_of_the_hypothesis_walk(ctc, lm_of, eos):
+    """ctc_hyp_kernel's lane of (utterance, rank) hands out the entry's LM sum: more ranks asked for than an utterance has entries
+    (no frames: only the empty prefix lives) beside an ordinary utterance; the plain call writes no LM sum at all."""
+    S, T, K, B, C, N, alpha, beta = 2, 2, 3, 4, 2, 3, 0.5, 0.1
+    model, lm = lm_of("k3_o3")
+    probs = cc.softmax32(np.random.default_rng(211).standard_normal((T * S, K)).astype(np.float32))
+    lens = np.array([0, T], np.int32)
+    got = _decode(ctc, lens, probs, B, C, N, lm, alpha, beta, eos)
+    hyps, scores, raw, hlen, lms = got
+    assert hyps[0] == [[]] and hlen[0].tolist() == [0, -1, -1]
+    want = lm.Score([], eos=eos)
+    assert abs(float(lms[0, 0]) - want) <= L.lm_term(model, alpha, [], eos)[1], (float(lms[0, 0]), want)
+    assert np.all(scores[0, 1:] == np.float32(-1e30)) and np.all(lms[0, 1:] == np.float32(-1e30))
+    ref = L.reference_of(lens, probs, S, B, C, model, alpha, beta, eos)
+    assert len(hyps[1]) == N
+    _invariants(f"lm sums, eos {eos}", lens, probs, S, got, N, [r["bar"] for r in ref], model, lm, alpha, beta, eos)   # every entry's lm_score
+    plain = _decode(ctc, lens, probs, B, C, N)
+    assert plain[4] is None and plain[0][0] == [[]]
+    assert plain[3][0].tolist() == [0, -1, -1] and np.all(plain[1][0, 1:] == np.float32(-1e30))
 
 
 @pytest.mark.parametrize("name", dc.TIE_CASES)

@@ -84,6 +84,19 @@ def test_persistent_tiles_stay_inside_their_budgets(table):
         assert r["lds"] <= lmax, f"{n}: {r['lds']} B LDS > budget {lmax}"
 
 
+def test_the_lm_state_exists_in_the_fused_beam_instantiation_only(table):
+    """csrc/ctc_decode.hip: the plain and the LM-fused prefix beam search are two instantiations of one kernel text.  The bounds are
+    the figures of the two separate kernels this text replaced (plain 40 VGPRs / 39440 B, fused 44 / 56848 B; VGPRs in their
+    allocation blocks of 8); a rise in the plain figures means LM state leaked into the plain instantiation.  The difference is the
+    LM state: ext_w and ext_next 2 x 8192 B, lm state and sum 2 x 512 B."""
+    assert not [n for n in table if "ctc_rank_gather" in n]
+    plain, fused = table["ctc_prefix_beam_kernel<false>"], table["ctc_prefix_beam_kernel<true>"]
+    assert plain["max_threads"] == 512 and fused["max_threads"] == 512
+    assert plain["lds"] <= 39440 and fused["lds"] <= 56848, (plain["lds"], fused["lds"])
+    assert fused["lds"] - plain["lds"] == 2 * 8192 + 2 * 512 == 17408
+    assert plain["vgprs"] <= 40 and fused["vgprs"] <= 48, (plain["vgprs"], fused["vgprs"])
+
+
 def test_side_stream_gemm_fits_beside_the_cfg2_backward_tile(table):
     """net.cpp's overlap rule: the weight-gradient GEMMs (gemm_f32_split_bf16_kernel, 256 threads = one wave per SIMD) run on the
     side stream UNDER the next-lower layer's backward recurrence (q4<8,4>, two waves per SIMD, one workgroup on every CU)."""
