@@ -6,7 +6,8 @@ eesen_amd/csrc/lstm_persistent.hip ship in.
              (read from lstm_fwd_plan / lstm_bwd_plan; the GPU test asserts them through Plan())
   VARIANTS   which dropout recipes run at which shape
   UNREACHED  DROP = true rows no case names, with the reason
-  lengths / features / top gradients / masks: deterministic generators (a function of the shape, and of the recipe for the masks)
+  lengths / features / top gradients / masks: deterministic generators (a function of the shape, and of the recipe for the masks);
+             the shape_* functions take (H, S, T, ndir) instead of a key of CASES (tests/recurrence_cases.py draws from them)
   seq_worst  the per-sequence metrics: the worst rel_err (max-norm) and the worst p999 of err_metrics over a case's sequences, each
              over that sequence's valid rows
 """
@@ -78,44 +79,85 @@ def bwd_row(case):
     return "lstm_bwd_persistent_kernel<%d,%d,true>" % CASES[case]["bwd"]
 
 
-def _rng(case, salt):
+def _shape(case):
     c = CASES[case]
-    return np.random.default_rng([c["H"], c["S"], c["T"], salt])
+    return c["H"], c["S"], c["T"], 2
 
 
-def _layout(case):
-    c = CASES[case]; S, T = c["S"], c["T"]
-    rng = _rng(case, 1)
+# ---- the generators, as functions of a shape (H cells per direction, S sequences, T frames, ndir directions): what the case-keyed
+# functions below and tests/recurrence_cases.py both draw from.  The seed holds H, S and T only, so that this module's inputs are what
+# they were before the generators took a shape.
+def shape_rng(H, S, T, salt):
+    return np.random.default_rng([H, S, T, salt])
+
+
+def shape_layout(H, S, T, ndir=2):
+    rng = shape_rng(H, S, T, 1)
     lens = rng.integers(3, T + 1, size=S).astype(np.int32)
     special, keep = set(), None
     for z in range(0, S, 16):
         at = z + rng.permutation(min(16, S - z))[:3]
-        lens[at[0]], lens[at[1]], lens[at[2]] = T, 1, 2
+        for a, n in zip(at, (T, 1, 2)):       # (a ragged last tile of fewer than three sequences: as many of them as it has)
+            lens[a] = n
         special.update(int(a) for a in at)
         if z == 0:
             keep = int(at[0])
-    drop = next(s for s in range(16 * ((S - 1) // 16), S) if s not in special)
-    lens[drop] = T
+    drop = next((s for s in range(16 * ((S - 1) // 16), S) if s not in special), None)
+    if drop is not None:
+        lens[drop] = T
     return lens, keep, drop
+
+
+def shape_lengths(H, S, T, ndir=2):
+    """[S] int32.  Every 16-sequence tile holds a sequence of length T, one of length 1 and one of length 2, at places that differ
+    from tile to tile; the rest are random in [3, T] (and the last tile holds a second sequence of length T: planted())."""
+    return shape_layout(H, S, T, ndir)[0]
+
+
+def shape_layer(kind, H):
+    """[the one recurrent layer] of `kind` (BiLstmParallel / LstmParallel) with synth.make_model's weights."""
+    return copy.deepcopy(synth.make_model(kind=kind, layers=1, H=H, D=D, K=4)[:1])
+
+
+def shape_features(H, S, T, ndir, lens):
+    """[T*S x D] fp32: N(0, 1) on valid rows, zero on padding."""
+    x = shape_rng(H, S, T, 2).standard_normal((T, S, D)).astype(np.float32)
+    x[np.arange(T)[:, None] >= lens[None, :]] = 0.0
+    return x.reshape(T * S, D)
+
+
+def shape_top_gradients(H, S, T, ndir, lens):
+    """([(profile, od [T*S x ndir*H])], zero): profile "a" N(0, 1) on valid rows; "b" the same scaled, in every aligned group of four
+    sequences, by 1, 2^-8, 2^-16, 2^-24, and every other group holds one sequence (`zero`) whose od is zero."""
+    base = shape_rng(H, S, T, 3).standard_normal((T, S, ndir * H)).astype(np.float32)
+    base[np.arange(T)[:, None] >= lens[None, :]] = 0.0
+    b = base * (2.0 ** (-8.0 * (np.arange(S) % 4))).astype(np.float32)[None, :, None]
+    zero = [4 * g + 1 for g in range(S // 4) if g % 2 == 1]
+    b[:, zero, :] = 0.0
+    return [("a", base.reshape(T * S, ndir * H)), ("b", b.reshape(T * S, ndir * H))], zero
+
+
+# ---- the same, by a key of CASES
+def _rng(case, salt):
+    return shape_rng(*_shape(case)[:3], salt)
 
 
 def lengths(case):
     """[S] int32.  Every 16-sequence tile holds a sequence of length T, one of length 1 and one of length 2, at places that differ
     from tile to tile (so the two sequence windows of bi1024_s64 get different patterns); the rest are random in [3, T]."""
-    return _layout(case)[0]
+    return shape_layout(*_shape(case))[0]
 
 
 def planted(case):
     """(keep, drop): the sequence whose masks keep every cell (the length-T one of the first tile) and the sequence that has every
     cell dropped at frame T // 2, which under RNNDrop restarts the cell there: of length T, in the LAST tile (the second window of
     bi1024_s64), the first of its sequences that is none of the tile's T / 1 / 2 ones."""
-    return _layout(case)[1:]
+    return shape_layout(*_shape(case))[1:]
 
 
 def layer(case, recipe=None):
     """[the one BiLstmParallel layer] with synth.make_model's weights; recipe None: no dropout (the twin)."""
-    c = CASES[case]
-    L = copy.deepcopy(synth.make_model(kind="BiLstmParallel", layers=1, H=c["H"], D=D, K=4)[:1])
+    L = shape_layer("BiLstmParallel", CASES[case]["H"])
     if recipe:
         L[0]["dropout"] = dict(RECIPES[recipe])
     return L
@@ -123,22 +165,13 @@ def layer(case, recipe=None):
 
 def features(case, lens):
     """[T*S x D] fp32: N(0, 1) on valid rows, zero on padding."""
-    c = CASES[case]; S, T = c["S"], c["T"]
-    x = _rng(case, 2).standard_normal((T, S, D)).astype(np.float32)
-    x[np.arange(T)[:, None] >= lens[None, :]] = 0.0
-    return x.reshape(T * S, D)
+    return shape_features(*_shape(case), lens)
 
 
 def top_gradients(case, lens):
     """([(profile, od [T*S x 2H])], zero): profile "a" N(0, 1) on valid rows; "b" the same scaled, in every aligned group of four
     sequences, by 1, 2^-8, 2^-16, 2^-24, and every other group holds one sequence (`zero`) whose od is zero."""
-    c = CASES[case]; S, T, H = c["S"], c["T"], c["H"]
-    base = _rng(case, 3).standard_normal((T, S, 2 * H)).astype(np.float32)
-    base[np.arange(T)[:, None] >= lens[None, :]] = 0.0
-    b = base * (2.0 ** (-8.0 * (np.arange(S) % 4))).astype(np.float32)[None, :, None]
-    zero = [4 * g + 1 for g in range(S // 4) if g % 2 == 1]
-    b[:, zero, :] = 0.0
-    return [("a", base.reshape(T * S, 2 * H)), ("b", b.reshape(T * S, 2 * H))], zero
+    return shape_top_gradients(*_shape(case), lens)
 
 
 def _draw(rng, rows, cols, p):
