@@ -102,6 +102,16 @@ SIGNATURES = {
     "eesen_lm_start": (_i, [_vp, _pi]),
     "eesen_lm_final": (_i, [_vp, _i, _pf]),
     "eesen_lm_score": (_i, [_vp, _vp, _i, _i, _pd, _pd]),
+    "eesen_lm_create_from_arpa_ex": (_i, [C.c_char_p, C.c_char_p, _i, _i, C.POINTER(_vp)]),
+    "eesen_lm_oov_dropped": (_i, [_vp, C.POINTER(C.c_longlong)]),
+    "eesen_lex_create": (_i, [C.c_char_p, C.c_char_p, _i, _i, C.POINTER(_vp)]),
+    "eesen_lex_destroy": (_i, [_vp]),
+    "eesen_lex_info": (_i, [_vp, _pi, _pi, _pi]),
+    "eesen_lex_write_words": (_i, [_vp, C.c_char_p]),
+    "eesen_lex_child": (_i, [_vp, _i, _i, _pi]),
+    "eesen_lex_word": (_i, [_vp, _i, _pi]),
+    "eesen_lex_words": (_i, [_vp, _vp, _i, _vp, _pi]),
+    "eesen_ctc_decode_parallel_lex": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eesen_ctc_decode_parallel_lm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "eesen_ce_destroy": (_i, [_vp]),

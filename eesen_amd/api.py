@@ -474,11 +474,16 @@ class TokenLm:
     automaton (eesen_lm_create_from_arpa; INTEGRATION.md "LM fusion").  units: the recipes' units.txt (`symbol id` per line); without
     it the ARPA's words are decimal class ids.  K: the net's class count, blank included.  Host only: needs no device."""
 
-    def __init__(self, arpa: str, units: Optional[str] = None, K: int = 0):
+    def __init__(self, arpa: str, units: Optional[str] = None, K: int = 0, skip_oov: bool = False):
+        """skip_oov: n-grams with a word outside the table are dropped and counted (OovDropped) instead of being an error
+        (eesen_lm_create_from_arpa_ex) -- what a word LM over a lexicon's words table usually needs."""
         self.lib = _lib.load()
         self.h = C.c_void_p()
         self.K = int(K)
-        check(self.lib.eesen_lm_create_from_arpa(str(arpa).encode(), str(units).encode() if units else None, int(K), C.byref(self.h)))
+        if skip_oov:
+            check(self.lib.eesen_lm_create_from_arpa_ex(str(arpa).encode(), str(units).encode() if units else None, int(K), 1, C.byref(self.h)))
+        else:
+            check(self.lib.eesen_lm_create_from_arpa(str(arpa).encode(), str(units).encode() if units else None, int(K), C.byref(self.h)))
 
     def __del__(self):
         if getattr(self, "h", None) and self.h:
@@ -487,6 +492,11 @@ class TokenLm:
             except Exception:
                 pass
             self.h = None
+
+    def OovDropped(self) -> int:
+        n = C.c_longlong()
+        check(self.lib.eesen_lm_oov_dropped(self.h, C.byref(n)))
+        return n.value
 
     def Info(self) -> dict:
         o, st, ar, eos = C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -515,6 +525,55 @@ class TokenLm:
         v, a = C.c_double(), C.c_double()
         check(self.lib.eesen_lm_score(self.h, _np_ptr(lab) if lab.size else None, int(lab.size), int(bool(eos)), C.byref(v), C.byref(a)))
         return (v.value, a.value) if with_abs else v.value
+
+
+class Lexicon:
+    """A lexicon for Ctc.DecodeParallel(lexicon=...): `word unit unit ...` lines compiled into a trie (eesen_lex_create; INTEGRATION.md
+    "Lexicon").  units: the recipes' units.txt; without it the units are decimal class ids (lexicon_numbers.txt).  K: the net's class
+    count, blank included; space: the class that separates words.  Host only: needs no device."""
+
+    def __init__(self, path: str, units: Optional[str] = None, K: int = 0, space: int = 0):
+        self.lib = _lib.load()
+        self.h = C.c_void_p()
+        self.K, self.space = int(K), int(space)
+        check(self.lib.eesen_lex_create(str(path).encode(), str(units).encode() if units else None, int(K), int(space), C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h:
+            try:
+                self.lib.eesen_lex_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def Info(self) -> dict:
+        w, n, m = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.eesen_lex_info(self.h, C.byref(w), C.byref(n), C.byref(m)))
+        return dict(words=w.value, nodes=n.value, max_word_len=m.value)
+
+    def WriteWords(self, path: str) -> None:
+        """`word id` lines: the units table of a word LM, TokenLm(arpa, path, K=words + 1)."""
+        check(self.lib.eesen_lex_write_words(self.h, str(path).encode()))
+
+    def Child(self, node: int, c: int) -> int:
+        """The child of a trie node for class c, or -1."""
+        ch = C.c_int()
+        check(self.lib.eesen_lex_child(self.h, int(node), int(c), C.byref(ch)))
+        return ch.value
+
+    def Word(self, node: int) -> int:
+        """The id (1 .. words) of the word whose spelling ends at the node, or 0."""
+        w = C.c_int()
+        check(self.lib.eesen_lex_word(self.h, int(node), C.byref(w)))
+        return w.value
+
+    def Words(self, labels: Sequence[int]) -> List[int]:
+        """The word ids of a labelling `w1 space w2 ... wn`; EesenError for a labelling that is none."""
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        out = np.empty(lab.size // 2 + 1, np.int32)
+        n = C.c_int()
+        check(self.lib.eesen_lex_words(self.h, _np_ptr(lab) if lab.size else None, int(lab.size), _np_ptr(out), C.byref(n)))
+        return out[:n.value].tolist()
 
 
 class Ctc:
@@ -580,21 +639,36 @@ class Ctc:
 
     def DecodeParallel(self, frame_num_utt: Sequence[int], net_out: CuMatrix, beam: int = 16, max_classes: int = 20, nbest: int = 1,
                        is_log: bool = False, lm: Optional["TokenLm"] = None, lm_weight: float = 1.0, insertion_bonus: float = 0.0,
-                       lm_eos: bool = False):
-        """Lexicon-free CTC prefix beam search (eesen_ctc_decode_parallel; no counterpart in the reference's src/net).  net_out: posteriors,
+                       lm_eos: bool = False, lexicon: Optional["Lexicon"] = None, word_bonus: float = 0.0):
+        """CTC prefix beam search (eesen_ctc_decode_parallel; no counterpart in the reference's src/net).  net_out: posteriors,
         or log-domain scores with is_log=True.  Returns (hyps, scores): hyps[s] is the list of the utterance's returned labellings, best
         first, each a list of ints (at most nbest; none where the beam died); scores [S, nbest] float32, -1e30 beyond the returned
         count (NaN under a raised guard word).  Statistics untouched.
         lm: a TokenLm fused into the search (eesen_ctc_decode_parallel_lm): every label adds lm_weight * ln P_lm(label | prefix) +
         insertion_bonus, with lm_eos lm_weight * ln P_lm(</s> | labels) joins at the end; self.lm_score [S, nbest] is then each
-        entry's unweighted ln P_lm (None without an LM).  lm=None is the plain call."""
+        entry's unweighted ln P_lm (None without an LM).  lm=None is the plain call.
+        lexicon: a Lexicon the labellings are held to (eesen_ctc_decode_parallel_lex): words of the lexicon separated by single
+        spaces.  lm is then an LM over the lexicon's word ids (TokenLm over Lexicon.WriteWords' table, K = words + 1) or None, stepped
+        once per word; word_bonus is added per word and insertion_bonus is not used.  self.words [S, nbest, T] / self.words_len
+        [S, nbest] are the word ids of every returned labelling (-1 beyond; None without a lexicon).  lexicon=None takes the calls
+        above unchanged."""
         fn = np.ascontiguousarray(frame_num_utt, np.int32)
         S = fn.size
         T = net_out.rows // max(S, 1)
         hyp = np.empty((S, int(nbest), max(T, 0)), np.int32)
         hlen = np.empty((S, int(nbest)), np.int32)
         score = np.empty((S, int(nbest)), np.float32)
-        if lm is None:
+        words = words_len = None
+        if lexicon is not None:
+            lm_score = np.empty((S, int(nbest)), np.float32)
+            words = np.empty((S, int(nbest), max(T, 0)), np.int32)
+            words_len = np.empty((S, int(nbest)), np.int32)
+            check(self.lib.eesen_ctc_decode_parallel_lex(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols,
+                                                         net_out.stride, int(bool(is_log)), int(beam), int(max_classes), int(nbest), lexicon.h,
+                                                         lm.h if lm is not None else None, float(lm_weight), float(word_bonus),
+                                                         int(bool(lm_eos)), _np_ptr(hyp), _np_ptr(hlen), _np_ptr(score), _np_ptr(lm_score),
+                                                         _np_ptr(words), _np_ptr(words_len)))
+        elif lm is None:
             lm_score = None
             check(self.lib.eesen_ctc_decode_parallel(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
                                                      int(bool(is_log)), int(beam), int(max_classes), int(nbest), _np_ptr(hyp), _np_ptr(hlen),
@@ -607,6 +681,7 @@ class Ctc:
                                                         _np_ptr(hlen), _np_ptr(score), _np_ptr(lm_score)))
         self.hyp, self.hyp_len = hyp, hlen          # the raw [S, nbest, T] labels (-1 beyond each length) and [S, nbest] lengths
         self.lm_score = lm_score
+        self.words, self.words_len = words, words_len
         hyps = [[hyp[s, i, :hlen[s, i]].tolist() for i in range(int(nbest)) if hlen[s, i] >= 0] for s in range(S)]
         return hyps, score
 

@@ -277,6 +277,17 @@ int eesen_lm_create_from_arpa(const char* arpa_path, const char* units_path, int
     *lm = made.release();
   });
 }
+int eesen_lm_create_from_arpa_ex(const char* arpa_path, const char* units_path, int K, int skip_oov, eesen_lm_t** lm) {
+  return guard([&] {
+    REQ_PTR(arpa_path); REQ_PTR(lm);
+    std::unique_ptr<eesen_lm> made(new eesen_lm);
+    made->from_arpa(arpa_path, units_path, K, skip_oov != 0);
+    *lm = made.release();
+  });
+}
+int eesen_lm_oov_dropped(eesen_lm_t* lm, long long* ngrams) {
+  return guard([&] { REQ_PTR(lm); REQ_PTR(ngrams); *ngrams = lm->oov_dropped; });
+}
 int eesen_lm_destroy(eesen_lm_t* lm) {
   return guard([&] { delete lm; });
 }
@@ -307,6 +318,55 @@ int eesen_lm_score(eesen_lm_t* lm, const int* labels, int n, int use_eos, double
     REQ_PTR(lm); REQ_PTR(logprob_f64);
     EESEN_REQUIRE(n >= 0 && (n == 0 || labels != nullptr), EESEN_ERR_INVALID, "labels: null pointer or negative count");
     *logprob_f64 = lm->score(labels, n, use_eos != 0, abs_sum_f64);
+  });
+}
+int eesen_lex_create(const char* lexicon_path, const char* units_path, int K, int space_class, eesen_lex_t** lex) {
+  return guard([&] {
+    REQ_PTR(lexicon_path); REQ_PTR(lex);
+    std::unique_ptr<eesen_lex> made(new eesen_lex);
+    made->from_file(lexicon_path, units_path, K, space_class);
+    *lex = made.release();
+  });
+}
+int eesen_lex_destroy(eesen_lex_t* lex) {
+  return guard([&] { delete lex; });
+}
+int eesen_lex_info(eesen_lex_t* lex, int* words, int* nodes, int* max_word_len) {
+  return guard([&] {
+    REQ_PTR(lex);
+    if (words) *words = lex->V();
+    if (nodes) *nodes = lex->nodes();
+    if (max_word_len) *max_word_len = lex->max_word_len;
+  });
+}
+int eesen_lex_write_words(eesen_lex_t* lex, const char* path) {
+  return guard([&] { REQ_PTR(lex); REQ_PTR(path); lex->write_words(path); });
+}
+int eesen_lex_child(eesen_lex_t* lex, int node, int c, int* child) {
+  return guard([&] { REQ_PTR(lex); REQ_PTR(child); *child = lex->child(node, c); });
+}
+int eesen_lex_word(eesen_lex_t* lex, int node, int* word) {
+  return guard([&] {
+    REQ_PTR(lex); REQ_PTR(word);
+    EESEN_REQUIRE(node >= 0 && node < lex->nodes(), EESEN_ERR_INVALID, "lexicon node out of range");
+    *word = lex->word[node];
+  });
+}
+int eesen_lex_words(eesen_lex_t* lex, const int* labels, int n, int* words_out, int* num_words) {
+  return guard([&] {
+    REQ_PTR(lex); REQ_PTR(num_words);
+    EESEN_REQUIRE(n >= 0 && (n == 0 || (labels != nullptr && words_out != nullptr)), EESEN_ERR_INVALID, "labels / words_out: null pointer or negative count");
+    EESEN_REQUIRE(lex->words(labels, n, words_out, num_words), EESEN_ERR_INVALID, "the labelling is no sequence of lexicon words separated by single spaces");
+  });
+}
+int eesen_ctc_decode_parallel_lex(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                                  int is_log, int beam, int max_classes, int nbest, eesen_lex_t* lex, eesen_lm_t* lm, float lm_weight,
+                                  float word_bonus, int use_eos, int* hyp_host, int* hyp_len_host, float* score_host, float* lm_score_host,
+                                  int* word_host, int* word_len_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev); REQ_PTR(hyp_host); REQ_PTR(hyp_len_host); REQ_PTR(score_host);
+    ctc->decode_parallel_lex(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, beam, max_classes, nbest, lex, lm, lm_weight, word_bonus,
+                             use_eos != 0, hyp_host, hyp_len_host, score_host, lm_score_host, word_host, word_len_host);
   });
 }
 int eesen_ctc_decode_parallel_lm(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,

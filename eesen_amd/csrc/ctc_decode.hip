@@ -1,16 +1,20 @@
-// ctc_decode.hip -- lexicon-free CTC prefix beam search over a padded utterance batch, for gfx950.
+// ctc_decode.hip -- CTC prefix beam search over a padded utterance batch, lexicon-free or along a lexicon trie, for gfx950.
 //
 // No counterpart in the reference, which decodes one utterance per process through a TLG graph and its WFST decoder.  The
 // computation is stated in INTEGRATION.md "Decoding" and "LM fusion" and restated in numpy in tests/ctc_beam_restatement.py and
-// tests/ctc_lm_restatement.py.  Three launches per minibatch, with or without a token n-gram LM fused into the beam, none per frame:
+// tests/ctc_lm_restatement.py; the lexicon mode in INTEGRATION.md "Lexicon" and tests/ctc_lex_restatement.py.  Three launches per
+// minibatch, whatever the mode, none per frame:
 //   ctc_row_topc_kernel     one wavefront per row: the C' best non-blank classes (ascending id), their scores, the blank's score
 //   ctc_prefix_beam_kernel  one workgroup per utterance walks its n frames: beam state and the frame's candidate keys in LDS, the trie
 //                           of surviving prefixes written (never read) to global memory; <false> the plain search, <true> the
-//                           LM-fused one: one text, and the LM's arguments, LDS and barrier exist in <true> only
+//                           LM-fused one, ctc_prefix_beam_lex_kernel the one that extends only along a lexicon trie and steps a
+//                           word LM once per word: one text (prefix_beam<mode>), and a mode's arguments, LDS and barrier exist in
+//                           that instantiation only
 //   ctc_hyp_kernel          one lane per (utterance, rank) walks the trie to the root
 // Every log-mass is an fp32 value in [-1e30, +inf): sums are clamped from below at the library's finite sentinel, so the sweep's
 // branch-free log-add (ctc.hip: LogAPlusB_fast) is exact on the special cases here too.
 #include "kernels.h"
+#include "lex.h"
 #include "lm.h"
 
 namespace eesen {
@@ -116,9 +120,12 @@ struct BeamState {
   unsigned long long hash[kMaxBeam];   // fingerprint of the labels
 };
 
-// What the fused search has and the plain one has not, as arguments (flm [S][B]: the LM sum of each final entry)
-template <bool LM> struct LmArgs {};
-template <> struct LmArgs<true> { LmTables tab; float alpha, beta; int use_eos; float* flm; };
+// The kernel's modes, and what each has that the plain one has not, as arguments (flm [S][B]: the LM sum of each final entry).  The
+// lexicon mode's LM is over word ids (class w = word w) and optional: have_lm == 0 never touches tab.
+enum BeamMode { kPlain = 0, kTokenLm = 1, kLexicon = 2 };
+template <int MODE> struct LmArgs {};
+template <> struct LmArgs<kTokenLm> { LmTables tab; float alpha, beta; int use_eos; float* flm; };
+template <> struct LmArgs<kLexicon> { LmTables tab; float alpha, beta; int use_eos; float* flm; LexTables lex; int have_lm; };
 // first index in [lo, hi) of the ascending v whose value is >= x; hi if there is none
 __device__ __forceinline__ int lower_bound(const int* __restrict__ v, int lo, int hi, int x) {
   while (lo < hi) {
@@ -166,7 +173,9 @@ __device__ __forceinline__ void sort_sync(bool wave_local) {
 
 // Grid (S), 64 .. 512 threads.  Frame t of an utterance, between workgroup barriers:
 //   0  LM only: one thread per (entry, candidate), nb * C' <= 2048 of them: (w, next) = lm_step(entry's LM state, class) into LDS --
-//      the only LM lookups of the frame; steps 1, 2 and 4 read w from there and form g = alpha * w + beta
+//      the only LM lookups of the frame; steps 1, 2 and 4 read w from there and form g = alpha * w + beta.  Lexicon: the same
+//      slots take (0, child of the entry's lexicon node) for a unit and (lm_step over the word LM, or 0, of the node's word) for
+//      the space; next = -1 marks a pair the lexicon does not allow, which ext_value turns into -1e30: no candidate
 //   1  entry q < nb: its stay candidate; the extension that spells q (found by fingerprint) is log-added into it and marked merged
 //   2  the nb * C' extensions write their keys behind the stays; the key array is padded with dead keys to a power of two
 //   3  bitonic sort of the keys (workgroup barriers only around strides >= 128)
@@ -178,14 +187,16 @@ __device__ __forceinline__ void sort_sync(bool wave_local) {
 // its prefix's LM weights; a stay keeps both.  After the last frame, with use_eos, alpha * fin[state] joins every total (fin into
 // the LM sum) and the live entries are re-ranked, ties by the previous rank.  Static LDS: the plain 38.5 KiB + 2 x 8 KiB (w, next)
 // + 1 KiB of LM state = 55.5 KiB of the 64.
-template <bool LM>
-__global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __restrict__ sc, int ld, int T, int S,
-                                                              const int* __restrict__ lens, int B, int Cc,
-                                                              const int* __restrict__ cid_g, const float* __restrict__ csc_g,
-                                                              const float* __restrict__ sblank_g, LmArgs<LM> lm,
-                                                              int* __restrict__ tparent, int* __restrict__ tlabel,
-                                                              int* __restrict__ fnode, int* __restrict__ flen,
-                                                              float* __restrict__ fscore, int* __restrict__ count) {
+// Lexicon (INTEGRATION.md "Lexicon"): an entry also carries its lexicon node (0.5 KiB more: 56 KiB).  A unit extends along the trie
+// with g = 0 -- the plain bits -- and keeps LM state and sum; the space closes the node's word w: g = alpha * lm_step(state, w) +
+// beta, the node returns to the root.  After the last frame the entries that do not stand on a word end are dropped, the others
+// close their last word (and take alpha * fin with use_eos), and are re-ranked.
+template <int MODE>
+__device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld, int T, int S, const int* __restrict__ lens, int B, int Cc,
+                                            const int* __restrict__ cid_g, const float* __restrict__ csc_g,
+                                            const float* __restrict__ sblank_g, LmArgs<MODE> lm, int* __restrict__ tparent,
+                                            int* __restrict__ tlabel, int* __restrict__ fnode, int* __restrict__ flen,
+                                            float* __restrict__ fscore, int* __restrict__ count) {
   __shared__ unsigned long long keys[kMaxKeys];
   __shared__ BeamState st[2];
   __shared__ float stay_lb[kMaxBeam], stay_lnb[kMaxBeam], nx_stay[kMaxBeam], nx_ext[kMaxCls];
@@ -193,11 +204,14 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
   __shared__ float c_sc[2][kMaxCls], c_bl[2];
   __shared__ unsigned long long merged[kMaxBeam];   // per entry: which of its extensions went into another entry's stay
   __shared__ int nb_sh;
+  constexpr bool LM = MODE != kPlain, LEX = MODE == kLexicon;
   // the fused search's alone (17 KiB): the plain instantiation never names them, and what is not named is not allocated
   __shared__ int lm_state[2][kMaxBeam];     // the entry's LM state
   __shared__ float lm_sum[2][kMaxBeam];     // ln P_lm of its prefix, unweighted
   __shared__ float ext_w[kMaxKeys / 2];     // this frame's lm_step of (entry p, candidate ci) at p * C' + ci
   __shared__ int ext_next[kMaxKeys / 2];
+  __shared__ int lex_node[2][kMaxBeam];     // the lexicon mode's alone: the entry's node of the lexicon trie
+  __shared__ int done_sh;                   // ... and the number of complete entries at the end (nb_sh is still being read then)
   const int s = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   const int n = min(lens[s], T);
   const size_t cap = 1 + (size_t)T * B;
@@ -207,6 +221,7 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
     st[0].lb[0] = 0.f; st[0].lnb[0] = kLogZero; st[0].se[0] = kLogZero;
     st[0].node[0] = 0; st[0].last[0] = -1; st[0].len[0] = 0; st[0].hash[0] = 0;
     if constexpr (LM) { lm_state[0][0] = lm.tab.start; lm_sum[0][0] = 0.f; }
+    if constexpr (LEX) lex_node[0][0] = 0;
     nb_sh = 1;
     tp[0] = -1; tl[0] = -1;
     if (n > 0) c_bl[0] = sblank_g[s];
@@ -231,7 +246,10 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
     auto ext_value = [&](int p, int ci) -> float {
       const float lb = a.lb[p], lnb = a.lnb[p];
       float g = 0.f;
-      if constexpr (LM) g = __fadd_rn(__fmul_rn(lm.alpha, ext_w[p * Cc + ci]), lm.beta);
+      if constexpr (LEX) {
+        if (ext_next[p * Cc + ci] < 0) return kLogZero;
+        if (ci_[ci] == lm.lex.space) g = __fadd_rn(__fmul_rn(lm.alpha, ext_w[p * Cc + ci]), lm.beta);
+      } else if constexpr (LM) g = __fadd_rn(__fmul_rn(lm.alpha, ext_w[p * Cc + ci]), lm.beta);
       const float cs = LM ? score_add(cs_[ci], g) : cs_[ci];
       return score_add(cs, ci_[ci] == a.last[p] ? lb : log_add(lb, lnb));
     };
@@ -250,9 +268,22 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
     if constexpr (LM) {   // ---- 0
       for (int x = tid; x < n_ext; x += NT) {
         const int p = x / Cc, ci = x - p * Cc;
-        float w;
-        int next;
-        lm_step(lm.tab, lm_state[cur][p], ci_[ci], w, next);
+        float w = 0.f;
+        int next = -1;
+        if constexpr (LEX) {
+          const int4 r = reinterpret_cast<const int4*>(lm.lex.node_rec)[lex_node[cur][p]];   // {first child, count, word, 0}
+          const int c = ci_[ci];
+          if (c != lm.lex.space) {
+            const int end = r.x + r.y;
+            const int lo = lower_bound(lm.lex.child_cls, r.x, end, c);
+            if (lo < end && lm.lex.child_cls[lo] == c) next = lm.lex.child_node[lo];
+          } else if (r.z != 0) {
+            next = 0;
+            if (lm.have_lm) lm_step(lm.tab, lm_state[cur][p], r.z, w, next);
+          }
+        } else {
+          lm_step(lm.tab, lm_state[cur][p], ci_[ci], w, next);
+        }
         ext_w[x] = w;
         ext_next[x] = next;
       }
@@ -325,13 +356,19 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
           nx.lb[tid] = stay_lb[idx]; nx.lnb[tid] = stay_lnb[idx]; nx.se[tid] = nx_stay[idx];
           nx.node[tid] = a.node[idx]; nx.last[tid] = a.last[idx]; nx.len[tid] = a.len[idx]; nx.hash[tid] = a.hash[idx];
           if constexpr (LM) { lm_state[cur ^ 1][tid] = lm_state[cur][idx]; lm_sum[cur ^ 1][tid] = lm_sum[cur][idx]; }
+          if constexpr (LEX) lex_node[cur ^ 1][tid] = lex_node[cur][idx];
         } else {
           const int x = idx - kMaxBeam, p = x / Cc, ci = x - p * Cc, c = ci_[ci];
           const int node = 1 + t * B + tid;   // < cap: t < n <= T, tid < B
           nx.lb[tid] = kLogZero; nx.lnb[tid] = ext_value(p, ci); nx.se[tid] = nx_ext[ci];
           nx.node[tid] = node; nx.last[tid] = c; nx.len[tid] = a.len[p] + 1;
           nx.hash[tid] = a.hash[p] * kHashMul + (unsigned long long)(c + 1);
-          if constexpr (LM) { lm_state[cur ^ 1][tid] = ext_next[x]; lm_sum[cur ^ 1][tid] = __fadd_rn(lm_sum[cur][p], ext_w[x]); }
+          if constexpr (LEX) {   // ext_next is the LM's next state behind a space, the lexicon's child behind a unit
+            const bool sp = c == lm.lex.space;
+            lex_node[cur ^ 1][tid] = sp ? 0 : ext_next[x];
+            lm_state[cur ^ 1][tid] = sp ? ext_next[x] : lm_state[cur][p];
+            lm_sum[cur ^ 1][tid] = sp ? __fadd_rn(lm_sum[cur][p], ext_w[x]) : lm_sum[cur][p];
+          } else if constexpr (LM) { lm_state[cur ^ 1][tid] = ext_next[x]; lm_sum[cur ^ 1][tid] = __fadd_rn(lm_sum[cur][p], ext_w[x]); }
           tp[node] = a.node[p];
           tl[node] = c;
         }
@@ -343,10 +380,61 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
     __syncthreads();
     cur ^= 1;
   }
-  const int nb = nb_sh;
+  int nb = nb_sh;
   const BeamState& a = st[cur];
   const size_t out = (size_t)s * B;
-  if constexpr (!LM) {
+  if constexpr (LEX) {
+    // the end of the utterance: an entry that stands on a word end closes that word (the empty prefix has none to close), fin
+    // joins, the others are dropped, and what is left (<= 64) takes the rank of its new total, ties by the previous rank
+    if (tid < kMaxBeam) {   // wave 0
+      float total = kLogZero, lsum = kLogZero;
+      bool complete = false;
+      if (tid < nb) {
+        total = log_add(a.lb[tid], a.lnb[tid]) + 0.f;
+        lsum = lm_sum[cur][tid];
+        int state = lm_state[cur][tid];
+        const int w = reinterpret_cast<const int4*>(lm.lex.node_rec)[lex_node[cur][tid]].z;
+        complete = a.len[tid] == 0 || w != 0;
+        if (complete && a.len[tid] != 0) {
+          float wt = 0.f;
+          int next = state;
+          if (lm.have_lm) lm_step(lm.tab, state, w, wt, next);
+          state = next;
+          total = clamp_score(__fadd_rn(total, __fadd_rn(__fmul_rn(lm.alpha, wt), lm.beta))) + 0.f;
+          lsum = __fadd_rn(lsum, wt);
+        }
+        if (complete && lm.use_eos) {
+          const float f = lm.tab.fin[state];
+          total = clamp_score(__fadd_rn(total, __fmul_rn(lm.alpha, f))) + 0.f;
+          lsum = __fadd_rn(lsum, f);
+        }
+      }
+      keys[tid] = complete ? make_key(total, tid) : kDeadKey;
+      stay_lb[tid] = total;
+      stay_lnb[tid] = lsum;
+      const int done = __popcll(__ballot(complete));
+      if (tid == 0) done_sh = done;
+    }
+    __syncthreads();
+    const int done = done_sh;
+    if (tid < B) {
+      if (tid < nb && keys[tid] != kDeadKey) {
+        int rank = 0;
+        for (int i = 0; i < nb; ++i) rank += keys[i] < keys[tid];   // (a dead key is above every live one)
+        fnode[out + rank] = a.node[tid];
+        flen[out + rank] = a.len[tid];
+        fscore[out + rank] = stay_lb[tid];
+        lm.flm[out + rank] = stay_lnb[tid];
+      }
+      if (tid >= done) {
+        fnode[out + tid] = -1;
+        flen[out + tid] = -1;
+        fscore[out + tid] = kLogZero;
+        lm.flm[out + tid] = kLogZero;
+      }
+    }
+    nb = done;
+  } else if constexpr (!LM) {
     if (tid < B) {
       const bool live = tid < nb;
       fnode[out + tid] = live ? a.node[tid] : -1;
@@ -393,6 +481,28 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __res
   if (tid == 0) count[s] = nb;
 }
 
+// The kernels of the one text above: <false> the plain search and <true> the token-LM one, as they were named before the text had
+// a third mode, and the lexicon search.
+template <bool LM>
+__global__ __launch_bounds__(512) void ctc_prefix_beam_kernel(const float* __restrict__ sc, int ld, int T, int S,
+                                                              const int* __restrict__ lens, int B, int Cc,
+                                                              const int* __restrict__ cid_g, const float* __restrict__ csc_g,
+                                                              const float* __restrict__ sblank_g, LmArgs<LM ? kTokenLm : kPlain> lm,
+                                                              int* __restrict__ tparent, int* __restrict__ tlabel,
+                                                              int* __restrict__ fnode, int* __restrict__ flen,
+                                                              float* __restrict__ fscore, int* __restrict__ count) {
+  prefix_beam<LM ? kTokenLm : kPlain>(sc, ld, T, S, lens, B, Cc, cid_g, csc_g, sblank_g, lm, tparent, tlabel, fnode, flen, fscore, count);
+}
+__global__ __launch_bounds__(512) void ctc_prefix_beam_lex_kernel(const float* __restrict__ sc, int ld, int T, int S,
+                                                                  const int* __restrict__ lens, int B, int Cc,
+                                                                  const int* __restrict__ cid_g, const float* __restrict__ csc_g,
+                                                                  const float* __restrict__ sblank_g, LmArgs<kLexicon> lm,
+                                                                  int* __restrict__ tparent, int* __restrict__ tlabel,
+                                                                  int* __restrict__ fnode, int* __restrict__ flen,
+                                                                  float* __restrict__ fscore, int* __restrict__ count) {
+  prefix_beam<kLexicon>(sc, ld, T, S, lens, B, Cc, cid_g, csc_g, sblank_g, lm, tparent, tlabel, fnode, flen, fscore, count);
+}
+
 // ---- hypotheses: one lane per (utterance, rank); with an LM (flm, lm_out not null) the lane also hands out its entry's LM sum ------
 __global__ __launch_bounds__(64) void ctc_hyp_kernel(const int* __restrict__ tparent, const int* __restrict__ tlabel,
                                                      const int* __restrict__ fnode, const int* __restrict__ flen,
@@ -430,17 +540,20 @@ void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, 
 }
 
 void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                     const float* csc, const float* sblank, const LmTables* lm, float alpha, float beta, bool use_eos, int* tparent,
-                     int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count) {
+                     const float* csc, const float* sblank, const LmTables* lm, const LexTables* lex, float alpha, float beta, bool use_eos,
+                     int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count) {
   EESEN_REQUIRE(B >= 1 && B <= kMaxBeam && Cc >= 1 && Cc <= kMaxCls && B * Cc <= kMaxKeys / 2, EESEN_ERR_INVALID, "ctc_prefix_beam: beam or class count outside the key array");
   // one thread per pair of the widest sort stage, 64 .. 512
   int keys = 2;
   while (keys < B + B * Cc) keys <<= 1;
   const int threads = std::min(512, std::max(64, keys / 2));
-  if (lm) hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
-                             LmArgs<true>{*lm, alpha, beta, use_eos ? 1 : 0, flm}, tparent, tlabel, fnode, flen, fscore, count);
+  if (lex) hipLaunchKernelGGL(ctc_prefix_beam_lex_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
+                              LmArgs<kLexicon>{lm ? *lm : LmTables{}, alpha, beta, use_eos ? 1 : 0, flm, *lex, lm ? 1 : 0}, tparent, tlabel, fnode,
+                              flen, fscore, count);
+  else if (lm) hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
+                                  LmArgs<kTokenLm>{*lm, alpha, beta, use_eos ? 1 : 0, flm}, tparent, tlabel, fnode, flen, fscore, count);
   else hipLaunchKernelGGL(ctc_prefix_beam_kernel<false>, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
-                          LmArgs<false>{}, tparent, tlabel, fnode, flen, fscore, count);
+                          LmArgs<kPlain>{}, tparent, tlabel, fnode, flen, fscore, count);
   check_launch("ctc_prefix_beam");
 }
 

@@ -220,7 +220,7 @@ void Ctc::align_times(float* out3) {
 // Prefix beam search of every utterance (INTEGRATION.md "Decoding").  The logarithms borrow `logp`; everything else is this call's own.
 void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                           int nbest, int* hyp_host, int* hyp_len_host, float* score_host) {
-  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, 0.f, 0.f, false, hyp_host, hyp_len_host, score_host, nullptr);
+  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, nullptr, 0.f, 0.f, false, hyp_host, hyp_len_host, score_host, nullptr);
 }
 
 // With a token LM fused into the beam (INTEGRATION.md "LM fusion"): ctc_prefix_beam with the tables, inside the same phase.  The
@@ -232,8 +232,53 @@ void Ctc::decode_parallel_lm(const int* frame_num_utt, int S, const float* score
   EESEN_REQUIRE(lm->K == K, EESEN_ERR_INVALID, "the LM was built for another class count K than the scores have");
   EESEN_REQUIRE(!use_eos || lm->has_eos, EESEN_ERR_INVALID, "use_eos on an LM whose file has no </s>");
   EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(insertion_bonus), EESEN_ERR_INVALID, "lm_weight and insertion_bonus must be finite");
-  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, lm, lm_weight, insertion_bonus, use_eos, hyp_host, hyp_len_host,
+  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, lm, lm_weight, insertion_bonus, use_eos, hyp_host,
+               hyp_len_host, score_host, lm_score_host);
+}
+
+// Along a lexicon trie, with or without an LM over its words (INTEGRATION.md "Lexicon"): the same three launches; the lexicon's
+// tables and the word LM's are uploaded when this Ctc meets them for the first time.  The words of every returned labelling are
+// its segmentation, done here on the host.
+void Ctc::decode_parallel_lex(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                              int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
+                              int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host) {
+  EESEN_REQUIRE(lex != nullptr, EESEN_ERR_INVALID, "decoding with a lexicon: the lexicon handle is null");
+  EESEN_REQUIRE(lex->K == K, EESEN_ERR_INVALID, "the lexicon was built for another class count K than the scores have");
+  EESEN_REQUIRE(lm == nullptr || lm->K == lex->V() + 1, EESEN_ERR_INVALID, "the word LM's K must be the lexicon's word count + 1 (build it over eesen_lex_write_words' table)");
+  EESEN_REQUIRE(!use_eos || (lm != nullptr && lm->has_eos), EESEN_ERR_INVALID, "use_eos without a word LM, or on one whose file has no </s>");
+  EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_bonus), EESEN_ERR_INVALID, "lm_weight and word_bonus must be finite");
+  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, lex, lm, lm_weight, word_bonus, use_eos, hyp_host, hyp_len_host,
                score_host, lm_score_host);
+  if (!word_host && !word_len_host) return;
+  const int T = rows / S;
+  std::vector<int> w((size_t)T / 2 + 1);
+  for (size_t i = 0; i < (size_t)S * nbest; ++i) {
+    int nw = -1;   // (no entry, or a raised guard word)
+    if (hyp_len_host[i] >= 0) {
+      const bool in_language = lex->words(hyp_host + i * T, hyp_len_host[i], w.data(), &nw);
+      EESEN_REQUIRE(in_language, EESEN_ERR_STATE, "decoding with a lexicon returned a labelling outside its language");
+    }
+    if (word_len_host) word_len_host[i] = nw;
+    if (word_host)
+      for (int j = 0; j < T; ++j) word_host[i * T + j] = j < nw ? w[j] : -1;
+  }
+}
+
+void Ctc::upload_lex(const Lexicon& lex) {
+  if (lex_serial == lex.serial) return;
+  EESEN_HIP_CHECK(hipStreamSynchronize(st));   // (a launch in flight may still read the tables this replaces)
+  const size_t nn = lex.word.size(), ne = lex.child_cls.size();
+  std::vector<int> packed(4 * nn + 2 * ne);
+  for (size_t v = 0; v < nn; ++v) {
+    int* r = packed.data() + 4 * v;
+    r[0] = lex.first[v]; r[1] = lex.count[v]; r[2] = lex.word[v]; r[3] = 0;
+  }
+  std::copy(lex.child_cls.begin(), lex.child_cls.end(), packed.begin() + 4 * nn);
+  std::copy(lex.child_node.begin(), lex.child_node.end(), packed.begin() + 4 * nn + ne);
+  lex_i.reserve(packed.size());
+  EESEN_HIP_CHECK(hipMemcpy(lex_i.p, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
+  lex_tab = LexTables{lex_i.p, lex_i.p + 4 * nn, lex_i.p + 4 * nn + ne, lex.space};
+  lex_serial = lex.serial;
 }
 
 void Ctc::upload_lm(const TokenLm& lm) {
@@ -260,8 +305,9 @@ void Ctc::upload_lm(const TokenLm& lm) {
 }
 
 void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
-                       int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
-                       float* score_host, float* lm_score_host) {
+                       int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host,
+                       int* hyp_len_host, float* score_host, float* lm_score_host) {
+  const bool fused = lm != nullptr || lex != nullptr;   // the beam carries LM sums (all 0 under a lexicon without an LM)
   EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
   EESEN_REQUIRE(K >= 2, EESEN_ERR_INVALID, "decoding needs the blank and at least one other class (K >= 2)");
   EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
@@ -275,8 +321,8 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   EESEN_HIP_CHECK(hipSetDevice(device));
   const int B = beam, N = nbest, Cc = std::min(max_classes, K - 1);
   const size_t n_cand = (size_t)rows * Cc, n_beam = (size_t)S * B, n_trie = (size_t)S * (1 + (size_t)T * B);
-  const size_t n_f = n_cand + rows + n_beam + (lm ? n_beam : 0), n_i = n_cand + S + 2 * n_beam + S;
-  const size_t n_hyp = (size_t)S * N * T, n_out = n_hyp + (lm ? 3 : 2) * (size_t)S * N;   // labels, lengths, scores (, LM sums)
+  const size_t n_f = n_cand + rows + n_beam + (fused ? n_beam : 0), n_i = n_cand + S + 2 * n_beam + S;
+  const size_t n_hyp = (size_t)S * N * T, n_out = n_hyp + (fused ? 3 : 2) * (size_t)S * N;   // labels, lengths, scores (, LM sums)
   EESEN_REQUIRE(n_trie <= ((size_t)1 << 30), EESEN_ERR_INVALID, "decoding: more than 2^30 trie nodes (S * (1 + T * beam)): decode fewer utterances together");
   if ((!is_log && logp.cap < (size_t)rows * K) || dec_f.cap < n_f || dec_i.cap < n_i || dec_trie.cap < 2 * n_trie || dec_out.cap < n_out)
     EESEN_HIP_CHECK(hipStreamSynchronize(st));
@@ -299,6 +345,7 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   float* flm = fscore + n_beam;             // (with an LM only)
   float* lmsum_d = score_d + (size_t)S * N;
   if (lm) upload_lm(*lm);
+  if (lex) upload_lex(*lex);
 
   PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
   int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
@@ -314,9 +361,9 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
   ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
   if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
-  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, lm ? flm : nullptr, count);
+  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, lex ? &lex_tab : nullptr, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, fused ? flm : nullptr, count);
   if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
-  ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, lm ? flm : nullptr, count, T, S, B, N, hyp_d, len_d, score_d, lm ? lmsum_d : nullptr);
+  ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, fused ? flm : nullptr, count, T, S, B, N, hyp_d, len_d, score_d, fused ? lmsum_d : nullptr);
   if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
   dec_rows = rows; dec_S = S; dec_C = Cc;
   dec_lens.assign(frame_num_utt, frame_num_utt + S);
@@ -335,7 +382,7 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   for (size_t i = 0; i < (size_t)S * N; ++i) {
     hyp_len_host[i] = bad ? -1 : out[n_hyp + i];
     score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
-    if (lm && lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[(size_t)S * N + i];
+    if (fused && lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[(size_t)S * N + i];
   }
 }
 

@@ -218,22 +218,25 @@ void ctc_best_path(hipStream_t st, const float* scores, int ld, int T, int S, in
 // every row of an utterance without a feasible path; score [S]: the path's log-score, -1e30 without one.
 void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, const int* labx, const int* lens, const int* lablens,
                    int* ali, int* pos, float* score);
-// Lexicon-free prefix beam search (ctc_decode.hip; the computation: INTEGRATION.md "Decoding").  scores: [T*S x K] (ld) log-domain.
+// Prefix beam search, lexicon-free or along a lexicon trie (ctc_decode.hip; the computation: INTEGRATION.md "Decoding").  scores: [T*S x K] (ld) log-domain.
 // ctc_row_topc: per row t*S + s with t < lens[s] the Cc = min(max_classes, K - 1) best non-blank classes -- ids ascending in
 // cid [rows][Cc], their scores in csc [rows][Cc], the blank's in sblank [rows]; every score clamped from below at -1e30.
 void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, int S, const int* lens, int Cc, int* cid, float* csc,
                   float* sblank);
 struct LmTables;
+struct LexTables;
 // ctc_prefix_beam: S workgroups, each walks its utterance's frames.  tparent / tlabel [S][1 + T*B]: the trie (node 0 = the empty
 // prefix), written only; fnode / flen / fscore [S][B]: node, length and total of the final beam, best first (-1, -1, -1e30 beyond
-// count[s] live entries).  1 <= B <= 64, 1 <= Cc <= 64, B * Cc <= 2048.  lm == null: the plain search (ctc_prefix_beam_kernel<false>;
-// alpha, beta, use_eos and flm are not read).  Otherwise the same search with a token n-gram LM fused in (<true>; INTEGRATION.md
+// count[s] live entries).  1 <= B <= 64, 1 <= Cc <= 64, B * Cc <= 2048.  lm == lex == null: the plain search (ctc_prefix_beam_kernel
+// <false>; alpha, beta, use_eos and flm are not read).  lm alone: the same search with a token n-gram LM fused in (<true>; INTEGRATION.md
 // "LM fusion"; the tables: lm.h): an extension by class c adds g = alpha * w + beta, (w, next) = lm_step(the entry's LM state, c);
 // with use_eos, alpha * fin[state] joins every total after the last frame and the final beam is re-ranked.  flm [S][B]: the
-// unweighted LM sum of each final entry.
+// unweighted LM sum of each final entry.  lex: extensions only along the lexicon trie (ctc_prefix_beam_lex_kernel; INTEGRATION.md "Lexicon"; the
+// tables: lex.h); lm is then a model over word ids, stepped once per closed word, or null; beta is per word; the final beam holds
+// only the entries that end on a word end, and count[s] counts those.
 void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                     const float* csc, const float* sblank, const LmTables* lm, float alpha, float beta, bool use_eos, int* tparent,
-                     int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count);
+                     const float* csc, const float* sblank, const LmTables* lm, const LexTables* lex, float alpha, float beta, bool use_eos,
+                     int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count);
 // ctc_hyp: hyp [S][N][T] the labels of the N best entries front to back (-1 beyond the length), hyp_len / score [S][N] (-1 / -1e30
 // beyond count[s]); with flm and lm_out (both null without an LM) lm_out [S][N] = flm of the same entries, -1e30 beyond count[s].
 void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const float* flm,

@@ -17,12 +17,7 @@
 #include "lm.h"
 
 namespace eesen {
-namespace {
-
-constexpr int kMaxOrder = 8;
-constexpr double kLn10 = 2.302585092994045684;
-using Gram = std::vector<int>;
-struct Entry { float w = 0.f, bo = 0.f; int state = -1; };
+namespace text {
 
 [[noreturn]] void fail(const std::string& path, long line, const std::string& what) {
   throw Error(EESEN_ERR_INVALID, path + (line > 0 ? ":" + std::to_string(line) : std::string()) + ": " + what);
@@ -43,13 +38,6 @@ bool decimal(const std::string& s, long* v) {
   return true;
 }
 
-bool number(const std::string& s, double* v) {
-  char* end = nullptr;
-  errno = 0;
-  *v = std::strtod(s.c_str(), &end);
-  return end != s.c_str() && *end == 0 && std::isfinite(*v);
-}
-
 std::unordered_map<std::string, int> read_units(const char* path, int K) {
   std::ifstream in(path);
   if (!in) fail(path, 0, "cannot open the units table");
@@ -66,9 +54,26 @@ std::unordered_map<std::string, int> read_units(const char* path, int K) {
   return u;
 }
 
+}  // namespace text
+
+namespace {
+
+using namespace text;
+constexpr int kMaxOrder = 8;
+constexpr double kLn10 = 2.302585092994045684;
+using Gram = std::vector<int>;
+struct Entry { float w = 0.f, bo = 0.f; int state = -1; };
+
+bool number(const std::string& s, double* v) {
+  char* end = nullptr;
+  errno = 0;
+  *v = std::strtod(s.c_str(), &end);
+  return end != s.c_str() && *end == 0 && std::isfinite(*v);
+}
+
 }  // namespace
 
-void TokenLm::from_arpa(const char* arpa, const char* units, int K) {
+void TokenLm::from_arpa(const char* arpa, const char* units, int K, bool skip_oov) {
   EESEN_REQUIRE(K >= 2, EESEN_ERR_INVALID, "a token LM needs the blank and at least one other class (K >= 2)");
   const int BOS = K, EOS = K + 1, UNK = K + 2;
   const bool have_units = units != nullptr && units[0] != 0;
@@ -83,13 +88,17 @@ void TokenLm::from_arpa(const char* arpa, const char* units, int K) {
     } else {
       long id = 0;
       if (decimal(w, &id)) {
-        if (id < 1 || id >= K) fail(arpa, ln, "word " + w + " is no class id in [1, K) with K = " + std::to_string(K));
+        if (id < 1 || id >= K) {
+          if (skip_oov) return -1;
+          fail(arpa, ln, "word " + w + " is no class id in [1, K) with K = " + std::to_string(K));
+        }
         return (int)id;
       }
     }
     if (w == "<s>") return BOS;
     if (w == "</s>") return EOS;
     if (w == "<unk>") return UNK;
+    if (skip_oov) return -1;
     fail(arpa, ln, "word " + w + (have_units ? " is neither a unit nor <s>, </s>, <unk>" : " is neither a decimal class id nor <s>, </s>, <unk>"));
   };
 
@@ -156,7 +165,13 @@ void TokenLm::from_arpa(const char* arpa, const char* units, int K) {
     if (!number(f[0], &v)) fail(arpa, ln, "value " + f[0] + " is not a finite number");
     if ((int)f.size() == n + 2 && !number(f[n + 1], &b)) fail(arpa, ln, "backoff weight " + f[n + 1] + " is not a finite number");
     Gram g(n);
-    for (int i = 0; i < n; ++i) g[i] = resolve(f[1 + i], ln);
+    bool oov = false;
+    for (int i = 0; i < n; ++i) oov |= (g[i] = resolve(f[1 + i], ln)) < 0;
+    if (oov) {   // skip_oov: counted towards its section, then dropped (as are, by the same rule, all n-grams that extend it)
+      ++seen;
+      ++oov_dropped;
+      continue;
+    }
     if (n > 1 && !grams[n - 1].count(Gram(g.begin(), g.end() - 1))) fail(arpa, ln, "the " + std::to_string(n - 1) + "-word prefix of this n-gram is not listed");
     Entry e;
     e.w = (float)(v * kLn10);
@@ -171,8 +186,12 @@ void TokenLm::from_arpa(const char* arpa, const char* units, int K) {
   // ---- coverage: every class has a unigram, its own or <unk>'s
   const auto unk = grams[1].find(Gram{UNK});
   for (int c = 1; c < K; ++c)
-    if (!grams[1].count(Gram{c}) && unk == grams[1].end())
-      throw Error(EESEN_ERR_INVALID, std::string(arpa) + ": class " + std::to_string(c) + " has no unigram and the file has no <unk>");
+    if (!grams[1].count(Gram{c}) && unk == grams[1].end()) {
+      std::string name;   // with a table, what the file would have called it (a word of a 20 000-word lexicon is not found by its id)
+      for (const auto& kv : table)
+        if (kv.second == c) name = " (" + kv.first + ")";
+      throw Error(EESEN_ERR_INVALID, std::string(arpa) + ": class " + std::to_string(c) + name + " has no unigram and the file has no <unk>");
+    }
 
   // ---- states: the empty context, then every n-gram of order < N that does not end in </s> or <unk>
   TokenLm* lm = this;

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "lex.h"
 #include "lm.h"
 #include "tuning.h"
 
@@ -278,6 +279,10 @@ struct Ctc {
   DevBuf<float> lm_f;
   LmTables lm_tab{};
   unsigned long long lm_serial = 0;
+  // the tables of the lexicon the last decode_parallel_lex used (lex.h), keyed in the same way
+  DevBuf<int> lex_i;
+  LexTables lex_tab{};
+  unsigned long long lex_serial = 0;
   // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
   // back through PinBufs that are folded into the statistics at the next call that needs them ("deferred").
@@ -312,6 +317,11 @@ struct Ctc {
   void decode_parallel_lm(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                           int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
                           float* score_host, float* lm_score_host);
+  // the search along a lexicon trie, with or without (lm == null) an LM over its word ids; word_host [S][nbest][T] / word_len_host
+  // [S][nbest]: the segmentation of every returned labelling (Lexicon::words on the host), -1 beyond; either may be null
+  void decode_parallel_lex(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                           int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
+                           int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host);
   void decode_times(float* out3);
   // the candidate classes the last decode_parallel selected: ids / scores [rows][C'], blank [rows]; rows beyond an utterance: -1 / -1e30
   void get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc);
@@ -319,9 +329,10 @@ struct Ctc {
   struct Lattices { const int *labx, *lens, *lablens; int Lpad, Lprime; };
   Lattices upload_lattices(const int* frame_num_utt, int S, const int* label_ids, const int* label_off);
   void decode_batch(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
-                    int nbest, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
-                    float* score_host, float* lm_score_host);
+                    int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host,
+                    int* hyp_len_host, float* score_host, float* lm_score_host);
   void upload_lm(const TokenLm& lm);
+  void upload_lex(const Lexicon& lex);
 };
 
 // LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: what Ctc::error_rate_mseq counts with (ctc_host.cpp)

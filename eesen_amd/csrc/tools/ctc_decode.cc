@@ -4,12 +4,18 @@
 // optional ClassPrior::SubtractOnLogpost (the options of net-output-extract) -> eesen_ctc_decode_parallel.  Written: one int32 vector
 // per hypothesis, the labels (blank-free); with --nbest > 1 under the keys utt-1, utt-2, ... (as lattice-to-nbest names them).
 // With --lm a token n-gram LM (an ARPA file over the net's tokens) is fused into the search: eesen_ctc_decode_parallel_lm.
+// With --lexicon the labellings are held to lexicon words separated by --space-unit, scored by an optional word n-gram LM
+// (--word-lm): eesen_ctc_decode_parallel_lex; the word ids go to --words-wspecifier and word errors are counted against
+// --word-ref-rspecifier.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <fstream>
 #include <iostream>
 #include <sstream>
+
+#include <unistd.h>
 
 #include "../../../include/eesen_hip.h"
 #include "kaldi_tables.h"
@@ -23,6 +29,22 @@ using namespace ktab;
 void ck(int rc) {
   if (rc != EESEN_OK) throw std::runtime_error(eesen_last_error());
 }
+// the class id of --space-unit: a symbol of the units table, or a decimal id without one
+int space_class(const std::string& unit, const std::string& units_path) {
+  if (units_path.empty()) {
+    if (unit.empty() || unit.find_first_not_of("0123456789") != std::string::npos || unit.size() > 9)
+      throw std::runtime_error("--space-unit=" + unit + " is no decimal class id (give --lexicon-units to name it by its symbol)");
+    return std::stoi(unit);
+  }
+  std::ifstream in(units_path);
+  if (!in) throw std::runtime_error("cannot open " + units_path);
+  std::string line, sym, id;
+  while (std::getline(in, line)) {
+    std::istringstream f(line);
+    if (f >> sym >> id && sym == unit && id.find_first_not_of("0123456789") == std::string::npos && id.size() <= 9) return std::stoi(id);
+  }
+  throw std::runtime_error("--space-unit=" + unit + " is not in " + units_path);
+}
 std::string fmt9(double v) {
   std::ostringstream o;
   o.precision(9);
@@ -34,8 +56,9 @@ std::string fmt9(double v) {
 int main(int argc, char** argv) {
   try {
     std::string class_frame_counts, scores_out, ref_rspecifier, lm_arpa, lm_units;
-    float prior_scale = 1.f, lm_weight = 1.f, insertion_bonus = 0.f;
-    bool lm_eos = false;
+    std::string lexicon, lexicon_units, space_unit = "<SPACE>", word_lm, words_wspecifier, words_table_out, word_ref_rspecifier;
+    float prior_scale = 1.f, lm_weight = 1.f, insertion_bonus = 0.f, word_bonus = 0.f;
+    bool lm_eos = false, lm_skip_oov = false;
     double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
     int num_sequence = 1, device = 0, beam = 16, max_classes = 20, nbest = 1;
     std::string use_gpu = "yes";
@@ -61,6 +84,15 @@ int main(int argc, char** argv) {
     po.Register("lm-weight", &lm_weight, "Weight of the LM's log-probability of every label");
     po.Register("insertion-bonus", &insertion_bonus, "Added per label, in nats");
     po.Register("lm-eos", &lm_eos, "Add the weighted log-probability of </s> at the end of every hypothesis");
+    po.Register("lexicon", &lexicon, "Lexicon, `word unit unit ...` per spelling: the hypotheses are its words separated by --space-unit");
+    po.Register("lexicon-units", &lexicon_units, "units.txt of the lexicon's units: `symbol id` per line; without it they are decimal class ids");
+    po.Register("space-unit", &space_unit, "The unit between words: a symbol of --lexicon-units, or a decimal class id without it");
+    po.Register("word-lm", &word_lm, "ARPA file of a word n-gram LM over the lexicon's words, stepped once per word (weight: --lm-weight)");
+    po.Register("word-bonus", &word_bonus, "Added per word, in nats");
+    po.Register("lm-skip-oov", &lm_skip_oov, "Drop the n-grams of --word-lm that hold a word outside the lexicon instead of refusing the file");
+    po.Register("words-wspecifier", &words_wspecifier, "Also write the word ids of every hypothesis (int32 vectors, the keys of <hyp-wspecifier>)");
+    po.Register("words-table-out", &words_table_out, "Write the lexicon's `word id` table to this file");
+    po.Register("word-ref-rspecifier", &word_ref_rspecifier, "Reference word-id sequences: the word errors of the best hypotheses against them are counted");
     po.Register("use-gpu", &use_gpu, "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)");
     po.Register("num-sequence", &num_sequence, "Utterances forwarded and decoded together");
     po.Register("frame-limit", &frame_limit, "Max number of frames forwarded together");
@@ -85,8 +117,36 @@ int main(int argc, char** argv) {
     ck(eesen_net_input_dim(net, &D));
     ck(eesen_net_output_dim(net, &K));
     eesen_lm_t* lm = nullptr;
+    if (!lexicon.empty() && !lm_arpa.empty()) throw std::runtime_error("--lexicon together with --lm: the token LM and the word LM cannot be combined");
     if (!lm_arpa.empty()) ck(eesen_lm_create_from_arpa(lm_arpa.c_str(), lm_units.empty() ? nullptr : lm_units.c_str(), K, &lm));
     else if (!lm_units.empty()) throw std::runtime_error("--lm-units without --lm");
+    eesen_lex_t* lex = nullptr;
+    int V = 0;
+    if (!lexicon.empty()) {
+      ck(eesen_lex_create(lexicon.c_str(), lexicon_units.empty() ? nullptr : lexicon_units.c_str(), K, space_class(space_unit, lexicon_units), &lex));
+      ck(eesen_lex_info(lex, &V, nullptr, nullptr));
+      if (!words_table_out.empty()) ck(eesen_lex_write_words(lex, words_table_out.c_str()));
+      if (!word_lm.empty()) {   // the word LM reads its words through the lexicon's table
+        std::string table = words_table_out;
+        if (table.empty()) {   // a file of our own, created exclusively (mkstemp), gone as soon as the LM has read it
+          const char* tmpdir = getenv("TMPDIR");
+          table = std::string(tmpdir && tmpdir[0] ? tmpdir : "/tmp") + "/ctc-decode-words.XXXXXX";
+          const int fd = mkstemp(&table[0]);
+          if (fd < 0) throw std::runtime_error("cannot create a temporary file for the words table: " + table);
+          close(fd);
+        }
+        int rc = words_table_out.empty() ? eesen_lex_write_words(lex, table.c_str()) : EESEN_OK;
+        if (rc == EESEN_OK) rc = eesen_lm_create_from_arpa_ex(word_lm.c_str(), table.c_str(), V + 1, lm_skip_oov ? 1 : 0, &lm);
+        if (words_table_out.empty()) std::remove(table.c_str());
+        ck(rc);
+        long long dropped = 0;
+        ck(eesen_lm_oov_dropped(lm, &dropped));
+        if (lm_skip_oov) std::cerr << "LOG (ctc-decode:main()) " << dropped << " n-grams of " << word_lm << " hold a word outside the lexicon and were dropped" << std::endl;
+      }
+    } else if (!lexicon_units.empty() || !word_lm.empty() || !words_wspecifier.empty() || !words_table_out.empty() || !word_ref_rspecifier.empty() ||
+               word_bonus != 0.f || lm_skip_oov) {
+      throw std::runtime_error("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and --word-ref-rspecifier need --lexicon");
+    }
     std::vector<float> log_pri;
     if (!class_frame_counts.empty()) {
       log_pri = class_log_priors(class_frame_counts, prior_cutoff, blank_scale);
@@ -104,6 +164,10 @@ int main(int argc, char** argv) {
     }
     std::map<std::string, std::vector<int32_t>> refs;
     if (!ref_rspecifier.empty()) refs = read_targets(ref_rspecifier);
+    std::map<std::string, std::vector<int32_t>> word_refs;
+    if (!word_ref_rspecifier.empty()) word_refs = read_targets(word_ref_rspecifier);
+    std::unique_ptr<IntVectorWriter> words_writer;
+    if (!words_wspecifier.empty()) words_writer.reset(new IntVectorWriter(words_wspecifier));
     FeatureReader reader(piped ? pipe.source : args[1]);
     IntVectorWriter writer(args[2]);
     std::ofstream scores;
@@ -111,13 +175,13 @@ int main(int argc, char** argv) {
       scores.open(scores_out);
       if (!scores) throw std::runtime_error("cannot open " + scores_out);
     }
-    long num_done = 0, num_empty = 0, num_dead = 0, tok_err = 0, tok_ref = 0, num_scored = 0;
+    long num_done = 0, num_empty = 0, num_dead = 0, tok_err = 0, tok_ref = 0, num_scored = 0, word_err = 0, word_ref = 0, num_word_scored = 0;
     double tot_t = 0, tot_score = 0, tot_lm = 0;
     long tot_labels = 0;
     std::vector<std::pair<std::string, Mat>> group;
     std::vector<int> out_frames;            // per utterance of the group: frames behind the pipeline
     std::vector<const float*> cmvn;
-    std::vector<int> hyp, hyp_len;
+    std::vector<int> hyp, hyp_len, words, words_len;
     std::vector<float> score, lm_score;
     auto flush = [&]() {
       const int S = (int)group.size();
@@ -137,7 +201,12 @@ int main(int argc, char** argv) {
       if (!log_pri.empty())
         ck(eesen_op_log_sub_prior(device, nullptr, const_cast<float*>(out), T * S, K, old, 1, log_pri.data(), prior_scale));
       hyp.resize((size_t)S * nbest * T); hyp_len.resize((size_t)S * nbest); score.resize((size_t)S * nbest);
-      if (lm) {
+      if (lex) {
+        lm_score.resize((size_t)S * nbest); words.resize((size_t)S * nbest * T); words_len.resize((size_t)S * nbest);
+        ck(eesen_ctc_decode_parallel_lex(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, lex, lm, lm_weight,
+                                         word_bonus, lm_eos ? 1 : 0, hyp.data(), hyp_len.data(), score.data(), lm_score.data(), words.data(),
+                                         words_len.data()));
+      } else if (lm) {
         lm_score.resize((size_t)S * nbest);
         ck(eesen_ctc_decode_parallel_lm(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, lm, lm_weight,
                                         insertion_bonus, lm_eos ? 1 : 0, hyp.data(), hyp_len.data(), score.data(), lm_score.data()));
@@ -150,14 +219,15 @@ int main(int argc, char** argv) {
         const size_t e0 = (size_t)s * nbest;
         if (std::isnan(score[e0])) throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no hypotheses");
         if (hyp_len[e0] < 0) {
-          std::cerr << "WARNING (ctc-decode:main()) " << utt << ", every prefix has probability zero on " << frames[s]
-                    << " frames, producing no output for this utterance" << std::endl;
+          std::cerr << "WARNING (ctc-decode:main()) " << utt << (lex ? ", no surviving prefix ends a lexicon word on " : ", every prefix has probability zero on ")
+                    << frames[s] << " frames, producing no output for this utterance" << std::endl;
           ++num_dead;
           continue;
         }
         for (int i = 0; i < nbest && hyp_len[e0 + i] >= 0; ++i) {
           const std::string key = nbest > 1 ? utt + "-" + std::to_string(i + 1) : utt;
           writer.Write(key, hyp.data() + (e0 + i) * T, hyp_len[e0 + i]);
+          if (words_writer) words_writer->Write(key, words.data() + (e0 + i) * T, words_len[e0 + i]);
           if (scores.is_open()) {
             scores << key << ' ' << fmt9(score[e0 + i]);
             if (lm) scores << ' ' << fmt9(lm_score[e0 + i]);
@@ -170,11 +240,17 @@ int main(int argc, char** argv) {
           ck(eesen_edit_distance(ref->second.data(), (int)ref->second.size(), hyp.data() + e0 * T, hyp_len[e0], &err));
           tok_err += err; tok_ref += (long)ref->second.size(); ++num_scored;
         }
+        const auto wref = word_refs.find(utt);
+        if (wref != word_refs.end()) {
+          int err = 0;
+          ck(eesen_edit_distance(wref->second.data(), (int)wref->second.size(), words.data() + e0 * T, words_len[e0], &err));
+          word_err += err; word_ref += (long)wref->second.size(); ++num_word_scored;
+        }
         ++num_done;
         if (hyp_len[e0] == 0) ++num_empty;
         tot_t += frames[s];
         tot_score += score[e0];
-        if (lm) { tot_lm += lm_score[e0]; tot_labels += hyp_len[e0]; }
+        if (lm) { tot_lm += lm_score[e0]; tot_labels += lex ? words_len[e0] : hyp_len[e0]; }
       }
       group.clear(); out_frames.clear(); cmvn.clear();
     };
@@ -215,12 +291,17 @@ int main(int argc, char** argv) {
       std::cerr << "LOG (ctc-decode:main()) " << tok_err << " token errors on " << tok_ref << " reference tokens of " << num_scored << " utterances" << std::endl;
       std::cerr << "LOG (ctc-decode:main()) \nTOKEN_ACCURACY >> " << 100.0 * (1.0 - (double)tok_err / (double)std::max(tok_ref, 1L)) << "% <<" << std::endl;
     }
+    if (!word_ref_rspecifier.empty()) {
+      std::cerr << "LOG (ctc-decode:main()) " << word_err << " word errors on " << word_ref << " reference words of " << num_word_scored << " utterances" << std::endl;
+      std::cerr << "LOG (ctc-decode:main()) \nWORD_ACCURACY >> " << 100.0 * (1.0 - (double)word_err / (double)std::max(word_ref, 1L)) << "% <<" << std::endl;
+    }
     if (num_dead) std::cerr << "LOG (ctc-decode:main()) " << num_dead << " utterances without a hypothesis" << std::endl;
     std::cerr << "LOG (ctc-decode:main()) Done " << num_done << " utterances, " << num_empty << " empty hypotheses; average log-probability per frame "
               << (tot_t > 0 ? tot_score / tot_t : 0.0);
-    if (lm) std::cerr << "; average LM log-probability per label " << (tot_labels > 0 ? tot_lm / tot_labels : 0.0);
+    if (lm) std::cerr << "; average LM log-probability per " << (lex ? "word " : "label ") << (tot_labels > 0 ? tot_lm / tot_labels : 0.0);
     std::cerr << std::endl;
     if (lm) eesen_lm_destroy(lm);
+    if (lex) eesen_lex_destroy(lex);
     eesen_ctc_destroy(ctc);
     eesen_feeder_destroy(feeder);
     eesen_net_destroy(net);

@@ -9,12 +9,31 @@ The reference has no such tool: it decodes ONE utterance per process through a T
 --num-sequence utterances: forward pass as net-output-extract -> optional log + prior subtraction (net-output-extract's options) ->
 Ctc.DecodeParallel.  Written: one int32 vector per hypothesis, the labels (blank-free); with --nbest > 1 under the keys utt-1, utt-2, ...
 With --lm a token n-gram LM (an ARPA file over the net's tokens) is fused into the search (api.TokenLm).
+With --lexicon the labellings are held to lexicon words separated by --space-unit, scored by an optional word n-gram LM (--word-lm):
+api.Lexicon; the word ids go to --words-wspecifier and word errors are counted against --word-ref-rspecifier.
 """
 from __future__ import annotations
 
 import math
 import os
 import sys
+
+
+def _space_class(unit: str, units_path: str) -> int:
+    """The class id of --space-unit: a symbol of the units table, or a decimal id without one."""
+    if not units_path:
+        if not (unit.isascii() and unit.isdigit() and len(unit) <= 9):
+            raise ValueError(f"--space-unit={unit} is no decimal class id (give --lexicon-units to name it by its symbol)")
+        return int(unit)
+    try:
+        lines = open(units_path).read().splitlines()
+    except OSError:
+        raise ValueError(f"cannot open {units_path}")
+    for line in lines:
+        f = line.split()
+        if len(f) >= 2 and f[0] == unit and f[1].isascii() and f[1].isdigit() and len(f[1]) <= 9:
+            return int(f[1])
+    raise ValueError(f"--space-unit={unit} is not in {units_path}")
 
 
 def main(argv=None) -> int:
@@ -40,6 +59,15 @@ def main(argv=None) -> int:
     ap.register("lm-weight", 1.0, "Weight of the LM's log-probability of every label")
     ap.register("insertion-bonus", 0.0, "Added per label, in nats")
     ap.register("lm-eos", False, "Add the weighted log-probability of </s> at the end of every hypothesis")
+    ap.register("lexicon", "", "Lexicon, `word unit unit ...` per spelling: the hypotheses are its words separated by --space-unit")
+    ap.register("lexicon-units", "", "units.txt of the lexicon's units: `symbol id` per line; without it they are decimal class ids")
+    ap.register("space-unit", "<SPACE>", "The unit between words: a symbol of --lexicon-units, or a decimal class id without it")
+    ap.register("word-lm", "", "ARPA file of a word n-gram LM over the lexicon's words, stepped once per word (weight: --lm-weight)")
+    ap.register("word-bonus", 0.0, "Added per word, in nats")
+    ap.register("lm-skip-oov", False, "Drop the n-grams of --word-lm that hold a word outside the lexicon instead of refusing the file")
+    ap.register("words-wspecifier", "", "Also write the word ids of every hypothesis (int32 vectors, the keys of <hyp-wspecifier>)")
+    ap.register("words-table-out", "", "Write the lexicon's `word id` table to this file")
+    ap.register("word-ref-rspecifier", "", "Reference word-id sequences: the word errors of the best hypotheses against them are counted")
     ap.register("use-gpu", "yes", "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)")
     ap.register("num-sequence", 1, "Utterances forwarded and decoded together")
     ap.register("frame-limit", 1e5, "Max number of frames forwarded together", kind="double")
@@ -64,7 +92,7 @@ def main(argv=None) -> int:
         import ctypes as C
         import numpy as np
         from eesen_amd import kaldi_io, _lib, frontend
-        from eesen_amd.api import Net, Ctc, TokenLm
+        from eesen_amd.api import Net, Ctc, TokenLm, Lexicon
         from eesen_amd.batching import interleave
         from eesen_amd.net_output_extract import class_log_priors
 
@@ -78,20 +106,52 @@ def main(argv=None) -> int:
         log_pri = class_log_priors(o.class_frame_counts, o.prior_cutoff, o.blank_scale) if o.class_frame_counts else None
         K = net.OutputDim()
         lm = None
+        if o.lexicon and o.lm:
+            raise kaldi_io.KaldiIOError("--lexicon together with --lm: the token LM and the word LM cannot be combined")
         if o.lm:
             lm = TokenLm(o.lm, o.lm_units or None, K=K)
         elif o.lm_units:
             raise kaldi_io.KaldiIOError("--lm-units without --lm")
+        lex = None
+        if o.lexicon:
+            lex = Lexicon(o.lexicon, o.lexicon_units or None, K=K, space=_space_class(o.space_unit, o.lexicon_units))
+            if o.words_table_out:
+                lex.WriteWords(o.words_table_out)
+            if o.word_lm:          # the word LM reads its words through the lexicon's table
+                table = o.words_table_out
+                if not table:          # a file of our own, created exclusively, gone as soon as the LM has read it
+                    import tempfile
+                    fd, table = tempfile.mkstemp(prefix="ctc-decode-words.")
+                    os.close(fd)
+                try:
+                    if not o.words_table_out:
+                        lex.WriteWords(table)
+                    lm = TokenLm(o.word_lm, table, K=lex.Info()["words"] + 1, skip_oov=o.lm_skip_oov)
+                finally:
+                    if not o.words_table_out:
+                        os.remove(table)
+                if o.lm_skip_oov:
+                    log(f"{lm.OovDropped()} n-grams of {o.word_lm} hold a word outside the lexicon and were dropped")
+        elif o.lexicon_units or o.word_lm or o.words_wspecifier or o.words_table_out or o.word_ref_rspecifier or o.word_bonus != 0.0 or o.lm_skip_oov:
+            raise kaldi_io.KaldiIOError("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and "
+                                        "--word-ref-rspecifier need --lexicon")
         if log_pri is not None and log_pri.size != K:
             raise kaldi_io.KaldiIOError(f"Dimensionality mismatch, class_frame_counts {log_pri.size} class_output_llk {K}")
         refs = kaldi_io.read_vec_int_table(o.ref_rspecifier) if o.ref_rspecifier else {}
+        word_refs = kaldi_io.read_vec_int_table(o.word_ref_rspecifier) if o.word_ref_rspecifier else {}
+        words_writer = None     # the word ids of every hypothesis, written as the hypotheses are
+        if o.words_wspecifier:
+            wkind, words_path, words_text = kaldi_io._parse_specifier(o.words_wspecifier)
+            if wkind != "ark":
+                raise kaldi_io.KaldiIOError("only ark: output is supported")
+            words_writer = kaldi_io.VecIntArkWriter(words_path, text=words_text)
         pipe = frontend.parse_feature_pipeline(feature_rspecifier) if not os.environ.get("EESEN_HOST_FEATURE_PIPES") else None
         feeder = None
         if pipe is not None:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
             feeder.set_pipeline(pipe.stages)
-        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0)
+        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0)
         scores = open(o.scores_out, "w") if o.scores_out else None
         lib = _lib.load()
 
@@ -113,14 +173,16 @@ def main(argv=None) -> int:
                 _lib.check(lib.eesen_op_log_sub_prior(o.device, None, C.c_void_p(out.ptr), out.rows, out.cols, out.stride, 1,
                                                       log_pri.ctypes.data_as(C.c_void_p), o.prior_scale))
             hyps, score = ctc.DecodeParallel(lens, out, beam=o.beam, max_classes=o.max_classes, nbest=o.nbest, is_log=log_pri is not None,
-                                             lm=lm, lm_weight=o.lm_weight, insertion_bonus=o.insertion_bonus, lm_eos=o.lm_eos)
-            lm_score = ctc.lm_score
+                                             lm=lm, lm_weight=o.lm_weight, insertion_bonus=o.insertion_bonus, lm_eos=o.lm_eos, lexicon=lex,
+                                             word_bonus=o.word_bonus)
+            lm_score, words, words_len = ctc.lm_score, ctc.words, ctc.words_len
             for s, (key, m) in enumerate(group):
                 frames = int(lens[s])
                 if math.isnan(score[s, 0]):
                     raise RuntimeError(f"the forward pass of {key} timed out on the device: no hypotheses")
                 if not hyps[s]:
-                    warn(f"{key}, every prefix has probability zero on {frames} frames, producing no output for this utterance")
+                    why = "no surviving prefix ends a lexicon word" if lex is not None else "every prefix has probability zero"
+                    warn(f"{key}, {why} on {frames} frames, producing no output for this utterance")
                     n["dead"] += 1
                     continue
                 for i, h in enumerate(hyps[s]):
@@ -128,14 +190,20 @@ def main(argv=None) -> int:
                     if scores:
                         scores.write(f"{k} {float(score[s, i]):.9g}" + (f" {float(lm_score[s, i]):.9g}" if lm is not None else "") + "\n")
                     yield k, np.asarray(h, np.int32)
+                    if words_writer is not None:          # (after the hypothesis is out, as the native tool orders its writes)
+                        words_writer.write(k, words[s, i, :words_len[s, i]])
                 if key in refs:
                     ref, best, err = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][0], np.int32), C.c_int(0)
                     _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
                     n["tok_err"] += err.value; n["tok_ref"] += int(ref.size); n["scored"] += 1
+                if key in word_refs:
+                    ref, best, err = np.ascontiguousarray(word_refs[key], np.int32), np.ascontiguousarray(words[s, 0, :words_len[s, 0]], np.int32), C.c_int(0)
+                    _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
+                    n["word_err"] += err.value; n["word_ref"] += int(ref.size); n["word_scored"] += 1
                 n["done"] += 1; n["frames"] += frames; n["score"] += float(score[s, 0])
                 n["empty"] += len(hyps[s][0]) == 0
                 if lm is not None:
-                    n["lm"] += float(lm_score[s, 0]); n["labels"] += len(hyps[s][0])
+                    n["lm"] += float(lm_score[s, 0]); n["labels"] += int(words_len[s, 0]) if lex is not None else len(hyps[s][0])
 
         def produce():
             group, max_len = [], 0
@@ -148,16 +216,23 @@ def main(argv=None) -> int:
             if group:
                 yield from flush(group)
 
-        kaldi_io.write_vec_int_ark(out_path, produce(), text=out_text)
+        try:
+            kaldi_io.write_vec_int_ark(out_path, produce(), text=out_text)
+        finally:
+            if words_writer is not None:
+                words_writer.close()
         if scores:
             scores.close()
         if o.ref_rspecifier:
             log(f"{n['tok_err']} token errors on {n['tok_ref']} reference tokens of {n['scored']} utterances")
             log(f"\nTOKEN_ACCURACY >> {100.0 * (1.0 - n['tok_err'] / max(n['tok_ref'], 1)):g}% <<")
+        if o.word_ref_rspecifier:
+            log(f"{n['word_err']} word errors on {n['word_ref']} reference words of {n['word_scored']} utterances")
+            log(f"\nWORD_ACCURACY >> {100.0 * (1.0 - n['word_err'] / max(n['word_ref'], 1)):g}% <<")
         if n["dead"]:
             log(f"{n['dead']} utterances without a hypothesis")
         avg = n["score"] / n["frames"] if n["frames"] else 0.0
-        tail = f"; average LM log-probability per label {(n['lm'] / n['labels'] if n['labels'] else 0.0):g}" if lm is not None else ""
+        tail = f"; average LM log-probability per {'word' if lex is not None else 'label'} {(n['lm'] / n['labels'] if n['labels'] else 0.0):g}" if lm is not None else ""
         log(f"Done {n['done']} utterances, {n['empty']} empty hypotheses; average log-probability per frame {avg:g}{tail}")
         return 0 if n["done"] else 255
     except Exception as e:

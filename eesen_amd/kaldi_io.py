@@ -345,17 +345,39 @@ def write_mat_ark(path: str, items, text: bool = False, scp_path: str = None):
         scp.close()
 
 
+class VecIntArkWriter:
+    """Int32VectorWriter to `ark:path` / `ark,t:path`, one entry per write(), flushed as it is written."""
+
+    def __init__(self, path: str, text: bool = False):
+        self.text = text
+        self.ctx = _open_out(path)
+        self.f = self.ctx.__enter__()
+
+    def write(self, key: str, v) -> None:
+        v = np.ascontiguousarray(v, np.int32)
+        f = self.f
+        f.write(key.encode() + b" ")
+        if self.text:
+            f.write(("".join(f"{int(x)} " for x in v) + "\n").encode())
+        else:
+            f.write(b"\x00B\x04" + struct.pack("<i", v.size))
+            out = np.empty((v.size, 5), np.uint8)
+            out[:, 0] = 4
+            out[:, 1:] = v.astype("<i4").view(np.uint8).reshape(v.size, 4)
+            f.write(out.tobytes())
+        f.flush()
+
+    def close(self) -> None:
+        if self.ctx is not None:
+            self.ctx.__exit__(None, None, None)
+            self.ctx = None
+
+
 def write_vec_int_ark(path: str, items, text: bool = False):
     """Int32VectorWriter to `ark:path` / `ark,t:path`."""
-    with _open_out(path) as f:
+    w = VecIntArkWriter(path, text)
+    try:
         for key, v in items:
-            v = np.ascontiguousarray(v, np.int32)
-            f.write(key.encode() + b" ")
-            if text:
-                f.write(("".join(f"{int(x)} " for x in v) + "\n").encode())
-            else:
-                f.write(b"\x00B\x04" + struct.pack("<i", v.size))
-                out = np.empty((v.size, 5), np.uint8)
-                out[:, 0] = 4
-                out[:, 1:] = v.astype("<i4").view(np.uint8).reshape(v.size, 4)
-                f.write(out.tobytes())
+            w.write(key, v)
+    finally:
+        w.close()

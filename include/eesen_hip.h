@@ -43,6 +43,7 @@ typedef struct eesen_net eesen_net_t; /* replaces eesen::Net, src/net/net.h:37-1
 typedef struct eesen_ctc eesen_ctc_t; /* replaces eesen::Ctc, src/net/ctc-loss.h:31-90       */
 typedef struct eesen_ce eesen_ce_t;   /* replaces eesen::CE, src/net/ce-loss.h:32-77          */
 typedef struct eesen_lm eesen_lm_t;   /* a token n-gram LM for eesen_ctc_decode_parallel_lm (no counterpart) */
+typedef struct eesen_lex eesen_lex_t; /* a lexicon trie for eesen_ctc_decode_parallel_lex (no counterpart)   */
 
 /* ---- library / device ------------------------------------------------------------------------ */
 const char* eesen_last_error(void);
@@ -417,6 +418,53 @@ int eesen_ctc_decode_parallel_lm(eesen_ctc_t* ctc, const int* frame_num_utt, int
                                  int is_log, int beam, int max_classes, int nbest, eesen_lm_t* lm, float lm_weight,
                                  float insertion_bonus, int use_eos, int* hyp_host /*S*nbest*T*/, int* hyp_len_host /*S*nbest*/,
                                  float* score_host /*S*nbest*/, float* lm_score_host /*S*nbest or NULL*/);
+
+/* eesen_lm_create_from_arpa with skip_oov != 0: an n-gram that holds a word which is neither in the table nor <s>, </s>, <unk>
+ * is dropped instead of being an error (the recipes' remove_oovs.pl before G is built).  Each section's count is checked against
+ * the header with the dropped lines included.  skip_oov == 0 is eesen_lm_create_from_arpa.  eesen_lm_oov_dropped: how many
+ * n-grams were dropped. */
+int eesen_lm_create_from_arpa_ex(const char* arpa_path, const char* units_path /*or NULL*/, int K, int skip_oov, eesen_lm_t** lm);
+int eesen_lm_oov_dropped(eesen_lm_t* lm, long long* ngrams);
+
+/* ---- lexicon-constrained decoding (INTEGRATION.md "Lexicon"; no counterpart: the reference walks a TLG graph) ----
+ * For systems whose words are sequences of units separated by one space unit (the recipes' character systems).  The lexicon file
+ * holds one `word unit unit ...` line per spelling; units resolve through units_path (`symbol id`) or, with NULL, are decimal class
+ * ids (the recipes' lexicon_numbers.txt).  A spelling is a non-empty sequence of classes in [1, K) other than space_class.  Word ids
+ * are 1 .. V in order of first appearance; a word may have several spellings and may be a prefix of another; an identical line given
+ * twice is accepted.  EESEN_ERR_INVALID with the file and the line: an unknown unit, a unit equal to space_class or outside [1, K),
+ * an empty spelling, the same spelling for two words (both are named), a file without a word.
+ * The trie: node 0 is the root, a node's children are sorted by class id, eesen_lex_word gives the word that ends at a node or 0,
+ * eesen_lex_child the child for a class or -1.  eesen_lex_write_words writes `word id` lines: the table eesen_lm_create_from_arpa
+ * takes as units_path, with K = V + 1, for a word LM.  eesen_lex_words segments a labelling of
+ *   L = { empty } + { w1 Sp w2 Sp ... wn }     (exactly one space between words, none leading or trailing)
+ * into words_out (room for (n + 1) / 2) and is EESEN_ERR_INVALID for a labelling outside L.  No device work here. */
+int eesen_lex_create(const char* lexicon_path, const char* units_path /*or NULL*/, int K, int space_class, eesen_lex_t** lex);
+int eesen_lex_destroy(eesen_lex_t* lex);
+int eesen_lex_info(eesen_lex_t* lex, int* words, int* nodes, int* max_word_len);   /* any pointer may be NULL */
+int eesen_lex_write_words(eesen_lex_t* lex, const char* path);
+int eesen_lex_child(eesen_lex_t* lex, int node, int c, int* child);
+int eesen_lex_word(eesen_lex_t* lex, int node, int* word);
+int eesen_lex_words(eesen_lex_t* lex, const int* labels, int n, int* words_out, int* num_words);
+/* eesen_ctc_decode_parallel restricted to L, with an optional LM over the word ids (lm: built with K = V + 1, or NULL).  An entry
+ * also carries its lexicon node v, an LM state and lmsum (the empty prefix: 0, the start state, 0).  The extension p + c:
+ *   c != Sp: allowed iff v has a child v' for c; the entry moves to v', LM state and lmsum stay, g = 0;
+ *   c == Sp: allowed iff w = word[v] != 0; (wt, next) = lm_step(state, w) (0 and no state without an LM), g = lm_weight * wt +
+ *            word_bonus, the entry moves to node 0, state next, lmsum + wt;
+ * lnb' = (s_t(c) + g) + (c == e ? lb : tot) as in eesen_ctc_decode_parallel_lm; a disallowed extension is no candidate.  After
+ * frame n-1 an entry is complete if it is empty or word[v] != 0; a non-empty complete one closes its last word (total += lm_weight
+ * * wt + word_bonus, then with use_eos lm_weight * final[next]; lmsum takes the same terms unweighted), the empty one takes only
+ * lm_weight * final[start] with use_eos; incomplete entries are dropped and the rest re-ranked, ties by previous rank.  An
+ * utterance without a complete entry returns count 0 (all lengths -1, scores -1e30).  The score of a result is
+ *   ln(sum over its paths of P_ac) + lm_weight * ln P_lm(words [, </s>]) + word_bonus * |words|.
+ * Outputs as eesen_ctc_decode_parallel_lm; word_host [S][nbest][T] / word_len_host [S][nbest] (either may be NULL): the word ids of
+ * each returned labelling, -1 beyond their number (and for absent entries).  EESEN_ERR_INVALID besides that call's limits:
+ * lex == NULL, a lexicon built for another K, an LM whose K is not V + 1, use_eos without an LM or on one without </s>, a
+ * non-finite lm_weight or word_bonus. */
+int eesen_ctc_decode_parallel_lex(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                                  int is_log, int beam, int max_classes, int nbest, eesen_lex_t* lex, eesen_lm_t* lm /*or NULL*/,
+                                  float lm_weight, float word_bonus, int use_eos, int* hyp_host /*S*nbest*T*/,
+                                  int* hyp_len_host /*S*nbest*/, float* score_host /*S*nbest*/, float* lm_score_host /*S*nbest or NULL*/,
+                                  int* word_host /*S*nbest*T or NULL*/, int* word_len_host /*S*nbest or NULL*/);
 
 /* LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: the count eesen_ctc_error_rate_mseq accumulates, for a
  * host that scores hypotheses of its own (ctc-decode --ref-rspecifier).  No device work. */

@@ -260,6 +260,38 @@ class TokenLm {
   eesen_lm_t* h_;
 };
 
+/* A lexicon for Ctc::DecodeParallel (eesen_lex_*; no counterpart in the reference, whose lexicon lives in the L of its TLG graphs):
+ * `word unit unit ...` lines -- the units are the symbols of units.txt, or decimal class ids when `units` is empty -- compiled on the
+ * host into a trie.  num_classes: the net's output dimension, blank included; space_class: the unit that separates words. */
+class Lexicon {
+ public:
+  Lexicon(const std::string& path, const std::string& units, int32 num_classes, int32 space_class) : h_(NULL) {
+    HipCheck(eesen_lex_create(path.c_str(), units.empty() ? NULL : units.c_str(), num_classes, space_class, &h_));
+  }
+  ~Lexicon() { if (h_) eesen_lex_destroy(h_); }
+  int32 NumWords() const { int v = 0; HipCheck(eesen_lex_info(h_, &v, NULL, NULL)); return v; }
+  int32 NumNodes() const { int v = 0; HipCheck(eesen_lex_info(h_, NULL, &v, NULL)); return v; }
+  int32 MaxWordLength() const { int v = 0; HipCheck(eesen_lex_info(h_, NULL, NULL, &v)); return v; }
+  /* `word id` lines: the table a word LM is built over, TokenLm(arpa, path, NumWords() + 1) */
+  void WriteWords(const std::string& path) const { HipCheck(eesen_lex_write_words(h_, path.c_str())); }
+  int32 Child(int32 node, int32 c) const { int v = 0; HipCheck(eesen_lex_child(h_, node, c, &v)); return v; }   /* -1: none */
+  int32 Word(int32 node) const { int v = 0; HipCheck(eesen_lex_word(h_, node, &v)); return v; }                /* 0: none ends here */
+  /* the word ids of a labelling `w1 space w2 ... wn`; false for a labelling that is none */
+  bool Words(const std::vector<int32>& labels, std::vector<int32>* words) const {
+    int n = 0;
+    words->resize(labels.size() / 2 + 1);
+    if (eesen_lex_words(h_, labels.empty() ? NULL : labels.data(), (int)labels.size(), words->data(), &n) != EESEN_OK) { words->clear(); return false; }
+    words->resize(n);
+    return true;
+  }
+  eesen_lex_t* Handle() const { return h_; }
+
+ private:
+  Lexicon(const Lexicon&);
+  Lexicon& operator=(const Lexicon&);
+  eesen_lex_t* h_;
+};
+
 /* eesen::Ctc (src/net/ctc-loss.h:29-90), the multi-sequence entry points */
 class Ctc {
  public:
@@ -356,6 +388,37 @@ class Ctc {
         (*hyps)[s].push_back(std::vector<int32>(h, h + len[(size_t)s * nbest + i]));
         (*scores)[s].push_back(sc[(size_t)s * nbest + i]);
         if (lm_scores) (*lm_scores)[s].push_back(lsc[(size_t)s * nbest + i]);
+      }
+  }
+  /* The search held to a lexicon, eesen_ctc_decode_parallel_lex: the labellings are lexicon words separated by single spaces.  lm
+   * (may be NULL): an LM over the lexicon's word ids (built over Lexicon::WriteWords' table with NumWords() + 1 classes), stepped once
+   * per word; every word adds lm_weight * ln P_lm(word | words before) + word_bonus.  words[s][i]: the word ids of hyps[s][i];
+   * lm_scores (may be NULL): the unweighted ln P_lm of those words.  An utterance none of whose surviving prefixes ends a word
+   * returns nothing. */
+  void DecodeParallel(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out, const Lexicon& lexicon, const TokenLm* lm,
+                      float lm_weight, float word_bonus, bool use_eos, std::vector<std::vector<std::vector<int32> > >* hyps,
+                      std::vector<std::vector<std::vector<int32> > >* words, std::vector<std::vector<BaseFloat> >* scores,
+                      std::vector<std::vector<BaseFloat> >* lm_scores = NULL, int32 beam = 16, int32 max_classes = 20, int32 nbest = 1,
+                      bool is_log = false) {
+    const int S = (int)frame_num_utt.size();
+    const int T = S > 0 ? net_out.NumRows() / S : 0;
+    if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
+    std::vector<int32> hyp((size_t)S * nbest * T + 1), len((size_t)S * nbest + 1), wrd((size_t)S * nbest * T + 1), wlen((size_t)S * nbest + 1);
+    std::vector<BaseFloat> sc((size_t)S * nbest + 1), lsc((size_t)S * nbest + 1);
+    HipCheck(eesen_ctc_decode_parallel_lex(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                           is_log ? 1 : 0, beam, max_classes, nbest, lexicon.Handle(), lm ? lm->Handle() : NULL, lm_weight,
+                                           word_bonus, use_eos ? 1 : 0, hyp.data(), len.data(), sc.data(), lsc.data(), wrd.data(), wlen.data()));
+    hyps->assign(S, std::vector<std::vector<int32> >());
+    words->assign(S, std::vector<std::vector<int32> >());
+    scores->assign(S, std::vector<BaseFloat>());
+    if (lm_scores) lm_scores->assign(S, std::vector<BaseFloat>());
+    for (int s = 0; s < S; ++s)
+      for (int i = 0; i < nbest && len[(size_t)s * nbest + i] >= 0; ++i) {
+        const size_t e = (size_t)s * nbest + i;
+        (*hyps)[s].push_back(std::vector<int32>(hyp.data() + e * T, hyp.data() + e * T + len[e]));
+        (*words)[s].push_back(std::vector<int32>(wrd.data() + e * T, wrd.data() + e * T + wlen[e]));
+        (*scores)[s].push_back(sc[e]);
+        if (lm_scores) (*lm_scores)[s].push_back(lsc[e]);
       }
   }
   void SetReportStep(int32 s) { report_step_ = s; }
