@@ -112,6 +112,10 @@ SIGNATURES = {
     "eesen_lex_word": (_i, [_vp, _i, _pi]),
     "eesen_lex_words": (_i, [_vp, _vp, _i, _vp, _pi]),
     "eesen_ctc_decode_parallel_lex": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eesen_lex_create_unspaced": (_i, [C.c_char_p, C.c_char_p, _i, C.POINTER(_vp)]),
+    "eesen_lex_max_homophones": (_i, [_vp, _pi]),
+    "eesen_lex_node_words": (_i, [_vp, _i, _vp, _i, _pi]),
+    "eesen_ctc_decode_parallel_words": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eesen_ctc_decode_parallel_lm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "eesen_ce_destroy": (_i, [_vp]),

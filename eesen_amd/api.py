@@ -530,13 +530,19 @@ class TokenLm:
 class Lexicon:
     """A lexicon for Ctc.DecodeParallel(lexicon=...): `word unit unit ...` lines compiled into a trie (eesen_lex_create; INTEGRATION.md
     "Lexicon").  units: the recipes' units.txt; without it the units are decimal class ids (lexicon_numbers.txt).  K: the net's class
-    count, blank included; space: the class that separates words.  Host only: needs no device."""
+    count, blank included; space: the class that separates words.  space=None: the unspaced kind (eesen_lex_create_unspaced;
+    INTEGRATION.md "Words without a boundary unit"): no boundary unit, several words per spelling; Ctc.DecodeParallel then takes
+    eesen_ctc_decode_parallel_words.  Host only: needs no device."""
 
-    def __init__(self, path: str, units: Optional[str] = None, K: int = 0, space: int = 0):
+    def __init__(self, path: str, units: Optional[str] = None, K: int = 0, space: Optional[int] = 0):
         self.lib = _lib.load()
         self.h = C.c_void_p()
-        self.K, self.space = int(K), int(space)
-        check(self.lib.eesen_lex_create(str(path).encode(), str(units).encode() if units else None, int(K), int(space), C.byref(self.h)))
+        self.K, self.space, self.unspaced = int(K), space if space is None else int(space), space is None
+        enc = str(units).encode() if units else None
+        if self.unspaced:
+            check(self.lib.eesen_lex_create_unspaced(str(path).encode(), enc, int(K), C.byref(self.h)))
+        else:
+            check(self.lib.eesen_lex_create(str(path).encode(), enc, int(K), int(space), C.byref(self.h)))
 
     def __del__(self):
         if getattr(self, "h", None) and self.h:
@@ -567,8 +573,21 @@ class Lexicon:
         check(self.lib.eesen_lex_word(self.h, int(node), C.byref(w)))
         return w.value
 
+    def MaxHomophones(self) -> int:
+        """H: the largest number of words on one spelling (0 for a lexicon with a space class)."""
+        h = C.c_int()
+        check(self.lib.eesen_lex_max_homophones(self.h, C.byref(h)))
+        return h.value
+
+    def NodeWords(self, node: int) -> List[int]:
+        """The ascending ids of the words whose spelling ends at the node."""
+        out = np.empty(16, np.int32)
+        n = C.c_int()
+        check(self.lib.eesen_lex_node_words(self.h, int(node), _np_ptr(out), int(out.size), C.byref(n)))
+        return out[:n.value].tolist()
+
     def Words(self, labels: Sequence[int]) -> List[int]:
-        """The word ids of a labelling `w1 space w2 ... wn`; EesenError for a labelling that is none."""
+        """The word ids of a labelling `w1 space w2 ... wn`; EesenError for a labelling that is none, and for an unspaced lexicon."""
         lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
         out = np.empty(lab.size // 2 + 1, np.int32)
         n = C.c_int()
@@ -651,15 +670,28 @@ class Ctc:
         spaces.  lm is then an LM over the lexicon's word ids (TokenLm over Lexicon.WriteWords' table, K = words + 1) or None, stepped
         once per word; word_bonus is added per word and insertion_bonus is not used.  self.words [S, nbest, T] / self.words_len
         [S, nbest] are the word ids of every returned labelling (-1 beyond; None without a lexicon).  lexicon=None takes the calls
-        above unchanged."""
+        above unchanged.  An unspaced lexicon (Lexicon(space=None)) takes eesen_ctc_decode_parallel_words: a returned entry is a
+        labelling and a segmentation of it into words, homophones and other segmentations of the same labels are entries of their
+        own, and self.word_ends [S, nbest, T] is the number of labels up to and including each word's last (-1 beyond the word
+        count; None in every other mode)."""
         fn = np.ascontiguousarray(frame_num_utt, np.int32)
         S = fn.size
         T = net_out.rows // max(S, 1)
         hyp = np.empty((S, int(nbest), max(T, 0)), np.int32)
         hlen = np.empty((S, int(nbest)), np.int32)
         score = np.empty((S, int(nbest)), np.float32)
-        words = words_len = None
-        if lexicon is not None:
+        words = words_len = word_ends = None
+        if lexicon is not None and lexicon.unspaced:
+            lm_score = np.empty((S, int(nbest)), np.float32)
+            words = np.empty((S, int(nbest), max(T, 0)), np.int32)
+            word_ends = np.empty((S, int(nbest), max(T, 0)), np.int32)
+            words_len = np.empty((S, int(nbest)), np.int32)
+            check(self.lib.eesen_ctc_decode_parallel_words(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols,
+                                                           net_out.stride, int(bool(is_log)), int(beam), int(max_classes), int(nbest), lexicon.h,
+                                                           lm.h if lm is not None else None, float(lm_weight), float(word_bonus),
+                                                           int(bool(lm_eos)), _np_ptr(hyp), _np_ptr(hlen), _np_ptr(score), _np_ptr(lm_score),
+                                                           _np_ptr(words), _np_ptr(words_len), _np_ptr(word_ends)))
+        elif lexicon is not None:
             lm_score = np.empty((S, int(nbest)), np.float32)
             words = np.empty((S, int(nbest), max(T, 0)), np.int32)
             words_len = np.empty((S, int(nbest)), np.int32)
@@ -681,7 +713,7 @@ class Ctc:
                                                         _np_ptr(hlen), _np_ptr(score), _np_ptr(lm_score)))
         self.hyp, self.hyp_len = hyp, hlen          # the raw [S, nbest, T] labels (-1 beyond each length) and [S, nbest] lengths
         self.lm_score = lm_score
-        self.words, self.words_len = words, words_len
+        self.words, self.words_len, self.word_ends = words, words_len, word_ends
         hyps = [[hyp[s, i, :hlen[s, i]].tolist() for i in range(int(nbest)) if hlen[s, i] >= 0] for s in range(S)]
         return hyps, score
 

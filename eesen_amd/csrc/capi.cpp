@@ -369,6 +369,37 @@ int eesen_ctc_decode_parallel_lex(eesen_ctc_t* ctc, const int* frame_num_utt, in
                              use_eos != 0, hyp_host, hyp_len_host, score_host, lm_score_host, word_host, word_len_host);
   });
 }
+int eesen_lex_create_unspaced(const char* lexicon_path, const char* units_path, int K, eesen_lex_t** lex) {
+  return guard([&] {
+    REQ_PTR(lexicon_path); REQ_PTR(lex);
+    std::unique_ptr<eesen_lex> made(new eesen_lex);
+    made->from_file_unspaced(lexicon_path, units_path, K);
+    *lex = made.release();
+  });
+}
+int eesen_lex_max_homophones(eesen_lex_t* lex, int* H) {
+  return guard([&] { REQ_PTR(lex); REQ_PTR(H); *H = lex->max_homophones; });
+}
+int eesen_lex_node_words(eesen_lex_t* lex, int node, int* out, int cap, int* count) {
+  return guard([&] {
+    REQ_PTR(lex); REQ_PTR(count);
+    EESEN_REQUIRE(node >= 0 && node < lex->nodes(), EESEN_ERR_INVALID, "lexicon node out of range");
+    EESEN_REQUIRE(cap >= 0 && (cap == 0 || out != nullptr), EESEN_ERR_INVALID, "out: null pointer or negative capacity");
+    const int n = lex->unspaced ? lex->wcount[node] : (lex->word[node] != 0 ? 1 : 0);
+    for (int i = 0; i < std::min(n, cap); ++i) out[i] = lex->unspaced ? lex->node_words[lex->wfirst[node] + i] : lex->word[node];
+    *count = n;
+  });
+}
+int eesen_ctc_decode_parallel_words(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                                    int is_log, int beam, int max_classes, int nbest, eesen_lex_t* lex, eesen_lm_t* lm, float lm_weight,
+                                    float word_bonus, int use_eos, int* hyp_host, int* hyp_len_host, float* score_host, float* lm_score_host,
+                                    int* word_host, int* word_len_host, int* word_end_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev); REQ_PTR(hyp_host); REQ_PTR(hyp_len_host); REQ_PTR(score_host);
+    ctc->decode_parallel_words(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, beam, max_classes, nbest, lex, lm, lm_weight, word_bonus,
+                               use_eos != 0, hyp_host, hyp_len_host, score_host, lm_score_host, word_host, word_len_host, word_end_host);
+  });
+}
 int eesen_ctc_decode_parallel_lm(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
                                  int is_log, int beam, int max_classes, int nbest, eesen_lm_t* lm, float lm_weight, float insertion_bonus,
                                  int use_eos, int* hyp_host, int* hyp_len_host, float* score_host, float* lm_score_host) {

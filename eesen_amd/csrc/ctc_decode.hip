@@ -11,6 +11,9 @@
 //                           word LM once per word: one text (prefix_beam<mode>), and a mode's arguments, LDS and barrier exist in
 //                           that instantiation only
 //   ctc_hyp_kernel          one lane per (utterance, rank) walks the trie to the root
+// Along a lexicon without a boundary unit (INTEGRATION.md "Words without a boundary unit", tests/ctc_words_restatement.py) the second
+// and third launch are ctc_word_beam_kernel and ctc_word_hyp_kernel, at the end of this file: hypotheses are labels and the words closed
+// between them, and labels, words and word ends all come out of the trie on the device.
 // Every log-mass is an fp32 value in [-1e30, +inf): sums are clamped from below at the library's finite sentinel, so the sweep's
 // branch-free log-add (ctc.hip: LogAPlusB_fast) is exact on the special cases here too.
 #include "kernels.h"
@@ -529,6 +532,317 @@ __global__ __launch_bounds__(64) void ctc_hyp_kernel(const int* __restrict__ tpa
   if (lm_out) lm_out[i] = have ? flm[(size_t)s * B + r] : kLogZero;
 }
 
+// ---- the word beam: lexicons without a boundary unit ----------------------------------------------------------------------------
+// INTEGRATION.md "Words without a boundary unit", restated in tests/ctc_words_restatement.py.  A sibling of prefix_beam, not a fourth
+// mode of it: an entry has 1 + |words(v)| successors per candidate class, so the successor index, the merge and the end of the
+// utterance are all different, and the three instantiations above stay as they are.
+struct WordBeamState {
+  float lb[kMaxBeam], lnb[kMaxBeam], lmsum[kMaxBeam];
+  int node[kMaxBeam], last[kMaxBeam];          // trie node, last label (-1: the empty hypothesis)
+  int len[kMaxBeam], nlab[kMaxBeam], nwords[kMaxBeam];   // augmented length (labels + marks), labels, marks
+  int closed[kMaxBeam];                        // the word the last step closed in front of its label, or 0
+  int lexnode[kMaxBeam], lmstate[kMaxBeam];
+  unsigned long long hash[kMaxBeam];           // fingerprint of the augmented sequence: h * M + c + 1 for a label, h * M + K + w for a mark
+};
+constexpr int kHomStride = 16;   // (entry, word-of-its-node) pairs live at p * 16 + i: Lexicon::kMaxHomophones = 15 < 16
+static_assert(Lexicon::kMaxHomophones < kHomStride, "a word index is four bits");
+
+// keys[0, npad), npad a power of two >= 2: ascending, by every thread of the workgroup; the caller's barrier stands before and after
+__device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int npad, int tid, int NT) {
+  bool first = true;
+  for (int k = 2; k <= npad; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      if (!first) sort_sync(j <= 32);   // the stage before had stride 2 j (<= 64) or 1
+      first = false;
+      for (int q = tid; q < (npad >> 1); q += NT) {
+        const int i = 2 * q - (q & (j - 1)), l = i | j;
+        const unsigned long long x = keys[i], y = keys[l];
+        if ((x > y) == ((i & k) == 0)) { keys[i] = y; keys[l] = x; }
+      }
+    }
+}
+
+// Grid (S), 64 .. 512 threads.  Successor x = (p * C' + ci) * (1 + H) + slot of entry p, candidate ci: slot 0 stays inside the word
+// (the child of p's lexicon node), slot 1 + i closes the i-th word of the node and enters the root's child.  Frame t, between
+// workgroup barriers:
+//   0  the frame's candidates and the root's child for each (C' lookups); the inside child of every (entry, candidate) (nb * C'
+//      bisections); (wt, next) = lm_step of every (entry, word of its node) (at most nb * H walks) -- nothing is looked up after this
+//   2  every successor writes its key behind the stays' places; the key array is padded with dead keys to a power of two
+//   1  entry q < nb: its stay; the successor that spells q (its parent found by fingerprint: one or two steps back, by whether q's
+//      last step closed a word) is log-added into it and its key is struck out -- no bitmask: a successor merges into one entry
+//   3  bitonic sort
+//   4  rank r < B takes key r: a stay copies its entry, a successor becomes trie node 1 + t * B + r, whose label and closed word
+//      are written beside its parent
+// Tie index: stays by previous rank, then 64 + x: parent's rank, class id, slot.  After the last frame every complete entry yields
+// one final hypothesis per word of its node (key index p * 16 + i), which are sorted and the best B written out.
+// Static LDS: 32 KiB keys + 6.5 KiB state + 8 KiB inside children + 12 KiB (wt, next, word) + 1.5 KiB = 60 KiB.
+__global__ __launch_bounds__(512) void ctc_word_beam_kernel(const float* __restrict__ sc, int ld, int T, int S, const int* __restrict__ lens, int B,
+                                                            int Cc, const int* __restrict__ cid_g, const float* __restrict__ csc_g,
+                                                            const float* __restrict__ sblank_g, LmTables tab, int have_lm, float alpha, float beta,
+                                                            int use_eos, WordLexTables lex, int* __restrict__ tparent, int* __restrict__ tlabel,
+                                                            int* __restrict__ tword, int* __restrict__ fnode, int* __restrict__ flen,
+                                                            float* __restrict__ fscore, float* __restrict__ flm, int* __restrict__ fword,
+                                                            int* __restrict__ fnw, int* __restrict__ count) {
+  __shared__ unsigned long long keys[kMaxKeys];
+  __shared__ WordBeamState st[2];
+  __shared__ float stay_lb[kMaxBeam], stay_lnb[kMaxBeam];
+  __shared__ int c_id[kMaxCls], root_next[kMaxCls];
+  __shared__ float c_sc[kMaxCls], c_bl;
+  __shared__ int in_next[kMaxKeys / 2];                 // the inside child of (p, ci) at p * C' + ci, or -1
+  __shared__ float cl_w[kMaxBeam * kHomStride];         // lm_step of (p, i-th word of p's node) at p * 16 + i
+  __shared__ int cl_next[kMaxBeam * kHomStride], cl_word[kMaxBeam * kHomStride];
+  __shared__ int ent_nw[kMaxBeam];                      // |words(v)| of the entry's node
+  __shared__ int nb_sh;
+  const int s = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
+  const int n = min(lens[s], T);
+  const size_t cap = 1 + (size_t)T * B;
+  int* tp = tparent + (size_t)s * cap;
+  int* tl = tlabel + (size_t)s * cap;
+  int* tw = tword + (size_t)s * cap;
+  const int4* __restrict__ nrec = reinterpret_cast<const int4*>(lex.node_rec);   // {first child, child count, first word slot, word count}
+  const int H1 = 1 + lex.H;
+  if (tid == 0) {
+    WordBeamState& z = st[0];
+    z.lb[0] = 0.f; z.lnb[0] = kLogZero; z.lmsum[0] = 0.f;
+    z.node[0] = 0; z.last[0] = -1; z.len[0] = 0; z.nlab[0] = 0; z.nwords[0] = 0; z.closed[0] = 0; z.lexnode[0] = 0;
+    z.lmstate[0] = have_lm ? tab.start : 0; z.hash[0] = 0;
+    nb_sh = 1;
+    tp[0] = -1; tl[0] = -1; tw[0] = 0;
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < n; ++t) {
+    const int nb = nb_sh;
+    if (nb == 0) break;   // the beam died (uniform): possible only with is_log input
+    const WordBeamState& a = st[cur];
+    WordBeamState& nx = st[cur ^ 1];
+    const size_t row = (size_t)t * S + s;
+    const int* cid_row = cid_g + row * Cc;
+    // ---- 0
+    if (tid < Cc) {
+      const int c = cid_row[tid];
+      c_id[tid] = c;
+      c_sc[tid] = csc_g[row * Cc + tid];
+      const int4 r = nrec[0];
+      const int end = r.x + r.y;
+      const int lo = lower_bound(lex.child_cls, r.x, end, c);
+      root_next[tid] = (lo < end && lex.child_cls[lo] == c) ? lex.child_node[lo] : -1;
+    }
+    if (tid == 0) c_bl = sblank_g[row];
+    for (int x = tid; x < nb * Cc; x += NT) {
+      const int p = x / Cc, ci = x - p * Cc;
+      const int4 r = nrec[a.lexnode[p]];
+      const int c = cid_row[ci];
+      const int end = r.x + r.y;
+      const int lo = lower_bound(lex.child_cls, r.x, end, c);
+      in_next[x] = (lo < end && lex.child_cls[lo] == c) ? lex.child_node[lo] : -1;
+    }
+    for (int x = tid; x < nb * kHomStride; x += NT) {
+      const int p = x / kHomStride, i = x - p * kHomStride;
+      const int4 r = nrec[a.lexnode[p]];
+      if (i == 0) ent_nw[p] = r.w;
+      if (i < r.w) {
+        const int w = lex.node_words[r.z + i];
+        float wt = 0.f;
+        int next = a.lmstate[p];
+        if (have_lm) lm_step(tab, a.lmstate[p], w, wt, next);
+        cl_w[x] = wt; cl_next[x] = next; cl_word[x] = w;
+      }
+    }
+    __syncthreads();
+    const float bl = c_bl;
+    auto succ_value = [&](int p, int ci, int slot) -> float {
+      float g = 0.f;
+      if (slot == 0) {
+        if (in_next[p * Cc + ci] < 0) return kLogZero;
+      } else {
+        if (slot - 1 >= ent_nw[p] || root_next[ci] < 0) return kLogZero;
+        g = __fadd_rn(__fmul_rn(alpha, cl_w[p * kHomStride + slot - 1]), beta);
+      }
+      const float lb = a.lb[p], lnb = a.lnb[p];
+      const float cs = score_add(c_sc[ci], g);
+      return score_add(cs, c_id[ci] == a.last[p] ? lb : log_add(lb, lnb));
+    };
+    const int n_succ = nb * Cc * H1;   // nb + n_succ <= B * (1 + C' * (1 + H)) <= kMaxKeys: the host's limit
+    int npad = 2;
+    while (npad < nb + n_succ) npad <<= 1;
+    for (int x = tid; x < npad - nb; x += NT) {   // ---- 2
+      unsigned long long key = kDeadKey;
+      if (x < n_succ) {
+        const int pc = x / H1, slot = x - pc * H1, p = pc / Cc, ci = pc - p * Cc;
+        const float v = succ_value(p, ci, slot) + 0.f;
+        if (v > kDead) key = make_key(v, kMaxBeam + x);
+      }
+      keys[nb + x] = key;
+    }
+    __syncthreads();
+    if (tid < nb) {   // ---- 1
+      const int q = tid, e = a.last[q];
+      const float lb = a.lb[q], lnb = a.lnb[q];
+      const float slb = score_add(bl, log_add(lb, lnb));
+      float slnb = kLogZero;
+      if (e >= 0) {
+        slnb = score_add(clamp_score(sc[row * ld + e]), lnb);
+        const int w = a.closed[q];
+        unsigned long long ph = (a.hash[q] - (unsigned long long)(e + 1)) * kHashMulInv;
+        int plen = a.len[q] - 1;
+        if (w != 0) { ph = (ph - (unsigned long long)(lex.K + w)) * kHashMulInv; --plen; }
+        int p = -1;
+        for (int i = 0; i < nb; ++i)
+          if (a.hash[i] == ph && a.len[i] == plen) p = i;
+        if (p >= 0) {
+          const int lo = lower_bound(c_id, 0, Cc, e);
+          if (lo < Cc && c_id[lo] == e) {
+            int slot = w == 0 ? 0 : -1;
+            for (int i = 0; w != 0 && i < ent_nw[p]; ++i)
+              if (cl_word[p * kHomStride + i] == w) slot = 1 + i;
+            if (slot >= 0) {
+              slnb = log_add(slnb, succ_value(p, lo, slot));
+              keys[nb + (p * Cc + lo) * H1 + slot] = kDeadKey;
+            }
+          }
+        }
+      }
+      stay_lb[q] = slb;
+      stay_lnb[q] = slnb;
+      const float total = log_add(slb, slnb) + 0.f;   // (+ 0: a -0 orders as +0)
+      keys[q] = total > kDead ? make_key(total, q) : kDeadKey;
+    }
+    __syncthreads();
+    bitonic_sort(keys, npad, tid, NT);   // ---- 3
+    __syncthreads();
+    if (tid < 64) {   // ---- 4 (wave 0)
+      const unsigned long long key = (tid < B && tid < npad) ? keys[tid] : kDeadKey;
+      const bool live = key != kDeadKey;
+      if (live) {
+        const int idx = (int)(unsigned)key;
+        if (idx < kMaxBeam) {
+          nx.lb[tid] = stay_lb[idx]; nx.lnb[tid] = stay_lnb[idx]; nx.lmsum[tid] = a.lmsum[idx];
+          nx.node[tid] = a.node[idx]; nx.last[tid] = a.last[idx]; nx.len[tid] = a.len[idx]; nx.nlab[tid] = a.nlab[idx];
+          nx.nwords[tid] = a.nwords[idx]; nx.closed[tid] = a.closed[idx]; nx.lexnode[tid] = a.lexnode[idx];
+          nx.lmstate[tid] = a.lmstate[idx]; nx.hash[tid] = a.hash[idx];
+        } else {
+          const int x = idx - kMaxBeam, pc = x / H1, slot = x - pc * H1, p = pc / Cc, ci = pc - p * Cc, c = c_id[ci];
+          const int node = 1 + t * B + tid;   // < cap: t < n <= T, tid < B
+          const int at = p * kHomStride + slot - 1;
+          const int w = slot == 0 ? 0 : cl_word[at];
+          unsigned long long h = a.hash[p];
+          if (slot != 0) h = h * kHashMul + (unsigned long long)(lex.K + w);
+          nx.lb[tid] = kLogZero; nx.lnb[tid] = succ_value(p, ci, slot);
+          nx.lmsum[tid] = slot == 0 ? a.lmsum[p] : __fadd_rn(a.lmsum[p], cl_w[at]);
+          nx.node[tid] = node; nx.last[tid] = c;
+          nx.len[tid] = a.len[p] + (slot == 0 ? 1 : 2); nx.nlab[tid] = a.nlab[p] + 1; nx.nwords[tid] = a.nwords[p] + (slot == 0 ? 0 : 1);
+          nx.closed[tid] = w;
+          nx.lexnode[tid] = slot == 0 ? in_next[p * Cc + ci] : root_next[ci];
+          nx.lmstate[tid] = slot == 0 ? a.lmstate[p] : cl_next[at];
+          nx.hash[tid] = h * kHashMul + (unsigned long long)(c + 1);
+          tp[node] = a.node[p];
+          tl[node] = c;
+          tw[node] = w;
+        }
+      }
+      const int alive = __popcll(__ballot(live));   // the live keys are a prefix of the sorted array
+      if (tid == 0) nb_sh = alive;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  // the end of the utterance: a complete entry yields one final hypothesis per word of its node (the empty one: itself), each closes
+  // its word and takes fin with use_eos; they are ranked by the new total, ties by (previous rank, word index)
+  const int nb = nb_sh;
+  const WordBeamState& a = st[cur];
+  float* fin_tot = reinterpret_cast<float*>(in_next);   // [64 * 16]: the frames' use of in_next is over
+  int npad = kHomStride;
+  while (npad < nb * kHomStride) npad <<= 1;   // <= 1024
+  for (int x = tid; x < npad; x += NT) {
+    const int p = x / kHomStride, i = x - p * kHomStride;
+    unsigned long long key = kDeadKey;
+    if (p < nb) {
+      const int4 r = nrec[a.lexnode[p]];
+      const bool empty = a.len[p] == 0;
+      if (empty ? i == 0 : i < r.w) {
+        float total = log_add(a.lb[p], a.lnb[p]) + 0.f, lsum = a.lmsum[p];
+        int state = a.lmstate[p], w = 0;
+        if (!empty) {
+          w = lex.node_words[r.z + i];
+          float wt = 0.f;
+          int next = state;
+          if (have_lm) lm_step(tab, state, w, wt, next);
+          state = next;
+          total = clamp_score(__fadd_rn(total, __fadd_rn(__fmul_rn(alpha, wt), beta))) + 0.f;
+          lsum = __fadd_rn(lsum, wt);
+        }
+        if (use_eos) {
+          const float f = tab.fin[state];
+          total = clamp_score(__fadd_rn(total, __fmul_rn(alpha, f))) + 0.f;
+          lsum = __fadd_rn(lsum, f);
+        }
+        key = make_key(total, x);
+        fin_tot[x] = total; cl_w[x] = lsum; cl_word[x] = w;
+      }
+    }
+    keys[x] = key;
+  }
+  __syncthreads();
+  bitonic_sort(keys, npad, tid, NT);
+  __syncthreads();
+  if (tid < 64) {   // wave 0; B <= 64
+    const unsigned long long key = (tid < B && tid < npad) ? keys[tid] : kDeadKey;
+    const bool live = key != kDeadKey;
+    if (tid < B) {
+      const size_t o = (size_t)s * B + tid;
+      const int x = (int)(unsigned)key, p = x / kHomStride;
+      fnode[o] = live ? a.node[p] : -1;
+      flen[o] = live ? a.nlab[p] : -1;
+      fscore[o] = live ? fin_tot[x] : kLogZero;
+      flm[o] = live ? cl_w[x] : kLogZero;
+      fword[o] = live ? cl_word[x] : -1;
+      fnw[o] = live ? a.nwords[p] + (cl_word[x] != 0 ? 1 : 0) : -1;
+    }
+    const int done = __popcll(__ballot(live));
+    if (tid == 0) count[s] = done;
+  }
+}
+
+// one lane per (utterance, rank): labels, words and word ends out of the trie, back to front
+__global__ __launch_bounds__(64) void ctc_word_hyp_kernel(const int* __restrict__ tparent, const int* __restrict__ tlabel,
+                                                          const int* __restrict__ tword, const int* __restrict__ fnode,
+                                                          const int* __restrict__ flen, const float* __restrict__ fscore,
+                                                          const float* __restrict__ flm, const int* __restrict__ fword,
+                                                          const int* __restrict__ fnw, const int* __restrict__ count, int T, int S, int B, int N,
+                                                          int* __restrict__ hyp, int* __restrict__ hyp_len, float* __restrict__ score,
+                                                          float* __restrict__ lm_out, int* __restrict__ words, int* __restrict__ ends,
+                                                          int* __restrict__ word_len) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S * N) return;
+  const int s = i / N, r = i - s * N;
+  const int cap = 1 + T * B;
+  const int* tp = tparent + (size_t)s * cap;
+  const int* tl = tlabel + (size_t)s * cap;
+  const int* tw = tword + (size_t)s * cap;
+  int* h = hyp + (size_t)i * T;
+  int* wd = words + (size_t)i * T;
+  int* en = ends + (size_t)i * T;
+  const bool have = r < count[s];
+  const size_t f = (size_t)s * B + r;
+  int node = have ? fnode[f] : 0;
+  const int L = have ? min(flen[f], T) : 0;
+  const int W = have ? min(fnw[f], L) : 0;   // every word has a label
+  for (int j = 0; j < T; ++j) { h[j] = -1; wd[j] = -1; en[j] = -1; }
+  int at = W - 1;
+  if (at >= 0) { wd[at] = fword[f]; en[at] = L; --at; }
+  for (int j = L - 1; j >= 0 && node > 0 && node < cap; --j) {   // the root is node 0
+    h[j] = tl[node];
+    const int w = tw[node];   // closed in front of label j: the word ends with label j - 1
+    if (w != 0 && at >= 0) { wd[at] = w; en[at] = j; --at; }
+    node = tp[node];
+  }
+  hyp_len[i] = have ? L : -1;
+  word_len[i] = have ? W : -1;
+  score[i] = have ? fscore[f] : kLogZero;
+  lm_out[i] = have ? flm[f] : kLogZero;
+}
+
 }  // namespace
 
 void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, int S, const int* lens, int Cc, int* cid, float* csc,
@@ -562,6 +876,28 @@ void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* f
   hipLaunchKernelGGL(ctc_hyp_kernel, dim3(cdiv(S * N, 64)), dim3(64), 0, st, tparent, tlabel, fnode, flen, fscore, flm, count, T, S, B, N, hyp, hyp_len,
                      score, lm_out);
   check_launch("ctc_hyp");
+}
+
+void ctc_word_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid, const float* csc,
+                   const float* sblank, const LmTables* lm, const WordLexTables& lex, float alpha, float beta, bool use_eos, int* tparent,
+                   int* tlabel, int* tword, int* fnode, int* flen, float* fscore, float* flm, int* fword, int* fnw, int* count) {
+  EESEN_REQUIRE(B >= 1 && B <= kMaxBeam && Cc >= 1 && Cc <= kMaxCls && lex.H >= 1 && lex.H <= Lexicon::kMaxHomophones &&
+                    B * (1 + Cc * (1 + lex.H)) <= kMaxKeys,
+                EESEN_ERR_INVALID, "ctc_word_beam: beam, class count or homophone count outside the key array");
+  int keys = 2;
+  while (keys < B * (1 + Cc * (1 + lex.H))) keys <<= 1;
+  const int threads = std::min(512, std::max(64, keys / 2));
+  hipLaunchKernelGGL(ctc_word_beam_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank, lm ? *lm : LmTables{},
+                     lm ? 1 : 0, alpha, beta, use_eos ? 1 : 0, lex, tparent, tlabel, tword, fnode, flen, fscore, flm, fword, fnw, count);
+  check_launch("ctc_word_beam");
+}
+
+void ctc_word_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* tword, const int* fnode, const int* flen, const float* fscore,
+                  const float* flm, const int* fword, const int* fnw, const int* count, int T, int S, int B, int N, int* hyp, int* hyp_len,
+                  float* score, float* lm_out, int* words, int* ends, int* word_len) {
+  hipLaunchKernelGGL(ctc_word_hyp_kernel, dim3(cdiv(S * N, 64)), dim3(64), 0, st, tparent, tlabel, tword, fnode, flen, fscore, flm, fword, fnw, count,
+                     T, S, B, N, hyp, hyp_len, score, lm_out, words, ends, word_len);
+  check_launch("ctc_word_hyp");
 }
 
 }  // namespace eesen

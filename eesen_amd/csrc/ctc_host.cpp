@@ -243,6 +243,7 @@ void Ctc::decode_parallel_lex(const int* frame_num_utt, int S, const float* scor
                               int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
                               int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host) {
   EESEN_REQUIRE(lex != nullptr, EESEN_ERR_INVALID, "decoding with a lexicon: the lexicon handle is null");
+  EESEN_REQUIRE(!lex->unspaced, EESEN_ERR_INVALID, "an unspaced lexicon (eesen_lex_create_unspaced) is decoded with eesen_ctc_decode_parallel_words");
   EESEN_REQUIRE(lex->K == K, EESEN_ERR_INVALID, "the lexicon was built for another class count K than the scores have");
   EESEN_REQUIRE(lm == nullptr || lm->K == lex->V() + 1, EESEN_ERR_INVALID, "the word LM's K must be the lexicon's word count + 1 (build it over eesen_lex_write_words' table)");
   EESEN_REQUIRE(!use_eos || (lm != nullptr && lm->has_eos), EESEN_ERR_INVALID, "use_eos without a word LM, or on one whose file has no </s>");
@@ -267,17 +268,21 @@ void Ctc::decode_parallel_lex(const int* frame_num_utt, int S, const float* scor
 void Ctc::upload_lex(const Lexicon& lex) {
   if (lex_serial == lex.serial) return;
   EESEN_HIP_CHECK(hipStreamSynchronize(st));   // (a launch in flight may still read the tables this replaces)
-  const size_t nn = lex.word.size(), ne = lex.child_cls.size();
-  std::vector<int> packed(4 * nn + 2 * ne);
+  const size_t nn = lex.word.size(), ne = lex.child_cls.size(), nw = lex.node_words.size();   // (nw: the unspaced kind's alone)
+  std::vector<int> packed(4 * nn + 2 * ne + nw);
   for (size_t v = 0; v < nn; ++v) {
     int* r = packed.data() + 4 * v;
-    r[0] = lex.first[v]; r[1] = lex.count[v]; r[2] = lex.word[v]; r[3] = 0;
+    r[0] = lex.first[v]; r[1] = lex.count[v];
+    r[2] = lex.unspaced ? lex.wfirst[v] : lex.word[v];
+    r[3] = lex.unspaced ? lex.wcount[v] : 0;
   }
   std::copy(lex.child_cls.begin(), lex.child_cls.end(), packed.begin() + 4 * nn);
   std::copy(lex.child_node.begin(), lex.child_node.end(), packed.begin() + 4 * nn + ne);
+  std::copy(lex.node_words.begin(), lex.node_words.end(), packed.begin() + 4 * nn + 2 * ne);
   lex_i.reserve(packed.size());
   EESEN_HIP_CHECK(hipMemcpy(lex_i.p, packed.data(), packed.size() * sizeof(int), hipMemcpyHostToDevice));
   lex_tab = LexTables{lex_i.p, lex_i.p + 4 * nn, lex_i.p + 4 * nn + ne, lex.space};
+  word_tab = WordLexTables{lex_i.p, lex_i.p + 4 * nn, lex_i.p + 4 * nn + ne, lex_i.p + 4 * nn + 2 * ne, lex.max_homophones, lex.K};
   lex_serial = lex.serial;
 }
 
@@ -383,6 +388,111 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
     hyp_len_host[i] = bad ? -1 : out[n_hyp + i];
     score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
     if (fused && lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[(size_t)S * N + i];
+  }
+}
+
+// Along an unspaced lexicon (INTEGRATION.md "Words without a boundary unit"): the candidate selection of decode_batch, then the word
+// beam and its hypothesis kernel, in decode_batch's buffers, phases and conventions.  The trie holds a third array (the word closed
+// in front of a node's label) and the final beam a word and a word count per hypothesis; nothing is segmented on the host.
+void Ctc::decode_parallel_words(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam,
+                                int max_classes, int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos,
+                                int* hyp_host, int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host,
+                                int* word_end_host) {
+  EESEN_REQUIRE(lex != nullptr, EESEN_ERR_INVALID, "decoding with a lexicon: the lexicon handle is null");
+  EESEN_REQUIRE(lex->unspaced, EESEN_ERR_INVALID, "a lexicon with a space class (eesen_lex_create) is decoded with eesen_ctc_decode_parallel_lex");
+  EESEN_REQUIRE(lex->K == K, EESEN_ERR_INVALID, "the lexicon was built for another class count K than the scores have");
+  EESEN_REQUIRE(lm == nullptr || lm->K == lex->V() + 1, EESEN_ERR_INVALID, "the word LM's K must be the lexicon's word count + 1 (build it over eesen_lex_write_words' table)");
+  EESEN_REQUIRE(!use_eos || (lm != nullptr && lm->has_eos), EESEN_ERR_INVALID, "use_eos without a word LM, or on one whose file has no </s>");
+  EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_bonus), EESEN_ERR_INVALID, "lm_weight and word_bonus must be finite");
+  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
+  EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  EESEN_REQUIRE(beam >= 1 && beam <= 64, EESEN_ERR_INVALID, "beam outside [1, 64]");
+  EESEN_REQUIRE(max_classes >= 1 && max_classes <= 64, EESEN_ERR_INVALID, "max_classes outside [1, 64]");
+  const int H = lex->max_homophones;
+  EESEN_REQUIRE((long)beam * (1 + (long)max_classes * (1 + H)) <= 4096, EESEN_ERR_INVALID,
+                "beam * (1 + max_classes * (1 + H)) above 4096, H = " + std::to_string(H) + " the lexicon's largest homophone set (the successor keys of a frame live in LDS)");
+  EESEN_REQUIRE(nbest >= 1 && nbest <= beam, EESEN_ERR_INVALID, "nbest outside [1, beam]");
+  const int T = rows / S;
+  for (int s = 0; s < S; ++s)
+    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  const int B = beam, N = nbest, Cc = std::min(max_classes, K - 1);
+  const size_t n_cand = (size_t)rows * Cc, n_beam = (size_t)S * B, n_trie = (size_t)S * (1 + (size_t)T * B), SN = (size_t)S * N;
+  const size_t n_f = n_cand + rows + 2 * n_beam, n_i = n_cand + S + 4 * n_beam + S;
+  const size_t n_hyp = SN * T, n_out = 3 * n_hyp + 4 * SN;   // labels, lengths, scores, LM sums, words, word ends, word counts
+  EESEN_REQUIRE(n_trie <= ((size_t)1 << 30), EESEN_ERR_INVALID, "decoding: more than 2^30 trie nodes (S * (1 + T * beam)): decode fewer utterances together");
+  if ((!is_log && logp.cap < (size_t)rows * K) || dec_f.cap < n_f || dec_i.cap < n_i || dec_trie.cap < 3 * n_trie || dec_out.cap < n_out)
+    EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  if (!is_log) logp.reserve((size_t)rows * K);
+  dec_f.reserve(n_f);
+  dec_i.reserve(n_i);
+  dec_trie.reserve(3 * n_trie);
+  dec_out.reserve(n_out);
+  float* csc = dec_f.p;
+  float* sblank = csc + n_cand;
+  float* fscore = sblank + rows;
+  float* flm = fscore + n_beam;
+  int* cid = dec_i.p;
+  int* lens_d = cid + n_cand;
+  int* fnode = lens_d + S;
+  int* flen = fnode + n_beam;
+  int* fword = flen + n_beam;
+  int* fnw = fword + n_beam;
+  int* count = fnw + n_beam;
+  int* hyp_d = dec_out.p;
+  int* len_d = hyp_d + n_hyp;
+  float* score_d = reinterpret_cast<float*>(len_d + SN);
+  float* lmsum_d = score_d + SN;
+  int* words_d = reinterpret_cast<int*>(lmsum_d + SN);
+  int* ends_d = words_d + n_hyp;
+  int* wlen_d = ends_d + n_hyp;
+  if (lm) upload_lm(*lm);
+  upload_lex(*lex);
+
+  PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
+  int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
+  std::copy(frame_num_utt, frame_num_utt + S, pinned);
+  EESEN_HIP_CHECK(hipMemcpyAsync(lens_d, pinned, S * sizeof(int), hipMemcpyHostToDevice, st));
+  sp.used(st);
+
+  const float* sc = is_log ? scores : logp.p;
+  const int sld = is_log ? ld : K;
+  const bool acc = decode_timer.enabled();
+  int sp0 = -1, sp1 = -1, sp2 = -1;
+  if (acc) sp0 = decode_timer.begin(st, 0); else dev[0].record(st);
+  if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
+  ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
+  if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
+  ctc_word_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, word_tab, lm_weight, word_bonus, use_eos, dec_trie.p,
+                dec_trie.p + n_trie, dec_trie.p + 2 * n_trie, fnode, flen, fscore, flm, fword, fnw, count);
+  if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
+  ctc_word_hyp(st, dec_trie.p, dec_trie.p + n_trie, dec_trie.p + 2 * n_trie, fnode, flen, fscore, flm, fword, fnw, count, T, S, B, N, hyp_d, len_d,
+               score_d, lmsum_d, words_d, ends_d, wlen_d);
+  if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
+  dec_rows = rows; dec_S = S; dec_C = Cc;
+  dec_lens.assign(frame_num_utt, frame_num_utt + S);
+
+  // results and the guard word's value when they were computed, through one pinned slot
+  int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
+  EESEN_HIP_CHECK(hipMemcpyAsync(out, hyp_d, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
+  out[n_out] = 0;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_out, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  decode_pin.used(st);
+  decode_pin.wait();
+  // computed from a timed-out forward pass (guard word set): no hypotheses -- NaN and -1, never garbage with status OK
+  const bool bad = out[n_out] != 0;
+  const int* w_out = out + n_hyp + 3 * SN;
+  for (size_t i = 0; i < n_hyp; ++i) {
+    hyp_host[i] = bad ? -1 : out[i];
+    if (word_host) word_host[i] = bad ? -1 : w_out[i];
+    if (word_end_host) word_end_host[i] = bad ? -1 : w_out[n_hyp + i];
+  }
+  const float* scr = reinterpret_cast<const float*>(out + n_hyp + SN);
+  for (size_t i = 0; i < SN; ++i) {
+    hyp_len_host[i] = bad ? -1 : out[n_hyp + i];
+    score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
+    if (lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[SN + i];
+    if (word_len_host) word_len_host[i] = bad ? -1 : w_out[2 * n_hyp + i];
   }
 }
 

@@ -241,6 +241,19 @@ void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, 
 // beyond count[s]); with flm and lm_out (both null without an LM) lm_out [S][N] = flm of the same entries, -1e30 beyond count[s].
 void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const float* flm,
              const int* count, int T, int S, int B, int N, int* hyp, int* hyp_len, float* score, float* lm_out);
+// ctc_word_beam: the word beam search along an unspaced lexicon (ctc_word_beam_kernel; INTEGRATION.md "Words without a boundary
+// unit"; the tables: lex.h), S workgroups as ctc_prefix_beam.  The trie gains tword [S][1 + T*B]: the word closed in front of a
+// node's label, or 0.  Final hypotheses, best first, [S][B]: fnode, flen (labels), fscore, flm, fword (the word closed at the end, 0
+// for the empty hypothesis), fnw (words, the last included); count[s] of them.  B * (1 + Cc * (1 + lex->H)) <= 4096.
+struct WordLexTables;
+void ctc_word_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
+                   const float* csc, const float* sblank, const LmTables* lm, const WordLexTables& lex, float alpha, float beta, bool use_eos,
+                   int* tparent, int* tlabel, int* tword, int* fnode, int* flen, float* fscore, float* flm, int* fword, int* fnw, int* count);
+// ctc_word_hyp: ctc_hyp's outputs plus words / ends [S][N][T] (word ids front to back and the number of labels up to and including
+// each word's last; -1 beyond the word count) and word_len [S][N] (-1 beyond count[s]).
+void ctc_word_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* tword, const int* fnode, const int* flen, const float* fscore,
+                  const float* flm, const int* fword, const int* fnw, const int* count, int T, int S, int B, int N, int* hyp, int* hyp_len,
+                  float* score, float* lm_out, int* words, int* ends, int* word_len);
 // diff[t*S+s][k] = y*rowsum(e) - gamma ... (error kernel + softmax Jacobian, ctc-loss.cc:156-168)
 // labx [S x Lpad]: the expanded labels (blank 0 at even positions), lablens [S] = 2 U_s + 1
 void ctc_error_diff(hipStream_t st, const float* probs, int ld, int T, int S, int K, int Lpad, int Lmax, const int* lens,

@@ -17,14 +17,28 @@ using namespace text;
 void Lexicon::from_file(const char* path, const char* units, int K_, int space_) {
   EESEN_REQUIRE(K_ >= 3, EESEN_ERR_INVALID, "a lexicon needs the blank, the space and at least one other class (K >= 3)");
   EESEN_REQUIRE(space_ >= 1 && space_ < K_, EESEN_ERR_INVALID, "the space class must lie in [1, K)");
-  const bool have_units = units != nullptr && units[0] != 0;
-  std::unordered_map<std::string, int> table;
-  if (have_units) table = read_units(units, K_);
-  std::ifstream in(path);
-  if (!in) fail(path, 0, "cannot open the lexicon");
   K = K_;
   space = space_;
+  unspaced = false;
+  compile(path, units);
+}
+
+void Lexicon::from_file_unspaced(const char* path, const char* units, int K_) {
+  EESEN_REQUIRE(K_ >= 2, EESEN_ERR_INVALID, "an unspaced lexicon needs the blank and at least one other class (K >= 2)");
+  K = K_;
+  space = 0;   // the blank's id: no unit can be it
+  unspaced = true;
+  compile(path, units);
+}
+
+void Lexicon::compile(const char* path, const char* units) {
+  const bool have_units = units != nullptr && units[0] != 0;
+  std::unordered_map<std::string, int> table;
+  if (have_units) table = read_units(units, K);
+  std::ifstream in(path);
+  if (!in) fail(path, 0, "cannot open the lexicon");
   names.assign(1, std::string());
+  std::vector<std::vector<std::pair<int, long>>> ends(1);   // unspaced, per node: (word, the line that put it there), ascending
   std::unordered_map<std::string, int> id_of;
   std::vector<std::map<int, int>> kids(1);   // per node: class -> child (ordered: the children come out sorted)
   word.assign(1, 0);
@@ -44,7 +58,7 @@ void Lexicon::from_file(const char* path, const char* units, int K_, int space_)
         fail(path, ln, "unit " + f[i] + " is no decimal class id");
       }
       if (id < 1 || id >= K) fail(path, ln, "unit " + f[i] + " outside [1, K) with K = " + std::to_string(K));
-      if (id == space) fail(path, ln, "unit " + f[i] + " is the space class: a spelling cannot hold it");
+      if (!unspaced && id == space) fail(path, ln, "unit " + f[i] + " is the space class: a spelling cannot hold it");
       sp.push_back((int)id);
     }
     int v = 0;
@@ -56,14 +70,24 @@ void Lexicon::from_file(const char* path, const char* units, int K_, int space_)
       kids[v].emplace(c, made);
       kids.emplace_back();
       word.push_back(0);
+      if (unspaced) ends.emplace_back();
       v = made;
     }
     // (the word takes its id only now: a line that fails leaves no word behind)
     const auto known = id_of.find(f[0]);
     const int w = known != id_of.end() ? known->second : (int)names.size();
-    if (word[v] != 0 && word[v] != w) fail(path, ln, "words " + names[word[v]] + " and " + f[0] + " have the same spelling: a labelling would not determine the word");
+    if (unspaced) {
+      auto& e = ends[v];
+      auto at = std::lower_bound(e.begin(), e.end(), std::make_pair(w, 0L));
+      if (at == e.end() || at->first != w) {
+        if ((int)e.size() >= kMaxHomophones)
+          fail(path, ln, "word " + f[0] + " is one more than " + std::to_string(kMaxHomophones) + " words with the same spelling (the first of them: " +
+                             names[e.front().first] + ", line " + std::to_string(e.front().second) + ")");
+        e.insert(at, std::make_pair(w, ln));
+      }
+    } else if (word[v] != 0 && word[v] != w) fail(path, ln, "words " + names[word[v]] + " and " + f[0] + " have the same spelling: a labelling would not determine the word");
     if (known == id_of.end()) { id_of.emplace(f[0], w); names.push_back(f[0]); }
-    word[v] = w;
+    word[v] = unspaced ? ends[v].front().first : w;
     max_word_len = std::max(max_word_len, (int)sp.size());
   }
   if (V() < 1) fail(path, 0, "the lexicon holds no word");
@@ -74,6 +98,16 @@ void Lexicon::from_file(const char* path, const char* units, int K_, int space_)
     first[v] = (int)child_cls.size();
     count[v] = (int)kids[v].size();
     for (const auto& kv : kids[v]) { child_cls.push_back(kv.first); child_node.push_back(kv.second); }
+  }
+  if (unspaced) {
+    wfirst.assign(n, 0);
+    wcount.assign(n, 0);
+    for (int v = 0; v < n; ++v) {
+      wfirst[v] = (int)node_words.size();
+      wcount[v] = (int)ends[v].size();
+      for (const auto& e : ends[v]) node_words.push_back(e.first);
+      max_homophones = std::max(max_homophones, wcount[v]);
+    }
   }
   static std::atomic<unsigned long long> next_serial{1};
   serial = next_serial++;
@@ -88,6 +122,7 @@ int Lexicon::child(int node, int c) const {
 }
 
 bool Lexicon::words(const int* labels, int n, int* out, int* num) const {
+  EESEN_REQUIRE(!unspaced, EESEN_ERR_INVALID, "an unspaced lexicon does not segment a labelling (the segmentation is ambiguous): the words come from eesen_ctc_decode_parallel_words");
   int v = 0, nw = 0;
   for (int i = 0; i < n; ++i) {
     const int c = labels[i];

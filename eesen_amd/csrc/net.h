@@ -282,6 +282,7 @@ struct Ctc {
   // the tables of the lexicon the last decode_parallel_lex used (lex.h), keyed in the same way
   DevBuf<int> lex_i;
   LexTables lex_tab{};
+  WordLexTables word_tab{};    // ... of an unspaced lexicon (decode_parallel_words): the same buffer and serial
   unsigned long long lex_serial = 0;
   // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
@@ -322,6 +323,12 @@ struct Ctc {
   void decode_parallel_lex(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                            int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
                            int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host);
+  // the word beam search along an unspaced lexicon (ctc_word_beam + ctc_word_hyp in ctc_decode.hip): hypotheses are labels and
+  // the words closed between them; words, word counts and word ends (word_end_host [S][nbest][T]: labels up to and including word
+  // j's last) come from the device; the three may be null
+  void decode_parallel_words(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
+                             int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
+                             int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host, int* word_end_host);
   void decode_times(float* out3);
   // the candidate classes the last decode_parallel selected: ids / scores [rows][C'], blank [rows]; rows beyond an utterance: -1 / -1e30
   void get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc);

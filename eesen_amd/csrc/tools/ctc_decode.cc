@@ -6,7 +6,8 @@
 // With --lm a token n-gram LM (an ARPA file over the net's tokens) is fused into the search: eesen_ctc_decode_parallel_lm.
 // With --lexicon the labellings are held to lexicon words separated by --space-unit, scored by an optional word n-gram LM
 // (--word-lm): eesen_ctc_decode_parallel_lex; the word ids go to --words-wspecifier and word errors are counted against
-// --word-ref-rspecifier.
+// --word-ref-rspecifier.  With --word-boundary=none the lexicon has no boundary unit (the phoneme systems: nothing but CTC's blank
+// between words, homophones allowed): eesen_ctc_decode_parallel_words; the word ends go to --word-ends-wspecifier.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -57,6 +58,7 @@ int main(int argc, char** argv) {
   try {
     std::string class_frame_counts, scores_out, ref_rspecifier, lm_arpa, lm_units;
     std::string lexicon, lexicon_units, space_unit = "<SPACE>", word_lm, words_wspecifier, words_table_out, word_ref_rspecifier;
+    std::string word_boundary = "unit", word_ends_wspecifier;
     float prior_scale = 1.f, lm_weight = 1.f, insertion_bonus = 0.f, word_bonus = 0.f;
     bool lm_eos = false, lm_skip_oov = false;
     double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
@@ -87,6 +89,10 @@ int main(int argc, char** argv) {
     po.Register("lexicon", &lexicon, "Lexicon, `word unit unit ...` per spelling: the hypotheses are its words separated by --space-unit");
     po.Register("lexicon-units", &lexicon_units, "units.txt of the lexicon's units: `symbol id` per line; without it they are decimal class ids");
     po.Register("space-unit", &space_unit, "The unit between words: a symbol of --lexicon-units, or a decimal class id without it");
+    po.Register("word-boundary", &word_boundary, "unit: words are separated by --space-unit; none: nothing but CTC's blank stands between words and "
+                                                 "several words may share a spelling (the phoneme systems)");
+    po.Register("word-ends-wspecifier", &word_ends_wspecifier, "With --word-boundary=none: also write, per hypothesis, the number of labels up to and "
+                                                               "including each word's last (int32 vectors)");
     po.Register("word-lm", &word_lm, "ARPA file of a word n-gram LM over the lexicon's words, stepped once per word (weight: --lm-weight)");
     po.Register("word-bonus", &word_bonus, "Added per word, in nats");
     po.Register("lm-skip-oov", &lm_skip_oov, "Drop the n-grams of --word-lm that hold a word outside the lexicon instead of refusing the file");
@@ -122,8 +128,20 @@ int main(int argc, char** argv) {
     else if (!lm_units.empty()) throw std::runtime_error("--lm-units without --lm");
     eesen_lex_t* lex = nullptr;
     int V = 0;
+    if (word_boundary != "unit" && word_boundary != "none") throw std::runtime_error("--word-boundary=" + word_boundary + " is neither unit nor none");
+    const bool unspaced = word_boundary == "none";
+    if (unspaced && lexicon.empty()) throw std::runtime_error("--word-boundary=none needs --lexicon");
+    if (unspaced && space_unit != "<SPACE>") throw std::runtime_error("--space-unit=" + space_unit + " together with --word-boundary=none: there is no unit between words");
+    if (!unspaced && !word_ends_wspecifier.empty()) throw std::runtime_error("--word-ends-wspecifier needs --word-boundary=none");
     if (!lexicon.empty()) {
-      ck(eesen_lex_create(lexicon.c_str(), lexicon_units.empty() ? nullptr : lexicon_units.c_str(), K, space_class(space_unit, lexicon_units), &lex));
+      if (unspaced) {
+        ck(eesen_lex_create_unspaced(lexicon.c_str(), lexicon_units.empty() ? nullptr : lexicon_units.c_str(), K, &lex));
+        int H = 0;
+        ck(eesen_lex_max_homophones(lex, &H));
+        std::cerr << "LOG (ctc-decode:main()) the largest homophone set of " << lexicon << " holds " << H << " words" << std::endl;
+      } else {
+        ck(eesen_lex_create(lexicon.c_str(), lexicon_units.empty() ? nullptr : lexicon_units.c_str(), K, space_class(space_unit, lexicon_units), &lex));
+      }
       ck(eesen_lex_info(lex, &V, nullptr, nullptr));
       if (!words_table_out.empty()) ck(eesen_lex_write_words(lex, words_table_out.c_str()));
       if (!word_lm.empty()) {   // the word LM reads its words through the lexicon's table
@@ -168,6 +186,8 @@ int main(int argc, char** argv) {
     if (!word_ref_rspecifier.empty()) word_refs = read_targets(word_ref_rspecifier);
     std::unique_ptr<IntVectorWriter> words_writer;
     if (!words_wspecifier.empty()) words_writer.reset(new IntVectorWriter(words_wspecifier));
+    std::unique_ptr<IntVectorWriter> ends_writer;
+    if (!word_ends_wspecifier.empty()) ends_writer.reset(new IntVectorWriter(word_ends_wspecifier));
     FeatureReader reader(piped ? pipe.source : args[1]);
     IntVectorWriter writer(args[2]);
     std::ofstream scores;
@@ -181,7 +201,7 @@ int main(int argc, char** argv) {
     std::vector<std::pair<std::string, Mat>> group;
     std::vector<int> out_frames;            // per utterance of the group: frames behind the pipeline
     std::vector<const float*> cmvn;
-    std::vector<int> hyp, hyp_len, words, words_len;
+    std::vector<int> hyp, hyp_len, words, words_len, word_ends;
     std::vector<float> score, lm_score;
     auto flush = [&]() {
       const int S = (int)group.size();
@@ -201,7 +221,12 @@ int main(int argc, char** argv) {
       if (!log_pri.empty())
         ck(eesen_op_log_sub_prior(device, nullptr, const_cast<float*>(out), T * S, K, old, 1, log_pri.data(), prior_scale));
       hyp.resize((size_t)S * nbest * T); hyp_len.resize((size_t)S * nbest); score.resize((size_t)S * nbest);
-      if (lex) {
+      if (lex && unspaced) {
+        lm_score.resize((size_t)S * nbest); words.resize((size_t)S * nbest * T); words_len.resize((size_t)S * nbest); word_ends.resize((size_t)S * nbest * T);
+        ck(eesen_ctc_decode_parallel_words(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, lex, lm, lm_weight,
+                                           word_bonus, lm_eos ? 1 : 0, hyp.data(), hyp_len.data(), score.data(), lm_score.data(), words.data(),
+                                           words_len.data(), word_ends.data()));
+      } else if (lex) {
         lm_score.resize((size_t)S * nbest); words.resize((size_t)S * nbest * T); words_len.resize((size_t)S * nbest);
         ck(eesen_ctc_decode_parallel_lex(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, lex, lm, lm_weight,
                                          word_bonus, lm_eos ? 1 : 0, hyp.data(), hyp_len.data(), score.data(), lm_score.data(), words.data(),
@@ -228,6 +253,7 @@ int main(int argc, char** argv) {
           const std::string key = nbest > 1 ? utt + "-" + std::to_string(i + 1) : utt;
           writer.Write(key, hyp.data() + (e0 + i) * T, hyp_len[e0 + i]);
           if (words_writer) words_writer->Write(key, words.data() + (e0 + i) * T, words_len[e0 + i]);
+          if (ends_writer) ends_writer->Write(key, word_ends.data() + (e0 + i) * T, words_len[e0 + i]);
           if (scores.is_open()) {
             scores << key << ' ' << fmt9(score[e0 + i]);
             if (lm) scores << ' ' << fmt9(lm_score[e0 + i]);

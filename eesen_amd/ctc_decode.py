@@ -11,6 +11,8 @@ Ctc.DecodeParallel.  Written: one int32 vector per hypothesis, the labels (blank
 With --lm a token n-gram LM (an ARPA file over the net's tokens) is fused into the search (api.TokenLm).
 With --lexicon the labellings are held to lexicon words separated by --space-unit, scored by an optional word n-gram LM (--word-lm):
 api.Lexicon; the word ids go to --words-wspecifier and word errors are counted against --word-ref-rspecifier.
+With --word-boundary=none the lexicon has no boundary unit (the phoneme systems: nothing but CTC's blank between words, homophones
+allowed): api.Lexicon(space=None); the word ends go to --word-ends-wspecifier.
 """
 from __future__ import annotations
 
@@ -62,6 +64,10 @@ def main(argv=None) -> int:
     ap.register("lexicon", "", "Lexicon, `word unit unit ...` per spelling: the hypotheses are its words separated by --space-unit")
     ap.register("lexicon-units", "", "units.txt of the lexicon's units: `symbol id` per line; without it they are decimal class ids")
     ap.register("space-unit", "<SPACE>", "The unit between words: a symbol of --lexicon-units, or a decimal class id without it")
+    ap.register("word-boundary", "unit", "unit: words are separated by --space-unit; none: nothing but CTC's blank stands between words and "
+                                         "several words may share a spelling (the phoneme systems)")
+    ap.register("word-ends-wspecifier", "", "With --word-boundary=none: also write, per hypothesis, the number of labels up to and "
+                                            "including each word's last (int32 vectors)")
     ap.register("word-lm", "", "ARPA file of a word n-gram LM over the lexicon's words, stepped once per word (weight: --lm-weight)")
     ap.register("word-bonus", 0.0, "Added per word, in nats")
     ap.register("lm-skip-oov", False, "Drop the n-grams of --word-lm that hold a word outside the lexicon instead of refusing the file")
@@ -113,8 +119,21 @@ def main(argv=None) -> int:
         elif o.lm_units:
             raise kaldi_io.KaldiIOError("--lm-units without --lm")
         lex = None
+        if o.word_boundary not in ("unit", "none"):
+            raise kaldi_io.KaldiIOError(f"--word-boundary={o.word_boundary} is neither unit nor none")
+        unspaced = o.word_boundary == "none"
+        if unspaced and not o.lexicon:
+            raise kaldi_io.KaldiIOError("--word-boundary=none needs --lexicon")
+        if unspaced and o.space_unit != "<SPACE>":
+            raise kaldi_io.KaldiIOError(f"--space-unit={o.space_unit} together with --word-boundary=none: there is no unit between words")
+        if not unspaced and o.word_ends_wspecifier:
+            raise kaldi_io.KaldiIOError("--word-ends-wspecifier needs --word-boundary=none")
         if o.lexicon:
-            lex = Lexicon(o.lexicon, o.lexicon_units or None, K=K, space=_space_class(o.space_unit, o.lexicon_units))
+            if unspaced:
+                lex = Lexicon(o.lexicon, o.lexicon_units or None, K=K, space=None)
+                log(f"the largest homophone set of {o.lexicon} holds {lex.MaxHomophones()} words")
+            else:
+                lex = Lexicon(o.lexicon, o.lexicon_units or None, K=K, space=_space_class(o.space_unit, o.lexicon_units))
             if o.words_table_out:
                 lex.WriteWords(o.words_table_out)
             if o.word_lm:          # the word LM reads its words through the lexicon's table
@@ -145,6 +164,12 @@ def main(argv=None) -> int:
             if wkind != "ark":
                 raise kaldi_io.KaldiIOError("only ark: output is supported")
             words_writer = kaldi_io.VecIntArkWriter(words_path, text=words_text)
+        ends_writer = None
+        if o.word_ends_wspecifier:
+            ekind, ends_path, ends_text = kaldi_io._parse_specifier(o.word_ends_wspecifier)
+            if ekind != "ark":
+                raise kaldi_io.KaldiIOError("only ark: output is supported")
+            ends_writer = kaldi_io.VecIntArkWriter(ends_path, text=ends_text)
         pipe = frontend.parse_feature_pipeline(feature_rspecifier) if not os.environ.get("EESEN_HOST_FEATURE_PIPES") else None
         feeder = None
         if pipe is not None:
@@ -175,7 +200,7 @@ def main(argv=None) -> int:
             hyps, score = ctc.DecodeParallel(lens, out, beam=o.beam, max_classes=o.max_classes, nbest=o.nbest, is_log=log_pri is not None,
                                              lm=lm, lm_weight=o.lm_weight, insertion_bonus=o.insertion_bonus, lm_eos=o.lm_eos, lexicon=lex,
                                              word_bonus=o.word_bonus)
-            lm_score, words, words_len = ctc.lm_score, ctc.words, ctc.words_len
+            lm_score, words, words_len, word_ends = ctc.lm_score, ctc.words, ctc.words_len, ctc.word_ends
             for s, (key, m) in enumerate(group):
                 frames = int(lens[s])
                 if math.isnan(score[s, 0]):
@@ -192,6 +217,8 @@ def main(argv=None) -> int:
                     yield k, np.asarray(h, np.int32)
                     if words_writer is not None:          # (after the hypothesis is out, as the native tool orders its writes)
                         words_writer.write(k, words[s, i, :words_len[s, i]])
+                    if ends_writer is not None:
+                        ends_writer.write(k, word_ends[s, i, :words_len[s, i]])
                 if key in refs:
                     ref, best, err = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][0], np.int32), C.c_int(0)
                     _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
@@ -221,6 +248,8 @@ def main(argv=None) -> int:
         finally:
             if words_writer is not None:
                 words_writer.close()
+            if ends_writer is not None:
+                ends_writer.close()
         if scores:
             scores.close()
         if o.ref_rspecifier:

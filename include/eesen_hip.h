@@ -466,6 +466,36 @@ int eesen_ctc_decode_parallel_lex(eesen_ctc_t* ctc, const int* frame_num_utt, in
                                   int* hyp_len_host /*S*nbest*/, float* score_host /*S*nbest*/, float* lm_score_host /*S*nbest or NULL*/,
                                   int* word_host /*S*nbest*T or NULL*/, int* word_len_host /*S*nbest or NULL*/);
 
+/* ---- words without a boundary unit (INTEGRATION.md "Words without a boundary unit": the recipes' phoneme systems) ----
+ * The unspaced lexicon: the file format and the word ids of eesen_lex_create, but no boundary unit (nothing but CTC's blank sits
+ * between words) and up to 15 words per spelling (homophones).  EESEN_ERR_INVALID with the file and the line: an unknown unit, a unit
+ * outside [1, K), an empty spelling, a 16th word on one spelling (that line and the spelling's first are named), a file without a
+ * word.  eesen_lex_max_homophones: H, the largest number of words on one spelling (0 for a lexicon of eesen_lex_create);
+ * eesen_lex_node_words: the ascending word ids whose spelling ends at the node -- their number into *count, the first
+ * min(count, cap) into out (out may be NULL with cap 0).  On an unspaced lexicon eesen_lex_word gives the smallest of them or 0 and
+ * eesen_lex_words is EESEN_ERR_INVALID: a labelling does not determine its segmentation. */
+int eesen_lex_create_unspaced(const char* lexicon_path, const char* units_path /*or NULL*/, int K, eesen_lex_t** lex);
+int eesen_lex_max_homophones(eesen_lex_t* lex, int* H);
+int eesen_lex_node_words(eesen_lex_t* lex, int node, int* out /*cap or NULL*/, int cap, int* count);
+/* The word beam search along an unspaced lexicon (ctc_word_beam_kernel).  A hypothesis is a sequence of units and closing marks #w;
+ * hypotheses with equal labels and different words are different entries and each carries the labels' full acoustic mass.  Entry p
+ * at lexicon node v and candidate class c (e: p's last label) give, in this order,
+ *   inside:  v has a child v' for c: p + c at v', g = 0, LM state and lmsum unchanged;
+ *   close i: for the i-th word w of words(v), if the root has a child r for c: p + #w + c at r, (wt, next) = lm_step(state, w) (0
+ *            without an LM), g = lm_weight * wt + word_bonus, state next, lmsum + wt;
+ * lnb' = (s_t(c) + g) + (c == e ? lb : tot).  After frame n-1 a complete entry (empty, or words(v) non-empty) yields one result per
+ * word of words(v), closed as in eesen_ctc_decode_parallel_lex; the results are ranked by total, ties by (previous rank, word
+ * index).  Outputs as eesen_ctc_decode_parallel_lex, all from the device; word_end_host [S][nbest][T] (may be NULL): the number of
+ * labels up to and including word j's last, -1 beyond the word count.  EESEN_ERR_INVALID besides that call's cases:
+ * beam * (1 + max_classes * (1 + H)) above 4096 (the successor keys of a frame live in LDS), a lexicon of eesen_lex_create (that
+ * one goes to eesen_ctc_decode_parallel_lex, which in turn refuses an unspaced lexicon). */
+int eesen_ctc_decode_parallel_words(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
+                                    int is_log, int beam, int max_classes, int nbest, eesen_lex_t* lex, eesen_lm_t* lm /*or NULL*/,
+                                    float lm_weight, float word_bonus, int use_eos, int* hyp_host /*S*nbest*T*/,
+                                    int* hyp_len_host /*S*nbest*/, float* score_host /*S*nbest*/, float* lm_score_host /*S*nbest or NULL*/,
+                                    int* word_host /*S*nbest*T or NULL*/, int* word_len_host /*S*nbest or NULL*/,
+                                    int* word_end_host /*S*nbest*T or NULL*/);
+
 /* LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: the count eesen_ctc_error_rate_mseq accumulates, for a
  * host that scores hypotheses of its own (ctc-decode --ref-rspecifier).  No device work. */
 int eesen_edit_distance(const int* ref, int num_ref, const int* hyp, int num_hyp, int* errors);

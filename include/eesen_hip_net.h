@@ -262,11 +262,28 @@ class TokenLm {
 
 /* A lexicon for Ctc::DecodeParallel (eesen_lex_*; no counterpart in the reference, whose lexicon lives in the L of its TLG graphs):
  * `word unit unit ...` lines -- the units are the symbols of units.txt, or decimal class ids when `units` is empty -- compiled on the
- * host into a trie.  num_classes: the net's output dimension, blank included; space_class: the unit that separates words. */
+ * host into a trie.  num_classes: the net's output dimension, blank included; space_class: the unit that separates words.  Without
+ * a space class: the unspaced kind (eesen_lex_create_unspaced) of the phoneme systems -- nothing but CTC's blank between words, several
+ * words (homophones) per spelling -- which Ctc::DecodeParallel decodes with eesen_ctc_decode_parallel_words. */
 class Lexicon {
  public:
-  Lexicon(const std::string& path, const std::string& units, int32 num_classes, int32 space_class) : h_(NULL) {
+  Lexicon(const std::string& path, const std::string& units, int32 num_classes, int32 space_class) : h_(NULL), space_(space_class) {
     HipCheck(eesen_lex_create(path.c_str(), units.empty() ? NULL : units.c_str(), num_classes, space_class, &h_));
+  }
+  Lexicon(const std::string& path, const std::string& units, int32 num_classes) : h_(NULL), space_(0) {
+    HipCheck(eesen_lex_create_unspaced(path.c_str(), units.empty() ? NULL : units.c_str(), num_classes, &h_));
+  }
+  bool Unspaced() const { return space_ == 0; }
+  int32 SpaceClass() const { return space_; }   /* 0: the unspaced kind */
+  int32 MaxHomophones() const { int v = 0; HipCheck(eesen_lex_max_homophones(h_, &v)); return v; }
+  /* the ascending ids of the words whose spelling ends at the node */
+  std::vector<int32> NodeWords(int32 node) const {
+    int n = 0;
+    HipCheck(eesen_lex_node_words(h_, node, NULL, 0, &n));
+    std::vector<int32> out(n + 1);
+    HipCheck(eesen_lex_node_words(h_, node, out.data(), n, &n));
+    out.resize(n);
+    return out;
   }
   ~Lexicon() { if (h_) eesen_lex_destroy(h_); }
   int32 NumWords() const { int v = 0; HipCheck(eesen_lex_info(h_, &v, NULL, NULL)); return v; }
@@ -290,6 +307,7 @@ class Lexicon {
   Lexicon(const Lexicon&);
   Lexicon& operator=(const Lexicon&);
   eesen_lex_t* h_;
+  int32 space_;
 };
 
 /* eesen::Ctc (src/net/ctc-loss.h:29-90), the multi-sequence entry points */
@@ -400,16 +418,35 @@ class Ctc {
                       std::vector<std::vector<std::vector<int32> > >* words, std::vector<std::vector<BaseFloat> >* scores,
                       std::vector<std::vector<BaseFloat> >* lm_scores = NULL, int32 beam = 16, int32 max_classes = 20, int32 nbest = 1,
                       bool is_log = false) {
+    DecodeParallel(frame_num_utt, net_out, lexicon, lm, lm_weight, word_bonus, use_eos, hyps, words, NULL, scores, lm_scores, beam, max_classes,
+                   nbest, is_log);
+  }
+  /* The same, and word_ends[s][i][j]: the number of labels of hyps[s][i] up to and including word j's last.  An unspaced lexicon takes
+   * eesen_ctc_decode_parallel_words: an entry is a labelling and a segmentation of it, both from the device; homophones and other
+   * segmentations of the same labels are entries of their own. */
+  void DecodeParallel(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out, const Lexicon& lexicon, const TokenLm* lm,
+                      float lm_weight, float word_bonus, bool use_eos, std::vector<std::vector<std::vector<int32> > >* hyps,
+                      std::vector<std::vector<std::vector<int32> > >* words, std::vector<std::vector<std::vector<int32> > >* word_ends,
+                      std::vector<std::vector<BaseFloat> >* scores, std::vector<std::vector<BaseFloat> >* lm_scores = NULL, int32 beam = 16,
+                      int32 max_classes = 20, int32 nbest = 1, bool is_log = false) {
     const int S = (int)frame_num_utt.size();
     const int T = S > 0 ? net_out.NumRows() / S : 0;
     if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
     std::vector<int32> hyp((size_t)S * nbest * T + 1), len((size_t)S * nbest + 1), wrd((size_t)S * nbest * T + 1), wlen((size_t)S * nbest + 1);
     std::vector<BaseFloat> sc((size_t)S * nbest + 1), lsc((size_t)S * nbest + 1);
-    HipCheck(eesen_ctc_decode_parallel_lex(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
-                                           is_log ? 1 : 0, beam, max_classes, nbest, lexicon.Handle(), lm ? lm->Handle() : NULL, lm_weight,
-                                           word_bonus, use_eos ? 1 : 0, hyp.data(), len.data(), sc.data(), lsc.data(), wrd.data(), wlen.data()));
+    std::vector<int32> wend(lexicon.Unspaced() ? (size_t)S * nbest * T + 1 : 1);
+    if (lexicon.Unspaced())
+      HipCheck(eesen_ctc_decode_parallel_words(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                               is_log ? 1 : 0, beam, max_classes, nbest, lexicon.Handle(), lm ? lm->Handle() : NULL, lm_weight,
+                                               word_bonus, use_eos ? 1 : 0, hyp.data(), len.data(), sc.data(), lsc.data(), wrd.data(), wlen.data(),
+                                               wend.data()));
+    else
+      HipCheck(eesen_ctc_decode_parallel_lex(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                             is_log ? 1 : 0, beam, max_classes, nbest, lexicon.Handle(), lm ? lm->Handle() : NULL, lm_weight,
+                                             word_bonus, use_eos ? 1 : 0, hyp.data(), len.data(), sc.data(), lsc.data(), wrd.data(), wlen.data()));
     hyps->assign(S, std::vector<std::vector<int32> >());
     words->assign(S, std::vector<std::vector<int32> >());
+    if (word_ends) word_ends->assign(S, std::vector<std::vector<int32> >());
     scores->assign(S, std::vector<BaseFloat>());
     if (lm_scores) lm_scores->assign(S, std::vector<BaseFloat>());
     for (int s = 0; s < S; ++s)
@@ -417,6 +454,14 @@ class Ctc {
         const size_t e = (size_t)s * nbest + i;
         (*hyps)[s].push_back(std::vector<int32>(hyp.data() + e * T, hyp.data() + e * T + len[e]));
         (*words)[s].push_back(std::vector<int32>(wrd.data() + e * T, wrd.data() + e * T + wlen[e]));
+        if (word_ends && lexicon.Unspaced()) (*word_ends)[s].push_back(std::vector<int32>(wend.data() + e * T, wend.data() + e * T + wlen[e]));
+        if (word_ends && !lexicon.Unspaced()) {   /* a word ends in front of every space and at the end */
+          std::vector<int32> ends;
+          for (int j = 0; j < len[e]; ++j)
+            if (hyp[e * T + j] == lexicon.SpaceClass()) ends.push_back(j);
+          if (len[e] > 0) ends.push_back(len[e]);
+          (*word_ends)[s].push_back(ends);
+        }
         (*scores)[s].push_back(sc[e]);
         if (lm_scores) (*lm_scores)[s].push_back(lsc[e]);
       }
