@@ -117,6 +117,10 @@ SIGNATURES = {
     "eesen_lex_node_words": (_i, [_vp, _i, _vp, _i, _pi]),
     "eesen_ctc_decode_parallel_words": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eesen_ctc_decode_parallel_lm": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "eesen_ctc_decode_stamps": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eesen_ctc_get_stamp_times": (_i, [_vp, _vp]),
+    "eesen_ctc_set_stamp_group": (_i, [_vp, _i]),
+    "eesen_word_confidence": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp]),
     "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "eesen_ce_destroy": (_i, [_vp]),
     "eesen_ce_eval_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -595,6 +595,29 @@ class Lexicon:
         return out[:n.value].tolist()
 
 
+class Stamps:
+    """What Ctc.DecodeStamps returns: frame intervals [start, end) per label and per word, word confidences, best-path scores."""
+
+    def __init__(self, label_start, label_end, word_start, word_end, word_conf, path_score):
+        self.label_start, self.label_end = label_start, label_end
+        self.word_start, self.word_end, self.word_conf = word_start, word_end, word_conf
+        self.path_score = path_score
+
+
+def word_confidence(scores, word_len, word_ids, wstart, wend, conf_scale: float = 1.0) -> np.ndarray:
+    """N-best posterior word confidences on the host in fp64 (eesen_word_confidence; no device work).  scores [n]; word_len [n] (< 0:
+    not an entry); word_ids / wstart / wend [n, stride].  Returns conf [n, stride] float64, -1e30 beyond each entry's words."""
+    z = np.ascontiguousarray(scores, np.float64)
+    wl = np.ascontiguousarray(word_len, np.int32)
+    ids, b, e = (np.ascontiguousarray(a, np.int32).reshape(z.size, -1) for a in (word_ids, wstart, wend))
+    if not (wl.size == z.size and ids.shape == b.shape == e.shape):
+        raise EesenError(-1, "word_confidence: array shapes differ")
+    out = np.empty(ids.shape, np.float64)
+    check(_lib.load().eesen_word_confidence(z.size, _np_ptr(z), _np_ptr(wl), _np_ptr(ids), _np_ptr(b), _np_ptr(e), ids.shape[1],
+                                            float(conf_scale), _np_ptr(out)))
+    return out
+
+
 class Ctc:
     """eesen::Ctc (ctc-loss.h:31-90) for the multi-sequence path."""
 
@@ -721,6 +744,36 @@ class Ctc:
         out = np.zeros(3, np.float32)
         check(self.lib.eesen_ctc_get_decode_times(self.h, _np_ptr(out)))
         return dict(zip(["topc", "beam", "hyp"], out.tolist()))
+
+    def DecodeStamps(self, frame_num_utt: Sequence[int], net_out: CuMatrix, is_log: bool = False, conf_scale: float = 1.0) -> "Stamps":
+        """Time stamps and confidences of the entries the last DecodeParallel returned (eesen_ctc_decode_stamps; INTEGRATION.md "Time
+        stamps and CTM").  frame_num_utt, net_out, is_log: that call's.  Every entry is aligned on the acoustic scores by AlignParallel's
+        recurrence and tie rule, all of them in one launch.  Returns a Stamps: label_start / label_end / word_start / word_end
+        [S, nbest, T] int32 (frames, end exclusive, -1 beyond the labels / words), word_conf [S, nbest, T] float32 (N-best posterior
+        of the word, -1e30 beyond the words), path_score [S, nbest] float32.  The words are those of self.hyp / self.words /
+        self.word_ends."""
+        fn = np.ascontiguousarray(frame_num_utt, np.int32)
+        S = fn.size
+        hlen = getattr(self, "hyp_len", None)
+        nbest = hlen.shape[1] if hlen is not None and hlen.shape[0] == S else 1   # (without a decode call the library refuses)
+        T = net_out.rows // max(S, 1)
+        shape = (S, nbest, max(T, 0))
+        ls, le, ws, we = (np.empty(shape, np.int32) for _ in range(4))
+        wc = np.empty(shape, np.float32)
+        ps = np.empty((S, nbest), np.float32)
+        check(self.lib.eesen_ctc_decode_stamps(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
+                                               int(bool(is_log)), float(conf_scale), _np_ptr(ls), _np_ptr(le), _np_ptr(ws), _np_ptr(we),
+                                               _np_ptr(wc), _np_ptr(ps)))
+        return Stamps(ls, le, ws, we, wc, ps)
+
+    def SetStampGroup(self, lattices: int):
+        """Test hook (eesen_ctc_set_stamp_group): sweep DecodeStamps' lattices in groups of `lattices`; 0 = automatic."""
+        check(self.lib.eesen_ctc_set_stamp_group(self.h, int(lattices)))
+
+    def StampTimes(self) -> dict:
+        out = np.zeros(3, np.float32)
+        check(self.lib.eesen_ctc_get_stamp_times(self.h, _np_ptr(out)))
+        return dict(zip(["lattices", "sweep", "stamps"], out.tolist()))
 
     def DecodeCandidates(self, rows: int, max_classes: int):
         """The candidate classes the last DecodeParallel selected (tests): (ids [rows, C'], scores [rows, C'], blank [rows])."""

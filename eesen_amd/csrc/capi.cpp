@@ -409,6 +409,32 @@ int eesen_ctc_decode_parallel_lm(eesen_ctc_t* ctc, const int* frame_num_utt, int
                             use_eos != 0, hyp_host, hyp_len_host, score_host, lm_score_host);
   });
 }
+int eesen_ctc_decode_stamps(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld, int is_log,
+                            double conf_scale, int* lstart_host, int* lend_host, int* wstart_host, int* wend_host, float* wconf_host,
+                            float* path_score_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev);
+    ctc->decode_stamps(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, conf_scale, lstart_host, lend_host, wstart_host, wend_host,
+                       wconf_host, path_score_host);
+  });
+}
+int eesen_ctc_get_stamp_times(eesen_ctc_t* ctc, float* out3) {
+  return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->stamp_times(out3); });
+}
+int eesen_ctc_set_stamp_group(eesen_ctc_t* ctc, int lattices) {
+  return guard([&] {
+    REQ_PTR(ctc);
+    EESEN_REQUIRE(lattices >= 0, EESEN_ERR_INVALID, "stamp group: a negative lattice count");
+    ctc->stamp_group = lattices;
+  });
+}
+int eesen_word_confidence(int n_entries, const double* scores, const int* word_len, const int* word_ids, const int* wstart, const int* wend,
+                          int stride, double conf_scale, double* conf_out) {
+  return guard([&] {
+    REQ_PTR(scores); REQ_PTR(word_len); REQ_PTR(word_ids); REQ_PTR(wstart); REQ_PTR(wend); REQ_PTR(conf_out);
+    word_confidence(n_entries, scores, word_len, word_ids, wstart, wend, stride, conf_scale, conf_out);
+  });
+}
 int eesen_edit_distance(const int* ref, int num_ref, const int* hyp, int num_hyp, int* errors) {
   return guard([&] {
     REQ_PTR(errors);
@@ -457,7 +483,8 @@ int eesen_ctc_dropped(eesen_ctc_t* ctc, long* minibatches) {
 }
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode) {
   return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); ctc->align_timer.enable(mode == 2); ctc->align_timer.set_accumulate(mode == 2);
-                     ctc->decode_timer.enable(mode == 2); ctc->decode_timer.set_accumulate(mode == 2); });
+                     ctc->decode_timer.enable(mode == 2); ctc->decode_timer.set_accumulate(mode == 2);
+                     ctc->stamp_timer.enable(mode == 2); ctc->stamp_timer.set_accumulate(mode == 2); });
 }
 int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->phase_times(out3); });

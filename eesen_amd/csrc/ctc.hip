@@ -116,12 +116,15 @@ template <int PL, int NW, bool is_beta, bool best_path = false>
 __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld, int T, int S, const int* __restrict__ labx,
                                           const int* __restrict__ lens, const int* __restrict__ lablens,
                                           float* __restrict__ alpha, float* __restrict__ beta, float* __restrict__ pzx,
-                                          float* last, float (*edge)[NW][2]) {
+                                          float* last, float (*edge)[NW][2], int lat0 = 0, int lpu = 1) {
   static_assert(NW == 1 || PL >= 2, "a wave boundary hands over TWO positions of the neighbouring lane");
   constexpr int Lpad = 64 * PL * NW;
   const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int len = lens[s], ll = lablens[s];
   const int* lab = labx + (size_t)s * Lpad;
+  // the utterance whose score rows lattice s reads: its own in the training sweeps; in the best-path sweep lattice lat0 + s of lpu
+  // per utterance (the N-best entries of ctc_stamp: one launch aligns them all)
+  const int us = best_path ? (lat0 + s) / lpu : s;
   const int j0 = (int)threadIdx.x * PL;
   // the lane whose chunk ends at a wave boundary publishes its two edge positions after every step; the lane on the other side
   // of the boundary takes them instead of the (wrapped) shuffle result
@@ -168,7 +171,7 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
   const int t_first = is_beta ? len - 1 : 0, dt = is_beta ? -1 : 1;   // sweep direction
   auto row = [&](int k) {  // log-prob row of the k-th step of this sweep (clamped to a valid frame past the end)
     const int t = t_first + dt * k;
-    return logp + (size_t)((k < len ? t : t_first) * S + s) * ld;
+    return logp + (size_t)((k < len ? t : t_first) * S + us) * ld;
   };
   {  // first row (:1391-1393 / :1527-1529)
     const float* lp = row(0);
@@ -271,9 +274,10 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_beta_kernel(const float* __
 template <int PL, int NW>
 __global__ __launch_bounds__(64 * NW) void ctc_best_path_kernel(const float* __restrict__ logp, int ld, int T, int S,
                                                                 const int* __restrict__ labx, const int* __restrict__ lens,
-                                                                const int* __restrict__ lablens, float* __restrict__ delta) {
+                                                                const int* __restrict__ lablens, float* __restrict__ delta, int lat0,
+                                                                int lpu) {
   __shared__ float edge[2][NW][2];
-  ctc_sweep<PL, NW, false, true>(logp, ld, T, S, labx, lens, lablens, delta, nullptr, nullptr, nullptr, edge);
+  ctc_sweep<PL, NW, false, true>(logp, ld, T, S, labx, lens, lablens, delta, nullptr, nullptr, nullptr, edge, lat0, lpu);
 }
 
 // Traceback: the move into (t, j) is re-derived from the stored delta row t-1 with the sweep's own comparisons on the sweep's own
@@ -281,7 +285,8 @@ __global__ __launch_bounds__(64 * NW) void ctc_best_path_kernel(const float* __r
 // last label L'-2.  One workgroup per utterance: lane 0 walks the n dependent steps (the three candidates and the two labels of a
 // step are independent loads), all lanes write -1 into the rows the path does not cover.  An utterance whose best final delta is
 // <= -1e29 (too few frames for its labels, no frames, or a zero-probability frame on every path) has no alignment: score -1e30,
-// every entry -1.
+// every entry -1.  The kernel reads no score row, so a launch over many lattices per utterance (ctc_stamp) is this launch with S =
+// the number of lattices.
 __global__ __launch_bounds__(64) void ctc_traceback_kernel(const float* __restrict__ delta, int T, int S, int Lpad,
                                                            const int* __restrict__ labx, const int* __restrict__ lens,
                                                            const int* __restrict__ lablens, int* __restrict__ ali,
@@ -318,6 +323,31 @@ __global__ __launch_bounds__(64) void ctc_traceback_kernel(const float* __restri
     const float a2 = (j > 1 && (j & 1) && c2 != c) ? r2 : kLogZero;
     const int move = (a0 >= a1 && a0 >= a2) ? 0 : (a1 >= a2 ? 1 : 2);
     j = max(j - move, 0);   // (a NaN score must not walk off the row)
+  }
+}
+
+// ---- label intervals of many best paths (INTEGRATION.md "Time stamps and CTM"): one workgroup per lattice.  pos holds the traceback's
+// positions of the lattices in groups of G, group g as [T][lattices of g] behind the groups before it.  A path is monotone, so
+// frame t opens label (pos_t - 1) / 2 iff pos_t is odd and pos_{t-1} differs, and closes it iff pos_{t+1} differs: every label's two
+// values have one writer each -- no atomics, no serial walk, lanes stride over the frames.  lstart / lend [NL][T], -1 where no label.
+__global__ __launch_bounds__(256) void ctc_stamp_kernel(const int* __restrict__ pos, int T, int NL, int G, const int* __restrict__ lens,
+                                                        int* __restrict__ lstart, int* __restrict__ lend) {
+  const int i = blockIdx.x;
+  const int g0 = (i / G) * G, gc = min(G, NL - g0);
+  const int* p = pos + (size_t)g0 * T + (i - g0);
+  int* ls = lstart + (size_t)i * T;
+  int* le = lend + (size_t)i * T;
+  const int n = min(lens[i], T);
+  for (int t = threadIdx.x; t < T; t += blockDim.x) { ls[t] = -1; le[t] = -1; }
+  __syncthreads();
+  for (int t = threadIdx.x; t < n; t += blockDim.x) {
+    const int j = p[(size_t)t * gc];
+    if (j <= 0 || !(j & 1)) continue;   // a blank's frame, or no path
+    const int u = (j - 1) >> 1;
+    if (u >= T) continue;               // (a label needs a frame: cannot happen on a path)
+    const int before = t > 0 ? p[(size_t)(t - 1) * gc] : -1, after = t + 1 < n ? p[(size_t)(t + 1) * gc] : -1;
+    if (before != j) ls[u] = t;
+    if (after != j) le[u] = t + 1;
   }
 }
 
@@ -554,12 +584,14 @@ void ctc_alpha_beta(hipStream_t st, const float* logp, int ld, int T, int S, int
 }
 
 void ctc_best_path(hipStream_t st, const float* logp, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
-                   const int* lablens, float* delta, int waves) {
+                   const int* lablens, float* delta, int waves, int lattices, int lat0, int lpu) {
   const int nw = ctc_sweep_waves(Lpad, waves);
   const int pl = Lpad / (64 * nw);
+  const int grid = lattices > 0 ? lattices : S;
+  EESEN_REQUIRE(lpu >= 1 && lat0 >= 0 && (lat0 + grid - 1) / lpu < S, EESEN_ERR_INVALID, "ctc_best_path: a lattice beyond the utterances' score rows");
   const bool launched = with_sweep_shape(pl, nw, [&](auto PL, auto NW) {
-    hipLaunchKernelGGL((ctc_best_path_kernel<decltype(PL)::value, decltype(NW)::value>), dim3(S), dim3(64 * nw), 0, st, logp, ld, T, S, labx, lens,
-                       lablens, delta);
+    hipLaunchKernelGGL((ctc_best_path_kernel<decltype(PL)::value, decltype(NW)::value>), dim3(grid), dim3(64 * nw), 0, st, logp, ld, T, S, labx, lens,
+                       lablens, delta, lat0, lpu);
   });
   if (!launched) throw Error(EESEN_ERR_INVALID, "ctc: no lattice kernel for this padded label length / wave count (at most 4096 positions)");
   check_launch("ctc_best_path");
@@ -569,6 +601,13 @@ void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, c
                    int* ali, int* pos, float* score) {
   hipLaunchKernelGGL(ctc_traceback_kernel, dim3(S), dim3(64), 0, st, delta, T, S, Lpad, labx, lens, lablens, ali, pos, score);
   check_launch("ctc_traceback");
+}
+
+void ctc_stamp(hipStream_t st, const int* pos, int T, int NL, int G, const int* lens, int* lstart, int* lend) {
+  if (NL <= 0) return;
+  EESEN_REQUIRE(G >= 1, EESEN_ERR_INVALID, "ctc_stamp: empty lattice group");
+  hipLaunchKernelGGL(ctc_stamp_kernel, dim3(NL), dim3(256), 0, st, pos, T, NL, G, lens, lstart, lend);
+  check_launch("ctc_stamp");
 }
 
 void ctc_error_diff(hipStream_t st, const float* probs, int ld, int T, int S, int K, int Lpad, int Lmax, const int* lens,

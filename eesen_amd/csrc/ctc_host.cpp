@@ -250,15 +250,19 @@ void Ctc::decode_parallel_lex(const int* frame_num_utt, int S, const float* scor
   EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_bonus), EESEN_ERR_INVALID, "lm_weight and word_bonus must be finite");
   decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, lex, lm, lm_weight, word_bonus, use_eos, hyp_host, hyp_len_host,
                score_host, lm_score_host);
-  if (!word_host && !word_len_host) return;
+  // (kept for decode_stamps, which speaks of these words and may run after the lexicon is gone: segmented whether asked for or not)
   const int T = rows / S;
   std::vector<int> w((size_t)T / 2 + 1);
+  dec_word.assign((size_t)S * nbest * T, -1);
+  dec_word_len.assign((size_t)S * nbest, -1);
   for (size_t i = 0; i < (size_t)S * nbest; ++i) {
     int nw = -1;   // (no entry, or a raised guard word)
     if (hyp_len_host[i] >= 0) {
       const bool in_language = lex->words(hyp_host + i * T, hyp_len_host[i], w.data(), &nw);
       EESEN_REQUIRE(in_language, EESEN_ERR_STATE, "decoding with a lexicon returned a labelling outside its language");
+      std::copy(w.begin(), w.begin() + nw, dec_word.begin() + i * T);
     }
+    dec_word_len[i] = nw;
     if (word_len_host) word_len_host[i] = nw;
     if (word_host)
       for (int j = 0; j < T; ++j) word_host[i * T + j] = j < nw ? w[j] : -1;
@@ -372,6 +376,8 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
   dec_rows = rows; dec_S = S; dec_C = Cc;
   dec_lens.assign(frame_num_utt, frame_num_utt + S);
+  dec_N = N; dec_T = T; dec_mode = lex ? 1 : 0; dec_fused = fused;   // (decode_stamps: the hypotheses stay in dec_out and decode_pin)
+  dec_space = lex ? lex->space : -1;
 
   // results and the guard word's value when they were computed, through one pinned slot
   int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
@@ -471,6 +477,7 @@ void Ctc::decode_parallel_words(const int* frame_num_utt, int S, const float* sc
   if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
   dec_rows = rows; dec_S = S; dec_C = Cc;
   dec_lens.assign(frame_num_utt, frame_num_utt + S);
+  dec_N = N; dec_T = T; dec_mode = 2; dec_fused = true;
 
   // results and the guard word's value when they were computed, through one pinned slot
   int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
@@ -493,6 +500,208 @@ void Ctc::decode_parallel_words(const int* frame_num_utt, int S, const float* sc
     score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
     if (lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[SN + i];
     if (word_len_host) word_len_host[i] = bad ? -1 : w_out[2 * n_hyp + i];
+  }
+}
+
+// N-best posterior word confidences (INTEGRATION.md "Time stamps and CTM"): lattice-to-ctm-conf's idea on a list instead of a lattice.
+void word_confidence(int n, const double* scores, const int* word_len, const int* word_ids, const int* wstart, const int* wend, int stride,
+                     double conf_scale, double* conf_out) {
+  EESEN_REQUIRE(n >= 0 && stride >= 0, EESEN_ERR_INVALID, "word_confidence: negative entry count or stride");
+  EESEN_REQUIRE(std::isfinite(conf_scale) && conf_scale >= 0, EESEN_ERR_INVALID, "conf_scale must be finite and >= 0");
+  for (int i = 0; i < n; ++i)
+    EESEN_REQUIRE(word_len[i] <= stride, EESEN_ERR_INVALID, "word_confidence: more words than the row holds");
+  // P_i = exp(c (z_i - z_max)) / sum_k exp(c (z_k - z_max)): every exponent is <= 0 (the best entry's is 0), so nothing overflows
+  double zmax = -std::numeric_limits<double>::infinity();
+  for (int i = 0; i < n; ++i)
+    if (word_len[i] >= 0) zmax = std::max(zmax, scores[i]);
+  std::vector<double> P(n, 0.0);
+  double sum = 0;
+  for (int i = 0; i < n; ++i)
+    if (word_len[i] >= 0) { P[i] = std::exp(conf_scale * (scores[i] - zmax)); sum += P[i]; }
+  for (int i = 0; i < n; ++i) P[i] = sum > 0 ? P[i] / sum : 0.0;
+  // every entry's words ordered by id: a word meets only the few of another entry that share its id (N-best lists of long
+  // labellings: the all-pairs scan took longer than the alignment of the whole minibatch on the device)
+  struct Occ { int id, b, e; };
+  std::vector<std::vector<Occ>> by_id(n);
+  for (int k = 0; k < n; ++k) {
+    for (int m = 0; m < word_len[k]; ++m) {
+      const size_t o = (size_t)k * stride + m;
+      by_id[k].push_back(Occ{word_ids[o], wstart[o], wend[o]});
+    }
+    std::stable_sort(by_id[k].begin(), by_id[k].end(), [](const Occ& x, const Occ& y) { return x.id < y.id; });
+  }
+  for (int i = 0; i < n; ++i) {
+    double* co = conf_out + (size_t)i * stride;
+    for (int j = 0; j < stride; ++j) co[j] = -1e30;
+    for (int j = 0; j < word_len[i]; ++j) {
+      const int w = word_ids[(size_t)i * stride + j], b = wstart[(size_t)i * stride + j], e = wend[(size_t)i * stride + j];
+      double c = 0;
+      for (int k = 0; k < n; ++k) {   // in entry order: the sum's order is part of the result; each entry counts at most once
+        auto it = std::lower_bound(by_id[k].begin(), by_id[k].end(), w, [](const Occ& x, int id) { return x.id < id; });
+        bool hit = false;
+        for (; it != by_id[k].end() && it->id == w && !hit; ++it) hit = it->b < e && b < it->e;
+        if (hit) c += P[k];
+      }
+      co[j] = c;
+    }
+  }
+}
+
+// Time stamps of the last decode call's entries.  The hypotheses are where that call left them: labels and lengths in dec_out (device)
+// and, with scores and words, in decode_pin (host); the frame counts behind the candidates in dec_i.  The delta rows borrow `alpha` as
+// align_parallel's do, the logarithms `logp`.
+void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, double conf_scale,
+                        int* lstart_host, int* lend_host, int* wstart_host, int* wend_host, float* wconf_host, float* path_score_host) {
+  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "time stamps: no decode call on this Ctc yet");
+  EESEN_REQUIRE(S == dec_S && rows == dec_rows, EESEN_ERR_STATE, "time stamps: S or rows differ from the last decode call's");
+  EESEN_REQUIRE(K > 0 && ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  EESEN_REQUIRE(std::isfinite(conf_scale) && conf_scale >= 0, EESEN_ERR_INVALID, "conf_scale must be finite and >= 0");
+  for (int s = 0; s < S; ++s)
+    EESEN_REQUIRE(frame_num_utt[s] == dec_lens[s], EESEN_ERR_STATE, "time stamps: frame_num_utt differs from the last decode call's");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  const int T = dec_T, N = dec_N;
+  const size_t NL = (size_t)S * N, n_hyp = NL * T;
+  const size_t n_dec = dec_mode == 2 ? 3 * n_hyp + 4 * NL : n_hyp + (dec_fused ? 3 : 2) * NL;
+  const int* dout = decode_pin.as<int>();
+  const int* hyp_h = dout;
+  const int* hlen = dout + n_hyp;
+  const float* z = reinterpret_cast<const float*>(hlen + NL);
+  const float kNaN = std::numeric_limits<float>::quiet_NaN();
+  auto fill = [&](int* p, size_t n, int v) { if (p) std::fill(p, p + n, v); };
+  auto fillf = [&](float* p, size_t n, float v) { if (p) std::fill(p, p + n, v); };
+  auto all_bad = [&] {   // decoded or aligned from a timed-out forward pass (guard word set): -1 and NaN, never garbage with status OK
+    fill(lstart_host, n_hyp, -1); fill(lend_host, n_hyp, -1); fill(wstart_host, n_hyp, -1); fill(wend_host, n_hyp, -1);
+    fillf(wconf_host, n_hyp, kNaN); fillf(path_score_host, NL, kNaN);
+  };
+  if (dout[n_dec] != 0) { all_bad(); return; }
+
+  constexpr int kMaxLabels = 2047;   // L' <= 4096
+  int maxU = 0;
+  for (size_t i = 0; i < NL; ++i)
+    if (hlen[i] <= kMaxLabels) maxU = std::max(maxU, hlen[i]);
+  int PL = 1;
+  while (64 * PL < 2 * maxU + 1) PL *= 2;
+  const int Lpad = 64 * PL;
+  const size_t per_lattice = (size_t)T * Lpad;
+  size_t G = stamp_group > 0 ? (size_t)stamp_group : std::max<size_t>(1, kStampDeltaBytes / (per_lattice * sizeof(float)));
+  G = std::min(G, NL);
+
+  const size_t n_res = 2 * n_hyp + NL;   // label starts, label ends, path scores
+  const size_t n_int = NL * Lpad + 2 * NL + 2 * n_hyp + n_res;
+  if ((!is_log && logp.cap < (size_t)rows * K) || alpha.cap < G * per_lattice || stamp_i.cap < n_int) EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  if (!is_log) logp.reserve((size_t)rows * K);
+  alpha.reserve(G * per_lattice);
+  stamp_i.reserve(n_int);
+  int* labx_d = stamp_i.p;
+  int* ll_d = labx_d + NL * Lpad;
+  int* lens_l = ll_d + NL;
+  int* pos_d = lens_l + NL;
+  int* ali_d2 = pos_d + n_hyp;
+  int* lstart_d = ali_d2 + n_hyp;
+  int* lend_d = lstart_d + n_hyp;
+  float* score_d = reinterpret_cast<float*>(lend_d + n_hyp);
+  const int* lens_d = dec_i.p + (size_t)dec_rows * dec_C;
+
+  const bool acc = stamp_timer.enabled();
+  int sp0 = -1, sp1 = -1, sp2 = -1;
+  if (acc) sp0 = stamp_timer.begin(st, 0); else sev[0].record(st);
+  if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
+  ctc_hyp_lattices(st, dec_out.p, dec_out.p + n_hyp, lens_d, T, (int)NL, N, Lpad, labx_d, ll_d, lens_l);
+  if (acc) { stamp_timer.end(st, sp0); sp1 = stamp_timer.begin(st, 1); } else sev[1].record(st);
+  for (size_t g0 = 0; g0 < NL; g0 += G) {   // groups of lattices: the delta rows stay within their budget
+    const int gc = (int)std::min(G, NL - g0);
+    ctc_best_path(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, Lpad, labx_d + g0 * Lpad, lens_l + g0, ll_d + g0, alpha.p, sweep_waves, gc,
+                  (int)g0, N);
+    ctc_traceback(st, alpha.p, T, gc, Lpad, labx_d + g0 * Lpad, lens_l + g0, ll_d + g0, ali_d2 + g0 * T, pos_d + g0 * T, score_d + g0);
+  }
+  if (acc) { stamp_timer.end(st, sp1); sp2 = stamp_timer.begin(st, 2); } else sev[2].record(st);
+  ctc_stamp(st, pos_d, T, (int)NL, (int)G, lens_l, lstart_d, lend_d);
+  if (acc) stamp_timer.end(st, sp2); else sev[3].record(st);
+
+  int* out = static_cast<int*>(loss_slot(stamp_pin, (n_res + 1) * sizeof(int)));
+  EESEN_HIP_CHECK(hipMemcpyAsync(out, lstart_d, n_res * sizeof(int), hipMemcpyDeviceToHost, st));
+  out[n_res] = 0;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_res, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  stamp_pin.used(st);
+  stamp_pin.wait();
+  if (out[n_res] != 0) { all_bad(); return; }
+  const int* ls = out;
+  const int* le = out + n_hyp;
+  const float* ps = reinterpret_cast<const float*>(out + 2 * n_hyp);
+
+  // words: runs of labels [a, b] with an id, per entry; then the confidences per utterance
+  const int* w_out = dout + n_hyp + 3 * NL;   // (unspaced mode: words, ends [NL][T], counts [NL])
+  std::vector<int> wid((size_t)N * T), wb((size_t)N * T), we((size_t)N * T), wl(N);
+  std::vector<double> zz(N), conf((size_t)N * T);
+  const bool want_words = wstart_host || wend_host || wconf_host;   // (a caller after the label intervals alone pays for neither)
+  for (int s = 0; s < S; ++s) {
+    for (int r = 0; r < N; ++r) {
+      const size_t i = (size_t)s * N + r;
+      const int U = hlen[i];
+      const bool stamped = U >= 1 && U <= kMaxLabels;
+      if (path_score_host) path_score_host[i] = U == 0 ? 0.f : stamped ? ps[i] : -1e30f;
+      for (int t = 0; t < T; ++t) {
+        if (lstart_host) lstart_host[i * T + t] = stamped ? ls[i * T + t] : -1;
+        if (lend_host) lend_host[i * T + t] = stamped ? le[i * T + t] : -1;
+      }
+      if (!want_words) continue;
+      int* id = wid.data() + (size_t)r * T;
+      int* b = wb.data() + (size_t)r * T;
+      int* e = we.data() + (size_t)r * T;
+      std::fill(id, id + T, -1); std::fill(b, b + T, -1); std::fill(e, e + T, -1);
+      int nw = U < 0 ? -1 : 0;
+      auto word = [&](int w, int first, int last) {   // labels [first, last] are word w
+        id[nw] = w;
+        b[nw] = stamped ? ls[i * T + first] : -1;
+        e[nw] = stamped ? le[i * T + last] : -1;
+        ++nw;
+      };
+      const int* h = hyp_h + i * T;
+      if (dec_mode == 0) {
+        for (int u = 0; u < U; ++u) word(h[u], u, u);
+      } else if (dec_mode == 1) {
+        const int want = dec_word_len[i];   // the runs between the space labels, whose frames belong to no word
+        int first = 0;
+        for (int u = 0; u <= U && U > 0; ++u) {
+          if (u < U && h[u] != dec_space) continue;
+          EESEN_REQUIRE(u > first && nw < want, EESEN_ERR_STATE, "time stamps: the labelling's spaces do not match its words");
+          word(dec_word[i * T + nw], first, u - 1);
+          first = u + 1;
+        }
+        EESEN_REQUIRE(nw == want, EESEN_ERR_STATE, "time stamps: the labelling's spaces do not match its words");
+      } else {
+        const int want = w_out[2 * n_hyp + i];
+        int first = 0;
+        for (int j = 0; j < want && j < T; ++j) {
+          const int end = w_out[n_hyp + i * T + j];
+          EESEN_REQUIRE(end > first && end <= U, EESEN_ERR_STATE, "time stamps: word ends outside the labelling");
+          word(w_out[i * T + j], first, end - 1);
+          first = end;
+        }
+      }
+      wl[r] = nw;
+      zz[r] = z[i];
+    }
+    if (!want_words) continue;
+    if (wconf_host) word_confidence(N, zz.data(), wl.data(), wid.data(), wb.data(), we.data(), T, conf_scale, conf.data());
+    for (int r = 0; r < N; ++r) {
+      const size_t i = (size_t)s * N + r;
+      for (int t = 0; t < T; ++t) {
+        if (wstart_host) wstart_host[i * T + t] = wb[(size_t)r * T + t];
+        if (wend_host) wend_host[i * T + t] = we[(size_t)r * T + t];
+        if (wconf_host) wconf_host[i * T + t] = (float)conf[(size_t)r * T + t];
+      }
+    }
+  }
+}
+
+void Ctc::stamp_times(float* out3) {
+  if (stamp_timer.enabled()) { stamp_timer.collect(out3, 3); return; }
+  sev[3].wait();
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.f;
+    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, sev[i], sev[i + 1]));
+    out3[i] = ms * 1e-3f;
   }
 }
 

@@ -211,13 +211,24 @@ void ctc_alpha_beta(hipStream_t st, const float* logp, int ld, int T, int S, int
 int ctc_sweep_waves(int Lpad, int waves = 0);
 // Best-path (Viterbi) alignment over the same lattices.  ctc_best_path: the alpha sweep in the max-plus semiring, S workgroups; the
 // delta rows are written in alpha's layout [S][T][Lpad] (rows t >= lens[s] are not written).  scores: [T*S x K] (ld) log-domain.
+// lattices > 0: that many workgroups instead of S, lattice i of the launch reading the score rows of utterance (lat0 + i) / lpu (labx,
+// lens, lablens and delta are indexed by i): the N-best entries of a decode call, lpu = nbest (Ctc::decode_stamps).
 void ctc_best_path(hipStream_t st, const float* scores, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
-                   const int* lablens, float* delta, int waves = 0);
+                   const int* lablens, float* delta, int waves = 0, int lattices = 0, int lat0 = 0, int lpu = 1);
 // ctc_traceback: from argmax(delta[n-1][L'-1], delta[n-1][L'-2]) (the final blank wins a tie) back to t = 0, the smallest move winning
 // among equal predecessors.  ali / pos [T*S] (row t*S + s): class id / lattice position per frame, -1 on rows t >= lens[s] and on
 // every row of an utterance without a feasible path; score [S]: the path's log-score, -1e30 without one.
 void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, const int* labx, const int* lens, const int* lablens,
                    int* ali, int* pos, float* score);
+// ctc_stamp: label intervals out of the positions of NL best paths (INTEGRATION.md "Time stamps and CTM").  pos: ctc_traceback's
+// output of the lattices in groups of G (the last may be smaller), group g as [T][lattices of g] at offset g * G * T; lens [NL].
+// lstart / lend [NL][T]: first frame of label u and one past its last, -1 beyond the labels and without a path.
+void ctc_stamp(hipStream_t st, const int* pos, int T, int NL, int G, const int* lens, int* lstart, int* lend);
+// ctc_hyp_lattices (ctc_decode.hip): the expanded labels of the NL = S * N hypotheses ctc_hyp / ctc_word_hyp left, for the sweeps above.
+// labx [NL][Lpad] blank-interleaved, -1 padded; lablens [NL] = 2 U + 1; lat_lens [NL] = the utterance's frames, or 0 -- no lattice --
+// for the empty hypothesis, for one of more labels than (Lpad - 1) / 2 and for ranks beyond the returned count (hyp_len < 0).
+void ctc_hyp_lattices(hipStream_t st, const int* hyp, const int* hyp_len, const int* lens, int T, int NL, int N, int Lpad, int* labx,
+                      int* lablens, int* lat_lens);
 // Prefix beam search, lexicon-free or along a lexicon trie (ctc_decode.hip; the computation: INTEGRATION.md "Decoding").  scores: [T*S x K] (ld) log-domain.
 // ctc_row_topc: per row t*S + s with t < lens[s] the Cc = min(max_classes, K - 1) best non-blank classes -- ids ascending in
 // cid [rows][Cc], their scores in csc [rows][Cc], the blank's in sblank [rows]; every score clamped from below at -1e30.

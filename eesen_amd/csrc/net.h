@@ -274,6 +274,17 @@ struct Ctc {
   PinBuf decode_pin;           // results of decode_parallel (D2H)
   int dec_rows = 0, dec_S = 0, dec_C = 0;   // shape of the candidates the last decode_parallel left (get_decode_candidates)
   std::vector<int> dec_lens;
+  // What the last decode call left for decode_stamps: its hypotheses stay in dec_out (device) and in decode_pin (host) until the next
+  // decode call.  dec_mode: 0 labels are words (plain, token LM), 1 spaced lexicon (the words in dec_word / dec_word_len: the
+  // lexicon may be gone by then), 2 unspaced lexicon (words and word ends in the pinned results).
+  int dec_N = 0, dec_T = 0, dec_mode = 0, dec_space = -1;
+  bool dec_fused = false;
+  std::vector<int> dec_word, dec_word_len;   // [S * N * T], [S * N]
+  DevBuf<int> stamp_i;         // decode_stamps: lattices, per-lattice lengths, positions, then the results (label starts, ends, path scores)
+  DevEvent sev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};  // stamp_times without the timer
+  PhaseTimer stamp_timer;      // phases: lattice build (with the logarithm), sweep + traceback, stamps
+  PinBuf stamp_pin;            // results of decode_stamps (D2H)
+  int stamp_group = 0;         // eesen_ctc_set_stamp_group: lattices per sweep launch, 0 = as many as kStampDeltaBytes holds (tuning.h)
   // the tables of the token LM the last decode_parallel_lm used (lm.h), keyed by the model's serial
   DevBuf<int> lm_i;
   DevBuf<float> lm_f;
@@ -330,6 +341,12 @@ struct Ctc {
                              int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
                              int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host, int* word_end_host);
   void decode_times(float* out3);
+  // Time stamps and confidences of the last decode call's entries (INTEGRATION.md "Time stamps and CTM"): ctc_hyp_lattices, then
+  // ctc_best_path + ctc_traceback over all S * nbest lattices in groups, then ctc_stamp; words and confidences on the host.
+  // lstart / lend / wstart / wend (int) and wconf (float) [S][nbest][T], path_score [S][nbest]; any may be null.
+  void decode_stamps(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, double conf_scale,
+                     int* lstart_host, int* lend_host, int* wstart_host, int* wend_host, float* wconf_host, float* path_score_host);
+  void stamp_times(float* out3);
   // the candidate classes the last decode_parallel selected: ids / scores [rows][C'], blank [rows]; rows beyond an utterance: -1 / -1e30
   void get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc);
  private:
@@ -341,6 +358,13 @@ struct Ctc {
   void upload_lm(const TokenLm& lm);
   void upload_lex(const Lexicon& lex);
 };
+
+// N-best posterior word confidences (eesen_word_confidence; INTEGRATION.md "Time stamps and CTM"), fp64, no device work.  Entry i of
+// n has total scores[i] and word_len[i] words (< 0: not an entry) with ids / intervals [wstart, wend) in rows of `stride`.
+// conf_out [n][stride]: sum over the entries k that hold a word of the same id whose interval intersects, of P_k = softmax(c * scores)_k;
+// -1e30 beyond an entry's words.
+void word_confidence(int n, const double* scores, const int* word_len, const int* word_ids, const int* wstart, const int* wend, int stride,
+                     double conf_scale, double* conf_out);
 
 // LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: what Ctc::error_rate_mseq counts with (ctc_host.cpp)
 int edit_distance(const int* ref, int nr, const int* hyp, int nh);

@@ -8,6 +8,8 @@
 // (--word-lm): eesen_ctc_decode_parallel_lex; the word ids go to --words-wspecifier and word errors are counted against
 // --word-ref-rspecifier.  With --word-boundary=none the lexicon has no boundary unit (the phoneme systems: nothing but CTC's blank
 // between words, homophones allowed): eesen_ctc_decode_parallel_words; the word ends go to --word-ends-wspecifier.
+// With --ctm-out the best hypothesis of every utterance is aligned to the frames (eesen_ctc_decode_stamps) and written as CTM lines
+// `key 1 start duration word [confidence]`, the file sclite scores.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -46,6 +48,23 @@ int space_class(const std::string& unit, const std::string& units_path) {
   }
   throw std::runtime_error("--space-unit=" + unit + " is not in " + units_path);
 }
+// `symbol id` lines -> id -> symbol (the first symbol of an id wins)
+std::map<int, std::string> id_symbols(const std::string& path) {
+  std::ifstream in(path);
+  if (!in) throw std::runtime_error("cannot open " + path);
+  std::map<int, std::string> out;
+  std::string line, sym, id;
+  while (std::getline(in, line)) {
+    std::istringstream f(line);
+    if (f >> sym >> id && id.find_first_not_of("0123456789") == std::string::npos && id.size() <= 9) out.emplace(std::stoi(id), sym);
+  }
+  return out;
+}
+std::string fixed(double v, int precision) {
+  char buf[512];
+  snprintf(buf, sizeof buf, "%.*f", precision, v);
+  return buf;
+}
 std::string fmt9(double v) {
   std::ostringstream o;
   o.precision(9);
@@ -58,7 +77,10 @@ int main(int argc, char** argv) {
   try {
     std::string class_frame_counts, scores_out, ref_rspecifier, lm_arpa, lm_units;
     std::string lexicon, lexicon_units, space_unit = "<SPACE>", word_lm, words_wspecifier, words_table_out, word_ref_rspecifier;
-    std::string word_boundary = "unit", word_ends_wspecifier;
+    std::string word_boundary = "unit", word_ends_wspecifier, ctm_out, ctm_units;
+    double frame_shift = 0.01, conf_scale = 1.0;
+    int ctm_precision = 2;
+    bool ctm_conf = false;
     float prior_scale = 1.f, lm_weight = 1.f, insertion_bonus = 0.f, word_bonus = 0.f;
     bool lm_eos = false, lm_skip_oov = false;
     double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
@@ -99,6 +121,13 @@ int main(int argc, char** argv) {
     po.Register("words-wspecifier", &words_wspecifier, "Also write the word ids of every hypothesis (int32 vectors, the keys of <hyp-wspecifier>)");
     po.Register("words-table-out", &words_table_out, "Write the lexicon's `word id` table to this file");
     po.Register("word-ref-rspecifier", &word_ref_rspecifier, "Reference word-id sequences: the word errors of the best hypotheses against them are counted");
+    po.Register("ctm-out", &ctm_out, "Also write the best hypothesis of every utterance as CTM lines `key 1 start duration word` to this file: "
+                                     "its words aligned to the frames");
+    po.Register("frame-shift", &frame_shift, "Seconds per frame of the network's output (the recipes subsample by 3: 0.03)");
+    po.Register("ctm-precision", &ctm_precision, "Digits behind the point of the CTM's times and confidences");
+    po.Register("ctm-conf", &ctm_conf, "A sixth CTM column: the word's posterior over the --nbest hypotheses");
+    po.Register("conf-scale", &conf_scale, "Scale of the hypotheses' log-probabilities in that posterior (>= 0)");
+    po.Register("ctm-units", &ctm_units, "units.txt naming the CTM's words without a lexicon: `symbol id` per line (default: --lm-units; else class ids)");
     po.Register("use-gpu", &use_gpu, "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)");
     po.Register("num-sequence", &num_sequence, "Utterances forwarded and decoded together");
     po.Register("frame-limit", &frame_limit, "Max number of frames forwarded together");
@@ -165,6 +194,36 @@ int main(int argc, char** argv) {
                word_bonus != 0.f || lm_skip_oov) {
       throw std::runtime_error("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and --word-ref-rspecifier need --lexicon");
     }
+    // the CTM's word symbols: the lexicon's words, else the units of --ctm-units / --lm-units, else decimal class ids
+    std::map<int, std::string> ctm_symbols;
+    std::ofstream ctm;
+    long num_ctm_words = 0;
+    if (!ctm_out.empty()) {
+      if (ctm_precision < 0 || ctm_precision > 17) throw std::runtime_error("--ctm-precision=" + std::to_string(ctm_precision) + " is outside [0, 17]");
+      if (!std::isfinite(frame_shift) || frame_shift <= 0) throw std::runtime_error("--frame-shift must be positive");
+      if (lex) {
+        std::string table = words_table_out;
+        if (table.empty()) {
+          const char* tmpdir = getenv("TMPDIR");
+          table = std::string(tmpdir && tmpdir[0] ? tmpdir : "/tmp") + "/ctc-decode-words.XXXXXX";
+          const int fd = mkstemp(&table[0]);
+          if (fd < 0) throw std::runtime_error("cannot create a temporary file for the words table: " + table);
+          close(fd);
+          const int rc = eesen_lex_write_words(lex, table.c_str());
+          if (rc == EESEN_OK) ctm_symbols = id_symbols(table);
+          std::remove(table.c_str());
+          ck(rc);
+        } else {
+          ctm_symbols = id_symbols(table);
+        }
+      } else if (!ctm_units.empty() || !lm_units.empty()) {
+        ctm_symbols = id_symbols(ctm_units.empty() ? lm_units : ctm_units);
+      }
+      ctm.open(ctm_out);
+      if (!ctm) throw std::runtime_error("cannot open " + ctm_out);
+    } else if (!ctm_units.empty() || ctm_conf) {
+      throw std::runtime_error("--ctm-units and --ctm-conf need --ctm-out");
+    }
     std::vector<float> log_pri;
     if (!class_frame_counts.empty()) {
       log_pri = class_log_priors(class_frame_counts, prior_cutoff, blank_scale);
@@ -202,7 +261,8 @@ int main(int argc, char** argv) {
     std::vector<int> out_frames;            // per utterance of the group: frames behind the pipeline
     std::vector<const float*> cmvn;
     std::vector<int> hyp, hyp_len, words, words_len, word_ends;
-    std::vector<float> score, lm_score;
+    std::vector<float> score, lm_score, wconf;
+    std::vector<int> wstart, wend;
     auto flush = [&]() {
       const int S = (int)group.size();
       std::vector<const float*> ptr(S);
@@ -239,6 +299,11 @@ int main(int argc, char** argv) {
         ck(eesen_ctc_decode_parallel(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, beam, max_classes, nbest, hyp.data(),
                                      hyp_len.data(), score.data()));
       }
+      if (ctm.is_open()) {
+        wstart.resize((size_t)S * nbest * T); wend.resize((size_t)S * nbest * T); wconf.resize((size_t)S * nbest * T);
+        ck(eesen_ctc_decode_stamps(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, conf_scale, nullptr, nullptr, wstart.data(),
+                                   wend.data(), wconf.data(), nullptr));
+      }
       for (int s = 0; s < S; ++s) {
         const std::string& utt = group[s].first;
         const size_t e0 = (size_t)s * nbest;
@@ -271,6 +336,21 @@ int main(int argc, char** argv) {
           int err = 0;
           ck(eesen_edit_distance(wref->second.data(), (int)wref->second.size(), words.data() + e0 * T, words_len[e0], &err));
           word_err += err; word_ref += (long)wref->second.size(); ++num_word_scored;
+        }
+        if (ctm.is_open()) {   // the best hypothesis' words: a label each without a lexicon
+          if (std::isnan(wconf[e0 * T])) throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no time stamps");
+          const int nw = lex ? words_len[e0] : hyp_len[e0];
+          const int* ids = (lex ? words.data() : hyp.data()) + e0 * T;
+          for (int j = 0; j < nw; ++j) {
+            if (wstart[e0 * T + j] < 0) continue;   // (a labelling too long to align)
+            const auto sym = ctm_symbols.find(ids[j]);
+            ctm << utt << " 1 " << fixed(frame_shift * wstart[e0 * T + j], ctm_precision) << ' '
+                << fixed(frame_shift * (wend[e0 * T + j] - wstart[e0 * T + j]), ctm_precision) << ' '
+                << (sym != ctm_symbols.end() ? sym->second : std::to_string(ids[j]));
+            if (ctm_conf) ctm << ' ' << fixed(wconf[e0 * T + j], ctm_precision);
+            ctm << '\n';
+            ++num_ctm_words;
+          }
         }
         ++num_done;
         if (hyp_len[e0] == 0) ++num_empty;
@@ -313,6 +393,10 @@ int main(int argc, char** argv) {
       scores.close();
       if (!scores) throw std::runtime_error("write error: " + scores_out);
     }
+    if (ctm.is_open()) {
+      ctm.close();
+      if (!ctm) throw std::runtime_error("write error: " + ctm_out);
+    }
     if (!ref_rspecifier.empty()) {
       std::cerr << "LOG (ctc-decode:main()) " << tok_err << " token errors on " << tok_ref << " reference tokens of " << num_scored << " utterances" << std::endl;
       std::cerr << "LOG (ctc-decode:main()) \nTOKEN_ACCURACY >> " << 100.0 * (1.0 - (double)tok_err / (double)std::max(tok_ref, 1L)) << "% <<" << std::endl;
@@ -325,6 +409,7 @@ int main(int argc, char** argv) {
     std::cerr << "LOG (ctc-decode:main()) Done " << num_done << " utterances, " << num_empty << " empty hypotheses; average log-probability per frame "
               << (tot_t > 0 ? tot_score / tot_t : 0.0);
     if (lm) std::cerr << "; average LM log-probability per " << (lex ? "word " : "label ") << (tot_labels > 0 ? tot_lm / tot_labels : 0.0);
+    if (!ctm_out.empty()) std::cerr << "; " << num_ctm_words << " CTM words";
     std::cerr << std::endl;
     if (lm) eesen_lm_destroy(lm);
     if (lex) eesen_lex_destroy(lex);

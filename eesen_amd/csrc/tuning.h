@@ -65,10 +65,16 @@
 //                                    wants while a peer is late (measured beside an RCCL-shaped stand-in: profiles/r06_rccl_shaped_soak.json).
 //                                    Every BASELINE shape is deferred; layers of <= 256 cells overlap.  Same buckets, order and sums.
 //   EESEN_COMM_PORT         MASTER_PORT+17  rendezvous port of the hosts that create the communicator from the environment
+//   ---- design constants (no environment variable) ------------------------------------------------------------------------
+//   kStampDeltaBytes        1 GiB    Ctc::decode_stamps: the delta rows [lattices][T][Lpad] of one best-path launch never take more; the
+//                                    S * nbest lattices of a call are swept in groups of that many (eesen_ctc_set_stamp_group: tests)
 #pragma once
+#include <cstddef>
 #include <cstdlib>
 
 namespace eesen {
+
+constexpr size_t kStampDeltaBytes = (size_t)1 << 30;
 
 struct Tuning {
   int persistent = 1;

@@ -13,6 +13,8 @@ With --lexicon the labellings are held to lexicon words separated by --space-uni
 api.Lexicon; the word ids go to --words-wspecifier and word errors are counted against --word-ref-rspecifier.
 With --word-boundary=none the lexicon has no boundary unit (the phoneme systems: nothing but CTC's blank between words, homophones
 allowed): api.Lexicon(space=None); the word ends go to --word-ends-wspecifier.
+With --ctm-out the best hypothesis of every utterance is aligned to the frames (Ctc.DecodeStamps) and written as CTM lines
+`key 1 start duration word [confidence]`, the file sclite scores.
 """
 from __future__ import annotations
 
@@ -36,6 +38,20 @@ def _space_class(unit: str, units_path: str) -> int:
         if len(f) >= 2 and f[0] == unit and f[1].isascii() and f[1].isdigit() and len(f[1]) <= 9:
             return int(f[1])
     raise ValueError(f"--space-unit={unit} is not in {units_path}")
+
+
+def _id_symbols(path: str) -> dict:
+    """`symbol id` lines -> id -> symbol (the first symbol of an id wins)."""
+    try:
+        lines = open(path).read().splitlines()
+    except OSError:
+        raise ValueError(f"cannot open {path}")
+    out = {}
+    for line in lines:
+        f = line.split()
+        if len(f) >= 2 and f[1].isascii() and f[1].isdigit() and len(f[1]) <= 9:
+            out.setdefault(int(f[1]), f[0])
+    return out
 
 
 def main(argv=None) -> int:
@@ -74,6 +90,13 @@ def main(argv=None) -> int:
     ap.register("words-wspecifier", "", "Also write the word ids of every hypothesis (int32 vectors, the keys of <hyp-wspecifier>)")
     ap.register("words-table-out", "", "Write the lexicon's `word id` table to this file")
     ap.register("word-ref-rspecifier", "", "Reference word-id sequences: the word errors of the best hypotheses against them are counted")
+    ap.register("ctm-out", "", "Also write the best hypothesis of every utterance as CTM lines `key 1 start duration word` to this file: "
+                               "its words aligned to the frames")
+    ap.register("frame-shift", 0.01, "Seconds per frame of the network's output (the recipes subsample by 3: 0.03)", kind="double")
+    ap.register("ctm-precision", 2, "Digits behind the point of the CTM's times and confidences")
+    ap.register("ctm-conf", False, "A sixth CTM column: the word's posterior over the --nbest hypotheses")
+    ap.register("conf-scale", 1.0, "Scale of the hypotheses' log-probabilities in that posterior (>= 0)", kind="double")
+    ap.register("ctm-units", "", "units.txt naming the CTM's words without a lexicon: `symbol id` per line (default: --lm-units; else class ids)")
     ap.register("use-gpu", "yes", "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)")
     ap.register("num-sequence", 1, "Utterances forwarded and decoded together")
     ap.register("frame-limit", 1e5, "Max number of frames forwarded together", kind="double")
@@ -154,6 +177,33 @@ def main(argv=None) -> int:
         elif o.lexicon_units or o.word_lm or o.words_wspecifier or o.words_table_out or o.word_ref_rspecifier or o.word_bonus != 0.0 or o.lm_skip_oov:
             raise kaldi_io.KaldiIOError("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and "
                                         "--word-ref-rspecifier need --lexicon")
+        # the CTM's word symbols: the lexicon's words, else the units of --ctm-units / --lm-units, else decimal class ids
+        ctm_symbols, ctm = {}, None
+        if o.ctm_out:
+            if not 0 <= o.ctm_precision <= 17:
+                raise kaldi_io.KaldiIOError(f"--ctm-precision={o.ctm_precision} is outside [0, 17]")
+            if not (math.isfinite(o.frame_shift) and o.frame_shift > 0):
+                raise kaldi_io.KaldiIOError("--frame-shift must be positive")
+            if lex is not None:
+                if o.words_table_out:
+                    ctm_symbols = _id_symbols(o.words_table_out)
+                else:
+                    import tempfile
+                    fd, table = tempfile.mkstemp(prefix="ctc-decode-words.")
+                    os.close(fd)
+                    try:
+                        lex.WriteWords(table)
+                        ctm_symbols = _id_symbols(table)
+                    finally:
+                        os.remove(table)
+            elif o.ctm_units or o.lm_units:
+                ctm_symbols = _id_symbols(o.ctm_units or o.lm_units)
+            try:
+                ctm = open(o.ctm_out, "w")
+            except OSError:
+                raise kaldi_io.KaldiIOError(f"cannot open {o.ctm_out}")
+        elif o.ctm_units or o.ctm_conf:
+            raise kaldi_io.KaldiIOError("--ctm-units and --ctm-conf need --ctm-out")
         if log_pri is not None and log_pri.size != K:
             raise kaldi_io.KaldiIOError(f"Dimensionality mismatch, class_frame_counts {log_pri.size} class_output_llk {K}")
         refs = kaldi_io.read_vec_int_table(o.ref_rspecifier) if o.ref_rspecifier else {}
@@ -176,7 +226,7 @@ def main(argv=None) -> int:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
             feeder.set_pipeline(pipe.stages)
-        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0)
+        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0, ctm=0)
         scores = open(o.scores_out, "w") if o.scores_out else None
         lib = _lib.load()
 
@@ -201,6 +251,7 @@ def main(argv=None) -> int:
                                              lm=lm, lm_weight=o.lm_weight, insertion_bonus=o.insertion_bonus, lm_eos=o.lm_eos, lexicon=lex,
                                              word_bonus=o.word_bonus)
             lm_score, words, words_len, word_ends = ctc.lm_score, ctc.words, ctc.words_len, ctc.word_ends
+            stamps = ctc.DecodeStamps(lens, out, is_log=log_pri is not None, conf_scale=o.conf_scale) if ctm is not None else None
             for s, (key, m) in enumerate(group):
                 frames = int(lens[s])
                 if math.isnan(score[s, 0]):
@@ -227,6 +278,19 @@ def main(argv=None) -> int:
                     ref, best, err = np.ascontiguousarray(word_refs[key], np.int32), np.ascontiguousarray(words[s, 0, :words_len[s, 0]], np.int32), C.c_int(0)
                     _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
                     n["word_err"] += err.value; n["word_ref"] += int(ref.size); n["word_scored"] += 1
+                if ctm is not None:       # the best hypothesis' words: a label each without a lexicon
+                    if math.isnan(stamps.word_conf[s, 0, 0]):
+                        raise RuntimeError(f"the forward pass of {key} timed out on the device: no time stamps")
+                    ids = words[s, 0, :words_len[s, 0]] if lex is not None else hyps[s][0]
+                    for j, w in enumerate(ids):
+                        b, e = int(stamps.word_start[s, 0, j]), int(stamps.word_end[s, 0, j])
+                        if b < 0:             # (a labelling too long to align)
+                            continue
+                        line = f"{key} 1 {o.frame_shift * b:.{o.ctm_precision}f} {o.frame_shift * (e - b):.{o.ctm_precision}f} {ctm_symbols.get(int(w), str(int(w)))}"
+                        if o.ctm_conf:
+                            line += f" {float(stamps.word_conf[s, 0, j]):.{o.ctm_precision}f}"
+                        ctm.write(line + "\n")
+                        n["ctm"] += 1
                 n["done"] += 1; n["frames"] += frames; n["score"] += float(score[s, 0])
                 n["empty"] += len(hyps[s][0]) == 0
                 if lm is not None:
@@ -252,6 +316,8 @@ def main(argv=None) -> int:
                 ends_writer.close()
         if scores:
             scores.close()
+        if ctm is not None:
+            ctm.close()
         if o.ref_rspecifier:
             log(f"{n['tok_err']} token errors on {n['tok_ref']} reference tokens of {n['scored']} utterances")
             log(f"\nTOKEN_ACCURACY >> {100.0 * (1.0 - n['tok_err'] / max(n['tok_ref'], 1)):g}% <<")
@@ -262,6 +328,8 @@ def main(argv=None) -> int:
             log(f"{n['dead']} utterances without a hypothesis")
         avg = n["score"] / n["frames"] if n["frames"] else 0.0
         tail = f"; average LM log-probability per {'word' if lex is not None else 'label'} {(n['lm'] / n['labels'] if n['labels'] else 0.0):g}" if lm is not None else ""
+        if o.ctm_out:
+            tail += f"; {n['ctm']} CTM words"
         log(f"Done {n['done']} utterances, {n['empty']} empty hypotheses; average log-probability per frame {avg:g}{tail}")
         return 0 if n["done"] else 255
     except Exception as e:

@@ -496,6 +496,42 @@ int eesen_ctc_decode_parallel_words(eesen_ctc_t* ctc, const int* frame_num_utt, 
                                     int* word_host /*S*nbest*T or NULL*/, int* word_len_host /*S*nbest or NULL*/,
                                     int* word_end_host /*S*nbest*T or NULL*/);
 
+/* ---- time stamps and confidences of decoded hypotheses (INTEGRATION.md "Time stamps and CTM") --------------------------------------
+ * Aligns every entry the LAST decode call on this Ctc returned (any of the four calls above) to the frames and says when each label
+ * and each word was spoken and how sure the N-best list is of the word.  frame_num_utt, S, scores_dev, rows, K, ld, is_log: that
+ * call's.  Each entry's labels are aligned on the acoustic scores alone by eesen_ctc_align_parallel's recurrence and tie rule (no LM
+ * term, no bonus: they do not depend on the frame) -- all S * nbest lattices in one sweep launch and one traceback launch per group
+ * of lattices (the delta rows of a group stay within 1 GiB), lattice i on the score rows of utterance i / nbest.
+ *   lstart_host / lend_host [S][nbest][T] int32: first frame of label u on the path and one past its last; blank frames belong to
+ *     no label; -1 beyond the labels.
+ *   words: a run of labels [a, b] -- every label by itself with its class as the id (plain, token LM), the runs between the spaces
+ *     with eesen_lex_words' ids (spaced lexicon; the space's frames belong to no word), the runs word_end_host gave (unspaced
+ *     lexicon).  wstart_host / wend_host [S][nbest][T] int32 = lstart[a], lend[b]: blanks inside a word are inside its interval.
+ *   wconf_host [S][nbest][T] float: eesen_word_confidence over the utterance's returned entries and their totals (score_host).
+ *   path_score_host [S][nbest]: the best path's log-score.
+ * Any output pointer may be NULL.  Conventions: the empty hypothesis has no lattice and no words, path score 0; an entry of more than
+ * 2047 labels (L' > 4096) has path score -1e30 and -1 stamps (its words: empty intervals, confidence 0); ranks beyond the returned
+ * count have -1 stamps, path score -1e30 and confidence -1e30, as have the slots beyond an entry's labels / words.  Under a raised
+ * guard word (in the decode call or in this one): every stamp -1, path scores and confidences NaN.
+ * EESEN_ERR_STATE: no decode call yet, or S, rows or frame_num_utt differ from the last decode call's.  EESEN_ERR_INVALID: ld < K, a
+ * non-finite or negative conf_scale.  The lattice buffers are borrowed as by eesen_ctc_align_parallel.  The call waits for its results. */
+int eesen_ctc_decode_stamps(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld, int is_log,
+                            double conf_scale, int* lstart_host /*S*nbest*T or NULL*/, int* lend_host /*S*nbest*T or NULL*/,
+                            int* wstart_host /*S*nbest*T or NULL*/, int* wend_host /*S*nbest*T or NULL*/, float* wconf_host /*S*nbest*T or NULL*/,
+                            float* path_score_host /*S*nbest or NULL*/);
+/* seconds of the last eesen_ctc_decode_stamps' device work: out[0]=lattice build (with the logarithm when is_log == 0), [1]=max-plus
+ * sweeps and tracebacks of all groups, [2]=stamps; summed over all calls since the last read under eesen_ctc_set_profiling(ctc, 2). */
+int eesen_ctc_get_stamp_times(eesen_ctc_t* ctc, float* out3);
+/* Test hook: sweep the lattices of eesen_ctc_decode_stamps in groups of `lattices` (0 = automatic: as many as 1 GiB of delta rows hold). */
+int eesen_ctc_set_stamp_group(eesen_ctc_t* ctc, int lattices);
+/* N-best posterior word confidences in fp64 on the host; no device work.  Entry i of n_entries has the total scores[i] and word_len[i]
+ * words (< 0: not an entry, skipped) with ids word_ids[i*stride + j] and frame intervals [wstart, wend).  With c = conf_scale (finite,
+ * >= 0): P_i = exp(c (z_i - z_max)) / sum_k exp(c (z_k - z_max)) over the entries, and
+ *   conf_out[i*stride + j] = sum_k P_k [entry k has a word of the same id whose interval intersects word j's]
+ * -- each entry counts at most once; -1e30 beyond an entry's words.  One entry gives 1 everywhere. */
+int eesen_word_confidence(int n_entries, const double* scores, const int* word_len, const int* word_ids, const int* wstart, const int* wend,
+                          int stride, double conf_scale, double* conf_out /*n_entries*stride*/);
+
 /* LevenshteinEditDistance (src/util/edit-distance-inl.h), total errors only: the count eesen_ctc_error_rate_mseq accumulates, for a
  * host that scores hypotheses of its own (ctc-decode --ref-rspecifier).  No device work. */
 int eesen_edit_distance(const int* ref, int num_ref, const int* hyp, int num_hyp, int* errors);

@@ -369,6 +369,7 @@ class Ctc {
     const int S = (int)frame_num_utt.size();
     const int T = S > 0 ? net_out.NumRows() / S : 0;
     if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
+    last_nbest_ = nbest;
     std::vector<int32> hyp((size_t)S * nbest * T + 1), len((size_t)S * nbest + 1);
     std::vector<BaseFloat> sc((size_t)S * nbest + 1);
     HipCheck(eesen_ctc_decode_parallel(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
@@ -392,6 +393,7 @@ class Ctc {
     const int S = (int)frame_num_utt.size();
     const int T = S > 0 ? net_out.NumRows() / S : 0;
     if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
+    last_nbest_ = nbest;
     std::vector<int32> hyp((size_t)S * nbest * T + 1), len((size_t)S * nbest + 1);
     std::vector<BaseFloat> sc((size_t)S * nbest + 1), lsc((size_t)S * nbest + 1);
     HipCheck(eesen_ctc_decode_parallel_lm(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
@@ -432,6 +434,7 @@ class Ctc {
     const int S = (int)frame_num_utt.size();
     const int T = S > 0 ? net_out.NumRows() / S : 0;
     if (!guarded_ && LastNet()) { HipCheck(eesen_ctc_set_guard(h_, LastNet())); guarded_ = true; }
+    last_nbest_ = nbest;
     std::vector<int32> hyp((size_t)S * nbest * T + 1), len((size_t)S * nbest + 1), wrd((size_t)S * nbest * T + 1), wlen((size_t)S * nbest + 1);
     std::vector<BaseFloat> sc((size_t)S * nbest + 1), lsc((size_t)S * nbest + 1);
     std::vector<int32> wend(lexicon.Unspaced() ? (size_t)S * nbest * T + 1 : 1);
@@ -466,6 +469,44 @@ class Ctc {
         if (lm_scores) (*lm_scores)[s].push_back(lsc[e]);
       }
   }
+  /* Time stamps and confidences of the entries the LAST DecodeParallel returned (any overload), eesen_ctc_decode_stamps: every entry is
+   * aligned on the acoustic scores by AlignParallel's recurrence and tie rule, all of them in one launch.  frame_num_utt, net_out,
+   * is_log: that call's; hyps: what it returned.  Per utterance s and returned entry i: label_start / label_end [labels] the frames
+   * [start, end) of every label; word_start / word_end / word_conf [words] the frames of every word (a label, a run between spaces, or
+   * a run up to a word end, by the call's kind) and its N-best posterior with conf_scale on the totals; path_score the best path's
+   * log-score (0 for the empty labelling). */
+  struct Stamps {
+    std::vector<std::vector<std::vector<int32> > > label_start, label_end, word_start, word_end;
+    std::vector<std::vector<std::vector<BaseFloat> > > word_conf;
+    std::vector<std::vector<BaseFloat> > path_score;
+  };
+  void DecodeStamps(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out,
+                    const std::vector<std::vector<std::vector<int32> > >& hyps, Stamps* out, bool is_log = false, double conf_scale = 1.0) {
+    const int S = (int)frame_num_utt.size(), nbest = last_nbest_;
+    const int T = S > 0 ? net_out.NumRows() / S : 0;
+    const size_t n = (size_t)S * nbest * T + 1;
+    std::vector<int32> ls(n), le(n), ws(n), we(n);
+    std::vector<BaseFloat> wc(n), ps((size_t)S * nbest + 1);
+    HipCheck(eesen_ctc_decode_stamps(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                     is_log ? 1 : 0, conf_scale, ls.data(), le.data(), ws.data(), we.data(), wc.data(), ps.data()));
+    out->label_start.assign(S, std::vector<std::vector<int32> >());
+    out->label_end = out->word_start = out->word_end = out->label_start;
+    out->word_conf.assign(S, std::vector<std::vector<BaseFloat> >());
+    out->path_score.assign(S, std::vector<BaseFloat>());
+    for (int s = 0; s < S && s < (int)hyps.size(); ++s)
+      for (int i = 0; i < nbest && i < (int)hyps[s].size(); ++i) {
+        const size_t e = ((size_t)s * nbest + i) * T;
+        const size_t nl = hyps[s][i].size() < (size_t)T ? hyps[s][i].size() : (size_t)T;
+        size_t nw = 0;
+        while (nw < (size_t)T && wc[e + nw] != -1e30f) ++nw;   /* -1e30 beyond the entry's words */
+        out->label_start[s].push_back(std::vector<int32>(ls.data() + e, ls.data() + e + nl));
+        out->label_end[s].push_back(std::vector<int32>(le.data() + e, le.data() + e + nl));
+        out->word_start[s].push_back(std::vector<int32>(ws.data() + e, ws.data() + e + nw));
+        out->word_end[s].push_back(std::vector<int32>(we.data() + e, we.data() + e + nw));
+        out->word_conf[s].push_back(std::vector<BaseFloat>(wc.data() + e, wc.data() + e + nw));
+        out->path_score[s].push_back(ps[(size_t)s * nbest + i]);
+      }
+  }
   void SetReportStep(int32 s) { report_step_ = s; }
   void SetFramesPerSec(float f) { frames_per_sec_ = f; }
   float NumErrorTokens() const { long e = 0; HipCheck(eesen_ctc_stats(h_, NULL, NULL, NULL, &e, NULL)); return (float)e; }   /* ctc-loss.h:62 */
@@ -491,6 +532,7 @@ class Ctc {
   std::vector<int> ids_, off_;
   std::string seq_out_;
   bool guarded_ = false;
+  int32 last_nbest_ = 1;   /* of the last DecodeParallel: the row count of DecodeStamps' arrays */
 };
 
 /* eesen::CE (src/net/ce-loss.h:32-77): frame-level cross-entropy, one fused pass on the device (eesen_ce_eval_parallel) fed by
