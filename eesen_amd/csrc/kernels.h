@@ -98,6 +98,11 @@ struct LstmLayerDev {
   // while the recurrence is still running (net.cpp: "the middle first")
   unsigned* milestone = nullptr;
   int milestone_step = 0;
+  // row guards of the narrow forward persistent kernel (lstm_fwd_persistent_bf_guard_kernel, RecPlan::fn_guard; null / -1: none): rows
+  // of G that another stream is still computing when the kernel is launched.  Before any workgroup touches the gate rows of step
+  // guard_step[i] (>= 2) it waits until *guard[i] != 0; the host sets the word behind the GEMM that writes those rows (net.cpp: "only the needed quadrants first")
+  const unsigned* guard[2] = {nullptr, nullptr};
+  int guard_step[2] = {-1, -1};
   // kernel selection switches (tuning.h; all 1 in production): XCD-aware role map, time-multiplexed forward kernel, 4 x 32 and
   // K-split backward tiles
   int xcd_map = 1, fwd_mux = 1, bwd_q4 = 1, bwd_ksplit = 1, bwd_mux = 1;
@@ -178,6 +183,7 @@ struct RecPlan {
   size_t ctl_words = 0;       // arrival-counter words one launch clears (at most kCtlHalf)
   int chunk = 0;
   const void* fn = nullptr;
+  const void* fn_guard = nullptr;   // forward: the same tile with the row guards of LstmLayerDev::guard, where that instantiation exists (launched when a guard is set)
 };
 RecPlan lstm_fwd_plan(const LstmLayerDev& L);
 RecPlan lstm_bwd_plan(const LstmLayerDev& L);

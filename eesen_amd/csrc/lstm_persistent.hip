@@ -147,6 +147,26 @@ __device__ __forceinline__ bool wait_counters(unsigned* cnt, unsigned nblk, unsi
   return false;
 }
 
+// LstmLayerDev::guard: rows of G that a GEMM on another stream is still writing when this kernel starts.  The host sets the word
+// (a 4-byte fill on that stream, i.e. behind the GEMM's end-of-kernel write-back) and the polling wave waits for it here with the
+// load, the bounded spin and the error-word path of wait_counters (about a second of polls at the default spin limit, tenfold
+// under a communicator; no wall-clock reading beside it).  The stale-line argument of the header holds for the guarded rows: a row
+// of G starts on a 128-byte line (the plan takes this path only where 4H floats are a whole number of 256-float tiles, so each
+// direction's columns of a row are whole lines too), and no workgroup of this launch has touched a guarded line before the word is
+// seen -- the check for step g sits in front of step g - 1 (between two segments of the time loop), followed by a barrier, and the
+// gate rows of step g are prefetched at the end of step g - 1 --, so neither an L1 nor an L2 can hold an older copy.  A guard that
+// gives up raises the error word with the value 3 (net.cpp: check_device_error) and the workgroup leaves, like one whose peers
+// never arrived.
+__device__ __forceinline__ bool wait_guard(const unsigned* word, unsigned* err, int spin_limit, int lane) {
+  for (int spins = 0; spins < spin_limit; ++spins) {
+    if (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return true;
+    if ((spins & 1023) == 1023 && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return false;
+    __builtin_amdgcn_s_sleep(EESEN_POLL_SLEEP);
+  }
+  if (lane == 0) __hip_atomic_store(err, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return false;
+}
+
 // Two workgroups (two CUs) hand a counter back and forth `rounds` times with the same agent-scope relaxed atomics the hand-off
 // uses; out[0] = wall-clock ticks (10 ns) of the whole exchange.  One round = two flights (A's store becomes visible to B's poll, B's to A's).
 __global__ __launch_bounds__(64) void handoff_pingpong_kernel(unsigned* flags, unsigned long long* out, int rounds) {
@@ -424,9 +444,10 @@ __device__ __forceinline__ unsigned rne_bf16(float x) {   // round-to-nearest-ev
 // lane i of every quad receives lane i ^ 1 / i ^ 2 (DPP quad_perm: a VALU move, where __shfl_xor goes through the LDS crossbar)
 __device__ __forceinline__ unsigned quad_xor1(unsigned v) { return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, true); }
 __device__ __forceinline__ unsigned quad_xor2(unsigned v) { return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, true); }
-template <int CPW, int NT, int AP, int WP, bool F16 = false>
-__global__ __launch_bounds__(NW * 64) void lstm_fwd_persistent_bf_kernel(LstmLayerDev L, unsigned* cnt, unsigned* err,
-                                                                         int spin_limit, unsigned long long* trace, Role R) {
+// GUARD: the instantiation with the row guards (lstm_fwd_persistent_bf_guard_kernel below); the plain kernel has none of their code
+template <int CPW, int NT, int AP, int WP, bool F16, bool GUARD>
+__device__ __forceinline__ void lstm_fwd_bf_body(const LstmLayerDev& L, unsigned* cnt, unsigned* err, int spin_limit, unsigned long long* trace,
+                                                 const Role& R) {
   constexpr int ST = 16, UB = 4 * NT, RW = 16 * NT + 4, SMAX = (AP > WP ? AP : WP) - 1;
   constexpr float kMScale = 16384.f;   // F16: m_t travels times 2^14
   __shared__ __attribute__((aligned(16))) float red[NW][ST][RW];
@@ -509,108 +530,49 @@ __global__ __launch_bounds__(NW * 64) void lstm_fwd_persistent_bf_kernel(LstmLay
   const int zt = (L.s_begin / ST) + bz;
   const int nzall = (S + ST - 1) / ST;
   unsigned char* const xbytes = reinterpret_cast<unsigned char*>(L.X);
+  // GUARD: the time loop in three segments with the row guards (wait_guard) BETWEEN them, so that the loop itself carries nothing of
+  // them (in the loop, two compares per step and the rarely taken wait cost 70-300 ns per step: the instantiations sit at the scalar
+  // file's limit).  Step g is the first to read guarded rows, and its gate rows are prefetched at the end of step g - 1: the wait
+  // sits in front of step g - 1.  The host sets both guards, 2 <= guard_step[0] <= guard_step[1] < T.
+  if constexpr (!GUARD) {
   for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
-    const int tp = dir == 0 ? t - 1 : t + 1;
-    f32x4 acc[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-    EESEN_STAMP(0);
-    if (step > 0) {
+#include "lstm_fwd_bf_step.inc"
+  }
+  } else {
+  int step0 = 0;
+#pragma unroll 1
+  for (int seg = 0; seg < (GUARD ? 3 : 1); ++seg) {
+  int send = T;
+  if constexpr (GUARD) {
+    if (seg < 2) send = min(max(L.guard_step[seg] - 1, step0), T);
+    if (seg > 0) {
       if (wave == EESEN_POLL_WAVE) {
-        const bool go = wait_counters(my_cnt, nblk, (unsigned)step, err, spin_limit, lane, L.poll_delay);
+        const bool go = wait_guard(L.guard[seg - 1], err, spin_limit, lane);
         if (lane == 0) s_go = go ? 1 : 0;
       }
       __syncthreads();
       if (!s_go) return;
-      EESEN_STAMP(1);
-      if (L.milestone && step == L.milestone_step + 1 && bx == 0 && tid == 0)
-        report_milestone(L.milestone, (unsigned)(R.ndir * R.nz));
-      const unsigned xb = ((unsigned)(tp * L.ndir + dir) * (unsigned)nzall + (unsigned)zt) * xblk;
-      constexpr unsigned kOob = 0x80000000u;
-      const bool rok = s0 + li < s_end;
-      f32x4 a[AP][CPW];
-#pragma unroll
-      for (int pl = 0; pl < AP; ++pl)
-#pragma unroll
-        for (int c = 0; c < CPW; ++c) {
-          const int ch = wave + c * NW;
-          a[pl][c] = __builtin_amdgcn_raw_buffer_load_b128(rX, (rok && ch < nch) ? xb + (unsigned)pl * xpl + (unsigned)(((ch * 4 + kq) * 16 + li) * 16) : kOob, 0, 0);
-        }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int sum = SMAX; sum >= 0; --sum)      // the smallest cross products first
-#pragma unroll
-        for (int i = 0; i < AP; ++i) {
-          const int j = sum - i;
-          if (j < 0 || j >= WP) continue;
-#pragma unroll
-          for (int c = 0; c < CPW; ++c)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-              const f32x4& bb = b[j < WP && j >= 0 ? j : 0][n][c];
-              if constexpr (F16) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a[i][c]), __builtin_bit_cast(f16x8_t, bb), acc[n], 0, 0, 0);
-              else acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[i][c]), __builtin_bit_cast(bf16x8_t, bb), acc[n], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int n = 0; n < NT; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) red[wave][4 * kq + r][n * 16 + li] = F16 ? acc[n][r] * unscale : acc[n][r];
-    __syncthreads();
-    EESEN_STAMP(2);
-    if (e_act) {
-      // the eight waves' partial sums: ALL eight LDS reads in flight, then the sum in the same order (hipcc kept two in flight and
-      // waited for each in turn: eight ~100-cycle round trips on the step's critical path)
-      float4 pv[NW];
-#pragma unroll
-      for (int w = 0; w < NW; ++w) pv[w] = *reinterpret_cast<const float4*>(&red[w][es][eu * 4]);
-      __builtin_amdgcn_sched_barrier(0);
-      float4 pre = gx;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { pre.x += pv[w].x; pre.y += pv[w].y; pre.z += pv[w].z; pre.w += pv[w].w; }
-      float g = tanhf_(pre.x);
-      float i = sigmoidf_(pre.y + p_i * cprev);
-      float f = sigmoidf_(pre.z + p_f * cprev);
-      float c = g * i + cprev * f;
-      float h = tanhf_(c);
-      float o = sigmoidf_(pre.w + p_o * c);
-      float m = h * o;
-      if (t >= len || !e_ok) { g = i = f = o = c = m = 0.f; }
-      if (e_ok) {
-        *reinterpret_cast<float4*>(L.G + (size_t)(t * S + s_e) * ldG + gcol) = make_float4(g, i, f, o);
-        const size_t o1 = (size_t)((t + 1) * S + s_e) * ldY + dir * H + u0 + eu;
-        L.C[o1] = c;
-        __hip_atomic_store(L.Y + o1, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        cprev = c;
-      }
-      // the AP planes of m: four adjacent units -> one 8-byte word per plane (a single 8-byte store is single-copy atomic; write-through)
-      const int k = u0 + eu;
-      const size_t xo = ((size_t)(t * L.ndir + dir) * nzall + zt) * (size_t)xblk +
-                        (size_t)((((k >> 5) * 4 + ((k & 31) >> 3)) * 16 + es) * 16 + (k & 7) * 2);
-      float rem = F16 ? m * kMScale : m;
-#pragma unroll
-      for (int pl = 0; pl < AP; ++pl) {
-        const unsigned hb = F16 ? rne_f16(rem) : rne_bf16(rem);
-        rem -= F16 ? f16_bits_to_f32(hb) : __uint_as_float(hb << 16);          // exact
-        const unsigned pk = hb | (quad_xor1(hb) << 16);                        // valid in even lanes: (unit eu, eu + 1)
-        const unsigned pk2 = quad_xor2(pk);                                     // lanes eu % 4 == 0: the pair of (eu + 2, eu + 3)
-        if (e_ok && (eu & 3) == 0)
-          __hip_atomic_store(reinterpret_cast<unsigned long long*>(xbytes + xo + (size_t)pl * xpl), (unsigned long long)pk | ((unsigned long long)pk2 << 32),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    EESEN_STAMP(3);
-    {
-      if (e_act) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      EESEN_STAMP(4);
-      if (tid == 0) __hip_atomic_fetch_add(my_cnt + (bx & (kShards - 1)) * kShardStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (e_ok && step + 1 < T)
-        gx = *reinterpret_cast<const float4*>(L.G + (size_t)((dir == 0 ? t + 1 : t - 1) * S + s_e) * ldG + gcol);
     }
   }
+  for (int step = step0; step < send; ++step) {
+#include "lstm_fwd_bf_step.inc"
+  }
+  step0 = send;
+  }
+  }
+}
+
+template <int CPW, int NT, int AP, int WP, bool F16 = false>
+__global__ __launch_bounds__(NW * 64) void lstm_fwd_persistent_bf_kernel(LstmLayerDev L, unsigned* cnt, unsigned* err,
+                                                                         int spin_limit, unsigned long long* trace, Role R) {
+  lstm_fwd_bf_body<CPW, NT, AP, WP, F16, false>(L, cnt, err, spin_limit, trace, R);
+}
+// The same tile with the row guards of LstmLayerDev::guard, a kernel of its own: the layer passes that set no guard (layer 0, every
+// fall-back, EESEN_FWD_QUAD=0) run a kernel without the segments and the waits between them.  The narrow tiles only: the schedule that sets guards needs room for a GEMM workgroup beside the grid (RecPlan::leaves_room).
+template <int CPW, int NT, int AP, int WP, bool F16 = false>
+__global__ __launch_bounds__(NW * 64) void lstm_fwd_persistent_bf_guard_kernel(LstmLayerDev L, unsigned* cnt, unsigned* err,
+                                                                               int spin_limit, unsigned long long* trace, Role R) {
+  lstm_fwd_bf_body<CPW, NT, AP, WP, F16, true>(L, cnt, err, spin_limit, trace, R);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2069,6 +2031,13 @@ const RecKernel kRecKernels[] = {
     EESEN_ROW(kBwdKsplitMux, kRecBwdKsplitMux, lstm_bwd_persistent_ksplit_mux_kernel, 2), EESEN_ROW(kBwdKsplitMux, kRecBwdKsplitMux, lstm_bwd_persistent_ksplit_mux_kernel, 3),
     EESEN_ROW(kBwdKsplitMux, kRecBwdKsplitMux, lstm_bwd_persistent_ksplit_mux_kernel, 4),
 };
+// The guarded siblings of the narrow bf16-pipe rows (same arguments, RecPlan::fn_guard).  Not rows of the table above: a plan never
+// NAMES one -- it names the plain row, whose step text (lstm_fwd_bf_step.inc) they share word for word -- and what holds them is not
+// the per-row fp64 cases of tests/recurrence_cases.py but tests/test_gpu_fwd_quadrants.py, bit for bit against the plain rows.
+const RecKernel kRecGuardKernels[] = {
+    EESEN_ROW(kFwdBfGuard, kRecFwdBf, lstm_fwd_persistent_bf_guard_kernel, 1,2,2,2,true), EESEN_ROW(kFwdBfGuard, kRecFwdBf, lstm_fwd_persistent_bf_guard_kernel, 2,2,2,2,true),
+    EESEN_ROW(kFwdBfGuard, kRecFwdBf, lstm_fwd_persistent_bf_guard_kernel, 1,2,3,3,false), EESEN_ROW(kFwdBfGuard, kRecFwdBf, lstm_fwd_persistent_bf_guard_kernel, 2,2,3,3,false),
+};
 #undef EESEN_BWD_Q4
 #undef EESEN_BWD_GEN
 #undef EESEN_FWD_BF
@@ -2080,6 +2049,8 @@ const RecKernel kRecKernels[] = {
 const RecKernel* rec_kernel(int family, int a0, int a1, int a2, int a3, int a4) {
   const int want[5] = {a0, a1, a2, a3, a4};
   for (const RecKernel& k : kRecKernels)
+    if (k.family == family && std::equal(want, want + 5, k.arg)) return &k;
+  for (const RecKernel& k : kRecGuardKernels)
     if (k.family == family && std::equal(want, want + 5, k.arg)) return &k;
   return nullptr;
 }

@@ -241,8 +241,13 @@ void Net::check_device_error(bool consumer) {
   // 2: only the side stream's wait for a forward milestone gave up (wait_for_word: something lets one kernel run at a time and ran the
   // waiter before the recurrence it waits for -- a counter-collecting profiler).  The early GEMM may have read unfinished rows:
   // the step is lost like any other, but the cure is to stop starting GEMMs early, not to give up the persistent kernels.
+  // 3: only a row guard of a forward recurrence gave up (wait_guard: the side stream's quadrants of its gate inputs did not arrive --
+  // the same tools, or a device on which the side stream's GEMM never became resident beside the grid).  Again the step is lost and the
+  // cure is the schedule's: every gate row in front of the recurrence from here on (EESEN_FWD_QUAD=0), for the rest of this Net's life.
   const bool only_waiter = e == 2 && tn.fwd_mid;
+  const bool only_guard = e == 3 && tn.fwd_quad;
   if (only_waiter) tn.fwd_mid = 0;
+  else if (only_guard) tn.fwd_quad = 0;
   else { persistent = 0; gate_fwd = false; overlap = false; }
   ++recoveries;
   const int lost = std::max(1, steps_since_clean);
@@ -255,6 +260,10 @@ void Net::check_device_error(bool consumer) {
   if (only_waiter)
     fprintf(stderr, "WARNING (eesen_hip) the side stream's wait for a forward-recurrence milestone gave up (kernels serialised by a tool?): "
                     "%d minibatch(es) in flight %s%s; continuing without the early input GEMM (EESEN_FWD_MID=0)\n", lost, what,
+            rerun ? " and the last forward pass is re-run" : "");
+  else if (only_guard)
+    fprintf(stderr, "WARNING (eesen_hip) a forward recurrence gave up waiting for gate-input rows from the side stream (kernels serialised by a tool?): "
+                    "%d minibatch(es) in flight %s%s; continuing with every gate-input row in front of its recurrence (EESEN_FWD_QUAD=0)\n", lost, what,
             rerun ? " and the last forward pass is re-run" : "");
   else
     fprintf(stderr, "WARNING (eesen_hip) a persistent recurrence kernel gave up waiting for a peer workgroup (GPU shared or preempted?): "
@@ -685,6 +694,47 @@ void Net::propagate(const float* in, int nrows, int ld, bool is_device) {
   forward_pass();
 }
 
+// What may run of the NEXT layer's input GEMM while LSTM layer li's forward recurrence (plan fp) is still stepping: see forward_pass,
+// where the two forms are described.
+Net::FwdEarly Net::fwd_early(int li, const RecPlan& fp, int T) const {
+  FwdEarly E;
+  const Layer& L = layers[li];
+  const Layer* nxt = li + 1 < (int)layers.size() ? &layers[li + 1] : nullptr;
+  const int nd = L.ndir, ldY = nd * L.H;
+  const long rows = (long)T * S;
+  const bool pers = fp.kind != kRecNone;
+  E.gate = pers && overlap && gate_fwd && !fwd_bf16 && !L.cur_fwd_drop && fp.units <= 8 && nxt && nxt->is_lstm() && T >= 2 && rows >= 128 &&
+           fp.one_window &&
+           (nxt->ndir * 4 * nxt->H) % 128 == 0 && ldY % 16 == 0 && nd * fp.seq_tiles * kShards <= 64;
+  E.mile_step = (3 * T) / 4;   // measured at cfg2, same box: 60 % 39.4, 67 % 38.7, 75 % 38.2, 82 % 38.85, 88 % 38.8, off 39.0 ms
+  E.mid = pers && overlap && tn.fwd_mid && !E.gate && !L.cur_fwd_drop && fp.leaves_room && nd == 2 && nxt && nxt->is_lstm() &&
+          T >= 32 && E.mile_step + 1 < T && fp.one_window;
+  if (E.mid) {
+    // whole 256-row tiles: the two ends (main stream, critical path) keep the GEMM's 256 x 256 flavour; the middle part takes the
+    // 128 x 128 flavour (256 threads), which shares a CU with the recurrence far better.  Measured at cfg2, same box, three runs
+    // each: off 38.45; unaligned split (all parts small) 37.6-38.0; aligned, middle big 38.1-38.6; aligned, middle small 37.55-37.7 ms
+    E.r0 = ((T - 1 - E.mile_step) * S + 255) / 256 * 256;
+    E.r1 = (E.mile_step + 1) * S / 256 * 256;
+    if (E.r1 <= E.r0) E.r0 = E.r1 = 0;
+  }
+  return E;
+}
+
+// "Only the needed quadrants first" (forward_pass): LSTM layer li, whose gate rows [r0, r1) the side stream computes early, starts its
+// recurrence (plan fp) behind the rows [0, r0) of its forward columns and [r1, rows) of its backward columns alone.  steps[0]: the
+// first step of either chain that reads a middle row, steps[1]: ... a row of the two quadrants that follow on the side stream.
+bool Net::fwd_quad_rule(int li, const RecPlan& fp, int T, int r0, int r1, int steps[2]) const {
+  steps[0] = steps[1] = -1;
+  if (!tn.fwd_quad || li < 1 || r1 <= r0 || r0 <= 0 || (long)r1 >= (long)T * S) return false;
+  const Layer& L = layers[li];
+  // the kernel with the row guard, the whole batch in one launch, room for the side stream's GEMM workgroups on its CUs (a guard
+  // whose GEMM cannot become resident beside the grid would wait for nothing), each direction's columns whole 256-column tiles
+  if (L.ndir != 2 || fp.kind != kRecFwdBf || !fp.fn_guard || !fp.one_window || !fp.leaves_room || (4 * L.H) % 256 != 0) return false;
+  steps[0] = std::min(r0 / S, T - 1 - (r1 - 1) / S);     // forward chain: frame t = step, rows [t S, (t + 1) S); backward: t = T - 1 - step
+  steps[1] = std::min(r1 / S, T - 1 - (r0 - 1) / S);
+  return steps[0] >= 2 && steps[1] >= steps[0];   // (the kernel checks at the top of the step before, and step 0 has no wait)
+}
+
 // the layer chain of Net::Propagate on the input already in HBM (also the re-run after a timed-out persistent kernel)
 void Net::forward_pass() {
   const float* x = input.p;
@@ -722,8 +772,56 @@ void Net::forward_pass() {
       EESEN_HIP_CHECK(hipMemsetAsync(L.C.p + (size_t)(T + 1) * S * ldY, 0, blk, st));
       EESEN_HIP_CHECK(hipMemsetAsync(L.Y.p + (size_t)(T + 1) * S * ldY, 0, blk, st));
       prepare_dropout(*this, L);
+      // The ONE forward plan of this layer pass: what runs the recurrence, and what may run beside it.  (A shape without a persistent
+      // tile -- kRecNone, the per-step kernels -- gets neither early form of the next layer's input GEMM.)
+      LstmLayerDev v = lstm_view(*this, L, T);
+      const RecPlan fp = persistent ? lstm_fwd_plan(v) : RecPlan{};
+      const bool pers = fp.kind != kRecNone;
+      int quad_steps[2];
+      const bool quad = !g_gated && fwd_quad_rule(li_, fp, T, mid_r0, mid_r1, quad_steps);
       // all gate pre-activations of both directions in one GEMM: G = x * Wx^T + bias  (:109-110, :163-164)
-      if (g_gated) {  // already computed on the side stream, gated on the previous layer's progress (see below)
+      if (quad) {
+        // ONLY THE NEEDED QUADRANTS FIRST.  The forward chain walks t = 0 -> T-1 and reads the forward gate columns [0, 4H) of G alone,
+        // the backward chain T-1 -> 0 and the columns [4H, 8H): of the two ends the middle-first schedule leaves to this stream, the
+        // recurrence needs rows [0, r0) x forward columns and [r1, rows) x backward columns to start, the other two quadrants only
+        // three quarters of the way through -- some 2 ms later at the headline shape -- and the middle rows a quarter of the way
+        // through.  So the main stream runs the first two (the same GEMM with offset C / W / bias pointers and N = 4H) and launches
+        // the recurrence WITHOUT waiting for the side stream; the side stream, behind the middle, sets guard word A, runs the other
+        // two quadrants (128 x 128 flavour: beside the narrow forward tile, where the side stream otherwise idles in its milestone
+        // wait) and sets word B.  The kernel waits for A / B in front of the first step that reads such a row (LstmLayerDev::guard).
+        // The words live in the region of `mile` that the layer below cleared before its own recurrence, i.e. before the side stream
+        // could set them.  Same kernels, same dot products per element: bit-identical to the other schedules.
+        unsigned* gw = mile.p + ((li_ - 1) & 1) * kMileRegion + kGuardWord;
+        const int N4 = 4 * H;
+        const float* Wx = params.p + L.p_off + L.off_wx;
+        const float* bias = params.p + L.p_off + L.off_bias;
+        GemmBound w_hi = w_amax;   // (one word per row of W_x: the backward direction's start 4H further on)
+        if (w_hi.p && w_hi.per_index) w_hi.p += N4;
+        const int ti_ = timer.begin(st, 0);
+        gemm_f32(st, true, true, mid_r0, N4, L.din, 1.f, x, ldx, Wx, pad4(L.din), 0.f, L.G.p, ldG, bias, nullptr, 0, 0, fwd_bf16, x_amax, w_amax);
+        gemm_f32(st, true, true, rows - mid_r1, N4, L.din, 1.f, x + (size_t)mid_r1 * ldx, ldx, Wx + (size_t)N4 * pad4(L.din), pad4(L.din), 0.f,
+                 L.G.p + (size_t)mid_r1 * ldG + N4, ldG, bias + N4, nullptr, 0, 0, fwd_bf16, x_amax, w_hi);
+        timer.end(st, ti_);
+        // the recurrence below is through (every row of x is final) AND the two quadrants above are: the late ones start with the
+        // recurrence, not beside the GEMMs it waits for (started at once they cost those 70 of their 240 us: profiles/fwd_quad_ab.md)
+        EESEN_HIP_CHECK(hipEventRecord(ev_quad_go, st));
+        EESEN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gw), 1, 1, st2));       // A: behind the middle GEMM
+        EESEN_HIP_CHECK(hipStreamWaitEvent(st2, ev_quad_go, 0));
+        // the 128 x 128 flavour, capped at one workgroup per CU as the backward pass's side-stream GEMMs are (EESEN_SIDE_LDS_KB);
+        // EESEN_FWD_QUAD=2: uncapped, with the token of extra LDS the middle GEMM passes (the losing A/B arm of DESIGN.md section 9)
+        const int late_lds = tn.fwd_quad == 2 ? 64 : (tn.side_lds_kb >= 0 ? tn.side_lds_kb : (gemm_mode() >= 1 ? 48 : 32)) * 1024;
+        const int tj_ = timer.begin(st2, 0);
+        gemm_f32(st2, true, true, rows - mid_r1, N4, L.din, 1.f, x + (size_t)mid_r1 * ldx, ldx, Wx, pad4(L.din), 0.f, L.G.p + (size_t)mid_r1 * ldG, ldG,
+                 bias, nullptr, 0, late_lds, fwd_bf16, x_amax, w_amax);
+        gemm_f32(st2, true, true, mid_r0, N4, L.din, 1.f, x, ldx, Wx + (size_t)N4 * pad4(L.din), pad4(L.din), 0.f, L.G.p + N4, ldG, bias + N4,
+                 nullptr, 0, late_lds, fwd_bf16, x_amax, w_hi);
+        timer.end(st2, tj_);
+        EESEN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(gw + 1), 1, 1, st2));   // B: behind the two late quadrants
+        EESEN_HIP_CHECK(hipEventRecord(ev_quad_done, st2));
+        v.guard[0] = gw; v.guard_step[0] = quad_steps[0];
+        v.guard[1] = gw + 1; v.guard_step[1] = quad_steps[1];
+        mid_r0 = mid_r1 = 0;
+      } else if (g_gated) {  // already computed on the side stream, gated on the previous layer's progress (see below)
         if (gated_rows < rows) {  // the last, partial row tile (T*S not a multiple of 128): its frames are the last to complete anyway
           const int ti_ = timer.begin(st, 0);
           gemm_f32(st, true, true, rows - gated_rows, ldG, L.din, 1.f, x + (size_t)gated_rows * ldx, ldx, params.p + L.p_off + L.off_wx,
@@ -751,17 +849,11 @@ void Net::forward_pass() {
       // The NEXT LSTM layer's input GEMM can run on the side stream WHILE this layer's persistent kernel is running:
       // its row tiles wait on the kernel's arrival counters and are visited middle-out in time (gemm_f32_nt_gated).
       Layer* nxt = (&L - layers.data()) + 1 < (long)layers.size() ? &layers[(&L - layers.data()) + 1] : nullptr;
-      // The ONE forward plan of this layer pass: what runs the recurrence, and what may run beside it.  (A shape without a persistent
-      // tile -- kRecNone, the per-step kernels -- gets neither early form of the next layer's input GEMM.)
-      LstmLayerDev v = lstm_view(*this, L, T);
-      const RecPlan fp = persistent ? lstm_fwd_plan(v) : RecPlan{};
-      const bool pers = fp.kind != kRecNone;
       // (with forward dropout the next layer reads the MASKED output, which exists only after the recurrence: no gating)
       // (the 16-unit tile of wide layers fills the register file -- 2 x 206 VGPRs per SIMD -- so spinning GEMM workgroups
       // could keep its cooperative kernel from becoming resident: no gating there)
-      const bool plan_gate = pers && overlap && gate_fwd && !fwd_bf16 && !L.cur_fwd_drop && fp.units <= 8 && nxt && nxt->is_lstm() && T >= 2 && rows >= 128 &&
-                             fp.one_window &&
-                             (nxt->ndir * 4 * nxt->H) % 128 == 0 && ldY % 16 == 0 && nd * fp.seq_tiles * kShards <= 64;
+      const FwdEarly early = fwd_early(li_, fp, T);
+      const bool plan_gate = early.gate;
       // The MIDDLE of the next layer's input GEMM under the END of this layer's recurrence.  A bidirectional layer has finished frame
       // t when its forward chain has passed step t and its backward chain step T-1-t: once both have published step m = 3T/4, the
       // frames [T-1-m, m] -- half of them -- are final, and the next layer's input GEMM for those rows runs on the side stream
@@ -771,9 +863,8 @@ void Net::forward_pass() {
       // the kernel never reports (per-step fallback, a kernel that gave up).  Narrow tiles only: beside the wide tiles (H = 1024)
       // no GEMM workgroup fits on a CU (section 9), the early part would only queue.  Same GEMM, same rows: results are
       // bit-identical to the one-launch GEMM (every output row is its own dot products).
-      const int mile_step = (3 * T) / 4;   // measured at cfg2, same box: 60 % 39.4, 67 % 38.7, 75 % 38.2, 82 % 38.85, 88 % 38.8, off 39.0 ms
-      const bool plan_mid = pers && overlap && tn.fwd_mid && !plan_gate && !L.cur_fwd_drop && fp.leaves_room && nd == 2 && nxt && nxt->is_lstm() &&
-                            T >= 32 && mile_step + 1 < T && fp.one_window;
+      const int mile_step = early.mile_step;
+      const bool plan_mid = early.mid;
       // (Round 3 built, and round 4 re-tried as a profiling arm, a COMMAND-PROCESSOR wait instead of the spinning waiter --
       // hipStreamWaitValue64 on signal memory.  It costs 2.2 ms per cfg2 step, and it is NOT immune to kernel-serialising tools, as
       // had been assumed: under `rocprofv3 --pmc` the run dead-locked for the whole 40 minutes of a GPU call (the tool holds the
@@ -783,10 +874,13 @@ void Net::forward_pass() {
       v.poll_delay = delay_fwd;
       v.poll_raw = poll_raw;
       if (plan_mid) {
-        mile.reserve(32);
-        EESEN_HIP_CHECK(hipMemsetAsync(mile.p, 0, 2 * sizeof(unsigned), st));
+        // this layer's region of `mile`: its milestone words and the row-guard words of the layer above (cleared here, in front of
+        // everything that may set them; the other region holds the guards this layer's own recurrence is about to wait on)
+        mile.reserve(2 * kMileRegion);
+        unsigned* region = mile.p + (li_ & 1) * kMileRegion;
+        EESEN_HIP_CHECK(hipMemsetAsync(region, 0, kMileRegion * sizeof(unsigned), st));
         EESEN_HIP_CHECK(hipEventRecord(ev_gate_reset, st));
-        v.milestone = mile.p;
+        v.milestone = region;
         v.milestone_step = mile_step;
       }
       if (pers) lstm_fwd_launch(st, fp, v, ctl.p, ctl.p + kCtlWords - 1, spin_limit, trace.p, plan_gate ? ev_gate_reset.get() : nullptr);
@@ -797,6 +891,9 @@ void Net::forward_pass() {
       ++info_lstm_layers;
       check_launch("lstm_fwd");
       timer.end(st, ti_);
+      // (nothing on this stream may overwrite or free what the side stream's quadrants read or write before they are through: they
+      // are by the time the recurrence passes guard word B, so this wait costs nothing)
+      if (quad) EESEN_HIP_CHECK(hipStreamWaitEvent(st, ev_quad_done, 0));
       if (pers && plan_gate) {
         const int ldG2 = nxt->ndir * 4 * nxt->H;
         nxt->G.reserve((size_t)rows * ldG2);
@@ -813,22 +910,18 @@ void Net::forward_pass() {
         g_gated = true;
       }
       if (plan_mid) {
-        EESEN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(mile.p + 1), 1, 1, st));   // released at the latest here
+        EESEN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(v.milestone + 1), 1, 1, st));   // released at the latest here
         const int ldG2 = nxt->ndir * 4 * nxt->H;
         nxt->G.reserve((size_t)rows * ldG2);
-        // whole 256-row tiles: the two ends (main stream, critical path) keep the GEMM's 256 x 256 flavour; the middle part takes the
-        // 128 x 128 flavour (256 threads), which shares a CU with the recurrence far better.  Measured at cfg2, same box, three runs
-        // each: off 38.45; unaligned split (all parts small) 37.6-38.0; aligned, middle big 38.1-38.6; aligned, middle small 37.55-37.7 ms
-        mid_r0 = ((T - 1 - mile_step) * S + 255) / 256 * 256;
-        mid_r1 = (mile_step + 1) * S / 256 * 256;
-        if (mid_r1 <= mid_r0) mid_r0 = mid_r1 = 0;
+        mid_r0 = early.r0;   // (whole 256-row tiles: fwd_early)
+        mid_r1 = early.r1;
       }
       if (plan_mid && mid_r1 > mid_r0) {
         const int ldG2 = nxt->ndir * 4 * nxt->H;
         EESEN_HIP_CHECK(hipStreamWaitEvent(st2, ev_gate_reset, 0));
         // bounded on the wall clock: 2 s for a recurrence of up to 1000 steps, longer for longer ones, tenfold under a communicator
         // (whose collectives may delay the recurrence's residency: set_comm raises spin_limit the same way)
-        wait_for_word(st2, mile.p + 1, 1u, ctl.p + kCtlWords - 1, 2.0 * std::max(1.0, T / 1000.0) * std::max(1.0, spin_limit / 400000.0));
+        wait_for_word(st2, v.milestone + 1, 1u, ctl.p + kCtlWords - 1, 2.0 * std::max(1.0, T / 1000.0) * std::max(1.0, spin_limit / 400000.0));
         const int tj_ = timer.begin(st2, 0);
         gemm_f32(st2, true, true, mid_r1 - mid_r0, ldG2, nxt->din, 1.f, L.Y.p + (size_t)S * ldY + (size_t)mid_r0 * ldY, ldY,
                  params.p + nxt->p_off + nxt->off_wx, pad4(nxt->din), 0.f, nxt->G.p + (size_t)mid_r0 * ldG2, ldG2,
@@ -1137,12 +1230,21 @@ std::string Net::plan_string() const {
   const std::vector<RecPlan> bwd = bwd_plans(T);
   std::string o = "{\"T\": " + std::to_string(T) + ", \"S\": " + std::to_string(S) + ", \"persistent\": " + (persistent ? "true" : "false") + ", \"layers\": [";
   bool first = true;
+  FwdEarly below;   // what the layer below runs early of this layer's input GEMM (forward_pass)
   for (size_t li = 0; li < layers.size(); ++li) {
     const Layer& L = layers[li];
-    if (!L.is_lstm()) continue;
+    if (!L.is_lstm()) { below = FwdEarly{}; continue; }
     const RecPlan fp = persistent && T >= 1 ? lstm_fwd_plan(lstm_view(*this, L, T)) : RecPlan{}, &bp = bwd[li];
+    int qs[2];
+    const char* sched = below.gate ? "gated under the recurrence below"
+                        : below.r1 > below.r0 ? (fwd_quad_rule((int)li, fp, T, below.r0, below.r1, qs) ? "middle under the recurrence below, needed quadrants, recurrence, late quadrants beside it"
+                                                                                                  : "middle under the recurrence below, both ends, recurrence")
+                                              : "whole, recurrence";
+    // (the key exists where there is a choice: behind an LSTM layer)
+    const bool lstm_below = li > 0 && layers[li - 1].is_lstm();
     o += std::string(first ? "" : ", ") + "{\"layer\": " + std::to_string(li) + ", \"cells\": " + std::to_string(L.H) + ", \"directions\": " + std::to_string(L.ndir) +
-         ", \"forward\": " + one(fp) + ", \"backward\": " + one(bp) + "}";
+         ", \"forward\": " + one(fp) + ", \"backward\": " + one(bp) + (lstm_below ? std::string(", \"input_gemm\": \"") + sched + "\"" : std::string()) + "}";
+    below = T >= 1 ? fwd_early((int)li, fp, T) : FwdEarly{};
     first = false;
   }
   const bool ov = overlap_for_minibatch(bwd);

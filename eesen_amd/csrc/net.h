@@ -144,7 +144,16 @@ struct Net {
   DevEvent ev_rec, ev_grad[2];
   bool overlap = true;
   DevEvent ev_gate_reset, ev_gate_done;  // gated / early input GEMM of the next layer (forward)
-  DevBuf<unsigned> mile;      // progress milestone of the running forward recurrence (LstmLayerDev::milestone)
+  DevBuf<unsigned> mile;      // progress milestone of the running forward recurrence (LstmLayerDev::milestone) and the row guards of the next
+                              // one (LstmLayerDev::guard): two regions of kMileRegion words, taken in turn by the layers (forward_pass)
+  static constexpr int kMileRegion = 64, kGuardWord = 32;
+  DevEvent ev_quad_go, ev_quad_done;   // "only the needed quadrants first": the recurrence below is through (main -> side); the deferred quadrants are in (side -> main)
+  // The early forms of the NEXT layer's input GEMM that may run beside / behind LSTM layer li's forward recurrence (plan `fp`, T frames),
+  // and which rows the early middle covers; and whether layer li, whose input GEMM's middle rows [r0, r1) are on the side stream, starts
+  // its own recurrence (plan `fp`) behind two quadrants only.  ONE rule each for forward_pass and plan_string.
+  struct FwdEarly { bool gate = false, mid = false; int mile_step = 0, r0 = 0, r1 = 0; };
+  FwdEarly fwd_early(int li, const RecPlan& fp, int T) const;
+  bool fwd_quad_rule(int li, const RecPlan& fp, int T, int r0, int r1, int steps[2]) const;
   bool gate_fwd = true;
   bool fwd_bf16 = false;      // eesen_net_set_forward_precision(1 | 2): forward GEMMs on bf16-rounded operands (BASELINE config 4)
   bool fwd_bf16_rec = false;  // ... (1 only): and the forward time recurrence on one bf16 plane of W_m / a bf16 exchange of m_t (lstm_fwd_persistent_bf16_kernel)

@@ -12,7 +12,7 @@ constexpr int kRecWaves = 8;   // wavefronts per workgroup of every recurrence k
 struct RecRole { int nblk, ndir, nz, xcd; };
 
 // the kernel templates; a row's arguments are its template's, in order (bool as 0 / 1)
-enum RecFamily { kFwdF32, kFwdBf, kFwdMux, kBwdGeneric, kBwdQ4, kBwdKsplit, kBwdKsplitH, kBwdKsplitMux };
+enum RecFamily { kFwdF32, kFwdBf, kFwdBfGuard, kFwdMux, kBwdGeneric, kBwdQ4, kBwdKsplit, kBwdKsplitH, kBwdKsplitMux };
 struct RecKernel {
   int family;
   int kind;          // kRec*: what RecPlan::kind reports, and the launcher's argument list

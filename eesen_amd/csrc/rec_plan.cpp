@@ -321,7 +321,10 @@ RecPlan lstm_fwd_plan(const LstmLayerDev& L) {
   const dim3 grid(L.H / (4 * nt), L.ndir, cdiv(L.S / nwin, 16 * mt));
   const size_t words = ctl_words(grid.y * grid.z);
   if (B.on) {
-    if (words <= (size_t)kCtlHalf) answer(*rec_kernel(kFwdBf, B.cpw, B.nt, B.ap, B.wp, B.f16), grid, words, 16, nwin, nwin == 1);
+    if (words <= (size_t)kCtlHalf) {
+      answer(*rec_kernel(kFwdBf, B.cpw, B.nt, B.ap, B.wp, B.f16), grid, words, 16, nwin, nwin == 1);
+      if (const RecKernel* g = rec_kernel(kFwdBfGuard, B.cpw, B.nt, B.ap, B.wp, B.f16)) P.fn_guard = g->fn;   // (same tile, same footprint class)
+    }
     return P;
   }
   // exchange-layout operand fetch: 16-sequence tiles, whole 32-unit chunks, block offsets within 32 bits
@@ -358,7 +361,11 @@ void lstm_fwd_launch(hipStream_t st, const RecPlan& P, const LstmLayerDev& L0, u
     EESEN_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(unsigned) * P.ctl_words, st));
     if (after_reset && P.one_window) EESEN_HIP_CHECK(hipEventRecord(after_reset, st));  // a gated consumer may start polling from here on
     if (P.kind == kRecFwdMux) plan_launch(st, P.fn, P.wgs, L, cnt, err, spin_limit, role);
-    else plan_launch(st, P.fn, P.wgs, L, cnt, err, spin_limit, trace, role);
+    else {
+      const bool guarded = L.guard[0] != nullptr || L.guard[1] != nullptr;
+      EESEN_REQUIRE(!guarded || P.fn_guard, EESEN_ERR_STATE, "row guards set for a forward plan without a guarded instantiation");
+      plan_launch(st, guarded ? P.fn_guard : P.fn, P.wgs, L, cnt, err, spin_limit, trace, role);
+    }
   }
 }
 

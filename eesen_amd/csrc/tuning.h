@@ -49,6 +49,11 @@
 //   EESEN_GATE_FWD          auto     next layer's input GEMM gated under the forward recurrence (auto: f32 GEMM mode only)
 //   EESEN_FWD_MID           1        0: the next layer's input GEMM waits for the whole forward recurrence (no early middle part):
 //                                    what counter-collecting runs (rocprofv3 --pmc lets ONE kernel run at a time) must set
+//   EESEN_FWD_QUAD          1        0: every gate-input row of a layer is computed before its forward recurrence starts (the schedule up to
+//                                    here) instead of only the two quadrants the recurrence reads first, the other two following on the
+//                                    side stream behind a row guard of the kernel (net.cpp: "only the needed quadrants first"); what
+//                                    counter-collecting runs must set as well (a serialised guard gives up once, like the waiter above)
+//                                    2: the A/B arm whose late quadrants are not capped at one workgroup per CU (slower: DESIGN.md section 9)
 //   EESEN_SIDE_LDS_KB       auto     occupancy cap of the side-stream GEMMs (unused dynamic LDS; auto: 48 half and split / 32 f32)
 //   ---- diagnostics -------------------------------------------------------------------------------------------------------
 //   EESEN_TRACE             0        1: in-kernel s_memtime timeline of workgroup 0, printed when the Net is destroyed
@@ -81,7 +86,7 @@ struct Tuning {
   int overlap = -1, gate_fwd = -1, side_lds_kb = -1;   // -1: decided by the Net (see above)
   int spin_limit = 400000;
   bool spin_limit_set = false;
-  int bwd_q4 = 1, bwd_q4_st8 = 1, fwd_narrow2 = 1, fwd_t16_small = 1, bwd_ksplit = 1, fwd_mux = 1, bwd_mux = 1, xcd_map = 1, fwd_mid = 1, fwd_split = 1, fwd_f16 = 1, bwd_f16 = 1;
+  int bwd_q4 = 1, bwd_q4_st8 = 1, fwd_narrow2 = 1, fwd_t16_small = 1, bwd_ksplit = 1, fwd_mux = 1, bwd_mux = 1, xcd_map = 1, fwd_mid = 1, fwd_quad = 1, fwd_split = 1, fwd_f16 = 1, bwd_f16 = 1;
   int comm_defer = -1;   // -1: decided per minibatch from the backward plans (Net::exchange_deferred_for_minibatch)
   int trace = 0;
   bool print_flight = false;
@@ -97,6 +102,7 @@ struct Tuning {
     t.overlap = num("EESEN_OVERLAP", -1);
     t.gate_fwd = num("EESEN_GATE_FWD", -1);
     t.fwd_mid = num("EESEN_FWD_MID", 1);
+    t.fwd_quad = num("EESEN_FWD_QUAD", 1);
     t.side_lds_kb = num("EESEN_SIDE_LDS_KB", -1);
     t.spin_limit_set = getenv("EESEN_SPIN_LIMIT") != nullptr;
     t.spin_limit = num("EESEN_SPIN_LIMIT", 400000);

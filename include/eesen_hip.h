@@ -184,7 +184,9 @@ int eesen_net_recurrence_info(eesen_net_t* net, int* out4);
 /* What WILL run the current minibatch shape (call after eesen_net_set_seq_lengths), as one JSON object: per LSTM layer the forward
  * and backward recurrence plans -- kernel instantiation, sequences / units per workgroup, grid, launches per pass, registers per
  * lane and LDS bytes of the instantiation, registers per SIMD lane its grid leaves free on a CU -- and the schedule decisions that
- * follow from them: weight-gradient GEMMs on the side stream or not, the exchange schedule with a communicator attached.  The
+ * follow from them: for a layer behind an LSTM layer which schedule its input GEMM takes around the forward recurrences ("input_gemm": whole; gated; the
+ * middle rows early and both ends, or only the needed quadrants, in front of the recurrence), weight-gradient GEMMs on the side
+ * stream or not, the exchange schedule with a communicator attached.  The
  * launchers execute exactly these plans (one selection function per pass, rec_plan.cpp: lstm_fwd_plan / lstm_bwd_plan).
  * Diagnostic; the reference has no counterpart (its kernels are chosen at compile time, src/gpucompute/cuda-kernels.cu). */
 int eesen_net_plan_string(eesen_net_t* net, char* json, int cap);
