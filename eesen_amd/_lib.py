@@ -120,6 +120,9 @@ SIGNATURES = {
     "eesen_ctc_decode_stamps": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eesen_ctc_get_stamp_times": (_i, [_vp, _vp]),
     "eesen_ctc_set_stamp_group": (_i, [_vp, _i]),
+    "eesen_lex_lookahead": (_i, [_vp, _vp, _vp, _i]),
+    "eesen_ctc_set_lm_lookahead": (_i, [_vp, _i]),
+    "eesen_ctc_get_lm_lookahead": (_i, [_vp, _pi]),
     "eesen_word_confidence": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp]),
     "eesen_ce_create": (_i, [_i, _vp, C.POINTER(_vp)]),
     "eesen_ce_destroy": (_i, [_vp]),

@@ -586,6 +586,13 @@ class Lexicon:
         check(self.lib.eesen_lex_node_words(self.h, int(node), _np_ptr(out), int(out.size), C.byref(n)))
         return out[:n.value].tolist()
 
+    def Lookahead(self, lm: "TokenLm") -> np.ndarray:
+        """The unigram look-ahead table of a word LM over this lexicon (eesen_lex_lookahead; INTEGRATION.md "LM look-ahead"):
+        float32 [nodes], la[v] = the largest unigram weight among the words whose spelling passes through or ends at node v."""
+        out = np.empty(self.Info()["nodes"], np.float32)
+        check(self.lib.eesen_lex_lookahead(self.h, lm.h, _np_ptr(out), int(out.size)))
+        return out
+
     def Words(self, labels: Sequence[int]) -> List[int]:
         """The word ids of a labelling `w1 space w2 ... wn`; EesenError for a labelling that is none, and for an unspaced lexicon."""
         lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
@@ -681,7 +688,8 @@ class Ctc:
 
     def DecodeParallel(self, frame_num_utt: Sequence[int], net_out: CuMatrix, beam: int = 16, max_classes: int = 20, nbest: int = 1,
                        is_log: bool = False, lm: Optional["TokenLm"] = None, lm_weight: float = 1.0, insertion_bonus: float = 0.0,
-                       lm_eos: bool = False, lexicon: Optional["Lexicon"] = None, word_bonus: float = 0.0):
+                       lm_eos: bool = False, lexicon: Optional["Lexicon"] = None, word_bonus: float = 0.0,
+                       lm_lookahead: Optional[bool] = None):
         """CTC prefix beam search (eesen_ctc_decode_parallel; no counterpart in the reference's src/net).  net_out: posteriors,
         or log-domain scores with is_log=True.  Returns (hyps, scores): hyps[s] is the list of the utterance's returned labellings, best
         first, each a list of ints (at most nbest; none where the beam died); scores [S, nbest] float32, -1e30 beyond the returned
@@ -696,7 +704,19 @@ class Ctc:
         above unchanged.  An unspaced lexicon (Lexicon(space=None)) takes eesen_ctc_decode_parallel_words: a returned entry is a
         labelling and a segmentation of it into words, homophones and other segmentations of the same labels are entries of their
         own, and self.word_ends [S, nbest, T] is the number of labels up to and including each word's last (-1 beyond the word
-        count; None in every other mode)."""
+        count; None in every other mode).
+        lm_lookahead: True / False sets the unigram LM look-ahead (SetLmLookahead; INTEGRATION.md "LM look-ahead") for this call and
+        restores the object's mode behind it; None (the default) decodes in the object's mode.  True needs a lexicon and an lm."""
+        if lm_lookahead is not None:
+            if lm_lookahead and lexicon is None:
+                raise EesenError(-1, "the LM look-ahead needs a lexicon and the word LM over it: this call has no lexicon")
+            before = self.LmLookahead()
+            self.SetLmLookahead(1 if lm_lookahead else 0)
+            try:
+                return self.DecodeParallel(frame_num_utt, net_out, beam, max_classes, nbest, is_log, lm, lm_weight, insertion_bonus, lm_eos,
+                                           lexicon, word_bonus)
+            finally:
+                self.SetLmLookahead(before)
         fn = np.ascontiguousarray(frame_num_utt, np.int32)
         S = fn.size
         T = net_out.rows // max(S, 1)
@@ -765,6 +785,15 @@ class Ctc:
                                                int(bool(is_log)), float(conf_scale), _np_ptr(ls), _np_ptr(le), _np_ptr(ws), _np_ptr(we),
                                                _np_ptr(wc), _np_ptr(ps)))
         return Stamps(ls, le, ws, we, wc, ps)
+
+    def SetLmLookahead(self, mode: int):
+        """eesen_ctc_set_lm_lookahead: 0 = off (the default), 1 = the unigram look-ahead in the two lexicon searches; it stays set."""
+        check(self.lib.eesen_ctc_set_lm_lookahead(self.h, int(mode)))
+
+    def LmLookahead(self) -> int:
+        m = C.c_int()
+        check(self.lib.eesen_ctc_get_lm_lookahead(self.h, C.byref(m)))
+        return m.value
 
     def SetStampGroup(self, lattices: int):
         """Test hook (eesen_ctc_set_stamp_group): sweep DecodeStamps' lattices in groups of `lattices`; 0 = automatic."""

@@ -400,6 +400,23 @@ int eesen_ctc_decode_parallel_words(eesen_ctc_t* ctc, const int* frame_num_utt, 
                                use_eos != 0, hyp_host, hyp_len_host, score_host, lm_score_host, word_host, word_len_host, word_end_host);
   });
 }
+int eesen_lex_lookahead(eesen_lex_t* lex, eesen_lm_t* lm, float* out_host, int cap) {
+  return guard([&] {
+    REQ_PTR(lex); REQ_PTR(lm); REQ_PTR(out_host);
+    EESEN_REQUIRE(cap >= lex->nodes(), EESEN_ERR_INVALID, "the look-ahead table has one value per lexicon node: cap is below eesen_lex_info's node count");
+    lex->lookahead(*lm, out_host);
+  });
+}
+int eesen_ctc_set_lm_lookahead(eesen_ctc_t* ctc, int mode) {
+  return guard([&] {
+    REQ_PTR(ctc);
+    EESEN_REQUIRE(mode == 0 || mode == 1, EESEN_ERR_INVALID, "LM look-ahead mode: 0 (off) or 1 (unigram)");
+    ctc->lm_lookahead = mode;
+  });
+}
+int eesen_ctc_get_lm_lookahead(eesen_ctc_t* ctc, int* mode) {
+  return guard([&] { REQ_PTR(ctc); REQ_PTR(mode); *mode = ctc->lm_lookahead; });
+}
 int eesen_ctc_decode_parallel_lm(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld,
                                  int is_log, int beam, int max_classes, int nbest, eesen_lm_t* lm, float lm_weight, float insertion_bonus,
                                  int use_eos, int* hyp_host, int* hyp_len_host, float* score_host, float* lm_score_host) {

@@ -12,8 +12,10 @@
 //                           that instantiation only
 //   ctc_hyp_kernel          one lane per (utterance, rank) walks the trie to the root
 // Along a lexicon without a boundary unit (INTEGRATION.md "Words without a boundary unit", tests/ctc_words_restatement.py) the second
-// and third launch are ctc_word_beam_kernel and ctc_word_hyp_kernel, at the end of this file: hypotheses are labels and the words closed
-// between them, and labels, words and word ends all come out of the trie on the device.
+// and third launch are ctc_word_beam_kernel (its text: ctc_word_beam.inc) and ctc_word_hyp_kernel, at the end of this file: hypotheses
+// are labels and the words closed between them, and labels, words and word ends all come out of the trie on the device.
+// With the unigram LM look-ahead (INTEGRATION.md "LM look-ahead", tests/ctc_lookahead_restatement.py) the two lexicon searches run
+// ctc_prefix_beam_lex_la_kernel / ctc_word_beam_la_kernel: the same two texts behind a compile-time flag, the keys alone differ.
 // Every log-mass is an fp32 value in [-1e30, +inf): sums are clamped from below at the library's finite sentinel, so the sweep's
 // branch-free log-add (ctc.hip: LogAPlusB_fast) is exact on the special cases here too.
 #include "kernels.h"
@@ -44,6 +46,8 @@ __device__ __forceinline__ float log_add(float a, float b) {
   return m + __logf(1.f + __expf(n - m));
 }
 __device__ __forceinline__ float score_add(float a, float b) { return fmaxf(a + b, kLogZero); }
+// the look-ahead's rank term of a candidate on a lexicon node whose table value is l (INTEGRATION.md "LM look-ahead")
+__device__ __forceinline__ float eta_of(float alpha, float beta, float l) { return __fadd_rn(__fmul_rn(alpha, l), beta); }
 // order-preserving map of a float onto an unsigned: a < b  <=>  ord(a) < ord(b)
 __device__ __forceinline__ unsigned ord(float v) {
   const unsigned u = __builtin_bit_cast(unsigned, v);
@@ -194,12 +198,19 @@ __device__ __forceinline__ void sort_sync(bool wave_local) {
 // with g = 0 -- the plain bits -- and keeps LM state and sum; the space closes the node's word w: g = alpha * lm_step(state, w) +
 // beta, the node returns to the root.  After the last frame the entries that do not stand on a word end are dropped, the others
 // close their last word (and take alpha * fin with use_eos), and are re-ranked.
-template <int MODE>
+// LA (lexicon mode only; INTEGRATION.md "LM look-ahead"): a candidate is ranked by score_add(total, eta), eta = alpha * la[v] + beta
+// for the lexicon node v it stands on after the step; the dead test and every carried value stay on the real total.  la[v] of a unit
+// extension's child rides in ext_w (which a unit otherwise leaves 0 and nobody reads) and is read per edge (la_edge[e] = la[child_node[e]],
+// beside child_node[e]: no hop more in step 0's chain of dependent loads), the root's is one register, an entry's own is loaded beside
+// step 0's lookups: 0.25 KiB more LDS, no barrier more.
+template <int MODE, bool LA = false>
 __device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld, int T, int S, const int* __restrict__ lens, int B, int Cc,
                                             const int* __restrict__ cid_g, const float* __restrict__ csc_g,
                                             const float* __restrict__ sblank_g, LmArgs<MODE> lm, int* __restrict__ tparent,
                                             int* __restrict__ tlabel, int* __restrict__ fnode, int* __restrict__ flen,
-                                            float* __restrict__ fscore, int* __restrict__ count) {
+                                            float* __restrict__ fscore, int* __restrict__ count, const float* __restrict__ la = nullptr,
+                                            const float* __restrict__ la_edge = nullptr) {
+  static_assert(!LA || MODE == kLexicon, "the look-ahead ranks along a lexicon");
   __shared__ unsigned long long keys[kMaxKeys];
   __shared__ BeamState st[2];
   __shared__ float stay_lb[kMaxBeam], stay_lnb[kMaxBeam], nx_stay[kMaxBeam], nx_ext[kMaxCls];
@@ -215,6 +226,7 @@ __device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld
   __shared__ int ext_next[kMaxKeys / 2];
   __shared__ int lex_node[2][kMaxBeam];     // the lexicon mode's alone: the entry's node of the lexicon trie
   __shared__ int done_sh;                   // ... and the number of complete entries at the end (nb_sh is still being read then)
+  __shared__ float la_ent[kMaxBeam];        // the look-ahead's alone: la of the entry's lexicon node, this frame
   const int s = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   const int n = min(lens[s], T);
   const size_t cap = 1 + (size_t)T * B;
@@ -235,6 +247,8 @@ __device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld
     c_sc[0][tid] = csc_g[(size_t)s * Cc + tid];
   }
   __syncthreads();
+  float la_root = 0.f;   // a space extension stands on the root
+  if constexpr (LA) la_root = la[0];
   int cur = 0;
   for (int t = 0; t < n; ++t) {
     const int nb = nb_sh;
@@ -279,7 +293,10 @@ __device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld
           if (c != lm.lex.space) {
             const int end = r.x + r.y;
             const int lo = lower_bound(lm.lex.child_cls, r.x, end, c);
-            if (lo < end && lm.lex.child_cls[lo] == c) next = lm.lex.child_node[lo];
+            if (lo < end && lm.lex.child_cls[lo] == c) {
+              next = lm.lex.child_node[lo];
+              if constexpr (LA) w = la_edge[lo];
+            }
           } else if (r.z != 0) {
             next = 0;
             if (lm.have_lm) lm_step(lm.tab, lm_state[cur][p], r.z, w, next);
@@ -290,6 +307,7 @@ __device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld
         ext_w[x] = w;
         ext_next[x] = next;
       }
+      if constexpr (LA) { if (tid < nb) la_ent[tid] = la[lex_node[cur][tid]]; }
       __syncthreads();
     }
     if (tid < nb) {   // ---- 1
@@ -314,7 +332,9 @@ __device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld
       stay_lb[q] = slb;
       stay_lnb[q] = slnb;
       const float total = log_add(slb, slnb) + 0.f;   // (+ 0: a -0 orders as +0)
-      keys[q] = total > kDead ? make_key(total, q) : kDeadKey;
+      float rank = total;
+      if constexpr (LA) rank = score_add(total, eta_of(lm.alpha, lm.beta, la_ent[q])) + 0.f;
+      keys[q] = total > kDead ? make_key(rank, q) : kDeadKey;
     }
     __syncthreads();
     int npad = 2;   // ---- 2
@@ -324,7 +344,9 @@ __device__ __forceinline__ void prefix_beam(const float* __restrict__ sc, int ld
       if (x < n_ext) {
         const int p = x / Cc, ci = x - p * Cc;
         const float v = ext_value(p, ci) + 0.f;
-        if (!((merged[p] >> ci) & 1) && v > kDead) key = make_key(v, kMaxBeam + x);
+        float rank = v;
+        if constexpr (LA) rank = score_add(v, eta_of(lm.alpha, lm.beta, ci_[ci] == lm.lex.space ? la_root : ext_w[x])) + 0.f;
+        if (!((merged[p] >> ci) & 1) && v > kDead) key = make_key(rank, kMaxBeam + x);
       }
       keys[nb + x] = key;
     }
@@ -505,6 +527,17 @@ __global__ __launch_bounds__(512) void ctc_prefix_beam_lex_kernel(const float* _
                                                                   float* __restrict__ fscore, int* __restrict__ count) {
   prefix_beam<kLexicon>(sc, ld, T, S, lens, B, Cc, cid_g, csc_g, sblank_g, lm, tparent, tlabel, fnode, flen, fscore, count);
 }
+// ... ranked with the unigram look-ahead la [nodes] (the lexicon's and the word LM's: Lexicon::lookahead)
+__global__ __launch_bounds__(512) void ctc_prefix_beam_lex_la_kernel(const float* __restrict__ sc, int ld, int T, int S,
+                                                                     const int* __restrict__ lens, int B, int Cc,
+                                                                     const int* __restrict__ cid_g, const float* __restrict__ csc_g,
+                                                                     const float* __restrict__ sblank_g, LmArgs<kLexicon> lm,
+                                                                     const float* __restrict__ la, const float* __restrict__ la_edge,
+                                                                     int* __restrict__ tparent,
+                                                                     int* __restrict__ tlabel, int* __restrict__ fnode, int* __restrict__ flen,
+                                                                     float* __restrict__ fscore, int* __restrict__ count) {
+  prefix_beam<kLexicon, true>(sc, ld, T, S, lens, B, Cc, cid_g, csc_g, sblank_g, lm, tparent, tlabel, fnode, flen, fscore, count, la, la_edge);
+}
 
 // ---- hypotheses: one lane per (utterance, rank); with an LM (flm, lm_out not null) the lane also hands out its entry's LM sum ------
 __global__ __launch_bounds__(64) void ctc_hyp_kernel(const int* __restrict__ tparent, const int* __restrict__ tlabel,
@@ -576,233 +609,21 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int npad,
 // Tie index: stays by previous rank, then 64 + x: parent's rank, class id, slot.  After the last frame every complete entry yields
 // one final hypothesis per word of its node (key index p * 16 + i), which are sorted and the best B written out.
 // Static LDS: 32 KiB keys + 6.5 KiB state + 8 KiB inside children + 12 KiB (wt, next, word) + 1.5 KiB = 60 KiB.
-__global__ __launch_bounds__(512) void ctc_word_beam_kernel(const float* __restrict__ sc, int ld, int T, int S, const int* __restrict__ lens, int B,
-                                                            int Cc, const int* __restrict__ cid_g, const float* __restrict__ csc_g,
-                                                            const float* __restrict__ sblank_g, LmTables tab, int have_lm, float alpha, float beta,
-                                                            int use_eos, WordLexTables lex, int* __restrict__ tparent, int* __restrict__ tlabel,
-                                                            int* __restrict__ tword, int* __restrict__ fnode, int* __restrict__ flen,
-                                                            float* __restrict__ fscore, float* __restrict__ flm, int* __restrict__ fword,
-                                                            int* __restrict__ fnw, int* __restrict__ count) {
-  __shared__ unsigned long long keys[kMaxKeys];
-  __shared__ WordBeamState st[2];
-  __shared__ float stay_lb[kMaxBeam], stay_lnb[kMaxBeam];
-  __shared__ int c_id[kMaxCls], root_next[kMaxCls];
-  __shared__ float c_sc[kMaxCls], c_bl;
-  __shared__ int in_next[kMaxKeys / 2];                 // the inside child of (p, ci) at p * C' + ci, or -1
-  __shared__ float cl_w[kMaxBeam * kHomStride];         // lm_step of (p, i-th word of p's node) at p * 16 + i
-  __shared__ int cl_next[kMaxBeam * kHomStride], cl_word[kMaxBeam * kHomStride];
-  __shared__ int ent_nw[kMaxBeam];                      // |words(v)| of the entry's node
-  __shared__ int nb_sh;
-  const int s = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
-  const int n = min(lens[s], T);
-  const size_t cap = 1 + (size_t)T * B;
-  int* tp = tparent + (size_t)s * cap;
-  int* tl = tlabel + (size_t)s * cap;
-  int* tw = tword + (size_t)s * cap;
-  const int4* __restrict__ nrec = reinterpret_cast<const int4*>(lex.node_rec);   // {first child, child count, first word slot, word count}
-  const int H1 = 1 + lex.H;
-  if (tid == 0) {
-    WordBeamState& z = st[0];
-    z.lb[0] = 0.f; z.lnb[0] = kLogZero; z.lmsum[0] = 0.f;
-    z.node[0] = 0; z.last[0] = -1; z.len[0] = 0; z.nlab[0] = 0; z.nwords[0] = 0; z.closed[0] = 0; z.lexnode[0] = 0;
-    z.lmstate[0] = have_lm ? tab.start : 0; z.hash[0] = 0;
-    nb_sh = 1;
-    tp[0] = -1; tl[0] = -1; tw[0] = 0;
-  }
-  __syncthreads();
-  int cur = 0;
-  for (int t = 0; t < n; ++t) {
-    const int nb = nb_sh;
-    if (nb == 0) break;   // the beam died (uniform): possible only with is_log input
-    const WordBeamState& a = st[cur];
-    WordBeamState& nx = st[cur ^ 1];
-    const size_t row = (size_t)t * S + s;
-    const int* cid_row = cid_g + row * Cc;
-    // ---- 0
-    if (tid < Cc) {
-      const int c = cid_row[tid];
-      c_id[tid] = c;
-      c_sc[tid] = csc_g[row * Cc + tid];
-      const int4 r = nrec[0];
-      const int end = r.x + r.y;
-      const int lo = lower_bound(lex.child_cls, r.x, end, c);
-      root_next[tid] = (lo < end && lex.child_cls[lo] == c) ? lex.child_node[lo] : -1;
-    }
-    if (tid == 0) c_bl = sblank_g[row];
-    for (int x = tid; x < nb * Cc; x += NT) {
-      const int p = x / Cc, ci = x - p * Cc;
-      const int4 r = nrec[a.lexnode[p]];
-      const int c = cid_row[ci];
-      const int end = r.x + r.y;
-      const int lo = lower_bound(lex.child_cls, r.x, end, c);
-      in_next[x] = (lo < end && lex.child_cls[lo] == c) ? lex.child_node[lo] : -1;
-    }
-    for (int x = tid; x < nb * kHomStride; x += NT) {
-      const int p = x / kHomStride, i = x - p * kHomStride;
-      const int4 r = nrec[a.lexnode[p]];
-      if (i == 0) ent_nw[p] = r.w;
-      if (i < r.w) {
-        const int w = lex.node_words[r.z + i];
-        float wt = 0.f;
-        int next = a.lmstate[p];
-        if (have_lm) lm_step(tab, a.lmstate[p], w, wt, next);
-        cl_w[x] = wt; cl_next[x] = next; cl_word[x] = w;
-      }
-    }
-    __syncthreads();
-    const float bl = c_bl;
-    auto succ_value = [&](int p, int ci, int slot) -> float {
-      float g = 0.f;
-      if (slot == 0) {
-        if (in_next[p * Cc + ci] < 0) return kLogZero;
-      } else {
-        if (slot - 1 >= ent_nw[p] || root_next[ci] < 0) return kLogZero;
-        g = __fadd_rn(__fmul_rn(alpha, cl_w[p * kHomStride + slot - 1]), beta);
-      }
-      const float lb = a.lb[p], lnb = a.lnb[p];
-      const float cs = score_add(c_sc[ci], g);
-      return score_add(cs, c_id[ci] == a.last[p] ? lb : log_add(lb, lnb));
-    };
-    const int n_succ = nb * Cc * H1;   // nb + n_succ <= B * (1 + C' * (1 + H)) <= kMaxKeys: the host's limit
-    int npad = 2;
-    while (npad < nb + n_succ) npad <<= 1;
-    for (int x = tid; x < npad - nb; x += NT) {   // ---- 2
-      unsigned long long key = kDeadKey;
-      if (x < n_succ) {
-        const int pc = x / H1, slot = x - pc * H1, p = pc / Cc, ci = pc - p * Cc;
-        const float v = succ_value(p, ci, slot) + 0.f;
-        if (v > kDead) key = make_key(v, kMaxBeam + x);
-      }
-      keys[nb + x] = key;
-    }
-    __syncthreads();
-    if (tid < nb) {   // ---- 1
-      const int q = tid, e = a.last[q];
-      const float lb = a.lb[q], lnb = a.lnb[q];
-      const float slb = score_add(bl, log_add(lb, lnb));
-      float slnb = kLogZero;
-      if (e >= 0) {
-        slnb = score_add(clamp_score(sc[row * ld + e]), lnb);
-        const int w = a.closed[q];
-        unsigned long long ph = (a.hash[q] - (unsigned long long)(e + 1)) * kHashMulInv;
-        int plen = a.len[q] - 1;
-        if (w != 0) { ph = (ph - (unsigned long long)(lex.K + w)) * kHashMulInv; --plen; }
-        int p = -1;
-        for (int i = 0; i < nb; ++i)
-          if (a.hash[i] == ph && a.len[i] == plen) p = i;
-        if (p >= 0) {
-          const int lo = lower_bound(c_id, 0, Cc, e);
-          if (lo < Cc && c_id[lo] == e) {
-            int slot = w == 0 ? 0 : -1;
-            for (int i = 0; w != 0 && i < ent_nw[p]; ++i)
-              if (cl_word[p * kHomStride + i] == w) slot = 1 + i;
-            if (slot >= 0) {
-              slnb = log_add(slnb, succ_value(p, lo, slot));
-              keys[nb + (p * Cc + lo) * H1 + slot] = kDeadKey;
-            }
-          }
-        }
-      }
-      stay_lb[q] = slb;
-      stay_lnb[q] = slnb;
-      const float total = log_add(slb, slnb) + 0.f;   // (+ 0: a -0 orders as +0)
-      keys[q] = total > kDead ? make_key(total, q) : kDeadKey;
-    }
-    __syncthreads();
-    bitonic_sort(keys, npad, tid, NT);   // ---- 3
-    __syncthreads();
-    if (tid < 64) {   // ---- 4 (wave 0)
-      const unsigned long long key = (tid < B && tid < npad) ? keys[tid] : kDeadKey;
-      const bool live = key != kDeadKey;
-      if (live) {
-        const int idx = (int)(unsigned)key;
-        if (idx < kMaxBeam) {
-          nx.lb[tid] = stay_lb[idx]; nx.lnb[tid] = stay_lnb[idx]; nx.lmsum[tid] = a.lmsum[idx];
-          nx.node[tid] = a.node[idx]; nx.last[tid] = a.last[idx]; nx.len[tid] = a.len[idx]; nx.nlab[tid] = a.nlab[idx];
-          nx.nwords[tid] = a.nwords[idx]; nx.closed[tid] = a.closed[idx]; nx.lexnode[tid] = a.lexnode[idx];
-          nx.lmstate[tid] = a.lmstate[idx]; nx.hash[tid] = a.hash[idx];
-        } else {
-          const int x = idx - kMaxBeam, pc = x / H1, slot = x - pc * H1, p = pc / Cc, ci = pc - p * Cc, c = c_id[ci];
-          const int node = 1 + t * B + tid;   // < cap: t < n <= T, tid < B
-          const int at = p * kHomStride + slot - 1;
-          const int w = slot == 0 ? 0 : cl_word[at];
-          unsigned long long h = a.hash[p];
-          if (slot != 0) h = h * kHashMul + (unsigned long long)(lex.K + w);
-          nx.lb[tid] = kLogZero; nx.lnb[tid] = succ_value(p, ci, slot);
-          nx.lmsum[tid] = slot == 0 ? a.lmsum[p] : __fadd_rn(a.lmsum[p], cl_w[at]);
-          nx.node[tid] = node; nx.last[tid] = c;
-          nx.len[tid] = a.len[p] + (slot == 0 ? 1 : 2); nx.nlab[tid] = a.nlab[p] + 1; nx.nwords[tid] = a.nwords[p] + (slot == 0 ? 0 : 1);
-          nx.closed[tid] = w;
-          nx.lexnode[tid] = slot == 0 ? in_next[p * Cc + ci] : root_next[ci];
-          nx.lmstate[tid] = slot == 0 ? a.lmstate[p] : cl_next[at];
-          nx.hash[tid] = h * kHashMul + (unsigned long long)(c + 1);
-          tp[node] = a.node[p];
-          tl[node] = c;
-          tw[node] = w;
-        }
-      }
-      const int alive = __popcll(__ballot(live));   // the live keys are a prefix of the sorted array
-      if (tid == 0) nb_sh = alive;
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  // the end of the utterance: a complete entry yields one final hypothesis per word of its node (the empty one: itself), each closes
-  // its word and takes fin with use_eos; they are ranked by the new total, ties by (previous rank, word index)
-  const int nb = nb_sh;
-  const WordBeamState& a = st[cur];
-  float* fin_tot = reinterpret_cast<float*>(in_next);   // [64 * 16]: the frames' use of in_next is over
-  int npad = kHomStride;
-  while (npad < nb * kHomStride) npad <<= 1;   // <= 1024
-  for (int x = tid; x < npad; x += NT) {
-    const int p = x / kHomStride, i = x - p * kHomStride;
-    unsigned long long key = kDeadKey;
-    if (p < nb) {
-      const int4 r = nrec[a.lexnode[p]];
-      const bool empty = a.len[p] == 0;
-      if (empty ? i == 0 : i < r.w) {
-        float total = log_add(a.lb[p], a.lnb[p]) + 0.f, lsum = a.lmsum[p];
-        int state = a.lmstate[p], w = 0;
-        if (!empty) {
-          w = lex.node_words[r.z + i];
-          float wt = 0.f;
-          int next = state;
-          if (have_lm) lm_step(tab, state, w, wt, next);
-          state = next;
-          total = clamp_score(__fadd_rn(total, __fadd_rn(__fmul_rn(alpha, wt), beta))) + 0.f;
-          lsum = __fadd_rn(lsum, wt);
-        }
-        if (use_eos) {
-          const float f = tab.fin[state];
-          total = clamp_score(__fadd_rn(total, __fmul_rn(alpha, f))) + 0.f;
-          lsum = __fadd_rn(lsum, f);
-        }
-        key = make_key(total, x);
-        fin_tot[x] = total; cl_w[x] = lsum; cl_word[x] = w;
-      }
-    }
-    keys[x] = key;
-  }
-  __syncthreads();
-  bitonic_sort(keys, npad, tid, NT);
-  __syncthreads();
-  if (tid < 64) {   // wave 0; B <= 64
-    const unsigned long long key = (tid < B && tid < npad) ? keys[tid] : kDeadKey;
-    const bool live = key != kDeadKey;
-    if (tid < B) {
-      const size_t o = (size_t)s * B + tid;
-      const int x = (int)(unsigned)key, p = x / kHomStride;
-      fnode[o] = live ? a.node[p] : -1;
-      flen[o] = live ? a.nlab[p] : -1;
-      fscore[o] = live ? fin_tot[x] : kLogZero;
-      flm[o] = live ? cl_w[x] : kLogZero;
-      fword[o] = live ? cl_word[x] : -1;
-      fnw[o] = live ? a.nwords[p] + (cl_word[x] != 0 ? 1 : 0) : -1;
-    }
-    const int done = __popcll(__ballot(live));
-    if (tid == 0) count[s] = done;
-  }
-}
+// LA (INTEGRATION.md "LM look-ahead"): a key holds score_add(total, eta), eta = alpha * la[v] + beta for the lexicon node v the
+// candidate stands on after the step -- step 4 recomputes every value from (p, ci, slot) and never decodes a key.  la of the root's
+// child per candidate and of every entry's own node are step 0's (0.5 KiB more LDS); an inside successor reads la[in_next] from
+// global memory where its key is written.
+// One text, two kernels (ctc_word_beam.inc): ctc_word_beam_kernel, and ctc_word_beam_la_kernel ranked with the unigram look-ahead.
+#define WORD_BEAM_KERNEL ctc_word_beam_kernel
+#define WORD_BEAM_LA 0
+#include "ctc_word_beam.inc"
+#undef WORD_BEAM_KERNEL
+#undef WORD_BEAM_LA
+#define WORD_BEAM_KERNEL ctc_word_beam_la_kernel
+#define WORD_BEAM_LA 1
+#include "ctc_word_beam.inc"
+#undef WORD_BEAM_KERNEL
+#undef WORD_BEAM_LA
 
 // one lane per (utterance, rank): labels, words and word ends out of the trie, back to front
 __global__ __launch_bounds__(64) void ctc_word_hyp_kernel(const int* __restrict__ tparent, const int* __restrict__ tlabel,
@@ -879,14 +700,17 @@ void ctc_row_topc(hipStream_t st, const float* scores, int ld, int rows, int K, 
 }
 
 void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                     const float* csc, const float* sblank, const LmTables* lm, const LexTables* lex, float alpha, float beta, bool use_eos,
-                     int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count) {
+                     const float* csc, const float* sblank, const LmTables* lm, const LexTables* lex, const float* la, const float* la_edge,
+                     float alpha, float beta, bool use_eos, int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count) {
+  EESEN_REQUIRE(la == nullptr || (lex != nullptr && lm != nullptr && la_edge != nullptr), EESEN_ERR_INVALID, "ctc_prefix_beam: the look-ahead table needs the lexicon and the word LM");
   EESEN_REQUIRE(B >= 1 && B <= kMaxBeam && Cc >= 1 && Cc <= kMaxCls && B * Cc <= kMaxKeys / 2, EESEN_ERR_INVALID, "ctc_prefix_beam: beam or class count outside the key array");
   // one thread per pair of the widest sort stage, 64 .. 512
   int keys = 2;
   while (keys < B + B * Cc) keys <<= 1;
   const int threads = std::min(512, std::max(64, keys / 2));
-  if (lex) hipLaunchKernelGGL(ctc_prefix_beam_lex_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
+  if (la) hipLaunchKernelGGL(ctc_prefix_beam_lex_la_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
+                             LmArgs<kLexicon>{*lm, alpha, beta, use_eos ? 1 : 0, flm, *lex, 1}, la, la_edge, tparent, tlabel, fnode, flen, fscore, count);
+  else if (lex) hipLaunchKernelGGL(ctc_prefix_beam_lex_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
                               LmArgs<kLexicon>{lm ? *lm : LmTables{}, alpha, beta, use_eos ? 1 : 0, flm, *lex, lm ? 1 : 0}, tparent, tlabel, fnode,
                               flen, fscore, count);
   else if (lm) hipLaunchKernelGGL(ctc_prefix_beam_kernel<true>, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank,
@@ -904,16 +728,19 @@ void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* f
 }
 
 void ctc_word_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid, const float* csc,
-                   const float* sblank, const LmTables* lm, const WordLexTables& lex, float alpha, float beta, bool use_eos, int* tparent,
-                   int* tlabel, int* tword, int* fnode, int* flen, float* fscore, float* flm, int* fword, int* fnw, int* count) {
+                   const float* sblank, const LmTables* lm, const WordLexTables& lex, const float* la, float alpha, float beta, bool use_eos,
+                   int* tparent, int* tlabel, int* tword, int* fnode, int* flen, float* fscore, float* flm, int* fword, int* fnw, int* count) {
+  EESEN_REQUIRE(la == nullptr || lm != nullptr, EESEN_ERR_INVALID, "ctc_word_beam: the look-ahead table needs the word LM");
   EESEN_REQUIRE(B >= 1 && B <= kMaxBeam && Cc >= 1 && Cc <= kMaxCls && lex.H >= 1 && lex.H <= Lexicon::kMaxHomophones &&
                     B * (1 + Cc * (1 + lex.H)) <= kMaxKeys,
                 EESEN_ERR_INVALID, "ctc_word_beam: beam, class count or homophone count outside the key array");
   int keys = 2;
   while (keys < B * (1 + Cc * (1 + lex.H))) keys <<= 1;
   const int threads = std::min(512, std::max(64, keys / 2));
-  hipLaunchKernelGGL(ctc_word_beam_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank, lm ? *lm : LmTables{},
-                     lm ? 1 : 0, alpha, beta, use_eos ? 1 : 0, lex, tparent, tlabel, tword, fnode, flen, fscore, flm, fword, fnw, count);
+  if (la) hipLaunchKernelGGL(ctc_word_beam_la_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank, *lm, 1, alpha, beta,
+                             use_eos ? 1 : 0, lex, la, tparent, tlabel, tword, fnode, flen, fscore, flm, fword, fnw, count);
+  else hipLaunchKernelGGL(ctc_word_beam_kernel, dim3(S), dim3(threads), 0, st, scores, ld, T, S, lens, B, Cc, cid, csc, sblank, lm ? *lm : LmTables{},
+                          lm ? 1 : 0, alpha, beta, use_eos ? 1 : 0, lex, tparent, tlabel, tword, fnode, flen, fscore, flm, fword, fnw, count);
   check_launch("ctc_word_beam");
 }
 

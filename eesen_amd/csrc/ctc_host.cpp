@@ -290,6 +290,23 @@ void Ctc::upload_lex(const Lexicon& lex) {
   lex_serial = lex.serial;
 }
 
+// The look-ahead table of (lex, lm) on the device, or null with the mode off.  Called behind upload_lex / upload_lm.
+const float* Ctc::upload_lookahead(const Lexicon* lex, const TokenLm* lm) {
+  if (lm_lookahead == 0) return nullptr;
+  EESEN_REQUIRE(lm != nullptr, EESEN_ERR_INVALID, "the LM look-ahead (eesen_ctc_set_lm_lookahead) needs the word LM: decoding with a lexicon alone has nothing to look ahead to");
+  if (la_lex_serial == lex->serial && la_lm_serial == lm->serial) return la_f.p;
+  EESEN_HIP_CHECK(hipStreamSynchronize(st));   // (a launch in flight may still read the table this replaces)
+  const size_t nn = (size_t)lex->nodes(), ne = lex->child_node.size();
+  std::vector<float> la(nn + ne);   // behind the table: la of every edge's target, which the spaced search reads beside the target
+  lex->lookahead(*lm, la.data());
+  for (size_t e = 0; e < ne; ++e) la[nn + e] = la[lex->child_node[e]];
+  la_f.reserve(la.size());
+  EESEN_HIP_CHECK(hipMemcpy(la_f.p, la.data(), la.size() * sizeof(float), hipMemcpyHostToDevice));
+  la_lex_serial = lex->serial;
+  la_lm_serial = lm->serial;
+  return la_f.p;
+}
+
 void Ctc::upload_lm(const TokenLm& lm) {
   if (lm_serial == lm.serial) return;
   EESEN_HIP_CHECK(hipStreamSynchronize(st));   // (a launch in flight may still read the tables this replaces)
@@ -355,6 +372,7 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   float* lmsum_d = score_d + (size_t)S * N;
   if (lm) upload_lm(*lm);
   if (lex) upload_lex(*lex);
+  const float* la = lex ? upload_lookahead(lex, lm) : nullptr;   // (the plain and the token-LM search ignore the mode)
 
   PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
   int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
@@ -370,7 +388,7 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
   ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
   if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
-  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, lex ? &lex_tab : nullptr, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, fused ? flm : nullptr, count);
+  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, lex ? &lex_tab : nullptr, la, la ? la + lex->nodes() : nullptr, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, fused ? flm : nullptr, count);
   if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
   ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, fused ? flm : nullptr, count, T, S, B, N, hyp_d, len_d, score_d, fused ? lmsum_d : nullptr);
   if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
@@ -454,6 +472,7 @@ void Ctc::decode_parallel_words(const int* frame_num_utt, int S, const float* sc
   int* wlen_d = ends_d + n_hyp;
   if (lm) upload_lm(*lm);
   upload_lex(*lex);
+  const float* la = upload_lookahead(lex, lm);
 
   PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
   int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
@@ -469,7 +488,7 @@ void Ctc::decode_parallel_words(const int* frame_num_utt, int S, const float* sc
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
   ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
   if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
-  ctc_word_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, word_tab, lm_weight, word_bonus, use_eos, dec_trie.p,
+  ctc_word_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, word_tab, la, lm_weight, word_bonus, use_eos, dec_trie.p,
                 dec_trie.p + n_trie, dec_trie.p + 2 * n_trie, fnode, flen, fscore, flm, fword, fnw, count);
   if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
   ctc_word_hyp(st, dec_trie.p, dec_trie.p + n_trie, dec_trie.p + 2 * n_trie, fnode, flen, fscore, flm, fword, fnw, count, T, S, B, N, hyp_d, len_d,

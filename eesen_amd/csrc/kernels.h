@@ -250,10 +250,12 @@ struct LexTables;
 // with use_eos, alpha * fin[state] joins every total after the last frame and the final beam is re-ranked.  flm [S][B]: the
 // unweighted LM sum of each final entry.  lex: extensions only along the lexicon trie (ctc_prefix_beam_lex_kernel; INTEGRATION.md "Lexicon"; the
 // tables: lex.h); lm is then a model over word ids, stepped once per closed word, or null; beta is per word; the final beam holds
-// only the entries that end on a word end, and count[s] counts those.
+// only the entries that end on a word end, and count[s] counts those.  la (device, [lexicon nodes], or null; needs lex and lm): the
+// unigram look-ahead (ctc_prefix_beam_lex_la_kernel; INTEGRATION.md "LM look-ahead"): candidates are ranked by total + alpha * la[node] + beta;
+// la_edge [edges]: la of every edge's target, la_edge[e] = la[child_node[e]].
 void ctc_prefix_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                     const float* csc, const float* sblank, const LmTables* lm, const LexTables* lex, float alpha, float beta, bool use_eos,
-                     int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count);
+                     const float* csc, const float* sblank, const LmTables* lm, const LexTables* lex, const float* la, const float* la_edge,
+                     float alpha, float beta, bool use_eos, int* tparent, int* tlabel, int* fnode, int* flen, float* fscore, float* flm, int* count);
 // ctc_hyp: hyp [S][N][T] the labels of the N best entries front to back (-1 beyond the length), hyp_len / score [S][N] (-1 / -1e30
 // beyond count[s]); with flm and lm_out (both null without an LM) lm_out [S][N] = flm of the same entries, -1e30 beyond count[s].
 void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* fnode, const int* flen, const float* fscore, const float* flm,
@@ -264,8 +266,8 @@ void ctc_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* f
 // for the empty hypothesis), fnw (words, the last included); count[s] of them.  B * (1 + Cc * (1 + lex->H)) <= 4096.
 struct WordLexTables;
 void ctc_word_beam(hipStream_t st, const float* scores, int ld, int T, int S, const int* lens, int B, int Cc, const int* cid,
-                   const float* csc, const float* sblank, const LmTables* lm, const WordLexTables& lex, float alpha, float beta, bool use_eos,
-                   int* tparent, int* tlabel, int* tword, int* fnode, int* flen, float* fscore, float* flm, int* fword, int* fnw, int* count);
+                   const float* csc, const float* sblank, const LmTables* lm, const WordLexTables& lex, const float* la /*or null: as above*/,
+                   float alpha, float beta, bool use_eos, int* tparent, int* tlabel, int* tword, int* fnode, int* flen, float* fscore, float* flm, int* fword, int* fnw, int* count);
 // ctc_word_hyp: ctc_hyp's outputs plus words / ends [S][N][T] (word ids front to back and the number of labels up to and including
 // each word's last; -1 beyond the word count) and word_len [S][N] (-1 beyond count[s]).
 void ctc_word_hyp(hipStream_t st, const int* tparent, const int* tlabel, const int* tword, const int* fnode, const int* flen, const float* fscore,

@@ -144,6 +144,22 @@ bool Lexicon::words(const int* labels, int n, int* out, int* num) const {
   return true;
 }
 
+void Lexicon::lookahead(const TokenLm& lm, float* out) const {
+  EESEN_REQUIRE(lm.K == V() + 1, EESEN_ERR_INVALID, "the word LM's K must be the lexicon's word count + 1 (build it over eesen_lex_write_words' table)");
+  const int n = nodes();
+  // a child's id is above its parent's (compile() makes a node behind its parent), so one descending pass is bottom-up
+  for (int v = n - 1; v >= 0; --v) {
+    bool have = false;
+    float best = 0.f;
+    auto take = [&](float u) { if (!have || u > best) best = u; have = true; };
+    auto unigram = [&](int w) { float u; int next; lm.step(0, w, &u, &next); return u; };
+    if (unspaced) for (int i = 0; i < wcount[v]; ++i) take(unigram(node_words[wfirst[v] + i]));
+    else if (word[v] != 0) take(unigram(word[v]));
+    for (int e = first[v]; e < first[v] + count[v]; ++e) take(out[child_node[e]]);
+    out[v] = best;   // (every node has a word at or below it: a leaf ends a spelling)
+  }
+}
+
 void Lexicon::write_words(const char* path) const {
   std::ofstream out(path);
   for (int w = 1; w <= V(); ++w) out << names[w] << ' ' << w << '\n';

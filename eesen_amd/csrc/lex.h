@@ -6,6 +6,8 @@
 
 namespace eesen {
 
+struct TokenLm;
+
 // Node 0 is the root.  Node v owns children [first[v], first[v] + count[v]) of child_cls (ascending class id) / child_node;
 // word[v] is the id (1 .. V, in order of first appearance in the file) of the word whose spelling ends at v, or 0.
 struct Lexicon {
@@ -35,6 +37,9 @@ struct Lexicon {
   // *num; false for a labelling outside L
   bool words(const int* labels, int n, int* out, int* num) const;
   void write_words(const char* path) const;   // `word id` lines: the units table of a word LM with K = V + 1
+  // The unigram look-ahead table of a word LM over this lexicon (lm.K == V + 1; INTEGRATION.md "LM look-ahead"): out [nodes],
+  // out[v] = max of lm.step(0, w) over the words w whose spelling passes through or ends at v, by comparisons only
+  void lookahead(const TokenLm& lm, float* out) const;
  private:
   void compile(const char* path, const char* units);
 };

@@ -304,6 +304,11 @@ struct Ctc {
   LexTables lex_tab{};
   WordLexTables word_tab{};    // ... of an unspaced lexicon (decode_parallel_words): the same buffer and serial
   unsigned long long lex_serial = 0;
+  // the unigram look-ahead (eesen_ctc_set_lm_lookahead; INTEGRATION.md "LM look-ahead"): 0 off, 1 unigram.  The table of the
+  // (lexicon, word LM) pair the last look-ahead decode used, keyed by the two serials
+  int lm_lookahead = 0;
+  DevBuf<float> la_f;          // [nodes], then [edges]: la of every edge's target
+  unsigned long long la_lex_serial = 0, la_lm_serial = 0;
   // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
   // back through PinBufs that are folded into the statistics at the next call that needs them ("deferred").
@@ -366,6 +371,7 @@ struct Ctc {
                     int* hyp_len_host, float* score_host, float* lm_score_host);
   void upload_lm(const TokenLm& lm);
   void upload_lex(const Lexicon& lex);
+  const float* upload_lookahead(const Lexicon* lex, const TokenLm* lm);   // null with the mode off; refuses a missing word LM
 };
 
 // N-best posterior word confidences (eesen_word_confidence; INTEGRATION.md "Time stamps and CTM"), fp64, no device work.  Entry i of

@@ -82,7 +82,7 @@ int main(int argc, char** argv) {
     int ctm_precision = 2;
     bool ctm_conf = false;
     float prior_scale = 1.f, lm_weight = 1.f, insertion_bonus = 0.f, word_bonus = 0.f;
-    bool lm_eos = false, lm_skip_oov = false;
+    bool lm_eos = false, lm_skip_oov = false, lm_lookahead = false;
     double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
     int num_sequence = 1, device = 0, beam = 16, max_classes = 20, nbest = 1;
     std::string use_gpu = "yes";
@@ -118,6 +118,8 @@ int main(int argc, char** argv) {
     po.Register("word-lm", &word_lm, "ARPA file of a word n-gram LM over the lexicon's words, stepped once per word (weight: --lm-weight)");
     po.Register("word-bonus", &word_bonus, "Added per word, in nats");
     po.Register("lm-skip-oov", &lm_skip_oov, "Drop the n-grams of --word-lm that hold a word outside the lexicon instead of refusing the file");
+    po.Register("lm-lookahead", &lm_lookahead, "Rank the candidates of a frame as if the most probable word (by --word-lm's unigrams) that the "
+                                               "lexicon still allows had been paid already: a narrow --beam prunes better");
     po.Register("words-wspecifier", &words_wspecifier, "Also write the word ids of every hypothesis (int32 vectors, the keys of <hyp-wspecifier>)");
     po.Register("words-table-out", &words_table_out, "Write the lexicon's `word id` table to this file");
     po.Register("word-ref-rspecifier", &word_ref_rspecifier, "Reference word-id sequences: the word errors of the best hypotheses against them are counted");
@@ -193,6 +195,18 @@ int main(int argc, char** argv) {
     } else if (!lexicon_units.empty() || !word_lm.empty() || !words_wspecifier.empty() || !words_table_out.empty() || !word_ref_rspecifier.empty() ||
                word_bonus != 0.f || lm_skip_oov) {
       throw std::runtime_error("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and --word-ref-rspecifier need --lexicon");
+    }
+    if (lm_lookahead) {
+      if (!lex) throw std::runtime_error("--lm-lookahead needs --lexicon and --word-lm");
+      ck(eesen_ctc_set_lm_lookahead(ctc, 1));   // (without --word-lm the library refuses the first decode call)
+      if (lm) {
+        int nodes = 0;
+        ck(eesen_lex_info(lex, nullptr, &nodes, nullptr));
+        std::vector<float> la(nodes);
+        ck(eesen_lex_lookahead(lex, lm, la.data(), nodes));
+        std::cerr << "LOG (ctc-decode:main()) unigram look-ahead over " << nodes << " lexicon nodes, la in [" << fmt9(*std::min_element(la.begin(), la.end()))
+                  << ", " << fmt9(la[0]) << "]" << std::endl;
+      }
     }
     // the CTM's word symbols: the lexicon's words, else the units of --ctm-units / --lm-units, else decimal class ids
     std::map<int, std::string> ctm_symbols;

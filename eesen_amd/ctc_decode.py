@@ -87,6 +87,8 @@ def main(argv=None) -> int:
     ap.register("word-lm", "", "ARPA file of a word n-gram LM over the lexicon's words, stepped once per word (weight: --lm-weight)")
     ap.register("word-bonus", 0.0, "Added per word, in nats")
     ap.register("lm-skip-oov", False, "Drop the n-grams of --word-lm that hold a word outside the lexicon instead of refusing the file")
+    ap.register("lm-lookahead", False, "Rank the candidates of a frame as if the most probable word (by --word-lm's unigrams) that the "
+                                       "lexicon still allows had been paid already: a narrow --beam prunes better")
     ap.register("words-wspecifier", "", "Also write the word ids of every hypothesis (int32 vectors, the keys of <hyp-wspecifier>)")
     ap.register("words-table-out", "", "Write the lexicon's `word id` table to this file")
     ap.register("word-ref-rspecifier", "", "Reference word-id sequences: the word errors of the best hypotheses against them are counted")
@@ -177,6 +179,13 @@ def main(argv=None) -> int:
         elif o.lexicon_units or o.word_lm or o.words_wspecifier or o.words_table_out or o.word_ref_rspecifier or o.word_bonus != 0.0 or o.lm_skip_oov:
             raise kaldi_io.KaldiIOError("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and "
                                         "--word-ref-rspecifier need --lexicon")
+        if o.lm_lookahead:
+            if lex is None:
+                raise kaldi_io.KaldiIOError("--lm-lookahead needs --lexicon and --word-lm")
+            ctc.SetLmLookahead(1)          # (without --word-lm the library refuses the first decode call)
+            if lm is not None:
+                la = lex.Lookahead(lm)
+                log(f"unigram look-ahead over {la.size} lexicon nodes, la in [{float(la.min()):.9g}, {float(la[0]):.9g}]")
         # the CTM's word symbols: the lexicon's words, else the units of --ctm-units / --lm-units, else decimal class ids
         ctm_symbols, ctm = {}, None
         if o.ctm_out:

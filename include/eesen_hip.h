@@ -498,6 +498,25 @@ int eesen_ctc_decode_parallel_words(eesen_ctc_t* ctc, const int* frame_num_utt, 
                                     int* word_host /*S*nbest*T or NULL*/, int* word_len_host /*S*nbest or NULL*/,
                                     int* word_end_host /*S*nbest*T or NULL*/);
 
+/* ---- unigram LM look-ahead in the two lexicon searches (INTEGRATION.md "LM look-ahead") --------------------------------------------
+ * The LM's weight joins a score only when a word closes; with the look-ahead on, a frame's candidates are RANKED as if the best
+ * word still reachable had been paid already, so a narrow beam keeps the hypotheses inside frequent words.
+ *   u(w)  = the weight eesen_lm_step(lm, 0, w) returns: ln P(w) in fp32, or <unk>'s where the file has no unigram for w;
+ *   la[v] = max { u(w) : a spelling of w passes through or ends at lexicon node v } (comparisons only; la[0]: over the vocabulary).
+ * eesen_lex_lookahead writes la into out_host [nodes] (eesen_lex_info); no device work.  EESEN_ERR_INVALID: an LM whose K is not
+ * V + 1, cap < nodes.
+ * eesen_ctc_set_lm_lookahead(ctc, mode): 0 = off (the default), 1 = unigram; any other value is EESEN_ERR_INVALID.  With mode 1
+ * eesen_ctc_decode_parallel_lex and eesen_ctc_decode_parallel_words select a frame's best `beam` candidates by
+ *   (total + eta) + 0,  eta = lm_weight * la[v] + word_bonus  (fp32; the sum clamped at -1e30 like every score)
+ * in place of total, v the lexicon node the candidate stands on after the step (a stay: the entry's; a unit / an inside successor:
+ * the child; a space: the root; a closing successor: the root's child for the class).  A candidate is dead by its real total; the
+ * tie index, every carried value, the end of the utterance and the final ranking by the real total are unchanged, and a returned
+ * score keeps its meaning.  The look-ahead is context-independent: one table per (lexicon, LM) pair, uploaded when the pair changes.
+ * With the mode set, either call without a word LM is EESEN_ERR_INVALID; eesen_ctc_decode_parallel and _lm ignore the mode. */
+int eesen_lex_lookahead(eesen_lex_t* lex, eesen_lm_t* lm, float* out_host /*cap*/, int cap);
+int eesen_ctc_set_lm_lookahead(eesen_ctc_t* ctc, int mode);
+int eesen_ctc_get_lm_lookahead(eesen_ctc_t* ctc, int* mode);
+
 /* ---- time stamps and confidences of decoded hypotheses (INTEGRATION.md "Time stamps and CTM") --------------------------------------
  * Aligns every entry the LAST decode call on this Ctc returned (any of the four calls above) to the frames and says when each label
  * and each word was spoken and how sure the N-best list is of the word.  frame_num_utt, S, scores_dev, rows, K, ld, is_log: that

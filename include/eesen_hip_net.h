@@ -301,6 +301,13 @@ class Lexicon {
     words->resize(n);
     return true;
   }
+  /* The unigram look-ahead table of a word LM over this lexicon, eesen_lex_lookahead: one value per trie node, the largest unigram
+   * weight among the words whose spelling passes through or ends at the node. */
+  std::vector<BaseFloat> Lookahead(const TokenLm& lm) const {
+    std::vector<BaseFloat> la(NumNodes());
+    HipCheck(eesen_lex_lookahead(h_, lm.Handle(), la.data(), (int)la.size()));
+    return la;
+  }
   eesen_lex_t* Handle() const { return h_; }
 
  private:
@@ -469,6 +476,10 @@ class Ctc {
         if (lm_scores) (*lm_scores)[s].push_back(lsc[e]);
       }
   }
+  /* eesen_ctc_set_lm_lookahead: 0 = off, 1 = the DecodeParallel overloads that take a Lexicon and a TokenLm rank a frame's candidates
+   * with the unigram look-ahead (INTEGRATION.md "LM look-ahead"); it stays set.  With 1 a lexicon call without an LM is refused. */
+  void SetLmLookahead(int32 mode) { HipCheck(eesen_ctc_set_lm_lookahead(h_, mode)); }
+  int32 LmLookahead() const { int v = 0; HipCheck(eesen_ctc_get_lm_lookahead(h_, &v)); return v; }
   /* Time stamps and confidences of the entries the LAST DecodeParallel returned (any overload), eesen_ctc_decode_stamps: every entry is
    * aligned on the acoustic scores by AlignParallel's recurrence and tie rule, all of them in one launch.  frame_num_utt, net_out,
    * is_log: that call's; hyps: what it returned.  Per utterance s and returned entry i: label_start / label_end [labels] the frames
