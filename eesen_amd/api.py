@@ -363,9 +363,11 @@ class Net:
         """Net::Info (net.cc:336-354): topology + MomentStatistics of every parameter tensor."""
         return _net_info(self, 0)
 
-    def InfoGradient(self) -> str:
-        """Net::InfoGradient (net.cc:356-366): MomentStatistics of every momentum buffer (*_corr_)."""
-        return _net_info(self, 1)
+    def InfoGradient(self, with_accumulators: bool = False) -> str:
+        """Net::InfoGradient (net.cc:356-366): MomentStatistics of every momentum buffer (*_corr_); with_accumulators: followed by
+        those of the adaptive accumulators, as the reference's layers print them once an adaptive rule has run
+        (bilstm-layer.h:515-531, affine-trans-layer.h:150-155)."""
+        return _net_info(self, 1, with_accumulators)
 
     def BucketOrder(self) -> List[int]:
         buf = (C.c_int * 64)()
@@ -435,12 +437,17 @@ _LSTM_TENSORS = ["wei_gifo_x", "wei_gifo_m", "bias", "phole_i_c", "phole_f_c", "
 
 
 def _g(v: float) -> str:
-    return f"{v:g}"     # what operator<< prints for a float by default (6 significant digits)
+    """What operator<< prints for a float by default (6 significant digits, printf's %g) -- a NaN with its sign: 0 / 0 of a constant
+    tensor's skewness reads `-nan` or `nan` by the sign bit there, and include/eesen_hip_info.h prints the same doubles that way."""
+    if v != v:
+        import math
+        return "-nan" if math.copysign(1.0, v) < 0 else "nan"
+    return f"{v:g}"
 
 
-def _net_info(net: "Net", which: int) -> str:
+def _net_info(net: "Net", which: int, with_accumulators: bool = False) -> str:
     """The strings of Net::Info / Net::InfoGradient (net.cc:336-366) with the per-layer parts of bilstm-layer.h:496-560,
-    lstm-layer.h:175-196, affine-trans-layer.h:145-159."""
+    lstm-layer.h:175-196, affine-trans-layer.h:145-159; the same text as include/eesen_hip_info.h::NetInfo."""
     layers = net.layers()
     out = []
     if which == 0:
@@ -449,18 +456,22 @@ def _net_info(net: "Net", which: int) -> str:
     else:
         out.append("### Gradient stats :")
     for i, L in enumerate(layers):
-        m = net.TensorMoments(which, i)
-        stats = [f" ( min {_g(r[0])}, max {_g(r[1])}, mean {_g(r[2])}, variance {_g(r[3])}, skewness {_g(r[4])}, kurtosis {_g(r[5])} ) "
-                 for r in m]
+        fmt = lambda m: [f" ( min {_g(r[0])}, max {_g(r[1])}, mean {_g(r[2])}, variance {_g(r[3])}, skewness {_g(r[4])}, kurtosis {_g(r[5])} ) "
+                         for r in m]
+        stats = fmt(net.TensorMoments(which, i))
+        accu = fmt(net.TensorMoments(2, i)) if which == 1 and with_accumulators else []
         suf = "" if which == 0 else "corr_"
         body = ""
         if L["type"] in ("BiLstmParallel", "LstmParallel"):
             dirs = ["_fw_", "_bw_"] if L["type"] == "BiLstmParallel" else ["_"]
             names = [f"{t}{d}{suf}" for d in dirs for t in _LSTM_TENSORS]
             body = "    " + "".join(f"\n  {nm}  {st}" for nm, st in zip(names, stats))
+            if L["type"] == "BiLstmParallel":     # (lstm-layer.h prints no accumulators)
+                body += "".join(f"\n  {nm}accu  {st}" for nm, st in zip(names, accu))
         elif L["type"] == "AffineTransform":
             names = ["linearity", "bias"] if which == 0 else ["linearity_corr_", "bias_corr_"]
             body = "".join(f"\n  {nm}{st}" for nm, st in zip(names, stats))
+            body += "".join(f"\n  {nm}{st}" for nm, st in zip(["linearity_grad_accu", "bias_grad_accu"], accu))
         marker = net.LayerMarker(i)
         if which == 0:
             out.append(f"layer {i + 1} : {marker}, input-dim {L['input_dim']}, output-dim {L['output_dim']}, {body}")

@@ -159,7 +159,7 @@ def main(argv=None) -> int:
         net.Synchronize()
         print_progress(True)
         if not o.cross_validate:                                                  # :172-174
-            log(net.InfoGradient())
+            log(net.InfoGradient(o.opt_algorithm != "SGD"))
             net.Write(target_model_filename, o.binary)                            # :176-178
         el = max(time.time() - t0, 1e-9)
         log(f"Done {num_done} files, {counts.num_no_tgt_mat} with no targets, {counts.num_other_error} with other errors. "

@@ -248,7 +248,7 @@ def main(argv=None) -> int:
         net.Synchronize()
         if not o.cross_validate:                                                      # :236-240
             log(net.Info())
-            log(net.InfoGradient())
+            log(net.InfoGradient(o.opt_algorithm != "SGD"))
         if ctc.Dropped():
             log(f"{ctc.Dropped()} minibatch(es) were computed from a timed-out forward pass and are not in the statistics", "WARNING")
         if not o.cross_validate and rank == 0:

@@ -126,6 +126,18 @@ def test_net_output_extract(gpu, tmp_path):
         assert np.array_equal(got1[key], got4[key])
 
 
+def _info_block(stderr):
+    """The Net::Info / Net::InfoGradient part of a trainer's log, from `num-layers` through the last gradient-stats line, without the
+    `LOG (program:function:file) ` prefix that differs between the two trainers."""
+    lines = [re.sub(r"^LOG \(train-ctc-parallel:main\(\):\S+\) ", "", l) for l in stderr.splitlines()]
+    first = next(i for i, l in enumerate(lines) if l.startswith("num-layers "))
+    last = next(i for i, l in enumerate(lines) if l.startswith("### Gradient stats :"))
+    assert first < last
+    while last + 1 < len(lines) and (lines[last + 1].startswith("Layer ") or lines[last + 1].startswith("  ")):
+        last += 1
+    return lines[first:last + 1]
+
+
 def test_native_trainer_binary_equals_python_mirror(gpu, tmp_path):
     """eesen_amd/bin/train-ctc-parallel (host C++ over the C-ABI, its own Kaldi table readers) against the Python mirror on the
     same archives: the same library calls in the same order, so the written models are byte-identical and the report lines
@@ -152,6 +164,20 @@ def test_native_trainer_binary_equals_python_mirror(gpu, tmp_path):
         assert acc[0] == acc[1]
         assert "TRAINING STARTED" in r2.stderr and re.search(r"Done 14 files, 0 with no targets, 0 with other errors", r2.stderr)
         assert "Obj(log[Pzx])" in r2.stderr
+        # the two formatters of Net::Info / Net::InfoGradient (eesen_amd/api.py::_net_info, include/eesen_hip_info.h) arrange the same
+        # figures of the same model: line for line the same text
+        b_py, b_cc = _info_block(r1.stderr), _info_block(r2.stderr)
+        assert sum("( min " in l for l in b_py) == 2 * 26 and b_py[-1].startswith("Layer 4 : <Softmax>")     # 12 + 12 + 2 tensors, twice
+        assert b_py == b_cc, [(a, b) for a, b in zip(b_py, b_cc) if a != b][:3]
+    # ... and under an adaptive rule, where the accumulators' statistics follow the momentum buffers' (bilstm-layer.h:515-531)
+    ada = [o for o in opts if not o.startswith("--learn-rate")] + ["--learn-rate=0.002", "--opt-algorithm=RMSProp"]
+    r1 = _run(ada + ["scp:" + scp, "ark:" + lab, m_in, o_py])
+    r2 = subprocess.run([exe] + ada + ["scp:" + scp, "ark:" + lab, m_in, o_cc], capture_output=True, text=True, timeout=600)
+    assert r1.returncode == 0 and r2.returncode == 0, (r1.stderr[-1500:], r2.stderr[-1500:])
+    assert open(o_py, "rb").read() == open(o_cc, "rb").read()
+    b_py, b_cc = _info_block(r1.stderr), _info_block(r2.stderr)
+    assert sum("corr_accu   ( min " in l for l in b_py) == 24 and sum("_grad_accu ( min " in l for l in b_py) == 2
+    assert b_py == b_cc, [(a, b) for a, b in zip(b_py, b_cc) if a != b][:3]
     # the compressed archive of the reference's writer (tests/golden/compressed_feats.ark): cross-validation over it runs
     g = os.path.join(ROOT, "tests", "golden")
     ref = np.load(os.path.join(g, "compressed_feats.npz"))

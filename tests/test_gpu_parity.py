@@ -138,6 +138,34 @@ def test_train_step_parity(gpu, cfg_name):
         assert rel_err(p, w) < TOL, f"layer {li} {name}: parameter mismatch after update"
 
 
+def _oracle_trajectory(layers, batch, prec, lr, mmt, steps, rule=None, eps=1e-6, rho=0.9):
+    """[theta_-1, theta_0, ...] of the CPU oracle in `prec`, as float64."""
+    from oracle import net as onet
+    ora = onet.OracleNet(layers, prec); ora.set_train_options(lr, mmt)
+    if rule:
+        ora.set_update_algorithm(rule, eps, rho)
+    traj = [ora.get_params().astype(np.float64)]
+    for _ in range(steps):
+        onet.train_step(ora, batch, prec)
+        traj.append(ora.get_params().astype(np.float64))
+    return traj
+
+
+def _hold_deltas(layers, hip, o32, o64, scale, what):
+    """The parameter DELTA theta_k - theta_k-1 of every step and tensor, HIP against the f32 oracle, max-norm, in units of `scale`
+    (lr * max_grad: the largest step a clipped SGD update can take).  The parameters themselves move by ~1e-4 of their size per
+    step, so a comparison of parameters at 1e-4 cannot see a wrong rule; the deltas can.  Bar: max(TOL, 3 x floor), the floor being
+    the f32 oracle's own distance to the f64 oracle in the same metric (the fp32 spacing of a parameter of size 0.1 is already
+    1.5e-4 of a 5e-5 step)."""
+    for k in range(1, len(hip)):
+        d = [split_params(layers, np.asarray(t[k], np.float64) - np.asarray(t[k - 1], np.float64)) for t in (hip, o32, o64)]
+        for (li, name, dh), (_, _, d32), (_, _, d64) in zip(*d):
+            floor = float(np.max(np.abs(d32 - d64))) / scale
+            err = float(np.max(np.abs(dh - d32))) / scale
+            print(f"{what} step {k - 1} layer {li} {name}: delta error {err:.3e} of lr*max_grad, floor {floor:.3e}")
+            assert err < max(TOL, 3 * floor), f"{what} step {k - 1} layer {li} {name}: delta error {err:.3e} of lr*max_grad, floor {floor:.3e}"
+
+
 def test_momentum_and_clipping(gpu):
     """Three steps with the recipe's settings scaled so that clipping bites (bilstm-layer.h:846-883)."""
     layers, batch, res = _run_both("small_bi", lr=1e-3, mmt=0.9, max_grad=0.05, steps=3)
@@ -146,6 +174,10 @@ def test_momentum_and_clipping(gpu):
             assert rel_err(p, w) < TOL, f"step {step} layer {li} {name}"
     g = res[0]["grads"]
     assert np.max(np.abs(g)) > 0.05, "test must exercise clipping"
+    theta = nnet_io.flatten_params(layers)
+    o64 = _oracle_trajectory(layers, batch, "f64", 1e-3, 0.9, 3)
+    assert np.array_equal(o64[0], theta.astype(np.float64))
+    _hold_deltas(layers, [theta] + [r["params"] for r in res], [theta] + [r["ora_params"] for r in res], o64, 1e-3 * 0.05, "momentum + clip")
 
 
 def test_unaligned_dims(gpu):
@@ -468,12 +500,18 @@ def test_adaptive_update_rules(gpu, rule, tmp_path):
     net = Net.from_layers(layers); net.SetTrainOptions(0.002, 0.9); net.SetUpdateAlgorithm(rule, 1e-6, 0.9)
     ora = onet.OracleNet(layers, "f32"); ora.set_train_options(0.002, 0.9); ora.set_update_algorithm(rule, 1e-6, 0.9)
     ctc = Ctc()
+    theta = [net.GetParams()]
     for step in range(3):
         net.SetSeqLengths(batch.lens)
         diff = ctc.EvalParallel(batch.lens, net.Propagate(batch.feats), batch.labels)
         net.Backpropagate(diff)
         onet.train_step(ora, batch, "f32")
         assert rel_err(net.GetParams(), ora.get_params()) < TOL, f"step {step}"
+        if step == 0:       # the parameter deltas of the first step, as in test_momentum_and_clipping (the later steps are chaotic)
+            theta.append(net.GetParams())
+            o32, o64 = (_oracle_trajectory(layers, batch, prec, 0.002, 0.9, 1, rule) for prec in ("f32", "f64"))
+            assert np.array_equal(o32[1], ora.get_params().astype(np.float64))
+            _hold_deltas(layers, theta, o32, o64, 0.002 * 0.05, rule)
         # squares double the relative error, and a normalised step moves noise-level gradient entries by O(lr): looser bar
         assert rel_err(net.GetAccumulators(), ora.get_accu()) < 2e-3, f"step {step}"
     path = str(tmp_path / "ada.nnet")
