@@ -313,9 +313,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_mfma_gated_kernel(GemmParams 
 // gfx950 runs f32-input MFMA at the f32 VECTOR rate -- 1/16 of the bf16 MFMA rate (CDNA4 guide, section 3) -- and has no
 // TF32-like form.  An fp32 value is EXACTLY the sum of three bf16 values: hi = top 8 significant bits (truncation),
 // mid = top 8 bits of x - hi, lo = top 8 bits of x - hi - mid (each subtraction is exact in fp32; 8 + 8 + 8 = 24 bits).
-// So a*b = sum of nine bf16 x bf16 products, each exact in fp32; the three smallest (mid*lo, lo*mid, lo*lo <= 2^-23 |ab|
-// together) are dropped and the other six go through v_mfma_f32_32x32x16_bf16 with fp32 accumulation:
-//     a*b ~ hi*hi' + (hi*mid' + mid*hi') + (hi*lo' + lo*hi' + mid*mid'),   |error| <= 2^-23 |a*b|  (one fp32 rounding: 2^-24)
+// So a*b = sum of nine bf16 x bf16 products, each exact in fp32; the three smallest (mid*lo, lo*mid, lo*lo) are dropped and
+// the other six go through v_mfma_f32_32x32x16_bf16 with fp32 accumulation:
+//     a*b ~ hi*hi' + (hi*mid' + mid*hi') + (hi*lo' + lo*hi' + mid*mid'),   |error| typically <= 2^-23 |a*b|  (one fp32 rounding: 2^-24)
+// Worst case: a truncation to 8 significant bits leaves |mid| < 2^-7 |a| and |lo| < 2^-15 |a|, so the dropped three sum to less than
+// (2^-21 + 2^-30) |a*b| -- the figure tests/layer_restatement.py holds this mode to, element by element.
 // Six MFMAs of K = 16 at 32 cycles against eight f32 MFMAs of K = 2 at 64 cycles for the same 32x32x16 block: 2.67x the
 // f32 matrix rate at the accuracy of an fp32 GEMM (tests/test_gpu_gemm.py measures both against fp64).  The split costs
 // ~5 VALU operations per element, once per element per workgroup, on the way into LDS; VALU and matrix pipe are separate.

@@ -84,13 +84,17 @@ def _batch(rng, S, T, K):
     return y, tg, lens, mask
 
 
-@pytest.mark.parametrize("K,layout", [(K, lay) for K in (1, 51, 4000, 9001) for lay in ("pad4", "wide")] +
-                         [(1, "misaligned"), (51, "misaligned")])     # misaligned: the scalar path, at the small class counts
-def test_kernel_equals_restatement(gpu, K, layout):
+# (S, T) = (7, 23): 161 rows, 41 workgroup partials.  (7, 150): 1050 rows, 263 partials -- ce_reduce_kernel folds 256 at a time, so its
+# loop iterates twice.  (5, 1700): 8500 rows, more than the 2048 x 4 wavefronts of ce_eval_kernel's grid: the row stride's second pass.
+@pytest.mark.parametrize("K,layout,S,T", [pytest.param(K, lay, 7, 23, id=f"{K}-{lay}") for K in (1, 51, 4000, 9001) for lay in ("pad4", "wide")] +
+                         [pytest.param(K, "misaligned", 7, 23, id=f"{K}-misaligned") for K in (1, 51)] +     # misaligned: the scalar path, at the small class counts
+                         [pytest.param(5, lay, 7, 150, id=f"7x150-5-{lay}") for lay in ("pad4", "misaligned")] +
+                         [pytest.param(6, lay, 5, 1700, id=f"5x1700-6-{lay}") for lay in ("pad4", "wide")])
+def test_kernel_equals_restatement(gpu, K, layout, S, T):
     from eesen_amd.api import CE
     rng = np.random.default_rng(K)
-    S, T = 7, 23
     y, tg, lens, mask = _batch(rng, S, T, K)
+    assert (S, T) == (7, 23) or (mask[256 * 4 if T == 150 else 8192:] == 1).sum() >= 3               # valid rows in the second pass too
     want_diff, want_obj, want_correct = ce_call(y, tg, mask)
     ref64 = -float(np.sum(np.log(y[np.arange(len(tg)), tg].astype(np.float64)) * mask))
     stats = []
@@ -107,6 +111,30 @@ def test_kernel_equals_restatement(gpu, K, layout):
         assert st["correct"] == want_correct and st["frames"] == T * S and st["sequences"] == S
         stats.append((np.float64(st["obj"]).tobytes(), st["correct"]))
     assert stats[0] == stats[1]                                       # fixed-order reduction: the same bits on every run
+
+
+@pytest.mark.parametrize("layout", ["pad4", "misaligned"])
+def test_correct_follows_the_first_maximum_on_ties(gpu, layout):
+    """K = 130, two equal maxima per row: classes 3 and 67 (one lane's stride on the scalar path) and classes 5 and 70 (different lanes
+    on either path).  FindRowMaxId takes the FIRST: a target on the first maximum counts as correct, one on the second does not."""
+    from eesen_amd.api import CE
+    rng = np.random.default_rng(130)
+    S, T, K = 2, 4, 130
+    lens = np.array([T, T], np.int32)
+    mask = np.ones(S * T, np.float32)
+    y = rng.uniform(1e-4, 2e-3, (S * T, K)).astype(np.float32)
+    first = np.array([3, 3, 3, 3, 5, 5, 5, 5]); second = np.array([67, 67, 67, 67, 70, 70, 70, 70])
+    y[np.arange(8), first] = y[np.arange(8), second] = np.float32(0.4)
+    for tg, want in ((first, 8), (second, 0)):
+        tg = tg.astype(np.int32)
+        want_diff, want_obj, want_correct = ce_call(y, tg, mask)
+        assert want_correct == want
+        ce = CE()
+        net_out, keep = _upload(y, misalign=layout == "misaligned")
+        diff = _diff_matrix(len(tg), K, net_out)
+        ce.EvalParallel(net_out, tg, diff, lens)
+        assert np.array_equal(_read(diff).view(np.uint32), want_diff.view(np.uint32))
+        assert ce.stats()["correct"] == want
 
 
 def test_bad_targets_refused_on_valid_rows_only(gpu):
