@@ -411,6 +411,15 @@ class Net:
         """Test hook: what a recurrence kernel (1) / the milestone waiter (2) stores when it gives up."""
         check(self.lib.eesen_net_debug_set_error_word(self.h, int(value)))
 
+    def DebugLayerBuffer(self, layer: int, which: int) -> np.ndarray:
+        """Test hook (eesen_net_debug_layer_buffer): the T*S interior rows of LSTM layer `layer`'s gate activations (0), cell state
+        c (1), unmasked output m (2) or gate gradients DG (3), in the model file's column order (per direction g, i, f, o)."""
+        r, c = C.c_int(0), C.c_int(0)
+        check(self.lib.eesen_net_debug_layer_buffer(self.h, int(layer), int(which), None, 0, C.byref(r), C.byref(c)))
+        buf = np.empty((r.value, c.value), np.float32)
+        check(self.lib.eesen_net_debug_layer_buffer(self.h, int(layer), int(which), _np_ptr(buf), buf.size, C.byref(r), C.byref(c)))
+        return buf
+
     def Synchronize(self):
         check(self.lib.eesen_net_synchronize(self.h))
 

@@ -219,6 +219,9 @@ int eesen_net_debug_set_error_word(eesen_net_t* net, unsigned value) {
     EESEN_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(net->ctl.p + kCtlWords - 1), (int)value, 1, net->st));
   });
 }
+int eesen_net_debug_layer_buffer(eesen_net_t* net, int layer, int which, float* host, long cap_floats, int* rows, int* cols) {
+  return guard([&] { REQ_PTR(net); net->debug_layer_buffer(layer, which, host, cap_floats, rows, cols); });
+}
 int eesen_net_synchronize(eesen_net_t* net) {
   return guard([&] { REQ_PTR(net); net->sync(); });
 }

@@ -606,6 +606,44 @@ void Net::get_dropout_masks(int layer, float* fwd_host, float* rec_host, int* in
   if (info4) { info4[0] = L.cur_fwd_drop; info4[1] = L.cur_drop_mode; info4[2] = L.cur_twiddle_coin; info4[3] = (int)wf; }
 }
 
+// eesen_net_debug_layer_buffer: the T * S interior rows of one intermediate buffer of LSTM layer `layer`, in the FILE's column order
+// (per direction the gate blocks g, i, f, o of Hf columns for G / DG -- the order of the W_x rows, for_each_param -- and Hf cells for
+// c / m).  Read-only: it drains both streams and copies; no schedule knows of it.
+void Net::debug_layer_buffer(int layer, int which, float* host, long cap_floats, int* rows_out, int* cols_out) {
+  EESEN_REQUIRE(layer >= 0 && layer < (int)layers.size() && layers[layer].is_lstm(), EESEN_ERR_STATE, "eesen_net_debug_layer_buffer: not an LSTM layer");
+  EESEN_REQUIRE(which >= 0 && which <= 3, EESEN_ERR_INVALID, "eesen_net_debug_layer_buffer: which must be 0 (gates), 1 (c), 2 (m) or 3 (gate gradients)");
+  EESEN_REQUIRE(propagated, EESEN_ERR_STATE, "eesen_net_debug_layer_buffer: no Propagate yet");
+  const Layer& L = layers[layer];
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  const bool gates = which == 0 || which == 3;
+  const int H = L.H, Hf = L.Hf, nd = L.ndir, ldi = gates ? nd * 4 * H : nd * H, ldo = gates ? nd * 4 * Hf : nd * Hf;
+  const float* src = nullptr;
+  if (which == 3) {
+    const int slot = dg_owner[0] == layer ? 0 : dg_owner[1] == layer ? 1 : -1;
+    EESEN_REQUIRE(slot >= 0 && DGb[slot].p, EESEN_ERR_STATE,
+                  "eesen_net_debug_layer_buffer: no gate gradients of this layer (no Backpropagate since the last Propagate, or a lower layer has reused the buffer)");
+    src = DGb[slot].p;
+  } else {
+    src = which == 0 ? L.G.p : (which == 1 ? L.C.p : L.Y.p) + (size_t)S * ldi;   // (c, m: behind the boundary block t = -1)
+  }
+  if (rows_out) *rows_out = rows;
+  if (cols_out) *cols_out = ldo;
+  if (!host) return;
+  EESEN_REQUIRE(cap_floats >= (long)rows * ldo, EESEN_ERR_INVALID, "eesen_net_debug_layer_buffer: host buffer too small");
+  sync();
+  EESEN_HIP_CHECK(hipStreamSynchronize(st2));
+  std::vector<float> tmp((size_t)rows * ldi);
+  EESEN_HIP_CHECK(hipMemcpy(tmp.data(), src, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (long r = 0; r < rows; ++r) {
+    const float* in = tmp.data() + (size_t)r * ldi;
+    float* out = host + (size_t)r * ldo;
+    for (int d = 0; d < nd; ++d)
+      for (int u = 0; u < Hf; ++u)
+        if (gates) for (int q = 0; q < 4; ++q) out[(size_t)d * 4 * Hf + (size_t)q * Hf + u] = in[(size_t)d * 4 * H + u * 4 + q];
+        else out[(size_t)d * Hf + u] = in[(size_t)d * H + u];
+  }
+}
+
 // Decides what this Propagate applies to layer L and puts the masks in HBM: injected ones if the caller supplied them
 // (one-shot), otherwise drawn on the device from (drop_seed, draw counter).
 static void prepare_dropout(Net& net, Layer& L) {
@@ -741,6 +779,7 @@ void Net::forward_pass() {
   int ldx = pad4(layers[0].din);
   ++steps_since_clean;
   info_fwd_persistent = info_lstm_layers = info_fwd_bf16 = 0;
+  dg_owner[0] = dg_owner[1] = -1;   // (gate gradients of an earlier minibatch: eesen_net_debug_layer_buffer no longer hands them out)
   bool g_gated = false;  // the current layer's input GEMM was launched gated on the side stream
   int gated_rows = 0;    // ... for its first gated_rows rows (whole 128-row tiles); the rest is a plain GEMM
   int mid_r0 = 0, mid_r1 = 0;   // rows [mid_r0, mid_r1) of the current layer's input GEMM already ran on the side stream (see plan_mid)
@@ -1012,6 +1051,7 @@ void Net::backpropagate_impl(const float* out_diff, int ldd, float* in_diff, int
   if (max_y) DCF.reserve((size_t)S * max_y);
   ws2.reserve(need_ws);
   int dg_slot = 0;
+  dg_owner[0] = dg_owner[1] = -1;
   bool side_pending[2] = {false, false};
   deferred_buckets.clear();
   // Weight-gradient GEMMs on the side stream, under the next-lower layer's recurrence: decided per minibatch.  It pays beside the
@@ -1106,6 +1146,7 @@ void Net::backpropagate_impl(const float* out_diff, int ldd, float* in_diff, int
       // Gate-gradient buffers alternate between LSTM layers: while this layer's weight-gradient GEMMs (side stream)
       // still read DGb[slot], the next-lower layer's recurrence (main stream) already fills the other one.
       float* DGl = DGb[dg_slot].p;
+      dg_owner[dg_slot] = li;   // (for eesen_net_debug_layer_buffer alone)
       if (side_pending[dg_slot]) {  // the layer two LSTM layers up used this buffer: its gradient GEMMs must be done
         EESEN_HIP_CHECK(hipStreamWaitEvent(st, ev_grad[dg_slot], 0));
         side_pending[dg_slot] = false;

@@ -180,6 +180,10 @@ struct Net {
   bool in_train = true;                       // BiLstm::in_train (bilstm-layer.h:38), Net::SetTrainMode / SetTestMode
   unsigned long long drop_seed = 777, drop_counter = 0;   // masks are a pure function of (seed, draw counter, element)
   void set_train_mode(bool train) { in_train = train; }
+  // eesen_net_debug_layer_buffer (test hook): which LSTM layer's gate gradients each of the two DGb slots holds since the last
+  // Backpropagate (-1: none; cleared by Propagate), and the read-out itself
+  int dg_owner[2] = {-1, -1};
+  void debug_layer_buffer(int layer, int which, float* host, long cap_floats, int* rows_out, int* cols_out);
   void set_layer_dropout(int layer, const float* nine);
   void get_layer_dropout(int layer, float* nine) const;
   void set_dropout_masks(int layer, const float* fwd, long fwd_n, const float* rec, int rec_rows, long rec_n, int coin);

@@ -193,6 +193,15 @@ int eesen_net_plan_string(eesen_net_t* net, char* json, int cap);
 /* Test hook: stores `value` into that device word on the handle's stream, as a kernel that gave up would (1: a recurrence
  * kernel's bounded spin, 2: the side stream's wait for a forward milestone), so that the recovery paths can be exercised. */
 int eesen_net_debug_set_error_word(eesen_net_t* net, unsigned value);
+/* Test hook, read-only: one intermediate buffer of LSTM layer `layer` as the last Propagate / Backpropagate left it.  which: 0 the
+ * gate activations (they overwrite the pre-activations G), 1 the cell state c, 2 the unmasked output m (what the recurrence and the
+ * W_m gradient read), 3 the gate gradients DG of the last Backpropagate.  The call drains the handle's stream and the side stream
+ * and copies the T * S interior rows (row t * S + s; the boundary blocks t = -1 and t = T are left out) into `host`, in the MODEL
+ * FILE's column order: per direction the gate blocks g, i, f, o of H columns each (the order of the W_x rows) for 0 and 3, H cells
+ * for 1 and 2.  *rows and *cols receive the shape; with host == NULL nothing else happens, otherwise cap_floats >= rows * cols.
+ * EESEN_ERR_STATE: not an LSTM layer, nothing propagated, or (3) no Backpropagate since the last Propagate / a lower layer has
+ * reused the layer's gate-gradient buffer (two buffers alternate between the LSTM layers).  It changes no schedule; no tool calls it. */
+int eesen_net_debug_layer_buffer(eesen_net_t* net, int layer, int which, float* host, long cap_floats, int* rows, int* cols);
 /* Block until everything enqueued on the handle's stream has finished. */
 int eesen_net_synchronize(eesen_net_t* net);
 /* Seconds spent (HIP events on the handle's stream) in the phases of the last step, for bench.py:

@@ -2,8 +2,9 @@
 gate-input rows the two chains read first -- rows [0, r0) of the forward columns, rows [r1, rows) of the backward columns --, the
 other two quadrants follow on the side stream behind the middle rows, and the narrow forward kernel waits for them at a row guard
 (LstmLayerDev::guard).  Every element of G is the same dot product from the same kernel: with the switch on and off one Propagate ->
-CTC -> Backpropagate must agree BIT FOR BIT in the network output, the input gradient and every parameter gradient.  (The library
-hands out no gate buffer; the gradients are functions of every layer's gate activations, which overwrite G.)
+CTC -> Backpropagate must agree BIT FOR BIT in the network output, the input gradient and every parameter gradient.  (The gradients
+are functions of every layer's gate activations, which overwrite G.  That the schedules are RIGHT, not only equal -- every gate held
+against an fp64 restatement through the gate buffer eesen_net_debug_layer_buffer hands out -- is tests/test_gpu_lstm_gemms.py.)
 
 Shapes: 3-layer BiLSTM, D = 8, K = 5.  (H, S, T) = (64, 32, 33) is listed in the issue as "middle empty"; at that shape the middle is
 rows [256, 768) of 1056 -- not empty -- so the schedule applies there and the case checks it as one more unequal split; (64, 4, 33)

@@ -14,7 +14,7 @@ injected again before every Propagate), identical for every arm and the oracle. 
   Ds  EESEN_PERSISTENT=0: the per-step kernels of lstm.hip and their drop_mode branches
   N   the same layer and lengths WITHOUT dropout on the DROP = false rows of the same families (the plane, 4 x 32 and K-split tiles
       switched off; EESEN_FWD_MUX=0 as well, or the two windows of bi1024_s64 would run as one multiplexed launch of another kernel)
-EESEN_GEMM_MODE=f32 in all three (the GEMMs' planes are tested in test_gpu_gemm.py).
+EESEN_GEMM_MODE=f32 in all three (the GEMMs' planes: test_gpu_gemm.py; with the bounds Net chooses around an LSTM layer: test_gpu_lstm_gemms.py).
 Reference: oracle.net.OracleNet(layers, "f64") with the same masks, computed on a thread pool while the GPU arms run.
 
 Accuracy, per sequence over its valid rows: rel_err (max-norm) and the p999 of err_metrics of the output per (sequence, direction)

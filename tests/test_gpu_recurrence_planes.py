@@ -11,7 +11,7 @@ gradients are 2^-24 of its neighbours' only shows in its own rows of in_diff: th
 
 One LSTM layer is the whole Net; the test picks the top gradient `od`.  Reference: oracle.net.OracleNet(..., "f64") on the same
 fp32 inputs.  Arms (a fresh Net each: the switches are read when a Net is created):
-  P   the product path with EESEN_GEMM_MODE=f32 (the GEMMs' own planes are tested in test_gpu_gemm.py)
+  P   the product path with EESEN_GEMM_MODE=f32 (the GEMMs' own planes: test_gpu_gemm.py; with the bounds Net chooses around an LSTM layer: test_gpu_lstm_gemms.py)
   Pd  the same with the default GEMM mode: the path that ships
   F   the same tiles and grids on the fp32-input MFMA (EESEN_FWD_SPLIT=0, EESEN_BWD_F16=0)
   S   the per-step fp32 kernels (EESEN_PERSISTENT=0)

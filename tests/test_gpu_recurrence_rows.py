@@ -8,7 +8,7 @@ without a GPU, that every row of the table is run by a case here, held by anothe
 
 One recurrent layer (40 inputs) is the whole Net; the test picks the top gradient `od`.  Arms, a fresh Net each (the switches are
 read when a Net is created):
-  K   the case's switches and EESEN_GEMM_MODE=f32 (the GEMMs' planes are tested in test_gpu_gemm.py).  Plan() must name exactly the
+  K   the case's switches and EESEN_GEMM_MODE=f32 (the GEMMs' planes: test_gpu_gemm.py; with the bounds Net chooses around an LSTM layer: test_gpu_lstm_gemms.py).  Plan() must name exactly the
       case's forward and backward rows and its launches per pass, RecurrenceInfo() both passes persistent, and nothing recovered.
       The same Net runs everything twice: the same bits
   St  EESEN_GEMM_MODE=f32, EESEN_PERSISTENT=0: the per-step kernels of lstm.hip at the same shape -- held like K, not a yardstick
