@@ -46,6 +46,8 @@ same, weighted by y_j, for the denominator; + (ceil(K / 64) + 8) 2^-24 for the l
 and the division.  Plus one denormal quantum where y_k underflows."""
 import numpy as np
 
+from oracle.bf16_forward import round_bf16
+
 U = 2.0 ** -24
 ULP_EXP = 2.0                   # ASSUMED (see above): ulps of the device expf / logf
 C1 = 2.0 ** -21 + 2.0 ** -30    # mode 1: the three dropped products
@@ -75,8 +77,14 @@ def plane_eps(a, scale):
     return np.where(a == 0, 0.0, np.maximum(2.0 ** -22 * a, 2.0 ** -25 / s))
 
 
-def gemm(a, b, mode, scale_a=None, scale_b=None, bias=None):
-    """C = a b^T + bias in fp64 and its bound; a [M x K], b [N x K]; scale_*: half_scale of the prescribed bounds (mode 2)."""
+def gemm(a, b, mode, scale_a=None, scale_b=None, bias=None, bf16_operands=False):
+    """C = a b^T + bias in fp64 and its bound; a [M x K], b [N x K]; scale_*: half_scale of the prescribed bounds (mode 2).
+    bf16_operands: the "bf16 forward" variant (eesen_net_set_forward_precision; gemm.hip: the nprod == 1 body) -- BOTH operands
+    rounded to nearest-even bf16, which IS the statement (include/eesen_hip.h), so the value is round(a) round(b)^T + bias; a product
+    of two 8-bit significands is exact in fp32, so there is no plane term and only mode 0's accumulation term remains, on the rounded
+    operands.  The variant does not look at the GEMM mode: `mode` is ignored."""
+    if bf16_operands:
+        a, b, mode = round_bf16(a), round_bf16(b), 0
     a, b = f64(a), f64(b)
     K = a.shape[1]
     val = a @ b.T
@@ -95,10 +103,10 @@ def gemm(a, b, mode, scale_a=None, scale_b=None, bias=None):
     return val, bound + (K + 3) * U * mag
 
 
-def affine_forward(x, W, b, mode, x_bounded=False):
+def affine_forward(x, W, b, mode, x_bounded=False, bf16_operands=False):
     """affine-trans-layer.h:161-166.  x [rows x din], W [dout x din], b [dout]."""
     sx = half_scale(1.0) if x_bounded else half_scale(amax(x, 1))
-    return gemm(x, W, mode, sx, half_scale(amax(W, 1)), b)
+    return gemm(x, W, mode, sx, half_scale(amax(W, 1)), b, bf16_operands)
 
 
 def affine_in_diff(d, W, mode):

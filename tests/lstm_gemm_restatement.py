@@ -141,9 +141,11 @@ def recurrence(layer, x, lens, S, T, d=None, dtype=np.float32):
     return out
 
 
-def gemm(a, b, mode, scale_a=None, scale_b=None, bias=None):
-    """layer_restatement.gemm plus the underflow term of the module docstring."""
-    val, bound = R.gemm(a, b, mode, scale_a, scale_b, bias)
+def gemm(a, b, mode, scale_a=None, scale_b=None, bias=None, bf16_operands=False):
+    """layer_restatement.gemm plus the underflow term of the module docstring (bf16_operands: of the ROUNDED operands, one plane)."""
+    val, bound = R.gemm(a, b, mode, scale_a, scale_b, bias, bf16_operands)
+    if bf16_operands:
+        a, b, mode = R.round_bf16(a), R.round_bf16(b), 0
     n = 3 if mode == 1 else 1
     uf = n * (np.abs(f64(a)).sum(1)[:, None] + np.abs(f64(b)).sum(1)[None, :] + 2 * f64(a).shape[1]) + 3
     if mode == 2:
@@ -235,13 +237,13 @@ def gate_activation(G, b, tanh):
     return y, yn * (1 - yn) * b + yn * (1 - yn) * _exp_err(zmax) + yhi * k + FLUSH
 
 
-def gates_restated(layer, x, lens, S, T, mode, x_bounded):
+def gates_restated(layer, x, lens, S, T, mode, x_bounded, bf16_operands=False):
     """The gate activations of a layer whose W_m and peepholes are zero: (value, bound, G, bound of G), each [R x nd 4H]; padded frames
-    0 +- 0."""
+    0 +- 0.  bf16_operands: the GEMM of the bf16 forward variant (layer_restatement.gemm)."""
     P = unpack(layer)
     assert all(not np.any(w) for w in P["Wm"]) and all(not np.any(v) for d in P["peep"] for v in d), "the layer is not neutralised"
     s = prescribed_scales(P, x, None, x_bounded)
-    G, Gb = gemm(x, P["Wx"], mode, s["fwd_a"], s["fwd_b"], P["b"])
+    G, Gb = gemm(x, P["Wx"], mode, s["fwd_a"], s["fwd_b"], P["b"], bf16_operands)
     assert np.isfinite(G).all() and (np.abs(G) + Gb).max() < 2.0 ** 100
     H, nd = P["H"], P["nd"]
     val, bound = np.zeros_like(G), np.zeros_like(G)

@@ -127,7 +127,7 @@ assert len(ALL) == len(CASES) + len(PER_STEP)
 
 
 def _held_elsewhere():
-    from tests import test_gpu_bf16_forward as bf16
+    from tests import bf16_forward_cases as bf16
     from tests import test_gpu_recurrence_planes as planes
     held = {}
     for case in dc.CASES:                         # the DROP = true rows
@@ -140,8 +140,8 @@ def _held_elsewhere():
         held.setdefault(ft, f"tests/test_gpu_recurrence_planes.py {name}")
         if bwd == "ksplit_h":
             held.setdefault(bwd_ksplit_h(H // 256), f"tests/test_gpu_recurrence_planes.py {name}")
-    for H, S, T in bf16.SHAPES:                   # config 4's bf16 forward, one step deep
-        held.setdefault(fwd_bf(H // 256, 4, 1, 2, False), f"tests/test_gpu_bf16_forward.py SHAPES ({H}, {S}, {T})")
+    for name, (_, H, *_) in bf16.RECURRENCE.items():   # config 4's bf16 forward: per element, one step deep in m and c, both directions
+        held.setdefault(fwd_bf(H // 256, 4, 1, 2, False), f"tests/test_gpu_bf16_forward_fp64.py {name} (tests/bf16_forward_cases.py RECURRENCE)")
     return held
 
 

@@ -6,7 +6,14 @@ golden fixtures on the CPU by tests/test_bf16_forward_oracle.py).
 What is asserted: mode 1 equals the restatement with BOTH roundings, mode 2 (GEMM operands only, the round-3 variant) the one with
 the GEMM rounding only, each to 2e-4 of the largest softmax output -- and they differ from each other by far more, so the test can
 tell the two apart; the recurrence really ran on the bf16 kernel (eesen_net_bf16_recurrence_layers); the backward pass, which stays
-fp32, runs on the bf16 forward's activations and lands within what eight-bit operands allow of the fp32 path's gradients."""
+fp32, runs on the bf16 forward's activations and lands within what eight-bit operands allow of the fp32 path's gradients.
+
+What holds the variant's arithmetic ELEMENT BY ELEMENT is tests/test_gpu_bf16_forward_fp64.py: its one-product GEMM body (guarded,
+unguarded, the side stream's early middle, an Affine layer's) and every tile of the recurrence kernel, one step deep in m and c, each
+element against an fp64 restatement within a derived bound, on operands that span tens of binades; tests/recurrence_cases.py counts the
+four bf16 rows of the kernel table as held THERE.  This module's comparisons are whole-tensor max-norms on N(0, 1) features, and what
+they still hold that nothing else does is the FREE-RUNNING net -- two layers, projection and softmax, where a rounding flip travels
+down the chain -- and the fp32 backward pass on the bf16 forward's activations."""
 import numpy as np
 import pytest
 
