@@ -121,6 +121,9 @@ SIGNATURES = {
     "eesen_ctc_decode_stamps": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "eesen_ctc_get_stamp_times": (_i, [_vp, _vp]),
     "eesen_ctc_set_stamp_group": (_i, [_vp, _i]),
+    "eesen_ctc_score_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "eesen_ctc_decode_rescore": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
+    "eesen_ctc_get_rescore_times": (_i, [_vp, _vp]),
     "eesen_lex_lookahead": (_i, [_vp, _vp, _vp, _i]),
     "eesen_ctc_set_lm_lookahead": (_i, [_vp, _i]),
     "eesen_ctc_get_lm_lookahead": (_i, [_vp, _pi]),

@@ -631,6 +631,13 @@ class Stamps:
         self.path_score = path_score
 
 
+class Rescored:
+    """What Ctc.RescoreNbest returns: exact acoustic scores, LM scores and totals [S, nbest], and the new order of the first-pass ranks."""
+
+    def __init__(self, am_score, lm_score, total, order):
+        self.am_score, self.lm_score, self.total, self.order = am_score, lm_score, total, order
+
+
 def word_confidence(scores, word_len, word_ids, wstart, wend, conf_scale: float = 1.0) -> np.ndarray:
     """N-best posterior word confidences on the host in fp64 (eesen_word_confidence; no device work).  scores [n]; word_len [n] (< 0:
     not an entry); word_ids / wstart / wend [n, stride].  Returns conf [n, stride] float64, -1e30 beyond each entry's words."""
@@ -805,6 +812,48 @@ class Ctc:
                                                int(bool(is_log)), float(conf_scale), _np_ptr(ls), _np_ptr(le), _np_ptr(ws), _np_ptr(we),
                                                _np_ptr(wc), _np_ptr(ps)))
         return Stamps(ls, le, ws, we, wc, ps)
+
+    def ScoreParallel(self, frame_num_utt: Sequence[int], net_out: CuMatrix, hyps: Sequence[Sequence[Sequence[int]]],
+                      is_log: bool = False) -> List[np.ndarray]:
+        """Exact log-scores ln p(labels | x) (eesen_ctc_score_parallel; INTEGRATION.md "Rescoring").  hyps[s]: any number of labellings
+        of utterance s, each a list of class ids in [1, K) (the empty list: the empty labelling).  net_out: posteriors, or log-domain
+        scores with is_log=True.  Returns one float32 array per utterance; -1e30 (read <= -1e29) where a labelling has no path.
+        Statistics untouched."""
+        fn = np.ascontiguousarray(frame_num_utt, np.int32)
+        S = fn.size
+        if len(hyps) != S:
+            raise EesenError(-1, "ScoreParallel: one list of labellings per utterance")
+        hoff = np.zeros(S + 1, np.int32)
+        hoff[1:] = np.cumsum([len(h) for h in hyps])
+        ids, off = self._csr([l for h in hyps for l in h])
+        out = np.empty(int(hoff[-1]), np.float32)
+        check(self.lib.eesen_ctc_score_parallel(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
+                                                int(bool(is_log)), _np_ptr(hoff), _np_ptr(off), _np_ptr(ids), _np_ptr(out) if out.size else None))
+        return [out[hoff[s]:hoff[s + 1]] for s in range(S)]
+
+    def RescoreNbest(self, frame_num_utt: Sequence[int], net_out: CuMatrix, is_log: bool = False, lm: Optional["TokenLm"] = None,
+                     lm_weight: float = 1.0, bonus: float = 0.0, lm_eos: bool = False) -> "Rescored":
+        """Second pass over the entries the last DecodeParallel returned (eesen_ctc_decode_rescore; INTEGRATION.md "Rescoring").
+        frame_num_utt, net_out, is_log: that call's.  Every entry gets its exact acoustic score; total = am + lm_weight * g + bonus * n
+        with g the fp64 score of `lm` over the entry's n LM tokens (labels, or word ids under a lexicon; lm_eos: with </s>), or, with
+        lm=None, the first pass's LM sum.  Returns a Rescored: am_score / lm_score / total [S, nbest] float32 (-1e30 for infeasible
+        entries and beyond the returned count), order [S, nbest] int32 -- first-pass ranks by total descending, ties to the smaller
+        rank, entries without a score last.  self.hyp and everything else DecodeParallel left keep their first-pass order."""
+        fn = np.ascontiguousarray(frame_num_utt, np.int32)
+        S = fn.size
+        hlen = getattr(self, "hyp_len", None)
+        nbest = hlen.shape[1] if hlen is not None and hlen.shape[0] == S else 1   # (without a decode call the library refuses)
+        am, lms, tot = (np.empty((S, nbest), np.float32) for _ in range(3))
+        order = np.empty((S, nbest), np.int32)
+        check(self.lib.eesen_ctc_decode_rescore(self.h, _np_ptr(fn), S, C.c_void_p(net_out.ptr), net_out.rows, net_out.cols, net_out.stride,
+                                                int(bool(is_log)), lm.h if lm is not None else None, float(lm_weight), float(bonus),
+                                                int(bool(lm_eos)), _np_ptr(am), _np_ptr(lms), _np_ptr(tot), _np_ptr(order)))
+        return Rescored(am, lms, tot, order)
+
+    def RescoreTimes(self) -> dict:
+        out = np.zeros(3, np.float32)
+        check(self.lib.eesen_ctc_get_rescore_times(self.h, _np_ptr(out)))
+        return dict(zip(["lattices", "sweep", "host"], out.tolist()))
 
     def SetLmLookahead(self, mode: int):
         """eesen_ctc_set_lm_lookahead: 0 = off (the default), 1 = the unigram look-ahead in the two lexicon searches; it stays set."""

@@ -438,6 +438,28 @@ int eesen_ctc_decode_stamps(eesen_ctc_t* ctc, const int* frame_num_utt, int S, c
                        wconf_host, path_score_host);
   });
 }
+int eesen_ctc_score_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld, int is_log,
+                             const int* hyp_off, const int* label_off, const int* label_ids, float* score_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev); REQ_PTR(hyp_off); REQ_PTR(label_off);
+    EESEN_REQUIRE(S > 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
+    // (every labelling may be empty: then there is no label to point to)
+    EESEN_REQUIRE(label_ids != nullptr || hyp_off[S] <= 0 || label_off[hyp_off[S]] == label_off[0], EESEN_ERR_INVALID, "label_ids is null");
+    ctc->score_parallel(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, hyp_off, label_off, label_ids, score_host);
+  });
+}
+int eesen_ctc_decode_rescore(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld, int is_log,
+                             eesen_lm_t* lm, float lm_weight, float bonus, int use_eos, float* am_score_host, float* lm_score_host,
+                             float* total_host, int* order_host) {
+  return guard([&] {
+    REQ_PTR(ctc); REQ_PTR(frame_num_utt); REQ_PTR(scores_dev);
+    ctc->decode_rescore(frame_num_utt, S, scores_dev, rows, K, ld, is_log != 0, lm, lm_weight, bonus, use_eos != 0, am_score_host,
+                        lm_score_host, total_host, order_host);
+  });
+}
+int eesen_ctc_get_rescore_times(eesen_ctc_t* ctc, float* out3) {
+  return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->rescore_times(out3); });
+}
 int eesen_ctc_get_stamp_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->stamp_times(out3); });
 }

@@ -112,19 +112,26 @@ __device__ __forceinline__ void store_row(float* __restrict__ dst, const float (
 // ---- alpha / beta sweeps: grid (S, 2), one wavefront each -------------------------------------------
 // best_path: the same sweep in the max-plus semiring (delta rows of the Viterbi alignment, ctc_best_path_kernel below): the
 // two log-adds of a step become two maxima, and a cell none of whose predecessors is reachable stays at exactly -1e30.
-template <int PL, int NW, bool is_beta, bool best_path = false>
+// score: the alpha sweep of the training kernel, step for step, that keeps no row (ctc_score_kernel below: the exact log-score of a
+// labelling, INTEGRATION.md "Rescoring").  Lattice s reads the score rows of utterance utt[s], every gathered score is clamped from
+// below at -1e30 as the decode calls clamp theirs, the close takes the LARGER final cell as its base, and its one float per lattice
+// (through `pzx`) is the kernel's only global write.
+template <int PL, int NW, bool is_beta, bool best_path = false, bool score = false>
 __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld, int T, int S, const int* __restrict__ labx,
                                           const int* __restrict__ lens, const int* __restrict__ lablens,
                                           float* __restrict__ alpha, float* __restrict__ beta, float* __restrict__ pzx,
-                                          float* last, float (*edge)[NW][2], int lat0 = 0, int lpu = 1) {
+                                          float* last, float (*edge)[NW][2], int lat0 = 0, int lpu = 1,
+                                          const int* __restrict__ utt = nullptr) {
   static_assert(NW == 1 || PL >= 2, "a wave boundary hands over TWO positions of the neighbouring lane");
+  static_assert(!score || (!is_beta && !best_path), "the scoring sweep is the forward sum-semiring sweep");
   constexpr int Lpad = 64 * PL * NW;
   const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int len = lens[s], ll = lablens[s];
   const int* lab = labx + (size_t)s * Lpad;
   // the utterance whose score rows lattice s reads: its own in the training sweeps; in the best-path sweep lattice lat0 + s of lpu
   // per utterance (the N-best entries of ctc_stamp: one launch aligns them all)
-  const int us = best_path ? (lat0 + s) / lpu : s;
+  int us = best_path ? (lat0 + s) / lpu : s;
+  if constexpr (score) us = utt[s];
   const int j0 = (int)threadIdx.x * PL;
   // the lane whose chunk ends at a wave boundary publishes its two edge positions after every step; the lane on the other side
   // of the boundary takes them instead of the (wrapped) shuffle result
@@ -159,11 +166,23 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
       use2[i] = valid[i] && j < ll - 2 && (j & 1) && lab[j + 2] != c;           // :1532
     }
   }
+  if constexpr (score) {
+    // no lattice (lablens 0: not an entry, or more labels than the row holds) or no frames: nothing to sweep.  The empty labelling
+    // (one position) over no frames is the empty sum
+    if (len <= 0 || ll <= 0) {
+      if (threadIdx.x == 0) pzx[s] = (ll == 1 && len == 0) ? 0.f : kLogZero;
+      return;
+    }
+  }
   if (len <= 0) {   // (uniform over the workgroup: len belongs to the lattice)
     if (!is_beta && !best_path && threadIdx.x == 0) pzx[s] = kLogZero;
     return;
   }
-  float* out = (is_beta ? beta : alpha) + (size_t)s * T * Lpad + j0;
+  [[maybe_unused]] float* out = score ? nullptr : (is_beta ? beta : alpha) + (size_t)s * T * Lpad + j0;
+  auto gather = [&](const float* lr, int c) {   // (the scoring sweep: clamped as ctc_row_topc clamps the decode calls' scores)
+    if constexpr (score) return fmaxf(lr[c], kLogZero);
+    else return lr[c];
+  };
   float cur[PL];
   // The gathers of the log-probabilities run DEPTH steps ahead of their use (a ring of DEPTH register sets): one step
   // of look-ahead leaves the chain bound by the HBM latency of the gather (measured 1.66 us per step).
@@ -179,10 +198,10 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
     for (int i = 0; i < PL; ++i) {
       const int j = j0 + i;
       const bool on = valid[i] && (is_beta ? j > ll - 3 : j < 2);
-      const float v = lp[gi[i]];
+      const float v = gather(lp, gi[i]);
       cur[i] = on ? v : kLogZero;
     }
-    store_row<PL>(out + (size_t)t_first * Lpad, cur);
+    if constexpr (!score) store_row<PL>(out + (size_t)t_first * Lpad, cur);
     publish(0, cur);
   }
   float P[DEPTH][PL];
@@ -190,7 +209,7 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
   for (int u = 0; u < DEPTH; ++u) {
     const float* lr = row(1 + u);
 #pragma unroll
-    for (int i = 0; i < PL; ++i) P[u][i] = lr[gi[i]];
+    for (int i = 0; i < PL; ++i) P[u][i] = gather(lr, gi[i]);
   }
   for (int base = 1; base < len; base += DEPTH) {
     float Q[DEPTH][PL];
@@ -198,7 +217,7 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
     for (int u = 0; u < DEPTH; ++u) {  // gathers for steps base+DEPTH .. base+2*DEPTH-1
       const float* lr = row(base + DEPTH + u);
 #pragma unroll
-      for (int i = 0; i < PL; ++i) Q[u][i] = lr[gi[i]];
+      for (int i = 0; i < PL; ++i) Q[u][i] = gather(lr, gi[i]);
     }
 #pragma unroll
     for (int u = 0; u < DEPTH; ++u) {
@@ -235,7 +254,7 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
         }
 #pragma unroll
         for (int i = 0; i < PL; ++i) cur[i] = nxt[i];
-        store_row<PL>(out + (size_t)(t_first + dt * k) * Lpad, cur);
+        if constexpr (!score) store_row<PL>(out + (size_t)(t_first + dt * k) * Lpad, cur);
         publish(k, cur);
       }
     }
@@ -251,7 +270,15 @@ __device__ __forceinline__ void ctc_sweep(const float* __restrict__ logp, int ld
     __syncthreads();
     if (threadIdx.x == 0) {
       const float tmp1 = last[ll - 1], tmp2 = ll >= 2 ? last[ll - 2] : kLogZero;
-      pzx[s] = tmp1 + logf(1.f + ExpA(tmp2 - tmp1));
+      if constexpr (score) {
+        // the same two cells, the larger as the base: a labelling that ends on a label in the last frame (the final blank far below,
+        // or unreachable) keeps its score.  Where the final blank is the larger these are the training close's bits.
+        const float m = fmaxf(tmp1, tmp2), n = fminf(tmp1, tmp2);
+        const float a = m + logf(1.f + ExpA(n - m));
+        pzx[s] = a <= -1e29f ? kLogZero : a;   // no path: too few frames, or a zero on every one
+      } else {
+        pzx[s] = tmp1 + logf(1.f + ExpA(tmp2 - tmp1));
+      }
     }
   }
 }
@@ -278,6 +305,19 @@ __global__ __launch_bounds__(64 * NW) void ctc_best_path_kernel(const float* __r
                                                                 int lpu) {
   __shared__ float edge[2][NW][2];
   ctc_sweep<PL, NW, false, true>(logp, ld, T, S, labx, lens, lablens, delta, nullptr, nullptr, nullptr, edge, lat0, lpu);
+}
+
+// ---- exact log-score of labellings (INTEGRATION.md "Rescoring"): the forward sum-semiring sweep over any number of lattices, lattice
+// i on the score rows of utterance utt[i].  Nothing is stored but score[i]: the launch needs no row buffer, so all the lattices of a
+// call (S * nbest of a decode call, or the host's CSR lists) go in ONE launch.
+template <int PL, int NW>
+__global__ __launch_bounds__(64 * NW) void ctc_score_kernel(const float* __restrict__ logp, int ld, int T, int S,
+                                                            const int* __restrict__ labx, const int* __restrict__ lens,
+                                                            const int* __restrict__ lablens, const int* __restrict__ utt,
+                                                            float* __restrict__ score) {
+  __shared__ float last[64 * PL * NW];
+  __shared__ float edge[2][NW][2];
+  ctc_sweep<PL, NW, false, false, true>(logp, ld, T, S, labx, lens, lablens, nullptr, nullptr, score, last, edge, 0, 1, utt);
 }
 
 // Traceback: the move into (t, j) is re-derived from the stored delta row t-1 with the sweep's own comparisons on the sweep's own
@@ -595,6 +635,19 @@ void ctc_best_path(hipStream_t st, const float* logp, int ld, int T, int S, int 
   });
   if (!launched) throw Error(EESEN_ERR_INVALID, "ctc: no lattice kernel for this padded label length / wave count (at most 4096 positions)");
   check_launch("ctc_best_path");
+}
+
+void ctc_score(hipStream_t st, const float* logp, int ld, int T, int S, int NL, int Lpad, const int* labx, const int* lens,
+               const int* lablens, const int* utt, float* score, int waves) {
+  if (NL <= 0) return;
+  const int nw = ctc_sweep_waves(Lpad, waves);
+  const int pl = Lpad / (64 * nw);
+  const bool launched = with_sweep_shape(pl, nw, [&](auto PL, auto NW) {
+    hipLaunchKernelGGL((ctc_score_kernel<decltype(PL)::value, decltype(NW)::value>), dim3(NL), dim3(64 * nw), 0, st, logp, ld, T, S, labx, lens,
+                       lablens, utt, score);
+  });
+  if (!launched) throw Error(EESEN_ERR_INVALID, "ctc: no lattice kernel for this padded label length / wave count (at most 4096 positions)");
+  check_launch("ctc_score");
 }
 
 void ctc_traceback(hipStream_t st, const float* delta, int T, int S, int Lpad, const int* labx, const int* lens, const int* lablens,

@@ -668,26 +668,31 @@ __global__ __launch_bounds__(64) void ctc_word_hyp_kernel(const int* __restrict_
 // labels the hypothesis kernels left on the device -- no host round trip between the search and the alignment of its results.
 __global__ __launch_bounds__(256) void ctc_hyp_lattices_kernel(const int* __restrict__ hyp, const int* __restrict__ hyp_len,
                                                                const int* __restrict__ lens, int T, int N, int Lpad,
-                                                               int* __restrict__ labx, int* __restrict__ lablens, int* __restrict__ lat_lens) {
+                                                               int* __restrict__ labx, int* __restrict__ lablens, int* __restrict__ lat_lens,
+                                                               int* __restrict__ utt) {
   const int i = blockIdx.x;
   const int U = hyp_len[i];
-  const bool have = U >= 1 && U <= T && 2 * U + 1 <= Lpad;   // (U <= T: a label needs a frame; the hypothesis rows hold T labels)
+  // utt != null: the lattices of the scoring sweep (ctc_score), where the empty hypothesis is a lattice of its own -- one blank
+  // position over the utterance's frames -- and an entry without a lattice is marked by lablens = 0
+  const bool scoring = utt != nullptr;
+  const bool have = U >= (scoring ? 0 : 1) && U <= T && 2 * U + 1 <= Lpad;   // (U <= T: a label needs a frame; the hypothesis rows hold T labels)
   const int ll = have ? 2 * U + 1 : 0;
   const int* h = hyp + (size_t)i * T;
   int* lx = labx + (size_t)i * Lpad;
   for (int j = threadIdx.x; j < Lpad; j += blockDim.x) lx[j] = j < ll ? ((j & 1) ? h[j >> 1] : 0) : -1;
   if (threadIdx.x == 0) {
-    lablens[i] = have ? ll : 1;
+    lablens[i] = have ? ll : scoring ? 0 : 1;
     lat_lens[i] = have ? lens[i / N] : 0;
+    if (scoring) utt[i] = i / N;
   }
 }
 
 }  // namespace
 
 void ctc_hyp_lattices(hipStream_t st, const int* hyp, const int* hyp_len, const int* lens, int T, int NL, int N, int Lpad, int* labx,
-                      int* lablens, int* lat_lens) {
+                      int* lablens, int* lat_lens, int* utt) {
   if (NL <= 0) return;
-  hipLaunchKernelGGL(ctc_hyp_lattices_kernel, dim3(NL), dim3(256), 0, st, hyp, hyp_len, lens, T, N, Lpad, labx, lablens, lat_lens);
+  hipLaunchKernelGGL(ctc_hyp_lattices_kernel, dim3(NL), dim3(256), 0, st, hyp, hyp_len, lens, T, N, Lpad, labx, lablens, lat_lens, utt);
   check_launch("ctc_hyp_lattices");
 }
 

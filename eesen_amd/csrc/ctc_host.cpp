@@ -2,6 +2,7 @@
 // decoding.  Replaces eesen::Ctc::EvalParallel / ErrorRateMSeq (the reference's src/net/ctc-loss.cc:101-194,
 // :235-298).  The lattice arithmetic itself is in ctc.hip.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -396,6 +397,7 @@ void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int
   dec_lens.assign(frame_num_utt, frame_num_utt + S);
   dec_N = N; dec_T = T; dec_mode = lex ? 1 : 0; dec_fused = fused;   // (decode_stamps: the hypotheses stay in dec_out and decode_pin)
   dec_space = lex ? lex->space : -1;
+  dec_V = lex ? lex->V() : 0;
 
   // results and the guard word's value when they were computed, through one pinned slot
   int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
@@ -497,6 +499,7 @@ void Ctc::decode_parallel_words(const int* frame_num_utt, int S, const float* sc
   dec_rows = rows; dec_S = S; dec_C = Cc;
   dec_lens.assign(frame_num_utt, frame_num_utt + S);
   dec_N = N; dec_T = T; dec_mode = 2; dec_fused = true;
+  dec_V = lex->V();
 
   // results and the guard word's value when they were computed, through one pinned slot
   int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
@@ -712,6 +715,199 @@ void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, in
       }
     }
   }
+}
+
+// Exact log-scores of labellings given by the host (INTEGRATION.md "Rescoring").  The lattices are expanded here and uploaded as
+// upload_lattices does, into buffers of this call's own: labx, alpha and the last_* accessors of eval_parallel stay as they are.
+void Ctc::score_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* hyp_off,
+                         const int* label_off, const int* label_ids, float* score_host) {
+  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
+  EESEN_REQUIRE(K > 0 && ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  const int T = rows / S;
+  EESEN_REQUIRE(hyp_off[0] == 0, EESEN_ERR_INVALID, "hyp_off must start at 0");
+  for (int s = 0; s < S; ++s) {
+    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
+    EESEN_REQUIRE(hyp_off[s + 1] >= hyp_off[s], EESEN_ERR_INVALID, "labelling offsets must be non-decreasing");
+  }
+  const int NH = hyp_off[S];
+  constexpr int kMaxLabels = 2047;   // L' <= 4096
+  int maxU = 0;
+  for (int h = 0; h < NH; ++h) {
+    const int U = label_off[h + 1] - label_off[h];
+    EESEN_REQUIRE(U >= 0, EESEN_ERR_INVALID, "label offsets must be non-decreasing");
+    EESEN_REQUIRE(U <= kMaxLabels, EESEN_ERR_INVALID, "expanded label length above 4096 (2047 labels per labelling) is not supported");
+    maxU = std::max(maxU, U);
+  }
+  if (NH > 0)
+    for (int i = label_off[0]; i < label_off[NH]; ++i)
+      EESEN_REQUIRE(label_ids[i] >= 1 && label_ids[i] < K, EESEN_ERR_INVALID, "label id outside [1, K)");
+  if (NH == 0) return;
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  int PL = 1;
+  while (64 * PL < 2 * maxU + 1) PL *= 2;
+  const int Lpad = 64 * PL;
+
+  const size_t n_labx = (size_t)NH * Lpad, n_in = n_labx + 3 * (size_t)NH, n_int = n_in + NH;
+  std::vector<int> hbuf(n_in);
+  int* labx_h = hbuf.data();
+  int* ll_h = labx_h + n_labx;
+  int* lens_h = ll_h + NH;
+  int* utt_h = lens_h + NH;
+  std::fill(labx_h, labx_h + n_labx, -1);
+  for (int s = 0; s < S; ++s) {
+    for (int h = hyp_off[s]; h < hyp_off[s + 1]; ++h) {
+      const int U = label_off[h + 1] - label_off[h];
+      const int* lab = label_ids + label_off[h];
+      int* lx = labx_h + (size_t)h * Lpad;
+      for (int l = 0; l < U; ++l) { lx[2 * l] = 0; lx[2 * l + 1] = lab[l]; }
+      lx[2 * U] = 0;
+      ll_h[h] = 2 * U + 1;
+      lens_h[h] = frame_num_utt[s];
+      utt_h[h] = s;
+    }
+  }
+  if ((!is_log && logp.cap < (size_t)rows * K) || score_i.cap < n_int) EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  if (!is_log) logp.reserve((size_t)rows * K);
+  score_i.reserve(n_int);
+  int* labx_d = score_i.p;
+  int* ll_d = labx_d + n_labx;
+  int* lens_l = ll_d + NH;
+  int* utt_d = lens_l + NH;
+  float* score_d = reinterpret_cast<float*>(utt_d + NH);
+  PinBuf& sp = stage[stage_idx++ & 1];   // in stream order (see upload_lattices)
+  int* pinned = static_cast<int*>(loss_slot(sp, n_in * sizeof(int)));
+  std::copy(hbuf.begin(), hbuf.end(), pinned);
+  EESEN_HIP_CHECK(hipMemcpyAsync(labx_d, pinned, n_in * sizeof(int), hipMemcpyHostToDevice, st));
+  sp.used(st);
+
+  rev[0].record(st);
+  if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
+  rev[1].record(st);
+  ctc_score(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, NH, Lpad, labx_d, lens_l, ll_d, utt_d, score_d, sweep_waves);
+  rev[2].record(st);
+  rescore_host_s = 0;
+
+  float* out = static_cast<float*>(loss_slot(score_pin, ((size_t)NH + 1) * sizeof(float)));
+  EESEN_HIP_CHECK(hipMemcpyAsync(out, score_d, (size_t)NH * sizeof(float), hipMemcpyDeviceToHost, st));
+  reinterpret_cast<unsigned*>(out)[NH] = 0;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + NH, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  score_pin.used(st);
+  score_pin.wait();
+  // computed from a timed-out forward pass (guard word set): NaN, never garbage with status OK
+  const bool bad = reinterpret_cast<const unsigned*>(out)[NH] != 0;
+  if (score_host)
+    for (int h = 0; h < NH; ++h) score_host[h] = bad ? std::numeric_limits<float>::quiet_NaN() : out[h];
+}
+
+// Second pass over the last decode call's entries.  The hypotheses are where decode_stamps finds them; their lattices are built on
+// the device (ctc_hyp_lattices in its scoring form) and swept in one launch; the LM scores and the ranking are the host's.
+void Ctc::decode_rescore(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const TokenLm* lm,
+                         float lm_weight, float bonus, bool use_eos, float* am_host, float* lm_host, float* total_host, int* order_host) {
+  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "rescoring: no decode call on this Ctc yet");
+  EESEN_REQUIRE(S == dec_S && rows == dec_rows, EESEN_ERR_STATE, "rescoring: S or rows differ from the last decode call's");
+  EESEN_REQUIRE(K > 0 && ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(bonus), EESEN_ERR_INVALID, "lm_weight and bonus must be finite");
+  if (lm) {
+    EESEN_REQUIRE(!use_eos || lm->has_eos, EESEN_ERR_INVALID, "use_eos on an LM whose file has no </s>");
+    if (dec_mode == 0) EESEN_REQUIRE(lm->K == K, EESEN_ERR_INVALID, "the rescoring LM was built for another class count K than the scores have");
+    else EESEN_REQUIRE(lm->K == dec_V + 1, EESEN_ERR_INVALID, "the rescoring word LM's K must be the lexicon's word count + 1");
+  }
+  for (int s = 0; s < S; ++s)
+    EESEN_REQUIRE(frame_num_utt[s] == dec_lens[s], EESEN_ERR_STATE, "rescoring: frame_num_utt differs from the last decode call's");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  const int T = dec_T, N = dec_N;
+  const size_t NL = (size_t)S * N, n_hyp = NL * T;
+  const size_t n_dec = dec_mode == 2 ? 3 * n_hyp + 4 * NL : n_hyp + (dec_fused ? 3 : 2) * NL;
+  const int* dout = decode_pin.as<int>();
+  const int* hyp_h = dout;
+  const int* hlen = dout + n_hyp;
+  const float* z = reinterpret_cast<const float*>(hlen + NL);   // totals, then (fused) the LM sums
+  const float kNaN = std::numeric_limits<float>::quiet_NaN();
+  auto all_bad = [&] {   // decoded or scored from a timed-out forward pass (guard word set): NaN and -1, never garbage with status OK
+    if (am_host) std::fill(am_host, am_host + NL, kNaN);
+    if (lm_host) std::fill(lm_host, lm_host + NL, kNaN);
+    if (total_host) std::fill(total_host, total_host + NL, kNaN);
+    if (order_host) std::fill(order_host, order_host + NL, -1);
+  };
+  if (dout[n_dec] != 0) { all_bad(); return; }
+
+  constexpr int kMaxLabels = 2047;   // L' <= 4096; an entry beyond has no lattice (ctc_hyp_lattices) and reads as infeasible
+  int maxU = 0;
+  for (size_t i = 0; i < NL; ++i)
+    if (hlen[i] <= kMaxLabels) maxU = std::max(maxU, hlen[i]);
+  int PL = 1;
+  while (64 * PL < 2 * maxU + 1) PL *= 2;
+  const int Lpad = 64 * PL;
+  const size_t n_int = NL * Lpad + 4 * NL;
+  if ((!is_log && logp.cap < (size_t)rows * K) || score_i.cap < n_int) EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  if (!is_log) logp.reserve((size_t)rows * K);
+  score_i.reserve(n_int);
+  int* labx_d = score_i.p;
+  int* ll_d = labx_d + NL * Lpad;
+  int* lens_l = ll_d + NL;
+  int* utt_d = lens_l + NL;
+  float* score_d = reinterpret_cast<float*>(utt_d + NL);
+  const int* lens_d = dec_i.p + (size_t)dec_rows * dec_C;
+
+  rev[0].record(st);
+  if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
+  ctc_hyp_lattices(st, dec_out.p, dec_out.p + n_hyp, lens_d, T, (int)NL, N, Lpad, labx_d, ll_d, lens_l, utt_d);
+  rev[1].record(st);
+  ctc_score(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, (int)NL, Lpad, labx_d, lens_l, ll_d, utt_d, score_d, sweep_waves);
+  rev[2].record(st);
+
+  float* out = static_cast<float*>(loss_slot(score_pin, (NL + 1) * sizeof(float)));
+  EESEN_HIP_CHECK(hipMemcpyAsync(out, score_d, NL * sizeof(float), hipMemcpyDeviceToHost, st));
+  reinterpret_cast<unsigned*>(out)[NL] = 0;
+  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + NL, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  score_pin.used(st);
+  score_pin.wait();
+  if (reinterpret_cast<const unsigned*>(out)[NL] != 0) { all_bad(); return; }
+
+  const auto t0 = std::chrono::steady_clock::now();
+  const int* w_out = dout + n_hyp + 3 * NL;   // (unspaced mode: words, ends [NL][T], counts [NL])
+  std::vector<float> tot(N);
+  std::vector<int> ord(N);
+  for (int s = 0; s < S; ++s) {
+    int nf = 0;   // feasible entries, in first-pass rank order
+    for (int r = 0; r < N; ++r) {
+      const size_t i = (size_t)s * N + r;
+      const int U = hlen[i];
+      const float a = out[i];
+      const bool feasible = U >= 0 && a > -1e29f;
+      float g32 = -1e30f;
+      tot[r] = -1e30f;
+      if (feasible) {
+        const int* tok = dec_mode == 0 ? hyp_h + i * T : dec_mode == 1 ? dec_word.data() + i * T : w_out + i * T;
+        const int n = dec_mode == 0 ? U : dec_mode == 1 ? dec_word_len[i] : w_out[2 * n_hyp + i];
+        const double g = lm ? lm->score(tok, n, use_eos, nullptr) : dec_fused ? (double)z[NL + i] : 0.0;
+        g32 = (float)g;
+        tot[r] = (float)((double)a + (double)lm_weight * g + (double)bonus * n);
+        ord[nf++] = r;
+      }
+      if (am_host) am_host[i] = feasible ? a : -1e30f;
+      if (lm_host) lm_host[i] = g32;
+      if (total_host) total_host[i] = tot[r];
+    }
+    // by total, descending; a tie keeps the first-pass order; then the entries without a score, in rank order
+    std::stable_sort(ord.begin(), ord.begin() + nf, [&](int x, int y) { return tot[x] > tot[y]; });
+    std::vector<char> placed(N, 0);
+    for (int k = 0; k < nf; ++k) placed[ord[k]] = 1;
+    for (int r = 0; r < N; ++r)
+      if (!placed[r]) ord[nf++] = r;
+    if (order_host) std::copy(ord.begin(), ord.end(), order_host + (size_t)s * N);
+  }
+  rescore_host_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void Ctc::rescore_times(float* out3) {
+  rev[2].wait();
+  for (int i = 0; i < 2; ++i) {
+    float ms = 0.f;
+    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, rev[i], rev[i + 1]));
+    out3[i] = ms * 1e-3f;
+  }
+  out3[2] = (float)rescore_host_s;
 }
 
 void Ctc::stamp_times(float* out3) {

@@ -221,6 +221,13 @@ int ctc_sweep_waves(int Lpad, int waves = 0);
 // lens, lablens and delta are indexed by i): the N-best entries of a decode call, lpu = nbest (Ctc::decode_stamps).
 void ctc_best_path(hipStream_t st, const float* scores, int ld, int T, int S, int Lpad, const int* labx, const int* lens,
                    const int* lablens, float* delta, int waves = 0, int lattices = 0, int lat0 = 0, int lpu = 1);
+// ctc_score: the exact log-score of NL labellings (INTEGRATION.md "Rescoring"): the alpha sweep of ctc_alpha_beta, step for step, that
+// stores no row; one workgroup per lattice, all in one launch.  Lattice i (labx [NL][Lpad], lens / lablens / utt [NL]) reads the score
+// rows of utterance utt[i] in [0, S); scores [T*S x K] (ld) log-domain, clamped from below at -1e30 as they are read.  score [NL] =
+// logadd of the two final cells with the larger as the base; -1e30 where no path exists (and where lablens[i] = 0: no lattice); 0 for
+// the one-position lattice of the empty labelling over no frames.
+void ctc_score(hipStream_t st, const float* scores, int ld, int T, int S, int NL, int Lpad, const int* labx, const int* lens,
+               const int* lablens, const int* utt, float* score, int waves = 0);
 // ctc_traceback: from argmax(delta[n-1][L'-1], delta[n-1][L'-2]) (the final blank wins a tie) back to t = 0, the smallest move winning
 // among equal predecessors.  ali / pos [T*S] (row t*S + s): class id / lattice position per frame, -1 on rows t >= lens[s] and on
 // every row of an utterance without a feasible path; score [S]: the path's log-score, -1e30 without one.
@@ -233,8 +240,10 @@ void ctc_stamp(hipStream_t st, const int* pos, int T, int NL, int G, const int* 
 // ctc_hyp_lattices (ctc_decode.hip): the expanded labels of the NL = S * N hypotheses ctc_hyp / ctc_word_hyp left, for the sweeps above.
 // labx [NL][Lpad] blank-interleaved, -1 padded; lablens [NL] = 2 U + 1; lat_lens [NL] = the utterance's frames, or 0 -- no lattice --
 // for the empty hypothesis, for one of more labels than (Lpad - 1) / 2 and for ranks beyond the returned count (hyp_len < 0).
+// utt != null: the lattices of ctc_score instead -- the empty hypothesis gets its one-position lattice (lablens 1) and its utterance's
+// frames, an entry without a lattice lablens = 0 and no frames, and utt [NL] = i / N, the utterance whose score rows lattice i reads.
 void ctc_hyp_lattices(hipStream_t st, const int* hyp, const int* hyp_len, const int* lens, int T, int NL, int N, int Lpad, int* labx,
-                      int* lablens, int* lat_lens);
+                      int* lablens, int* lat_lens, int* utt = nullptr);
 // Prefix beam search, lexicon-free or along a lexicon trie (ctc_decode.hip; the computation: INTEGRATION.md "Decoding").  scores: [T*S x K] (ld) log-domain.
 // ctc_row_topc: per row t*S + s with t < lens[s] the Cc = min(max_classes, K - 1) best non-blank classes -- ids ascending in
 // cid [rows][Cc], their scores in csc [rows][Cc], the blank's in sblank [rows]; every score clamped from below at -1e30.

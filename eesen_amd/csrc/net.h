@@ -298,6 +298,13 @@ struct Ctc {
   PhaseTimer stamp_timer;      // phases: lattice build (with the logarithm), sweep + traceback, stamps
   PinBuf stamp_pin;            // results of decode_stamps (D2H)
   int stamp_group = 0;         // eesen_ctc_set_stamp_group: lattices per sweep launch, 0 = as many as kStampDeltaBytes holds (tuning.h)
+  // score_parallel / decode_rescore (INTEGRATION.md "Rescoring"): lattices, expanded-label lengths, frame counts and utterance of
+  // every lattice, then the scores.  Nothing else: the scoring sweep keeps no row
+  DevBuf<int> score_i;
+  DevEvent rev[3] = {DevEvent(true), DevEvent(true), DevEvent(true)};   // rescore_times: lattice build (+ log), sweep
+  double rescore_host_s = 0;   // ... and the host's LM scoring and ranking of the last decode_rescore
+  PinBuf score_pin;            // results of the scoring sweep (D2H)
+  int dec_V = 0;               // the lexicon's word count of the last decode call (0: none): what a second word LM must fit
   // the tables of the token LM the last decode_parallel_lm used (lm.h), keyed by the model's serial
   DevBuf<int> lm_i;
   DevBuf<float> lm_f;
@@ -365,6 +372,17 @@ struct Ctc {
   void decode_stamps(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, double conf_scale,
                      int* lstart_host, int* lend_host, int* wstart_host, int* wend_host, float* wconf_host, float* path_score_host);
   void stamp_times(float* out3);
+  // Exact log-scores ln p(labels | x) (INTEGRATION.md "Rescoring"; ctc_score in ctc.hip): utterance s has the labellings
+  // hyp_off[s] .. hyp_off[s + 1], labelling h the labels label_ids[label_off[h] .. label_off[h + 1]) (none: the empty labelling).
+  // Touches neither the statistics nor the lattices of the last eval_parallel; the logarithms borrow `logp`.
+  void score_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* hyp_off,
+                      const int* label_off, const int* label_ids, float* score_host);
+  // The last decode call's entries scored exactly and ranked again: total = am + lm_weight * g + bonus * n with g the second LM's
+  // fp64 score of the entry's LM tokens (lm == null: the first pass's LM sum).  am / lm / total (float) and order (int) [S][nbest];
+  // any may be null.  Leaves what the decode call left untouched.
+  void decode_rescore(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const TokenLm* lm,
+                      float lm_weight, float bonus, bool use_eos, float* am_host, float* lm_host, float* total_host, int* order_host);
+  void rescore_times(float* out3);
   // the candidate classes the last decode_parallel selected: ids / scores [rows][C'], blank [rows]; rows beyond an utterance: -1 / -1e30
   void get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc);
  private:

@@ -10,6 +10,8 @@
 // between words, homophones allowed): eesen_ctc_decode_parallel_words; the word ends go to --word-ends-wspecifier.
 // With --ctm-out the best hypothesis of every utterance is aligned to the frames (eesen_ctc_decode_stamps) and written as CTM lines
 // `key 1 start duration word [confidence]`, the file sclite scores.
+// With --rescore=true every returned hypothesis gets its exact acoustic score and the list is ranked again, optionally with a second
+// LM (--rescore-lm): eesen_ctc_decode_rescore.  Everything is then written in the new order and speaks of the new best hypothesis.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -65,6 +67,19 @@ std::string fixed(double v, int precision) {
   snprintf(buf, sizeof buf, "%.*f", precision, v);
   return buf;
 }
+// the value of a --rescore-* option that is kept as text so that "not given" can stand for the first pass's value
+float number_option(const std::string& name, const std::string& text) {
+  char* end = nullptr;
+  const double v = std::strtod(text.c_str(), &end);
+  if (end == text.c_str()) throw std::runtime_error("Invalid floating-point option \"" + text + "\" of --" + name);
+  return (float)v;
+}
+bool bool_option(const std::string& name, std::string text) {
+  std::transform(text.begin(), text.end(), text.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+  if (text == "true" || text == "t" || text == "1") return true;
+  if (text == "false" || text == "f" || text == "0") return false;
+  throw std::runtime_error("Invalid format for boolean argument [expected true or false] of --" + name + ": " + text);
+}
 std::string fmt9(double v) {
   std::ostringstream o;
   o.precision(9);
@@ -83,6 +98,8 @@ int main(int argc, char** argv) {
     bool ctm_conf = false;
     float prior_scale = 1.f, lm_weight = 1.f, insertion_bonus = 0.f, word_bonus = 0.f;
     bool lm_eos = false, lm_skip_oov = false, lm_lookahead = false;
+    bool rescore = false;
+    std::string rescore_lm, rescore_lm_weight, rescore_bonus, rescore_lm_eos;
     double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
     int num_sequence = 1, device = 0, beam = 16, max_classes = 20, nbest = 1;
     std::string use_gpu = "yes";
@@ -130,6 +147,12 @@ int main(int argc, char** argv) {
     po.Register("ctm-conf", &ctm_conf, "A sixth CTM column: the word's posterior over the --nbest hypotheses");
     po.Register("conf-scale", &conf_scale, "Scale of the hypotheses' log-probabilities in that posterior (>= 0)");
     po.Register("ctm-units", &ctm_units, "units.txt naming the CTM's words without a lexicon: `symbol id` per line (default: --lm-units; else class ids)");
+    po.Register("rescore", &rescore, "Second pass: score every hypothesis exactly, rank the list again and write everything in the new order");
+    po.Register("rescore-lm", &rescore_lm, "ARPA file of the second pass's LM: over --lm-units' tokens, or over the lexicon's words with --lexicon "
+                                           "(default: the first pass's LM scores)");
+    po.Register("rescore-lm-weight", &rescore_lm_weight, "Weight of the LM score in the second pass (default: --lm-weight)");
+    po.Register("rescore-bonus", &rescore_bonus, "Added per label or, with --lexicon, per word in the second pass (default: --insertion-bonus or --word-bonus)");
+    po.Register("rescore-lm-eos", &rescore_lm_eos, "true|false: --rescore-lm's log-probability of </s> joins at the end (default: --lm-eos)");
     po.Register("use-gpu", &use_gpu, "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)");
     po.Register("num-sequence", &num_sequence, "Utterances forwarded and decoded together");
     po.Register("frame-limit", &frame_limit, "Max number of frames forwarded together");
@@ -141,6 +164,11 @@ int main(int argc, char** argv) {
       po.PrintUsage();
       return 1;
     }
+    if (!rescore && !(rescore_lm.empty() && rescore_lm_weight.empty() && rescore_bonus.empty() && rescore_lm_eos.empty()))
+      throw std::runtime_error("--rescore-lm, --rescore-lm-weight, --rescore-bonus and --rescore-lm-eos need --rescore=true");
+    const float second_weight = rescore_lm_weight.empty() ? lm_weight : number_option("rescore-lm-weight", rescore_lm_weight);
+    const float second_bonus = rescore_bonus.empty() ? (lexicon.empty() ? insertion_bonus : word_bonus) : number_option("rescore-bonus", rescore_bonus);
+    const bool second_eos = rescore_lm_eos.empty() ? lm_eos : bool_option("rescore-lm-eos", rescore_lm_eos);
     eesen_net_t* net = nullptr;
     eesen_feeder_t* feeder = nullptr;
     eesen_ctc_t* ctc = nullptr;
@@ -156,7 +184,8 @@ int main(int argc, char** argv) {
     eesen_lm_t* lm = nullptr;
     if (!lexicon.empty() && !lm_arpa.empty()) throw std::runtime_error("--lexicon together with --lm: the token LM and the word LM cannot be combined");
     if (!lm_arpa.empty()) ck(eesen_lm_create_from_arpa(lm_arpa.c_str(), lm_units.empty() ? nullptr : lm_units.c_str(), K, &lm));
-    else if (!lm_units.empty()) throw std::runtime_error("--lm-units without --lm");
+    else if (!lm_units.empty() && rescore_lm.empty()) throw std::runtime_error("--lm-units without --lm");
+    eesen_lm_t* second_lm = nullptr;
     eesen_lex_t* lex = nullptr;
     int V = 0;
     if (word_boundary != "unit" && word_boundary != "none") throw std::runtime_error("--word-boundary=" + word_boundary + " is neither unit nor none");
@@ -175,7 +204,8 @@ int main(int argc, char** argv) {
       }
       ck(eesen_lex_info(lex, &V, nullptr, nullptr));
       if (!words_table_out.empty()) ck(eesen_lex_write_words(lex, words_table_out.c_str()));
-      if (!word_lm.empty()) {   // the word LM reads its words through the lexicon's table
+      // a word LM reads its words through the lexicon's table
+      auto word_lm_of = [&](const std::string& arpa, eesen_lm_t** made) {
         std::string table = words_table_out;
         if (table.empty()) {   // a file of our own, created exclusively (mkstemp), gone as soon as the LM has read it
           const char* tmpdir = getenv("TMPDIR");
@@ -185,17 +215,20 @@ int main(int argc, char** argv) {
           close(fd);
         }
         int rc = words_table_out.empty() ? eesen_lex_write_words(lex, table.c_str()) : EESEN_OK;
-        if (rc == EESEN_OK) rc = eesen_lm_create_from_arpa_ex(word_lm.c_str(), table.c_str(), V + 1, lm_skip_oov ? 1 : 0, &lm);
+        if (rc == EESEN_OK) rc = eesen_lm_create_from_arpa_ex(arpa.c_str(), table.c_str(), V + 1, lm_skip_oov ? 1 : 0, made);
         if (words_table_out.empty()) std::remove(table.c_str());
         ck(rc);
         long long dropped = 0;
-        ck(eesen_lm_oov_dropped(lm, &dropped));
-        if (lm_skip_oov) std::cerr << "LOG (ctc-decode:main()) " << dropped << " n-grams of " << word_lm << " hold a word outside the lexicon and were dropped" << std::endl;
-      }
+        ck(eesen_lm_oov_dropped(*made, &dropped));
+        if (lm_skip_oov) std::cerr << "LOG (ctc-decode:main()) " << dropped << " n-grams of " << arpa << " hold a word outside the lexicon and were dropped" << std::endl;
+      };
+      if (!word_lm.empty()) word_lm_of(word_lm, &lm);
+      if (!rescore_lm.empty()) word_lm_of(rescore_lm, &second_lm);
     } else if (!lexicon_units.empty() || !word_lm.empty() || !words_wspecifier.empty() || !words_table_out.empty() || !word_ref_rspecifier.empty() ||
                word_bonus != 0.f || lm_skip_oov) {
       throw std::runtime_error("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and --word-ref-rspecifier need --lexicon");
     }
+    if (!lex && !rescore_lm.empty()) ck(eesen_lm_create_from_arpa(rescore_lm.c_str(), lm_units.empty() ? nullptr : lm_units.c_str(), K, &second_lm));
     if (lm_lookahead) {
       if (!lex) throw std::runtime_error("--lm-lookahead needs --lexicon and --word-lm");
       ck(eesen_ctc_set_lm_lookahead(ctc, 1));   // (without --word-lm the library refuses the first decode call)
@@ -270,7 +303,10 @@ int main(int argc, char** argv) {
     }
     long num_done = 0, num_empty = 0, num_dead = 0, tok_err = 0, tok_ref = 0, num_scored = 0, word_err = 0, word_ref = 0, num_word_scored = 0;
     double tot_t = 0, tot_score = 0, tot_lm = 0;
-    long tot_labels = 0;
+    long tot_labels = 0, num_reranked = 0;
+    std::vector<float> am2, lm2, total2;
+    std::vector<int> order2, ranks, conf_len;
+    std::vector<double> conf_z, conf2;
     std::vector<std::pair<std::string, Mat>> group;
     std::vector<int> out_frames;            // per utterance of the group: frames behind the pipeline
     std::vector<const float*> cmvn;
@@ -318,59 +354,88 @@ int main(int argc, char** argv) {
         ck(eesen_ctc_decode_stamps(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, conf_scale, nullptr, nullptr, wstart.data(),
                                    wend.data(), wconf.data(), nullptr));
       }
+      if (rescore) {
+        am2.resize((size_t)S * nbest); lm2.resize((size_t)S * nbest); total2.resize((size_t)S * nbest); order2.resize((size_t)S * nbest);
+        ck(eesen_ctc_decode_rescore(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, second_lm, second_weight, second_bonus,
+                                    second_eos ? 1 : 0, am2.data(), lm2.data(), total2.data(), order2.data()));
+      }
       for (int s = 0; s < S; ++s) {
         const std::string& utt = group[s].first;
         const size_t e0 = (size_t)s * nbest;
-        if (std::isnan(score[e0])) throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no hypotheses");
+        if (std::isnan(score[e0]) || (rescore && std::isnan(total2[e0])))
+          throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no hypotheses");
         if (hyp_len[e0] < 0) {
           std::cerr << "WARNING (ctc-decode:main()) " << utt << (lex ? ", no surviving prefix ends a lexicon word on " : ", every prefix has probability zero on ")
                     << frames[s] << " frames, producing no output for this utterance" << std::endl;
           ++num_dead;
           continue;
         }
-        for (int i = 0; i < nbest && hyp_len[e0 + i] >= 0; ++i) {
+        // the first-pass ranks of the returned entries in the order they are written: the second pass's, or the beam's
+        ranks.clear();
+        for (int i = 0; i < nbest; ++i) {
+          const int r = rescore ? order2[e0 + i] : i;
+          if (r >= 0 && r < nbest && hyp_len[e0 + r] >= 0) ranks.push_back(r);
+        }
+        for (size_t i = 0; i < ranks.size(); ++i)
+          if (ranks[i] != (int)i) { ++num_reranked; break; }
+        for (size_t i = 0; i < ranks.size(); ++i) {
+          const size_t e = e0 + ranks[i];
           const std::string key = nbest > 1 ? utt + "-" + std::to_string(i + 1) : utt;
-          writer.Write(key, hyp.data() + (e0 + i) * T, hyp_len[e0 + i]);
-          if (words_writer) words_writer->Write(key, words.data() + (e0 + i) * T, words_len[e0 + i]);
-          if (ends_writer) ends_writer->Write(key, word_ends.data() + (e0 + i) * T, words_len[e0 + i]);
+          writer.Write(key, hyp.data() + e * T, hyp_len[e]);
+          if (words_writer) words_writer->Write(key, words.data() + e * T, words_len[e]);
+          if (ends_writer) ends_writer->Write(key, word_ends.data() + e * T, words_len[e]);
           if (scores.is_open()) {
-            scores << key << ' ' << fmt9(score[e0 + i]);
-            if (lm) scores << ' ' << fmt9(lm_score[e0 + i]);
+            if (rescore) {
+              scores << key << ' ' << fmt9(total2[e]) << ' ' << fmt9(am2[e]) << ' ' << fmt9(lm2[e]);
+            } else {
+              scores << key << ' ' << fmt9(score[e]);
+              if (lm) scores << ' ' << fmt9(lm_score[e]);
+            }
             scores << '\n';
           }
         }
+        const size_t eb = e0 + ranks[0];   // the best hypothesis: what is scored against the references and written to the CTM
         const auto ref = refs.find(utt);
         if (ref != refs.end()) {
           int err = 0;
-          ck(eesen_edit_distance(ref->second.data(), (int)ref->second.size(), hyp.data() + e0 * T, hyp_len[e0], &err));
+          ck(eesen_edit_distance(ref->second.data(), (int)ref->second.size(), hyp.data() + eb * T, hyp_len[eb], &err));
           tok_err += err; tok_ref += (long)ref->second.size(); ++num_scored;
         }
         const auto wref = word_refs.find(utt);
         if (wref != word_refs.end()) {
           int err = 0;
-          ck(eesen_edit_distance(wref->second.data(), (int)wref->second.size(), words.data() + e0 * T, words_len[e0], &err));
+          ck(eesen_edit_distance(wref->second.data(), (int)wref->second.size(), words.data() + eb * T, words_len[eb], &err));
           word_err += err; word_ref += (long)wref->second.size(); ++num_word_scored;
         }
         if (ctm.is_open()) {   // the best hypothesis' words: a label each without a lexicon
           if (std::isnan(wconf[e0 * T])) throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no time stamps");
-          const int nw = lex ? words_len[e0] : hyp_len[e0];
-          const int* ids = (lex ? words.data() : hyp.data()) + e0 * T;
+          const int nw = lex ? words_len[eb] : hyp_len[eb];
+          const int* ids = (lex ? words.data() : hyp.data()) + eb * T;
+          if (rescore && ctm_conf) {   // the posterior over the list by the second pass's totals (the stamps' own is by the beam's)
+            conf_z.assign(nbest, 0.0); conf_len.assign(nbest, -1); conf2.assign((size_t)nbest * T, 0.0);
+            for (int r = 0; r < nbest; ++r) {
+              conf_z[r] = total2[e0 + r];
+              conf_len[r] = hyp_len[e0 + r] < 0 ? -1 : lex ? words_len[e0 + r] : hyp_len[e0 + r];
+            }
+            ck(eesen_word_confidence(nbest, conf_z.data(), conf_len.data(), (lex ? words.data() : hyp.data()) + e0 * T, wstart.data() + e0 * T,
+                                     wend.data() + e0 * T, T, conf_scale, conf2.data()));
+          }
           for (int j = 0; j < nw; ++j) {
-            if (wstart[e0 * T + j] < 0) continue;   // (a labelling too long to align)
+            if (wstart[eb * T + j] < 0) continue;   // (a labelling too long to align)
             const auto sym = ctm_symbols.find(ids[j]);
-            ctm << utt << " 1 " << fixed(frame_shift * wstart[e0 * T + j], ctm_precision) << ' '
-                << fixed(frame_shift * (wend[e0 * T + j] - wstart[e0 * T + j]), ctm_precision) << ' '
+            ctm << utt << " 1 " << fixed(frame_shift * wstart[eb * T + j], ctm_precision) << ' '
+                << fixed(frame_shift * (wend[eb * T + j] - wstart[eb * T + j]), ctm_precision) << ' '
                 << (sym != ctm_symbols.end() ? sym->second : std::to_string(ids[j]));
-            if (ctm_conf) ctm << ' ' << fixed(wconf[e0 * T + j], ctm_precision);
+            if (ctm_conf) ctm << ' ' << fixed(rescore ? (float)conf2[(eb - e0) * T + j] : wconf[eb * T + j], ctm_precision);
             ctm << '\n';
             ++num_ctm_words;
           }
         }
         ++num_done;
-        if (hyp_len[e0] == 0) ++num_empty;
+        if (hyp_len[eb] == 0) ++num_empty;
         tot_t += frames[s];
-        tot_score += score[e0];
-        if (lm) { tot_lm += lm_score[e0]; tot_labels += lex ? words_len[e0] : hyp_len[e0]; }
+        tot_score += rescore ? total2[eb] : score[eb];
+        if (lm || second_lm) { tot_lm += rescore ? lm2[eb] : lm_score[eb]; tot_labels += lex ? words_len[eb] : hyp_len[eb]; }
       }
       group.clear(); out_frames.clear(); cmvn.clear();
     };
@@ -422,9 +487,11 @@ int main(int argc, char** argv) {
     if (num_dead) std::cerr << "LOG (ctc-decode:main()) " << num_dead << " utterances without a hypothesis" << std::endl;
     std::cerr << "LOG (ctc-decode:main()) Done " << num_done << " utterances, " << num_empty << " empty hypotheses; average log-probability per frame "
               << (tot_t > 0 ? tot_score / tot_t : 0.0);
-    if (lm) std::cerr << "; average LM log-probability per " << (lex ? "word " : "label ") << (tot_labels > 0 ? tot_lm / tot_labels : 0.0);
+    if (lm || second_lm) std::cerr << "; average LM log-probability per " << (lex ? "word " : "label ") << (tot_labels > 0 ? tot_lm / tot_labels : 0.0);
     if (!ctm_out.empty()) std::cerr << "; " << num_ctm_words << " CTM words";
+    if (rescore) std::cerr << "; " << num_reranked << " utterances re-ranked";
     std::cerr << std::endl;
+    if (second_lm) eesen_lm_destroy(second_lm);
     if (lm) eesen_lm_destroy(lm);
     if (lex) eesen_lex_destroy(lex);
     eesen_ctc_destroy(ctc);

@@ -15,6 +15,8 @@ With --word-boundary=none the lexicon has no boundary unit (the phoneme systems:
 allowed): api.Lexicon(space=None); the word ends go to --word-ends-wspecifier.
 With --ctm-out the best hypothesis of every utterance is aligned to the frames (Ctc.DecodeStamps) and written as CTM lines
 `key 1 start duration word [confidence]`, the file sclite scores.
+With --rescore=true every returned hypothesis gets its exact acoustic score and the list is ranked again, optionally with a second LM
+(--rescore-lm): Ctc.RescoreNbest.  Everything is then written in the new order and speaks of the new best hypothesis.
 """
 from __future__ import annotations
 
@@ -99,6 +101,12 @@ def main(argv=None) -> int:
     ap.register("ctm-conf", False, "A sixth CTM column: the word's posterior over the --nbest hypotheses")
     ap.register("conf-scale", 1.0, "Scale of the hypotheses' log-probabilities in that posterior (>= 0)", kind="double")
     ap.register("ctm-units", "", "units.txt naming the CTM's words without a lexicon: `symbol id` per line (default: --lm-units; else class ids)")
+    ap.register("rescore", False, "Second pass: score every hypothesis exactly, rank the list again and write everything in the new order")
+    ap.register("rescore-lm", "", "ARPA file of the second pass's LM: over --lm-units' tokens, or over the lexicon's words with --lexicon "
+                                  "(default: the first pass's LM scores)")
+    ap.register("rescore-lm-weight", "", "Weight of the LM score in the second pass (default: --lm-weight)")
+    ap.register("rescore-bonus", "", "Added per label or, with --lexicon, per word in the second pass (default: --insertion-bonus or --word-bonus)")
+    ap.register("rescore-lm-eos", "", "true|false: --rescore-lm's log-probability of </s> joins at the end (default: --lm-eos)")
     ap.register("use-gpu", "yes", "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)")
     ap.register("num-sequence", 1, "Utterances forwarded and decoded together")
     ap.register("frame-limit", 1e5, "Max number of frames forwarded together", kind="double")
@@ -119,7 +127,26 @@ def main(argv=None) -> int:
     def log(msg):
         print(f"LOG (ctc-decode:main()) {msg}", file=sys.stderr)
 
+    def number_option(name, text):      # a --rescore-* value kept as text so that "not given" can stand for the first pass's value
+        from eesen_amd.parse_options import _strtod
+        v = _strtod(text)
+        if v is None:
+            raise ValueError(f'Invalid floating-point option "{text}" of --{name}')
+        return v
+
+    def bool_option(name, text):
+        if text.lower() in ("true", "t", "1"):
+            return True
+        if text.lower() in ("false", "f", "0"):
+            return False
+        raise ValueError(f"Invalid format for boolean argument [expected true or false] of --{name}: {text.lower()}")
+
     try:
+        if not o.rescore and (o.rescore_lm or o.rescore_lm_weight or o.rescore_bonus or o.rescore_lm_eos):
+            raise ValueError("--rescore-lm, --rescore-lm-weight, --rescore-bonus and --rescore-lm-eos need --rescore=true")
+        second_weight = number_option("rescore-lm-weight", o.rescore_lm_weight) if o.rescore_lm_weight else o.lm_weight
+        second_bonus = number_option("rescore-bonus", o.rescore_bonus) if o.rescore_bonus else (o.word_bonus if o.lexicon else o.insertion_bonus)
+        second_eos = bool_option("rescore-lm-eos", o.rescore_lm_eos) if o.rescore_lm_eos else o.lm_eos
         import ctypes as C
         import numpy as np
         from eesen_amd import kaldi_io, _lib, frontend
@@ -141,8 +168,9 @@ def main(argv=None) -> int:
             raise kaldi_io.KaldiIOError("--lexicon together with --lm: the token LM and the word LM cannot be combined")
         if o.lm:
             lm = TokenLm(o.lm, o.lm_units or None, K=K)
-        elif o.lm_units:
+        elif o.lm_units and not o.rescore_lm:
             raise kaldi_io.KaldiIOError("--lm-units without --lm")
+        second_lm = None
         lex = None
         if o.word_boundary not in ("unit", "none"):
             raise kaldi_io.KaldiIOError(f"--word-boundary={o.word_boundary} is neither unit nor none")
@@ -161,7 +189,7 @@ def main(argv=None) -> int:
                 lex = Lexicon(o.lexicon, o.lexicon_units or None, K=K, space=_space_class(o.space_unit, o.lexicon_units))
             if o.words_table_out:
                 lex.WriteWords(o.words_table_out)
-            if o.word_lm:          # the word LM reads its words through the lexicon's table
+            def word_lm_of(arpa):          # a word LM reads its words through the lexicon's table
                 table = o.words_table_out
                 if not table:          # a file of our own, created exclusively, gone as soon as the LM has read it
                     import tempfile
@@ -170,15 +198,22 @@ def main(argv=None) -> int:
                 try:
                     if not o.words_table_out:
                         lex.WriteWords(table)
-                    lm = TokenLm(o.word_lm, table, K=lex.Info()["words"] + 1, skip_oov=o.lm_skip_oov)
+                    made = TokenLm(arpa, table, K=lex.Info()["words"] + 1, skip_oov=o.lm_skip_oov)
                 finally:
                     if not o.words_table_out:
                         os.remove(table)
                 if o.lm_skip_oov:
-                    log(f"{lm.OovDropped()} n-grams of {o.word_lm} hold a word outside the lexicon and were dropped")
+                    log(f"{made.OovDropped()} n-grams of {arpa} hold a word outside the lexicon and were dropped")
+                return made
+            if o.word_lm:
+                lm = word_lm_of(o.word_lm)
+            if o.rescore_lm:
+                second_lm = word_lm_of(o.rescore_lm)
         elif o.lexicon_units or o.word_lm or o.words_wspecifier or o.words_table_out or o.word_ref_rspecifier or o.word_bonus != 0.0 or o.lm_skip_oov:
             raise kaldi_io.KaldiIOError("--lexicon-units, --word-lm, --word-bonus, --lm-skip-oov, --words-wspecifier, --words-table-out and "
                                         "--word-ref-rspecifier need --lexicon")
+        if lex is None and o.rescore_lm:
+            second_lm = TokenLm(o.rescore_lm, o.lm_units or None, K=K)
         if o.lm_lookahead:
             if lex is None:
                 raise kaldi_io.KaldiIOError("--lm-lookahead needs --lexicon and --word-lm")
@@ -235,7 +270,7 @@ def main(argv=None) -> int:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
             feeder.set_pipeline(pipe.stages)
-        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0, ctm=0)
+        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0, ctm=0, reranked=0)
         scores = open(o.scores_out, "w") if o.scores_out else None
         lib = _lib.load()
 
@@ -261,49 +296,66 @@ def main(argv=None) -> int:
                                              word_bonus=o.word_bonus)
             lm_score, words, words_len, word_ends = ctc.lm_score, ctc.words, ctc.words_len, ctc.word_ends
             stamps = ctc.DecodeStamps(lens, out, is_log=log_pri is not None, conf_scale=o.conf_scale) if ctm is not None else None
+            second = ctc.RescoreNbest(lens, out, is_log=log_pri is not None, lm=second_lm, lm_weight=second_weight, bonus=second_bonus,
+                                      lm_eos=second_eos) if o.rescore else None
+            hlen = ctc.hyp_len
             for s, (key, m) in enumerate(group):
                 frames = int(lens[s])
-                if math.isnan(score[s, 0]):
+                if math.isnan(score[s, 0]) or (second is not None and math.isnan(second.total[s, 0])):
                     raise RuntimeError(f"the forward pass of {key} timed out on the device: no hypotheses")
                 if not hyps[s]:
                     why = "no surviving prefix ends a lexicon word" if lex is not None else "every prefix has probability zero"
                     warn(f"{key}, {why} on {frames} frames, producing no output for this utterance")
                     n["dead"] += 1
                     continue
-                for i, h in enumerate(hyps[s]):
+                # the first-pass ranks of the returned entries in the order they are written: the second pass's, or the beam's
+                ranks = [int(r) for r in (second.order[s] if second is not None else range(o.nbest)) if 0 <= r < o.nbest and hlen[s, r] >= 0]
+                n["reranked"] += ranks != list(range(len(ranks)))
+                for i, r in enumerate(ranks):
                     k = f"{key}-{i + 1}" if o.nbest > 1 else key
                     if scores:
-                        scores.write(f"{k} {float(score[s, i]):.9g}" + (f" {float(lm_score[s, i]):.9g}" if lm is not None else "") + "\n")
-                    yield k, np.asarray(h, np.int32)
+                        if second is not None:
+                            scores.write(f"{k} {float(second.total[s, r]):.9g} {float(second.am_score[s, r]):.9g} {float(second.lm_score[s, r]):.9g}\n")
+                        else:
+                            scores.write(f"{k} {float(score[s, r]):.9g}" + (f" {float(lm_score[s, r]):.9g}" if lm is not None else "") + "\n")
+                    yield k, np.asarray(hyps[s][r], np.int32)
                     if words_writer is not None:          # (after the hypothesis is out, as the native tool orders its writes)
-                        words_writer.write(k, words[s, i, :words_len[s, i]])
+                        words_writer.write(k, words[s, r, :words_len[s, r]])
                     if ends_writer is not None:
-                        ends_writer.write(k, word_ends[s, i, :words_len[s, i]])
+                        ends_writer.write(k, word_ends[s, r, :words_len[s, r]])
+                b0 = ranks[0]             # the best hypothesis: what is scored against the references and written to the CTM
                 if key in refs:
-                    ref, best, err = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][0], np.int32), C.c_int(0)
+                    ref, best, err = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][b0], np.int32), C.c_int(0)
                     _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
                     n["tok_err"] += err.value; n["tok_ref"] += int(ref.size); n["scored"] += 1
                 if key in word_refs:
-                    ref, best, err = np.ascontiguousarray(word_refs[key], np.int32), np.ascontiguousarray(words[s, 0, :words_len[s, 0]], np.int32), C.c_int(0)
+                    ref, best, err = np.ascontiguousarray(word_refs[key], np.int32), np.ascontiguousarray(words[s, b0, :words_len[s, b0]], np.int32), C.c_int(0)
                     _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
                     n["word_err"] += err.value; n["word_ref"] += int(ref.size); n["word_scored"] += 1
                 if ctm is not None:       # the best hypothesis' words: a label each without a lexicon
                     if math.isnan(stamps.word_conf[s, 0, 0]):
                         raise RuntimeError(f"the forward pass of {key} timed out on the device: no time stamps")
-                    ids = words[s, 0, :words_len[s, 0]] if lex is not None else hyps[s][0]
+                    ids = words[s, b0, :words_len[s, b0]] if lex is not None else hyps[s][b0]
+                    conf = stamps.word_conf[s]
+                    if second is not None and o.ctm_conf:   # the posterior over the list by the second pass's totals (the stamps' own is by the beam's)
+                        from eesen_amd.api import word_confidence
+                        wl = np.where(hlen[s] < 0, -1, words_len[s] if lex is not None else hlen[s])
+                        conf = word_confidence(second.total[s], wl, words[s] if lex is not None else ctc.hyp[s], stamps.word_start[s], stamps.word_end[s],
+                                               o.conf_scale).astype(np.float32)
                     for j, w in enumerate(ids):
-                        b, e = int(stamps.word_start[s, 0, j]), int(stamps.word_end[s, 0, j])
+                        b, e = int(stamps.word_start[s, b0, j]), int(stamps.word_end[s, b0, j])
                         if b < 0:             # (a labelling too long to align)
                             continue
                         line = f"{key} 1 {o.frame_shift * b:.{o.ctm_precision}f} {o.frame_shift * (e - b):.{o.ctm_precision}f} {ctm_symbols.get(int(w), str(int(w)))}"
                         if o.ctm_conf:
-                            line += f" {float(stamps.word_conf[s, 0, j]):.{o.ctm_precision}f}"
+                            line += f" {float(conf[b0, j]):.{o.ctm_precision}f}"
                         ctm.write(line + "\n")
                         n["ctm"] += 1
-                n["done"] += 1; n["frames"] += frames; n["score"] += float(score[s, 0])
-                n["empty"] += len(hyps[s][0]) == 0
-                if lm is not None:
-                    n["lm"] += float(lm_score[s, 0]); n["labels"] += int(words_len[s, 0]) if lex is not None else len(hyps[s][0])
+                n["done"] += 1; n["frames"] += frames; n["score"] += float(second.total[s, b0] if second is not None else score[s, b0])
+                n["empty"] += len(hyps[s][b0]) == 0
+                if lm is not None or second_lm is not None:
+                    n["lm"] += float(second.lm_score[s, b0] if second is not None else lm_score[s, b0])
+                    n["labels"] += int(words_len[s, b0]) if lex is not None else len(hyps[s][b0])
 
         def produce():
             group, max_len = [], 0
@@ -336,9 +388,11 @@ def main(argv=None) -> int:
         if n["dead"]:
             log(f"{n['dead']} utterances without a hypothesis")
         avg = n["score"] / n["frames"] if n["frames"] else 0.0
-        tail = f"; average LM log-probability per {'word' if lex is not None else 'label'} {(n['lm'] / n['labels'] if n['labels'] else 0.0):g}" if lm is not None else ""
+        tail = f"; average LM log-probability per {'word' if lex is not None else 'label'} {(n['lm'] / n['labels'] if n['labels'] else 0.0):g}" if lm is not None or second_lm is not None else ""
         if o.ctm_out:
             tail += f"; {n['ctm']} CTM words"
+        if o.rescore:
+            tail += f"; {n['reranked']} utterances re-ranked"
         log(f"Done {n['done']} utterances, {n['empty']} empty hypotheses; average log-probability per frame {avg:g}{tail}")
         return 0 if n["done"] else 255
     except Exception as e:

@@ -554,6 +554,40 @@ int eesen_ctc_decode_stamps(eesen_ctc_t* ctc, const int* frame_num_utt, int S, c
 int eesen_ctc_get_stamp_times(eesen_ctc_t* ctc, float* out3);
 /* Test hook: sweep the lattices of eesen_ctc_decode_stamps in groups of `lattices` (0 = automatic: as many as 1 GiB of delta rows hold). */
 int eesen_ctc_set_stamp_group(eesen_ctc_t* ctc, int lattices);
+/* ---- exact scores and second-pass rescoring (INTEGRATION.md "Rescoring") -----------------------------------------------------------
+ * a = ln p(labels | x) = ln of the sum over all CTC paths that collapse to the labels, by the alpha recurrence of
+ * eesen_ctc_eval_parallel on the log-scores of the decode calls (posteriors through the logarithm, or given with is_log; clamped from
+ * below at -1e30; blank = class 0), closed on the LARGER of the two final cells: a = m + log(1 + exp(n - m)).  (eval_parallel's own
+ * ln p closes on the final blank, as the reference does, and is wrong where that cell is unreachable or far below the last label's.)
+ * The sweep keeps no row: every labelling of a call is one workgroup of one launch, and the only device output is one float each.
+ * The empty labelling: a = sum_t s_t(0), 0 over no frames.  No path (too few frames, a zero on every path): a = -1e30; read a result
+ * <= -1e29 as infeasible.
+ *
+ * eesen_ctc_score_parallel: any labellings per utterance.  Utterance s owns the labellings hyp_off[s] .. hyp_off[s + 1] (hyp_off[0] = 0,
+ * NH = hyp_off[S]); labelling h the labels label_ids[label_off[h] .. label_off[h + 1]).  score_host [NH].  EESEN_ERR_INVALID: a label
+ * outside [1, K), ld < K, more than 2047 labels in a labelling, offsets that decrease.  Touches no statistic and nothing
+ * eesen_ctc_get_alpha_beta reads.  NaN under a raised guard word.  The call waits for its results. */
+int eesen_ctc_score_parallel(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld, int is_log,
+                             const int* hyp_off /*S+1*/, const int* label_off /*NH+1*/, const int* label_ids, float* score_host /*NH*/);
+/* eesen_ctc_decode_rescore: the entries the LAST decode call on this Ctc returned (any of the four), scored exactly and ranked again.
+ * frame_num_utt, S, scores_dev, rows, K, ld, is_log: that call's.  For entry i of an utterance:
+ *   g_i = eesen_lm_score(lm, tokens_i, use_eos) in fp64 -- the tokens are the labels (plain, token LM; lm's K = K) or the word ids
+ *         (both lexicon modes; lm's K = V + 1); with lm == NULL the first pass's LM sum (0 if that call had no LM);
+ *   n_i = the number of tokens;   total_i = (float)((double)a_i + (double)lm_weight * g_i + (double)bonus * n_i).
+ * am_score_host / lm_score_host / total_host [S][nbest] float, order_host [S][nbest] int32: the first-pass ranks by total descending,
+ * ties to the smaller rank, then -- in rank order -- the infeasible entries (a <= -1e29, more than 2047 labels) and the ranks beyond
+ * the returned count, all of which read -1e30 in the three score arrays.  Any output pointer may be NULL.  Under a raised guard word
+ * (in the decode call or in this one): NaN scores, order -1.  Nothing the decode call left is changed: eesen_ctc_decode_stamps
+ * afterwards is indexed by first-pass rank as before.
+ * EESEN_ERR_STATE: no decode call yet, or S, rows or frame_num_utt differ from its.  EESEN_ERR_INVALID: ld < K, a non-finite lm_weight
+ * or bonus, use_eos on an LM without </s>, an LM whose class count does not fit the mode.  The call waits for its results. */
+int eesen_ctc_decode_rescore(eesen_ctc_t* ctc, const int* frame_num_utt, int S, const float* scores_dev, int rows, int K, int ld, int is_log,
+                             eesen_lm_t* lm /*or NULL*/, float lm_weight, float bonus, int use_eos, float* am_score_host /*S*nbest or NULL*/,
+                             float* lm_score_host /*S*nbest or NULL*/, float* total_host /*S*nbest or NULL*/, int* order_host /*S*nbest or NULL*/);
+/* seconds of the last of the two calls above: out[0]=lattice build (with the logarithm when is_log == 0), [1]=the scoring sweep (both
+ * device time), [2]=the host's LM scoring and ranking (0 after eesen_ctc_score_parallel). */
+int eesen_ctc_get_rescore_times(eesen_ctc_t* ctc, float* out3);
+
 /* N-best posterior word confidences in fp64 on the host; no device work.  Entry i of n_entries has the total scores[i] and word_len[i]
  * words (< 0: not an entry, skipped) with ids word_ids[i*stride + j] and frame intervals [wstart, wend).  With c = conf_scale (finite,
  * >= 0): P_i = exp(c (z_i - z_max)) / sum_k exp(c (z_k - z_max)) over the entries, and

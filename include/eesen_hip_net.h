@@ -518,6 +518,62 @@ class Ctc {
         out->path_score[s].push_back(ps[(size_t)s * nbest + i]);
       }
   }
+  /* Exact log-scores ln p(labels | x), eesen_ctc_score_parallel (INTEGRATION.md "Rescoring"): hyps[s] any labellings of utterance s
+   * (an empty one: the empty labelling); scores[s][i] that of hyps[s][i], -1e30 (read <= -1e29) where it has no path. */
+  void ScoreParallel(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out,
+                     const std::vector<std::vector<std::vector<int32> > >& hyps, std::vector<std::vector<BaseFloat> >* scores,
+                     bool is_log = false) {
+    const int S = (int)frame_num_utt.size();
+    std::vector<int> hoff(1, 0), loff(1, 0), ids;
+    for (int s = 0; s < S && s < (int)hyps.size(); ++s) {
+      for (size_t i = 0; i < hyps[s].size(); ++i) {
+        ids.insert(ids.end(), hyps[s][i].begin(), hyps[s][i].end());
+        loff.push_back((int)ids.size());
+      }
+      hoff.push_back((int)loff.size() - 1);
+    }
+    while ((int)hoff.size() < S + 1) hoff.push_back(hoff.back());
+    if (ids.empty()) ids.push_back(0);
+    std::vector<BaseFloat> sc(loff.size());
+    HipCheck(eesen_ctc_score_parallel(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                      is_log ? 1 : 0, hoff.data(), loff.data(), ids.data(), sc.data()));
+    scores->assign(S, std::vector<BaseFloat>());
+    for (int s = 0; s < S; ++s) (*scores)[s].assign(sc.begin() + hoff[s], sc.begin() + hoff[s + 1]);
+  }
+  /* Second pass over the entries the LAST DecodeParallel returned (any overload), eesen_ctc_decode_rescore: am_score the exact
+   * ln p(labels | x), lm_score the fp64 score of `lm` (may be NULL: the first pass's LM sums) over the entry's labels or, after a
+   * lexicon call, words, total = am + lm_weight * lm + bonus * tokens; order[s] the first-pass ranks by total, best first, ties to
+   * the smaller rank, entries without a path last.  frame_num_utt, net_out, is_log: that call's; hyps: what it returned (every array
+   * is cut to the utterance's count). */
+  struct Rescored {
+    std::vector<std::vector<BaseFloat> > am_score, lm_score, total;
+    std::vector<std::vector<int32> > order;
+  };
+  void RescoreNbest(const std::vector<int32>& frame_num_utt, const CuMatrixBase<BaseFloat>& net_out,
+                    const std::vector<std::vector<std::vector<int32> > >& hyps, Rescored* out, const TokenLm* lm = NULL, float lm_weight = 1.0f,
+                    float bonus = 0.0f, bool use_eos = false, bool is_log = false) {
+    const int S = (int)frame_num_utt.size(), nbest = last_nbest_;
+    const size_t n = (size_t)S * nbest + 1;
+    std::vector<BaseFloat> am(n), ls(n), tot(n);
+    std::vector<int32> ord(n);
+    HipCheck(eesen_ctc_decode_rescore(h_, frame_num_utt.data(), S, net_out.Data(), net_out.NumRows(), net_out.NumCols(), net_out.Stride(),
+                                      is_log ? 1 : 0, lm ? lm->Handle() : NULL, lm_weight, bonus, use_eos ? 1 : 0, am.data(), ls.data(), tot.data(),
+                                      ord.data()));
+    out->am_score.assign(S, std::vector<BaseFloat>());
+    out->lm_score = out->total = out->am_score;
+    out->order.assign(S, std::vector<int32>());
+    for (int s = 0; s < S && s < (int)hyps.size(); ++s) {
+      const int count = (int)hyps[s].size() < nbest ? (int)hyps[s].size() : nbest;
+      for (int i = 0; i < count; ++i) {
+        const size_t e = (size_t)s * nbest + i;
+        out->am_score[s].push_back(am[e]);
+        out->lm_score[s].push_back(ls[e]);
+        out->total[s].push_back(tot[e]);
+      }
+      for (int i = 0; i < nbest; ++i)   /* the ranks beyond the count come last in the library's order: dropped */
+        if (ord[(size_t)s * nbest + i] >= 0 && ord[(size_t)s * nbest + i] < count) out->order[s].push_back(ord[(size_t)s * nbest + i]);
+    }
+  }
   void SetReportStep(int32 s) { report_step_ = s; }
   void SetFramesPerSec(float f) { frames_per_sec_ = f; }
   float NumErrorTokens() const { long e = 0; HipCheck(eesen_ctc_stats(h_, NULL, NULL, NULL, &e, NULL)); return (float)e; }   /* ctc-loss.h:62 */
