@@ -124,6 +124,9 @@ SIGNATURES = {
     "eesen_ctc_score_parallel": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "eesen_ctc_decode_rescore": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp, _vp, _vp]),
     "eesen_ctc_get_rescore_times": (_i, [_vp, _vp]),
+    "eesen_edit_distance_parallel": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eesen_ctc_decode_mbr": (_i, [_vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "eesen_ctc_get_mbr_times": (_i, [_vp, _vp]),
     "eesen_lex_lookahead": (_i, [_vp, _vp, _vp, _i]),
     "eesen_ctc_set_lm_lookahead": (_i, [_vp, _i]),
     "eesen_ctc_get_lm_lookahead": (_i, [_vp, _pi]),

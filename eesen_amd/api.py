@@ -638,6 +638,14 @@ class Rescored:
         self.am_score, self.lm_score, self.total, self.order = am_score, lm_score, total, order
 
 
+class Mbr:
+    """What Ctc.MbrNbest returns: dist [S, nbest, nbest] and ref_dist [S, nbest] int32 (-1 where an entry does not count; ref_dist is
+    None without refs), posterior and risk [S, nbest] float64 (-1e30 there), order [S, nbest] int32 -- the first-pass ranks by risk."""
+
+    def __init__(self, dist, ref_dist, posterior, risk, order):
+        self.dist, self.ref_dist, self.posterior, self.risk, self.order = dist, ref_dist, posterior, risk, order
+
+
 def word_confidence(scores, word_len, word_ids, wstart, wend, conf_scale: float = 1.0) -> np.ndarray:
     """N-best posterior word confidences on the host in fp64 (eesen_word_confidence; no device work).  scores [n]; word_len [n] (< 0:
     not an entry); word_ids / wstart / wend [n, stride].  Returns conf [n, stride] float64, -1e30 beyond each entry's words."""
@@ -854,6 +862,64 @@ class Ctc:
         out = np.zeros(3, np.float32)
         check(self.lib.eesen_ctc_get_rescore_times(self.h, _np_ptr(out)))
         return dict(zip(["lattices", "sweep", "host"], out.tolist()))
+
+    def EditDistanceParallel(self, seqs: Sequence[Sequence[Sequence[int]]], refs: Optional[Sequence[Sequence[int]]] = None):
+        """Levenshtein distances on the device (eesen_edit_distance_parallel; INTEGRATION.md "Minimum Bayes risk"), every integer
+        equal to edit_distance().  seqs[g]: the sequences of group g, each a list of any int32 tokens.  Returns (pair, ref_dist):
+        pair[g] [n_g, n_g] int32, the distances among the group's sequences; ref_dist[g] [n_g] int32, each sequence against
+        refs[g] (None without refs).  More than 8192 tokens in a sequence or reference: EESEN_ERR_INVALID.  Statistics untouched."""
+        G = len(seqs)
+        if refs is not None and len(refs) != G:
+            raise EesenError(-1, "EditDistanceParallel: one reference per group")
+        soff = np.zeros(G + 1, np.int32)
+        soff[1:] = np.cumsum([len(g) for g in seqs])
+        ids, off = self._csr([q for g in seqs for q in g])
+        nq = int(soff[-1])
+        n2 = [len(g) * len(g) for g in seqs]
+        pair = np.empty(max(sum(n2), 1), np.int32)
+        rd = np.empty(max(nq, 1), np.int32) if refs is not None else None
+        rids, roff = self._csr(refs) if refs is not None else (None, None)
+        check(self.lib.eesen_edit_distance_parallel(self.h, G, _np_ptr(soff), _np_ptr(off), _np_ptr(ids), _np_ptr(roff) if refs is not None else None,
+                                                    _np_ptr(rids) if refs is not None else None, _np_ptr(pair),
+                                                    _np_ptr(rd) if refs is not None else None))
+        poff = np.concatenate([[0], np.cumsum(n2)]).astype(np.int64)
+        pairs = [pair[poff[g]:poff[g + 1]].reshape(len(seqs[g]), len(seqs[g])) for g in range(G)]
+        return pairs, ([rd[soff[g]:soff[g + 1]] for g in range(G)] if refs is not None else None)
+
+    def MbrNbest(self, level: int = 0, scale: float = 1.0, totals=None, refs: Optional[Sequence[Sequence[int]]] = None,
+                 ref_only: bool = False) -> "Mbr":
+        """Minimum Bayes risk over the entries the last DecodeParallel returned (eesen_ctc_decode_mbr; INTEGRATION.md "Minimum Bayes
+        risk").  level 0: distances over the mode's LM tokens (labels, or word ids under a lexicon), 1: over labels.  The posterior
+        is softmax(scale * z) over the entries that count, z = totals [S, nbest] if given (RescoreNbest's totals) else the decode
+        call's scores; risk_i = sum_k P_k d(i, k).  refs[s]: utterance s's reference tokens, for ref_dist.  Returns an Mbr.  ref_only:
+        nothing but ref_dist is asked for (no pairwise distances are computed; the other fields are None).  Nothing the decode call
+        left is changed."""
+        hlen = getattr(self, "hyp_len", None)
+        S, nbest = hlen.shape if hlen is not None else (1, 1)   # (without a decode call the library refuses)
+        if refs is not None and len(refs) != S:
+            raise EesenError(-1, "MbrNbest: one reference per utterance")
+        tot = np.ascontiguousarray(totals, np.float32) if totals is not None else None
+        if tot is not None and tot.shape != (S, nbest):
+            raise EesenError(-1, "MbrNbest: totals must be [S, nbest]")
+        rd = np.empty((S, nbest), np.int32) if refs is not None else None
+        rids, roff = self._csr(refs) if refs is not None else (None, None)
+        if ref_only:
+            check(self.lib.eesen_ctc_decode_mbr(self.h, S, int(level), float(scale), _np_ptr(tot) if tot is not None else None,
+                                                _np_ptr(roff) if refs is not None else None, _np_ptr(rids) if refs is not None else None,
+                                                None, _np_ptr(rd) if refs is not None else None, None, None, None))
+            return Mbr(None, rd, None, None, None)
+        dist = np.empty((S, nbest, nbest), np.int32)
+        post, risk = np.empty((S, nbest), np.float64), np.empty((S, nbest), np.float64)
+        order = np.empty((S, nbest), np.int32)
+        check(self.lib.eesen_ctc_decode_mbr(self.h, S, int(level), float(scale), _np_ptr(tot) if tot is not None else None,
+                                            _np_ptr(roff) if refs is not None else None, _np_ptr(rids) if refs is not None else None,
+                                            _np_ptr(dist), _np_ptr(rd) if refs is not None else None, _np_ptr(post), _np_ptr(risk), _np_ptr(order)))
+        return Mbr(dist, rd, post, risk, order)
+
+    def MbrTimes(self) -> dict:
+        out = np.zeros(3, np.float32)
+        check(self.lib.eesen_ctc_get_mbr_times(self.h, _np_ptr(out)))
+        return dict(zip(["build", "kernel", "host"], out.tolist()))
 
     def SetLmLookahead(self, mode: int):
         """eesen_ctc_set_lm_lookahead: 0 = off (the default), 1 = the unigram look-ahead in the two lexicon searches; it stays set."""

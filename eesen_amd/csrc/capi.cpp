@@ -460,6 +460,26 @@ int eesen_ctc_decode_rescore(eesen_ctc_t* ctc, const int* frame_num_utt, int S, 
 int eesen_ctc_get_rescore_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->rescore_times(out3); });
 }
+int eesen_edit_distance_parallel(eesen_ctc_t* ctc, int G, const int* seq_off, const int* tok_off, const int* tok_ids, const int* ref_off,
+                                 const int* ref_ids, int* pair_host, int* ref_dist_host) {
+  return guard([&] {
+    REQ_PTR(ctc);
+    EESEN_REQUIRE(G >= 0, EESEN_ERR_INVALID, "edit distances: negative group count");
+    if (G == 0) return;
+    REQ_PTR(seq_off); REQ_PTR(tok_off);
+    ctc->edit_distance_parallel(G, seq_off, tok_off, tok_ids, ref_off, ref_ids, pair_host, ref_dist_host);
+  });
+}
+int eesen_ctc_decode_mbr(eesen_ctc_t* ctc, int S, int level, double scale, const float* total_host, const int* ref_off, const int* ref_ids,
+                         int* dist_host, int* ref_dist_host, double* post_host, double* risk_host, int* order_host) {
+  return guard([&] {
+    REQ_PTR(ctc);
+    ctc->decode_mbr(S, level, scale, total_host, ref_off, ref_ids, dist_host, ref_dist_host, post_host, risk_host, order_host);
+  });
+}
+int eesen_ctc_get_mbr_times(eesen_ctc_t* ctc, float* out3) {
+  return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->mbr_times(out3); });
+}
 int eesen_ctc_get_stamp_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->stamp_times(out3); });
 }
@@ -526,7 +546,8 @@ int eesen_ctc_dropped(eesen_ctc_t* ctc, long* minibatches) {
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode) {
   return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); ctc->align_timer.enable(mode == 2); ctc->align_timer.set_accumulate(mode == 2);
                      ctc->decode_timer.enable(mode == 2); ctc->decode_timer.set_accumulate(mode == 2);
-                     ctc->stamp_timer.enable(mode == 2); ctc->stamp_timer.set_accumulate(mode == 2); });
+                     ctc->stamp_timer.enable(mode == 2); ctc->stamp_timer.set_accumulate(mode == 2);
+                     ctc->mbr_accumulate = mode == 2; ctc->mbr_t[0] = ctc->mbr_t[1] = ctc->mbr_t[2] = 0; });
 }
 int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->phase_times(out3); });

@@ -910,6 +910,255 @@ void Ctc::rescore_times(float* out3) {
   out3[2] = (float)rescore_host_s;
 }
 
+namespace {
+double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+}  // namespace
+
+const int* Ctc::ed_run(const int* tok_h, size_t n_tok, const int* dev_tok, const std::vector<int>& jobs, size_t n_same, int max_len, bool* bad) {
+  const bool guarded = bad != nullptr && guard.word != nullptr;   // (bad == null: the tokens are the caller's, no forward pass to guard)
+  const auto t0 = std::chrono::steady_clock::now();
+  const size_t nj = jobs.size() / 4, n_in = n_tok + 4 * nj, n_all = n_in + nj;
+  EESEN_REQUIRE(n_all < ((size_t)1 << 31), EESEN_ERR_INVALID, "edit distances: more than 2^31 tokens and jobs in one call");
+  EESEN_HIP_CHECK(hipSetDevice(device));
+  if (ed_i.cap < n_all) EESEN_HIP_CHECK(hipStreamSynchronize(st));
+  ed_i.reserve(std::max<size_t>(n_all, 1));
+  int* tok_d = ed_i.p;
+  int* jobs_d = tok_d + n_tok;
+  int* out_d = jobs_d + 4 * nj;
+  if (n_in > 0) {
+    PinBuf& sp = stage[stage_idx++ & 1];   // in stream order (see upload_lattices)
+    int* pinned = static_cast<int*>(loss_slot(sp, n_in * sizeof(int)));
+    if (n_tok > 0) std::copy(tok_h, tok_h + n_tok, pinned);
+    std::copy(jobs.begin(), jobs.end(), pinned + n_tok);
+    EESEN_HIP_CHECK(hipMemcpyAsync(tok_d, pinned, n_in * sizeof(int), hipMemcpyHostToDevice, st));
+    sp.used(st);
+  }
+  const double build_s = seconds_since(t0);
+  if (nj > 0) {
+    const int* first = dev_tok ? dev_tok : tok_d;
+    n_same = std::min(n_same, nj);
+    mev[0].record(st);
+    if (!dev_tok) edit_distance_jobs(st, tok_d, tok_d, jobs_d, (int)nj, max_len, out_d);
+    else {
+      edit_distance_jobs(st, first, first, jobs_d, (int)n_same, max_len, out_d);
+      edit_distance_jobs(st, first, tok_d, jobs_d + 4 * n_same, (int)(nj - n_same), max_len, out_d + n_same);
+    }
+    mev[1].record(st);
+  }
+  int* out = static_cast<int*>(loss_slot(ed_pin, (nj + 1) * sizeof(int)));
+  if (nj > 0) EESEN_HIP_CHECK(hipMemcpyAsync(out, out_d, nj * sizeof(int), hipMemcpyDeviceToHost, st));
+  out[nj] = 0;
+  if (guarded) EESEN_HIP_CHECK(hipMemcpyAsync(out + nj, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  if (nj > 0 || guarded) { ed_pin.used(st); ed_pin.wait(); }
+  if (bad) *bad = out[nj] != 0;
+  float ms = 0.f;
+  if (nj > 0) EESEN_HIP_CHECK(hipEventElapsedTime(&ms, mev[0], mev[1]));
+  mbr_t[0] += build_s;
+  mbr_t[1] += ms * 1e-3;
+  return out;
+}
+
+// Distances among and from sequences given by the host (INTEGRATION.md "Minimum Bayes risk").  Every group's pairs i < j are one job
+// each and mirrored here; a sequence against its group's reference is one more.
+void Ctc::edit_distance_parallel(int G, const int* seq_off, const int* tok_off, const int* tok_ids, const int* ref_off, const int* ref_ids,
+                                 int* pair_host, int* ref_dist_host) {
+  const auto t0 = std::chrono::steady_clock::now();
+  EESEN_REQUIRE(seq_off[0] == 0, EESEN_ERR_INVALID, "seq_off must start at 0");
+  for (int g = 0; g < G; ++g) EESEN_REQUIRE(seq_off[g + 1] >= seq_off[g], EESEN_ERR_INVALID, "sequence offsets must be non-decreasing");
+  const int NQ = seq_off[G];
+  int max_len = 0;
+  for (int q = 0; q < NQ; ++q) {
+    const int n = tok_off[q + 1] - tok_off[q];
+    EESEN_REQUIRE(n >= 0, EESEN_ERR_INVALID, "token offsets must be non-decreasing");
+    EESEN_REQUIRE(n <= kEditDistanceMaxLen, EESEN_ERR_INVALID, "a sequence of more than 8192 tokens is not supported");
+    max_len = std::max(max_len, n);
+  }
+  const bool refs = ref_off != nullptr;
+  if (refs)
+    for (int g = 0; g < G; ++g) {
+      const int n = ref_off[g + 1] - ref_off[g];
+      EESEN_REQUIRE(n >= 0, EESEN_ERR_INVALID, "reference offsets must be non-decreasing");
+      EESEN_REQUIRE(n <= kEditDistanceMaxLen, EESEN_ERR_INVALID, "a reference of more than 8192 tokens is not supported");
+      max_len = std::max(max_len, n);
+    }
+  const size_t n_seq_tok = NQ > 0 ? (size_t)(tok_off[NQ] - tok_off[0]) : 0, n_ref_tok = refs ? (size_t)(ref_off[G] - ref_off[0]) : 0;
+  EESEN_REQUIRE(n_seq_tok == 0 || tok_ids != nullptr, EESEN_ERR_INVALID, "tok_ids is null");
+  EESEN_REQUIRE(n_ref_tok == 0 || ref_ids != nullptr, EESEN_ERR_INVALID, "ref_ids is null");
+  if (!mbr_accumulate) mbr_t[0] = mbr_t[1] = mbr_t[2] = 0;
+  if (NQ == 0) return;
+  std::vector<int> tok(n_seq_tok + n_ref_tok);
+  if (n_seq_tok) std::copy(tok_ids + tok_off[0], tok_ids + tok_off[NQ], tok.begin());
+  if (n_ref_tok) std::copy(ref_ids + ref_off[0], ref_ids + ref_off[G], tok.begin() + n_seq_tok);
+  std::vector<int> jobs;
+  auto span = [&](int q, int* off, int* len) { *off = tok_off[q] - tok_off[0]; *len = tok_off[q + 1] - tok_off[q]; };
+  size_t n_pairs = 0;
+  if (pair_host)
+    for (int g = 0; g < G; ++g)
+      for (int i = seq_off[g]; i < seq_off[g + 1]; ++i)
+        for (int j = i + 1; j < seq_off[g + 1]; ++j) {
+          int oa, la, ob, lb;
+          span(i, &oa, &la); span(j, &ob, &lb);
+          jobs.insert(jobs.end(), {oa, la, ob, lb});
+          ++n_pairs;
+        }
+  if (refs && ref_dist_host)
+    for (int g = 0; g < G; ++g)
+      for (int i = seq_off[g]; i < seq_off[g + 1]; ++i) {
+        int oa, la;
+        span(i, &oa, &la);
+        jobs.insert(jobs.end(), {oa, la, (int)n_seq_tok + ref_off[g] - ref_off[0], ref_off[g + 1] - ref_off[g]});
+      }
+  mbr_t[0] += seconds_since(t0);
+  const int* d = ed_run(tok.data(), tok.size(), nullptr, jobs, jobs.size() / 4, max_len, nullptr);   // (no guard: the tokens are the caller's)
+  const auto t1 = std::chrono::steady_clock::now();
+  if (pair_host) {
+    size_t k = 0;
+    int* out = pair_host;
+    for (int g = 0; g < G; ++g) {
+      const int n = seq_off[g + 1] - seq_off[g];
+      for (int i = 0; i < n; ++i) {
+        out[(size_t)i * n + i] = 0;
+        for (int j = i + 1; j < n; ++j) out[(size_t)i * n + j] = out[(size_t)j * n + i] = d[k++];
+      }
+      out += (size_t)n * n;
+    }
+  }
+  if (refs && ref_dist_host) std::copy(d + n_pairs, d + n_pairs + NQ, ref_dist_host);
+  mbr_t[2] += seconds_since(t1);
+}
+
+// Minimum Bayes risk over the last decode call's entries.  The tokens are where that call left them: labels and the unspaced mode's
+// words in dec_out (device), the spaced mode's words in dec_word (host, uploaded); lengths and scores in decode_pin.
+void Ctc::decode_mbr(int S, int level, double scale, const float* total_host, const int* ref_off, const int* ref_ids, int* dist_host,
+                     int* ref_dist_host, double* post_host, double* risk_host, int* order_host) {
+  const auto t0 = std::chrono::steady_clock::now();
+  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "MBR: no decode call on this Ctc yet");
+  EESEN_REQUIRE(S == dec_S, EESEN_ERR_STATE, "MBR: S differs from the last decode call's");
+  EESEN_REQUIRE(level == 0 || level == 1, EESEN_ERR_INVALID, "MBR: level must be 0 (LM tokens) or 1 (labels)");
+  EESEN_REQUIRE(std::isfinite(scale) && scale >= 0, EESEN_ERR_INVALID, "MBR: scale must be finite and >= 0");
+  const bool refs = ref_off != nullptr;
+  int max_len = 0;
+  if (refs) {
+    for (int s = 0; s < S; ++s) {
+      const int n = ref_off[s + 1] - ref_off[s];
+      EESEN_REQUIRE(n >= 0, EESEN_ERR_INVALID, "reference offsets must be non-decreasing");
+      EESEN_REQUIRE(n <= kEditDistanceMaxLen, EESEN_ERR_INVALID, "a reference of more than 8192 tokens is not supported");
+      max_len = std::max(max_len, n);
+    }
+    EESEN_REQUIRE(ref_off[S] == ref_off[0] || ref_ids != nullptr, EESEN_ERR_INVALID, "ref_ids is null");
+  }
+  if (!mbr_accumulate) mbr_t[0] = mbr_t[1] = mbr_t[2] = 0;
+  const int T = dec_T, N = dec_N;
+  const size_t NL = (size_t)S * N, n_hyp = NL * T;
+  const size_t n_dec = dec_mode == 2 ? 3 * n_hyp + 4 * NL : n_hyp + (dec_fused ? 3 : 2) * NL;
+  const int* dout = decode_pin.as<int>();
+  const int* hlen = dout + n_hyp;
+  const float* z32 = total_host ? total_host : reinterpret_cast<const float*>(hlen + NL);
+  const int* w_out = dout + n_hyp + 3 * NL;   // (unspaced mode: words, ends [NL][T], counts [NL])
+  const double kNaN = std::numeric_limits<double>::quiet_NaN();
+  auto all_bad = [&] {   // decoded from a timed-out forward pass (guard word set): -1 and NaN, never garbage with status OK
+    if (dist_host) std::fill(dist_host, dist_host + NL * N, -1);
+    if (ref_dist_host) std::fill(ref_dist_host, ref_dist_host + NL, -1);
+    if (post_host) std::fill(post_host, post_host + NL, kNaN);
+    if (risk_host) std::fill(risk_host, risk_host + NL, kNaN);
+    if (order_host) std::fill(order_host, order_host + NL, -1);
+  };
+  if (dout[n_dec] != 0) { all_bad(); return; }
+
+  // every entry's tokens: where they are and how many; the entries that count
+  const int kind = level == 1 ? 0 : dec_mode;   // 0 labels, 1 the spaced mode's words, 2 the unspaced mode's
+  std::vector<int> off(NL), len(NL), tok;       // (tok: the uploaded tokens -- the spaced mode's words, then the references)
+  std::vector<char> counts(NL);
+  for (size_t i = 0; i < NL; ++i) {
+    const int n = hlen[i] < 0 ? -1 : kind == 0 ? hlen[i] : kind == 1 ? dec_word_len[i] : w_out[2 * n_hyp + i];
+    const float z = z32[i];
+    counts[i] = n >= 0 && n <= kEditDistanceMaxLen && z > -1e29f && !std::isnan(z);
+    len[i] = n;
+    if (kind == 1) {
+      off[i] = (int)tok.size();
+      if (counts[i]) tok.insert(tok.end(), dec_word.begin() + i * T, dec_word.begin() + i * T + n);
+    } else {
+      EESEN_REQUIRE(i * T + (kind == 2 ? n_hyp + 3 * NL : 0) < ((size_t)1 << 31), EESEN_ERR_INVALID, "MBR: hypothesis buffer beyond 2^31 ints");
+      off[i] = (int)(i * T);
+    }
+    if (counts[i]) max_len = std::max(max_len, n);
+  }
+  const int* dev_tok = kind == 0 ? dec_out.p : kind == 2 ? dec_out.p + n_hyp + 3 * NL : nullptr;
+  const int ref_base = (int)tok.size();
+  if (refs && ref_off[S] > ref_off[0]) tok.insert(tok.end(), ref_ids + ref_off[0], ref_ids + ref_off[S]);
+  const bool need_pairs = dist_host || risk_host || order_host, need_ref = refs && ref_dist_host;
+  std::vector<int> jobs;
+  size_t n_pairs = 0;
+  if (need_pairs)
+    for (int s = 0; s < S; ++s)
+      for (int i = 0; i < N; ++i)
+        for (int k = i + 1; k < N; ++k) {
+          const size_t a = (size_t)s * N + i, b = (size_t)s * N + k;
+          if (!counts[a] || !counts[b]) continue;
+          jobs.insert(jobs.end(), {off[a], len[a], off[b], len[b]});
+          ++n_pairs;
+        }
+  if (need_ref)
+    for (size_t i = 0; i < NL; ++i)
+      if (counts[i]) jobs.insert(jobs.end(), {off[i], len[i], ref_base + ref_off[i / N] - ref_off[0], ref_off[i / N + 1] - ref_off[i / N]});
+  mbr_t[0] += seconds_since(t0);
+  bool bad = false;
+  const int* d = ed_run(tok.data(), tok.size(), dev_tok, jobs, n_pairs, max_len, &bad);
+  if (bad) { all_bad(); return; }
+
+  const auto t1 = std::chrono::steady_clock::now();
+  std::vector<int> D((size_t)N * N), ord(N);
+  std::vector<double> P(N), R(N);
+  size_t kp = 0, kr = n_pairs;
+  for (int s = 0; s < S; ++s) {
+    const char* cnt = counts.data() + (size_t)s * N;
+    const float* z = z32 + (size_t)s * N;
+    std::fill(D.begin(), D.end(), -1);
+    if (need_pairs)
+      for (int i = 0; i < N; ++i) {
+        if (!cnt[i]) continue;
+        D[(size_t)i * N + i] = 0;
+        for (int k = i + 1; k < N; ++k)
+          if (cnt[k]) D[(size_t)i * N + k] = D[(size_t)k * N + i] = d[kp++];
+      }
+    if (dist_host) std::copy(D.begin(), D.end(), dist_host + (size_t)s * N * N);
+    if (ref_dist_host)
+      for (int i = 0; i < N; ++i) ref_dist_host[(size_t)s * N + i] = need_ref && cnt[i] ? d[kr++] : -1;
+    // P_i = exp(c (z_i - z_max)) / sum_k exp(c (z_k - z_max)) over the counting entries in rank order: every exponent is <= 0
+    double zmax = -std::numeric_limits<double>::infinity(), sum = 0;
+    for (int i = 0; i < N; ++i)
+      if (cnt[i]) zmax = std::max(zmax, (double)z[i]);
+    for (int i = 0; i < N; ++i) {
+      P[i] = cnt[i] ? std::exp(scale * ((double)z[i] - zmax)) : 0.0;
+      if (cnt[i]) sum += P[i];
+    }
+    int nc = 0;
+    for (int i = 0; i < N; ++i)
+      if (cnt[i]) { P[i] = P[i] / sum; ord[nc++] = i; }
+    // risk_i = sum_k P_k d(i, k), over the counting k in rank order
+    for (int i = 0; i < N; ++i) {
+      double r = 0;
+      if (cnt[i] && need_pairs)
+        for (int k = 0; k < N; ++k)
+          if (cnt[k]) r += P[k] * (double)D[(size_t)i * N + k];
+      R[i] = r;
+      if (post_host) post_host[(size_t)s * N + i] = cnt[i] ? P[i] : -1e30;
+      if (risk_host) risk_host[(size_t)s * N + i] = cnt[i] ? R[i] : -1e30;
+    }
+    // by expected errors, ascending; a tie goes to the larger z, then to the smaller rank; then the others, in rank order
+    std::stable_sort(ord.begin(), ord.begin() + nc, [&](int x, int y) { return R[x] != R[y] ? R[x] < R[y] : z[x] > z[y]; });
+    for (int i = 0; i < N; ++i)
+      if (!cnt[i]) ord[nc++] = i;
+    if (order_host) std::copy(ord.begin(), ord.end(), order_host + (size_t)s * N);
+  }
+  mbr_t[2] += seconds_since(t1);
+}
+
+void Ctc::mbr_times(float* out3) {
+  for (int i = 0; i < 3; ++i) out3[i] = (float)mbr_t[i];
+  if (mbr_accumulate) mbr_t[0] = mbr_t[1] = mbr_t[2] = 0;
+}
+
 void Ctc::stamp_times(float* out3) {
   if (stamp_timer.enabled()) { stamp_timer.collect(out3, 3); return; }
   sev[3].wait();

@@ -244,6 +244,11 @@ void ctc_stamp(hipStream_t st, const int* pos, int T, int NL, int G, const int* 
 // frames, an entry without a lattice lablens = 0 and no frames, and utt [NL] = i / N, the utterance whose score rows lattice i reads.
 void ctc_hyp_lattices(hipStream_t st, const int* hyp, const int* hyp_len, const int* lens, int T, int NL, int N, int Lpad, int* labx,
                       int* lablens, int* lat_lens, int* utt = nullptr);
+// edit_distance_jobs (edit_distance.hip): batched Levenshtein distance, unit costs, the total only -- edit_distance() of ctc_host.cpp,
+// integer for integer.  jobs [njobs][4] = (offset a, length a, offset b, length b), a into tok_a, b into tok_b; out [njobs].  One wavefront per job, all in
+// one launch.  max_len: the longest sequence any job names (<= kEditDistanceMaxLen), which sizes the boundary column in LDS.
+constexpr int kEditDistanceMaxLen = 8192;
+void edit_distance_jobs(hipStream_t st, const int* tok_a, const int* tok_b, const int* jobs, int njobs, int max_len, int* out);
 // Prefix beam search, lexicon-free or along a lexicon trie (ctc_decode.hip; the computation: INTEGRATION.md "Decoding").  scores: [T*S x K] (ld) log-domain.
 // ctc_row_topc: per row t*S + s with t < lens[s] the Cc = min(max_classes, K - 1) best non-blank classes -- ids ascending in
 // cid [rows][Cc], their scores in csc [rows][Cc], the blank's in sblank [rows]; every score clamped from below at -1e30.

@@ -305,6 +305,12 @@ struct Ctc {
   double rescore_host_s = 0;   // ... and the host's LM scoring and ranking of the last decode_rescore
   PinBuf score_pin;            // results of the scoring sweep (D2H)
   int dec_V = 0;               // the lexicon's word count of the last decode call (0: none): what a second word LM must fit
+  // edit_distance_parallel / decode_mbr (INTEGRATION.md "Minimum Bayes risk"): uploaded tokens, jobs, then the distances
+  DevBuf<int> ed_i;
+  PinBuf ed_pin;               // the distances and the guard word (D2H)
+  DevEvent mev[2] = {DevEvent(true), DevEvent(true)};   // around the distance kernel
+  double mbr_t[3] = {0, 0, 0}; // mbr_times: job build + uploads, the kernel, the host's posterior / risk / ranking
+  bool mbr_accumulate = false; // eesen_ctc_set_profiling(2): the three are summed over the calls until they are read
   // the tables of the token LM the last decode_parallel_lm used (lm.h), keyed by the model's serial
   DevBuf<int> lm_i;
   DevBuf<float> lm_f;
@@ -383,6 +389,17 @@ struct Ctc {
   void decode_rescore(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const TokenLm* lm,
                       float lm_weight, float bonus, bool use_eos, float* am_host, float* lm_host, float* total_host, int* order_host);
   void rescore_times(float* out3);
+  // Levenshtein distances on the device (edit_distance_jobs in edit_distance.hip), every integer equal to edit_distance() below.
+  // Group g owns the sequences seq_off[g] .. seq_off[g + 1], sequence q the tokens tok_ids[tok_off[q] .. tok_off[q + 1]); pair_host:
+  // n_g x n_g distances per group, packed; ref_dist_host [NQ]: every sequence against its group's reference.  No statistic touched.
+  void edit_distance_parallel(int G, const int* seq_off, const int* tok_off, const int* tok_ids, const int* ref_off, const int* ref_ids,
+                              int* pair_host, int* ref_dist_host);
+  // Minimum Bayes risk over the last decode call's entries: pairwise distances [S][nbest][nbest], distances to the references
+  // [S][nbest], posteriors and expected errors (double) [S][nbest], and the ranks by expected errors [S][nbest]; any may be null.
+  // level 0: the mode's LM tokens, 1: labels.  z: total_host if given, else the decode call's scores.  Leaves what that call left.
+  void decode_mbr(int S, int level, double scale, const float* total_host, const int* ref_off, const int* ref_ids, int* dist_host,
+                  int* ref_dist_host, double* post_host, double* risk_host, int* order_host);
+  void mbr_times(float* out3);
   // the candidate classes the last decode_parallel selected: ids / scores [rows][C'], blank [rows]; rows beyond an utterance: -1 / -1e30
   void get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc);
  private:
@@ -394,6 +411,10 @@ struct Ctc {
   void upload_lm(const TokenLm& lm);
   void upload_lex(const Lexicon& lex);
   const float* upload_lookahead(const Lexicon* lex, const TokenLm* lm);   // null with the mode off; refuses a missing word LM
+  // The distances of `jobs` ([n][4], kernels.h) through ed_i and ed_pin.  tok_h [n_tok] is uploaded.  Jobs [0, n_same) take both spans
+  // from dev_tok (null: the uploaded array), the others their first span from there and their second from the uploaded array.
+  // Returns the pinned results, *bad = the guard word's value behind them (bad == null: not read); adds its times to mbr_t[0] and [1].
+  const int* ed_run(const int* tok_h, size_t n_tok, const int* dev_tok, const std::vector<int>& jobs, size_t n_same, int max_len, bool* bad);
 };
 
 // N-best posterior word confidences (eesen_word_confidence; INTEGRATION.md "Time stamps and CTM"), fp64, no device work.  Entry i of

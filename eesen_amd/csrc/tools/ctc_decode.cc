@@ -12,6 +12,9 @@
 // `key 1 start duration word [confidence]`, the file sclite scores.
 // With --rescore=true every returned hypothesis gets its exact acoustic score and the list is ranked again, optionally with a second
 // LM (--rescore-lm): eesen_ctc_decode_rescore.  Everything is then written in the new order and speaks of the new best hypothesis.
+// With --mbr=true every list is ranked by expected errors under its own posterior (over the second pass's totals with --rescore):
+// eesen_ctc_decode_mbr.  Everything is written in that order, the errors against the references come back with it, and the summary
+// adds the errors of the N-best oracle.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -74,6 +77,12 @@ float number_option(const std::string& name, const std::string& text) {
   if (end == text.c_str()) throw std::runtime_error("Invalid floating-point option \"" + text + "\" of --" + name);
   return (float)v;
 }
+double double_option(const std::string& name, const std::string& text) {
+  char* end = nullptr;
+  const double v = std::strtod(text.c_str(), &end);
+  if (end == text.c_str()) throw std::runtime_error("Invalid floating-point option \"" + text + "\" of --" + name);
+  return v;
+}
 bool bool_option(const std::string& name, std::string text) {
   std::transform(text.begin(), text.end(), text.begin(), [](unsigned char c) { return (char)std::tolower(c); });
   if (text == "true" || text == "t" || text == "1") return true;
@@ -100,6 +109,8 @@ int main(int argc, char** argv) {
     bool lm_eos = false, lm_skip_oov = false, lm_lookahead = false;
     bool rescore = false;
     std::string rescore_lm, rescore_lm_weight, rescore_bonus, rescore_lm_eos;
+    bool mbr = false, mbr_units = false;
+    std::string mbr_scale;
     double prior_cutoff = 1e-10, blank_scale = 1.0, frame_limit = 1e5;
     int num_sequence = 1, device = 0, beam = 16, max_classes = 20, nbest = 1;
     std::string use_gpu = "yes";
@@ -153,6 +164,10 @@ int main(int argc, char** argv) {
     po.Register("rescore-lm-weight", &rescore_lm_weight, "Weight of the LM score in the second pass (default: --lm-weight)");
     po.Register("rescore-bonus", &rescore_bonus, "Added per label or, with --lexicon, per word in the second pass (default: --insertion-bonus or --word-bonus)");
     po.Register("rescore-lm-eos", &rescore_lm_eos, "true|false: --rescore-lm's log-probability of </s> joins at the end (default: --lm-eos)");
+    po.Register("mbr", &mbr, "Minimum Bayes risk: rank every list by its hypotheses' expected errors under the list's own posterior and write "
+                             "everything in that order");
+    po.Register("mbr-scale", &mbr_scale, "Scale of the hypotheses' log-probabilities in that posterior, >= 0 (default: 1.0)");
+    po.Register("mbr-units", &mbr_units, "Count the expected errors in labels even with --lexicon (default: in labels, or in words with --lexicon)");
     po.Register("use-gpu", &use_gpu, "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)");
     po.Register("num-sequence", &num_sequence, "Utterances forwarded and decoded together");
     po.Register("frame-limit", &frame_limit, "Max number of frames forwarded together");
@@ -166,6 +181,8 @@ int main(int argc, char** argv) {
     }
     if (!rescore && !(rescore_lm.empty() && rescore_lm_weight.empty() && rescore_bonus.empty() && rescore_lm_eos.empty()))
       throw std::runtime_error("--rescore-lm, --rescore-lm-weight, --rescore-bonus and --rescore-lm-eos need --rescore=true");
+    if (!mbr && (!mbr_scale.empty() || mbr_units)) throw std::runtime_error("--mbr-scale and --mbr-units need --mbr=true");
+    const double mbr_c = mbr_scale.empty() ? 1.0 : double_option("mbr-scale", mbr_scale);
     const float second_weight = rescore_lm_weight.empty() ? lm_weight : number_option("rescore-lm-weight", rescore_lm_weight);
     const float second_bonus = rescore_bonus.empty() ? (lexicon.empty() ? insertion_bonus : word_bonus) : number_option("rescore-bonus", rescore_bonus);
     const bool second_eos = rescore_lm_eos.empty() ? lm_eos : bool_option("rescore-lm-eos", rescore_lm_eos);
@@ -304,6 +321,9 @@ int main(int argc, char** argv) {
     long num_done = 0, num_empty = 0, num_dead = 0, tok_err = 0, tok_ref = 0, num_scored = 0, word_err = 0, word_ref = 0, num_word_scored = 0;
     double tot_t = 0, tot_score = 0, tot_lm = 0;
     long tot_labels = 0, num_reranked = 0;
+    long tok_oracle = 0, word_oracle = 0, num_mbr_moved = 0;
+    std::vector<int> order3, tok_dist, word_dist, ref_off, ref_ids, second_ranks;
+    std::vector<double> post3;
     std::vector<float> am2, lm2, total2;
     std::vector<int> order2, ranks, conf_len;
     std::vector<double> conf_z, conf2;
@@ -359,10 +379,34 @@ int main(int argc, char** argv) {
         ck(eesen_ctc_decode_rescore(ctc, frames.data(), S, out, T * S, K, old, log_pri.empty() ? 0 : 1, second_lm, second_weight, second_bonus,
                                     second_eos ? 1 : 0, am2.data(), lm2.data(), total2.data(), order2.data()));
       }
+      if (mbr) {
+        // the references in the level's tokens ride along (an utterance without one: an empty reference, never read back)
+        const int level = mbr_units ? 1 : 0;
+        const bool words_level = lex && !mbr_units;
+        auto pack = [&](const std::map<std::string, std::vector<int32_t>>& table) {
+          ref_off.assign(1, 0); ref_ids.clear();
+          for (int s = 0; s < S; ++s) {
+            const auto r = table.find(group[s].first);
+            if (r != table.end()) ref_ids.insert(ref_ids.end(), r->second.begin(), r->second.end());
+            ref_off.push_back((int)ref_ids.size());
+          }
+          ref_ids.push_back(0);
+        };
+        order3.resize((size_t)S * nbest); post3.resize((size_t)S * nbest);
+        tok_dist.assign((size_t)S * nbest, -1); word_dist.assign((size_t)S * nbest, -1);
+        pack(words_level ? word_refs : refs);
+        ck(eesen_ctc_decode_mbr(ctc, S, level, mbr_c, rescore ? total2.data() : nullptr, ref_off.data(), ref_ids.data(), nullptr,
+                                (words_level ? word_dist : tok_dist).data(), post3.data(), nullptr, order3.data()));
+        if (lex && !(words_level ? refs : word_refs).empty()) {   // the other kind of reference: distances alone, at the other level
+          pack(words_level ? refs : word_refs);
+          ck(eesen_ctc_decode_mbr(ctc, S, 1 - level, mbr_c, rescore ? total2.data() : nullptr, ref_off.data(), ref_ids.data(), nullptr,
+                                  (words_level ? tok_dist : word_dist).data(), nullptr, nullptr, nullptr));
+        }
+      }
       for (int s = 0; s < S; ++s) {
         const std::string& utt = group[s].first;
         const size_t e0 = (size_t)s * nbest;
-        if (std::isnan(score[e0]) || (rescore && std::isnan(total2[e0])))
+        if (std::isnan(score[e0]) || (rescore && std::isnan(total2[e0])) || (mbr && std::isnan(post3[e0])))
           throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no hypotheses");
         if (hyp_len[e0] < 0) {
           std::cerr << "WARNING (ctc-decode:main()) " << utt << (lex ? ", no surviving prefix ends a lexicon word on " : ", every prefix has probability zero on ")
@@ -370,14 +414,17 @@ int main(int argc, char** argv) {
           ++num_dead;
           continue;
         }
-        // the first-pass ranks of the returned entries in the order they are written: the second pass's, or the beam's
-        ranks.clear();
+        // the first-pass ranks of the returned entries in the order they are written: by expected errors, the second pass's, or the beam's
+        ranks.clear(); second_ranks.clear();
         for (int i = 0; i < nbest; ++i) {
           const int r = rescore ? order2[e0 + i] : i;
-          if (r >= 0 && r < nbest && hyp_len[e0 + r] >= 0) ranks.push_back(r);
+          if (r >= 0 && r < nbest && hyp_len[e0 + r] >= 0) second_ranks.push_back(r);
+          const int q = mbr ? order3[e0 + i] : r;
+          if (q >= 0 && q < nbest && hyp_len[e0 + q] >= 0) ranks.push_back(q);
         }
-        for (size_t i = 0; i < ranks.size(); ++i)
-          if (ranks[i] != (int)i) { ++num_reranked; break; }
+        for (size_t i = 0; i < second_ranks.size(); ++i)
+          if (second_ranks[i] != (int)i) { ++num_reranked; break; }
+        if (mbr && ranks[0] != second_ranks[0]) ++num_mbr_moved;
         for (size_t i = 0; i < ranks.size(); ++i) {
           const size_t e = e0 + ranks[i];
           const std::string key = nbest > 1 ? utt + "-" + std::to_string(i + 1) : utt;
@@ -396,16 +443,26 @@ int main(int argc, char** argv) {
         }
         const size_t eb = e0 + ranks[0];   // the best hypothesis: what is scored against the references and written to the CTM
         const auto ref = refs.find(utt);
+        // with --mbr the distances came back with the list (an entry that does not count has none: the host routine); the oracle is
+        // the list's best
+        auto oracle_of = [&](const std::vector<int>& dist, int err) {
+          int best = -1;
+          for (int r : ranks)
+            if (dist[e0 + r] >= 0 && (best < 0 || dist[e0 + r] < best)) best = dist[e0 + r];
+          return best < 0 ? err : best;
+        };
         if (ref != refs.end()) {
-          int err = 0;
-          ck(eesen_edit_distance(ref->second.data(), (int)ref->second.size(), hyp.data() + eb * T, hyp_len[eb], &err));
+          int err = mbr ? tok_dist[eb] : -1;
+          if (err < 0) ck(eesen_edit_distance(ref->second.data(), (int)ref->second.size(), hyp.data() + eb * T, hyp_len[eb], &err));
           tok_err += err; tok_ref += (long)ref->second.size(); ++num_scored;
+          if (mbr) tok_oracle += oracle_of(tok_dist, err);
         }
         const auto wref = word_refs.find(utt);
         if (wref != word_refs.end()) {
-          int err = 0;
-          ck(eesen_edit_distance(wref->second.data(), (int)wref->second.size(), words.data() + eb * T, words_len[eb], &err));
+          int err = mbr ? word_dist[eb] : -1;
+          if (err < 0) ck(eesen_edit_distance(wref->second.data(), (int)wref->second.size(), words.data() + eb * T, words_len[eb], &err));
           word_err += err; word_ref += (long)wref->second.size(); ++num_word_scored;
+          if (mbr) word_oracle += oracle_of(word_dist, err);
         }
         if (ctm.is_open()) {   // the best hypothesis' words: a label each without a lexicon
           if (std::isnan(wconf[e0 * T])) throw std::runtime_error("the forward pass of " + utt + " timed out on the device: no time stamps");
@@ -478,10 +535,12 @@ int main(int argc, char** argv) {
     }
     if (!ref_rspecifier.empty()) {
       std::cerr << "LOG (ctc-decode:main()) " << tok_err << " token errors on " << tok_ref << " reference tokens of " << num_scored << " utterances" << std::endl;
+      if (mbr) std::cerr << "LOG (ctc-decode:main()) " << tok_oracle << " token errors of the N-best oracle (the best of up to " << nbest << " hypotheses per utterance)" << std::endl;
       std::cerr << "LOG (ctc-decode:main()) \nTOKEN_ACCURACY >> " << 100.0 * (1.0 - (double)tok_err / (double)std::max(tok_ref, 1L)) << "% <<" << std::endl;
     }
     if (!word_ref_rspecifier.empty()) {
       std::cerr << "LOG (ctc-decode:main()) " << word_err << " word errors on " << word_ref << " reference words of " << num_word_scored << " utterances" << std::endl;
+      if (mbr) std::cerr << "LOG (ctc-decode:main()) " << word_oracle << " word errors of the N-best oracle (the best of up to " << nbest << " hypotheses per utterance)" << std::endl;
       std::cerr << "LOG (ctc-decode:main()) \nWORD_ACCURACY >> " << 100.0 * (1.0 - (double)word_err / (double)std::max(word_ref, 1L)) << "% <<" << std::endl;
     }
     if (num_dead) std::cerr << "LOG (ctc-decode:main()) " << num_dead << " utterances without a hypothesis" << std::endl;
@@ -490,6 +549,7 @@ int main(int argc, char** argv) {
     if (lm || second_lm) std::cerr << "; average LM log-probability per " << (lex ? "word " : "label ") << (tot_labels > 0 ? tot_lm / tot_labels : 0.0);
     if (!ctm_out.empty()) std::cerr << "; " << num_ctm_words << " CTM words";
     if (rescore) std::cerr << "; " << num_reranked << " utterances re-ranked";
+    if (mbr) std::cerr << "; " << num_mbr_moved << " utterances whose hypothesis of least expected errors is not the most probable";
     std::cerr << std::endl;
     if (second_lm) eesen_lm_destroy(second_lm);
     if (lm) eesen_lm_destroy(lm);

@@ -17,6 +17,9 @@ With --ctm-out the best hypothesis of every utterance is aligned to the frames (
 `key 1 start duration word [confidence]`, the file sclite scores.
 With --rescore=true every returned hypothesis gets its exact acoustic score and the list is ranked again, optionally with a second LM
 (--rescore-lm): Ctc.RescoreNbest.  Everything is then written in the new order and speaks of the new best hypothesis.
+With --mbr=true every list is ranked by expected errors under its own posterior (over the second pass's totals with --rescore):
+Ctc.MbrNbest.  Everything is written in that order, the errors against the references come back with it, and the summary adds the
+errors of the N-best oracle.
 """
 from __future__ import annotations
 
@@ -107,6 +110,10 @@ def main(argv=None) -> int:
     ap.register("rescore-lm-weight", "", "Weight of the LM score in the second pass (default: --lm-weight)")
     ap.register("rescore-bonus", "", "Added per label or, with --lexicon, per word in the second pass (default: --insertion-bonus or --word-bonus)")
     ap.register("rescore-lm-eos", "", "true|false: --rescore-lm's log-probability of </s> joins at the end (default: --lm-eos)")
+    ap.register("mbr", False, "Minimum Bayes risk: rank every list by its hypotheses' expected errors under the list's own posterior and write "
+                              "everything in that order")
+    ap.register("mbr-scale", "", "Scale of the hypotheses' log-probabilities in that posterior, >= 0 (default: 1.0)")
+    ap.register("mbr-units", False, "Count the expected errors in labels even with --lexicon (default: in labels, or in words with --lexicon)")
     ap.register("use-gpu", "yes", "yes|no|optional (accepted for the recipes' command lines; this tool always runs on the GPU)")
     ap.register("num-sequence", 1, "Utterances forwarded and decoded together")
     ap.register("frame-limit", 1e5, "Max number of frames forwarded together", kind="double")
@@ -144,6 +151,9 @@ def main(argv=None) -> int:
     try:
         if not o.rescore and (o.rescore_lm or o.rescore_lm_weight or o.rescore_bonus or o.rescore_lm_eos):
             raise ValueError("--rescore-lm, --rescore-lm-weight, --rescore-bonus and --rescore-lm-eos need --rescore=true")
+        if not o.mbr and (o.mbr_scale or o.mbr_units):
+            raise ValueError("--mbr-scale and --mbr-units need --mbr=true")
+        mbr_c = number_option("mbr-scale", o.mbr_scale) if o.mbr_scale else 1.0
         second_weight = number_option("rescore-lm-weight", o.rescore_lm_weight) if o.rescore_lm_weight else o.lm_weight
         second_bonus = number_option("rescore-bonus", o.rescore_bonus) if o.rescore_bonus else (o.word_bonus if o.lexicon else o.insertion_bonus)
         second_eos = bool_option("rescore-lm-eos", o.rescore_lm_eos) if o.rescore_lm_eos else o.lm_eos
@@ -270,7 +280,7 @@ def main(argv=None) -> int:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
             feeder.set_pipeline(pipe.stages)
-        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0, ctm=0, reranked=0)
+        n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0, ctm=0, reranked=0, tok_oracle=0, word_oracle=0, mbr_moved=0)
         scores = open(o.scores_out, "w") if o.scores_out else None
         lib = _lib.load()
 
@@ -299,18 +309,32 @@ def main(argv=None) -> int:
             second = ctc.RescoreNbest(lens, out, is_log=log_pri is not None, lm=second_lm, lm_weight=second_weight, bonus=second_bonus,
                                       lm_eos=second_eos) if o.rescore else None
             hlen = ctc.hyp_len
+            mbr = tok_dist = word_dist = None
+            if o.mbr:
+                # the references in the level's tokens ride along (an utterance without one: an empty reference, never read back)
+                level = 1 if o.mbr_units else 0
+                words_level = lex is not None and not o.mbr_units
+                totals = second.total if second is not None else None
+                pack = lambda table: [table.get(key, []) for key, _ in group]
+                mbr = ctc.MbrNbest(level=level, scale=mbr_c, totals=totals, refs=pack(word_refs if words_level else refs))
+                tok_dist, word_dist = (None, mbr.ref_dist) if words_level else (mbr.ref_dist, None)
+                if lex is not None and (refs if words_level else word_refs):   # the other kind of reference: distances alone, at the other level
+                    other = ctc.MbrNbest(level=1 - level, scale=mbr_c, totals=totals, refs=pack(refs if words_level else word_refs), ref_only=True).ref_dist
+                    tok_dist, word_dist = (other, word_dist) if words_level else (tok_dist, other)
             for s, (key, m) in enumerate(group):
                 frames = int(lens[s])
-                if math.isnan(score[s, 0]) or (second is not None and math.isnan(second.total[s, 0])):
+                if math.isnan(score[s, 0]) or (second is not None and math.isnan(second.total[s, 0])) or (mbr is not None and math.isnan(mbr.posterior[s, 0])):
                     raise RuntimeError(f"the forward pass of {key} timed out on the device: no hypotheses")
                 if not hyps[s]:
                     why = "no surviving prefix ends a lexicon word" if lex is not None else "every prefix has probability zero"
                     warn(f"{key}, {why} on {frames} frames, producing no output for this utterance")
                     n["dead"] += 1
                     continue
-                # the first-pass ranks of the returned entries in the order they are written: the second pass's, or the beam's
-                ranks = [int(r) for r in (second.order[s] if second is not None else range(o.nbest)) if 0 <= r < o.nbest and hlen[s, r] >= 0]
-                n["reranked"] += ranks != list(range(len(ranks)))
+                # the first-pass ranks of the returned entries in the order they are written: by expected errors, the second pass's, or the beam's
+                second_ranks = [int(r) for r in (second.order[s] if second is not None else range(o.nbest)) if 0 <= r < o.nbest and hlen[s, r] >= 0]
+                ranks = [int(r) for r in mbr.order[s] if 0 <= r < o.nbest and hlen[s, r] >= 0] if mbr is not None else second_ranks
+                n["reranked"] += second_ranks != list(range(len(second_ranks)))
+                n["mbr_moved"] += mbr is not None and ranks[0] != second_ranks[0]
                 for i, r in enumerate(ranks):
                     k = f"{key}-{i + 1}" if o.nbest > 1 else key
                     if scores:
@@ -324,14 +348,24 @@ def main(argv=None) -> int:
                     if ends_writer is not None:
                         ends_writer.write(k, word_ends[s, r, :words_len[s, r]])
                 b0 = ranks[0]             # the best hypothesis: what is scored against the references and written to the CTM
+                # with --mbr the distances came back with the list (an entry that does not count has none: the host routine); the oracle
+                # is the list's best
+                def errors_of(dist, ref, best):
+                    err = int(dist[s, b0]) if dist is not None else -1
+                    if err < 0:
+                        e = C.c_int(0)
+                        _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(e)))
+                        err = e.value
+                    found = [int(dist[s, r]) for r in ranks if dist[s, r] >= 0] if dist is not None else []
+                    return err, min(found) if found else err
                 if key in refs:
-                    ref, best, err = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][b0], np.int32), C.c_int(0)
-                    _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
-                    n["tok_err"] += err.value; n["tok_ref"] += int(ref.size); n["scored"] += 1
+                    ref, best = np.ascontiguousarray(refs[key], np.int32), np.asarray(hyps[s][b0], np.int32)
+                    err, oracle = errors_of(tok_dist, ref, best)
+                    n["tok_err"] += err; n["tok_ref"] += int(ref.size); n["scored"] += 1; n["tok_oracle"] += oracle
                 if key in word_refs:
-                    ref, best, err = np.ascontiguousarray(word_refs[key], np.int32), np.ascontiguousarray(words[s, b0, :words_len[s, b0]], np.int32), C.c_int(0)
-                    _lib.check(lib.eesen_edit_distance(ref.ctypes.data_as(C.c_void_p), ref.size, best.ctypes.data_as(C.c_void_p), best.size, C.byref(err)))
-                    n["word_err"] += err.value; n["word_ref"] += int(ref.size); n["word_scored"] += 1
+                    ref, best = np.ascontiguousarray(word_refs[key], np.int32), np.ascontiguousarray(words[s, b0, :words_len[s, b0]], np.int32)
+                    err, oracle = errors_of(word_dist, ref, best)
+                    n["word_err"] += err; n["word_ref"] += int(ref.size); n["word_scored"] += 1; n["word_oracle"] += oracle
                 if ctm is not None:       # the best hypothesis' words: a label each without a lexicon
                     if math.isnan(stamps.word_conf[s, 0, 0]):
                         raise RuntimeError(f"the forward pass of {key} timed out on the device: no time stamps")
@@ -381,9 +415,13 @@ def main(argv=None) -> int:
             ctm.close()
         if o.ref_rspecifier:
             log(f"{n['tok_err']} token errors on {n['tok_ref']} reference tokens of {n['scored']} utterances")
+            if o.mbr:
+                log(f"{n['tok_oracle']} token errors of the N-best oracle (the best of up to {o.nbest} hypotheses per utterance)")
             log(f"\nTOKEN_ACCURACY >> {100.0 * (1.0 - n['tok_err'] / max(n['tok_ref'], 1)):g}% <<")
         if o.word_ref_rspecifier:
             log(f"{n['word_err']} word errors on {n['word_ref']} reference words of {n['word_scored']} utterances")
+            if o.mbr:
+                log(f"{n['word_oracle']} word errors of the N-best oracle (the best of up to {o.nbest} hypotheses per utterance)")
             log(f"\nWORD_ACCURACY >> {100.0 * (1.0 - n['word_err'] / max(n['word_ref'], 1)):g}% <<")
         if n["dead"]:
             log(f"{n['dead']} utterances without a hypothesis")
@@ -393,6 +431,8 @@ def main(argv=None) -> int:
             tail += f"; {n['ctm']} CTM words"
         if o.rescore:
             tail += f"; {n['reranked']} utterances re-ranked"
+        if o.mbr:
+            tail += f"; {n['mbr_moved']} utterances whose hypothesis of least expected errors is not the most probable"
         log(f"Done {n['done']} utterances, {n['empty']} empty hypotheses; average log-probability per frame {avg:g}{tail}")
         return 0 if n["done"] else 255
     except Exception as e:

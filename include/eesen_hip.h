@@ -587,6 +587,47 @@ int eesen_ctc_decode_rescore(eesen_ctc_t* ctc, const int* frame_num_utt, int S, 
 /* seconds of the last of the two calls above: out[0]=lattice build (with the logarithm when is_log == 0), [1]=the scoring sweep (both
  * device time), [2]=the host's LM scoring and ranking (0 after eesen_ctc_score_parallel). */
 int eesen_ctc_get_rescore_times(eesen_ctc_t* ctc, float* out3);
+/* ---- edit distances on the device and minimum Bayes risk over N-best lists (INTEGRATION.md "Minimum Bayes risk") --------------------
+ * d(a, b) = the Levenshtein distance of two int32 token sequences, unit costs, the total only: what eesen_edit_distance returns, and
+ * every integer equal to it.  One wavefront per pair, all pairs of a call in one launch (edit_distance_kernel).  At most 8192 tokens
+ * per sequence.
+ *
+ * eesen_edit_distance_parallel: G groups of sequences.  Group g owns the sequences seq_off[g] .. seq_off[g + 1] (seq_off[0] = 0,
+ * NQ = seq_off[G], n_g its count); sequence q the tokens tok_ids[tok_off[q] .. tok_off[q + 1]), any int32.  pair_host receives
+ * n_g x n_g int32 per group, packed group after group: d of every two sequences of the group, 0 on the diagonal (the pairs i < j are
+ * computed and mirrored).  With ref_off / ref_ids (group g's reference: ref_ids[ref_off[g] .. ref_off[g + 1]), may be empty)
+ * ref_dist_host [NQ] receives every sequence's distance to its group's reference.  pair_host may be NULL; ref_off, ref_ids and
+ * ref_dist_host are NULL together.  G = 0 and groups without a sequence are allowed.  EESEN_ERR_INVALID, before any launch: offsets
+ * that decrease, a sequence or reference of more than 8192 tokens.  Touches no statistic and no buffer another call reads
+ * afterwards.  The call waits for its results. */
+int eesen_edit_distance_parallel(eesen_ctc_t* ctc, int G, const int* seq_off /*G+1*/, const int* tok_off /*NQ+1*/, const int* tok_ids,
+                                 const int* ref_off /*G+1 or NULL*/, const int* ref_ids /*or NULL*/, int* pair_host /*sum n_g^2 or NULL*/,
+                                 int* ref_dist_host /*NQ or NULL*/);
+/* eesen_ctc_decode_mbr: N-best minimum Bayes risk (Stolcke et al. 1997) over the entries the LAST decode call on this Ctc returned (any
+ * of the four), taken from where that call left them -- no labels travel through the caller.  S: that call's.
+ *   level 0: an entry's tokens are the mode's LM tokens -- its labels (plain, token LM) or its word ids (both lexicon modes), the
+ *            tokens eesen_ctc_decode_rescore scores;   level 1: always its labels (under a lexicon the space is a label like any other).
+ *   z_i = total_host[s * nbest + i] if total_host is given (eesen_ctc_decode_rescore's totals), else the decode call's score.
+ *   Entry i COUNTS if it is within the returned count, z_i > -1e29, z_i is not NaN and it has no more than 8192 tokens.
+ * With c = scale (finite, >= 0), in fp64, every sum over the counting k in ascending rank:
+ *   P_i = exp(c (z_i - z_max)) / sum_k exp(c (z_k - z_max));   risk_i = sum_k P_k d(i, k).
+ * dist_host [S][nbest][nbest] int32: d(i, k), -1 where either entry does not count.  ref_dist_host [S][nbest] int32: d(i, reference of
+ * utterance s) with ref_ids[ref_off[s] .. ref_off[s + 1]) the reference in the level's tokens; -1 where the entry does not count, and
+ * everywhere without ref_off.  post_host / risk_host [S][nbest] double, -1e30 where the entry does not count.  order_host [S][nbest]
+ * int32: the counting ranks by risk ascending, ties to the larger z, then to the smaller rank; then the others in rank order.
+ * Any output may be NULL; when only ref_dist_host (or post_host) is asked for, the pairwise jobs are not launched.  Under a raised guard
+ * word (in the decode call or in this one): dist, ref_dist and order -1, post and risk NaN.  Nothing the decode call left is changed:
+ * eesen_ctc_decode_stamps and eesen_ctc_decode_rescore afterwards behave as before.
+ * EESEN_ERR_STATE: no decode call yet, or S differs from its.  EESEN_ERR_INVALID: a non-finite or negative scale, a level outside
+ * {0, 1}, reference offsets that decrease, a reference of more than 8192 tokens.  The call waits for its results. */
+int eesen_ctc_decode_mbr(eesen_ctc_t* ctc, int S, int level, double scale, const float* total_host /*S*nbest or NULL*/,
+                         const int* ref_off /*S+1 or NULL*/, const int* ref_ids /*or NULL*/, int* dist_host /*S*nbest*nbest or NULL*/,
+                         int* ref_dist_host /*S*nbest or NULL*/, double* post_host /*S*nbest or NULL*/, double* risk_host /*S*nbest or NULL*/,
+                         int* order_host /*S*nbest or NULL*/);
+/* seconds of the last of the two calls above (all 0 before the first): out[0]=job build and uploads (host), [1]=the distance kernel
+ * (device time), [2]=the host's mirroring, posteriors, risks and ranking.  Under eesen_ctc_set_profiling(ctc, 2) the three are summed
+ * over the calls since they were last read. */
+int eesen_ctc_get_mbr_times(eesen_ctc_t* ctc, float* out3);
 
 /* N-best posterior word confidences in fp64 on the host; no device work.  Entry i of n_entries has the total scores[i] and word_len[i]
  * words (< 0: not an entry, skipped) with ids word_ids[i*stride + j] and frame intervals [wstart, wend).  With c = conf_scale (finite,

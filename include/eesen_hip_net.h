@@ -574,6 +574,80 @@ class Ctc {
         if (ord[(size_t)s * nbest + i] >= 0 && ord[(size_t)s * nbest + i] < count) out->order[s].push_back(ord[(size_t)s * nbest + i]);
     }
   }
+  /* Levenshtein distances on the device, eesen_edit_distance_parallel (INTEGRATION.md "Minimum Bayes risk"): seqs[g] the sequences of
+   * group g (any int32 tokens, at most 8192 each); pair[g] the n_g x n_g distances among them, row-major; with refs (one per group)
+   * ref_dist[g][i] the distance of seqs[g][i] to refs[g].  pair may be NULL (no pairwise distances are computed); refs and ref_dist
+   * go together: with either NULL no reference distances are computed. */
+  void EditDistanceParallel(const std::vector<std::vector<std::vector<int32> > >& seqs, std::vector<std::vector<int32> >* pair,
+                            const std::vector<std::vector<int32> >* refs = NULL, std::vector<std::vector<int32> >* ref_dist = NULL) {
+    const int G = (int)seqs.size();
+    std::vector<int> soff(1, 0), toff(1, 0), ids, roff(1, 0), rids;
+    size_t n2 = 0;
+    for (int g = 0; g < G; ++g) {
+      for (size_t i = 0; i < seqs[g].size(); ++i) {
+        ids.insert(ids.end(), seqs[g][i].begin(), seqs[g][i].end());
+        toff.push_back((int)ids.size());
+      }
+      soff.push_back((int)toff.size() - 1);
+      n2 += seqs[g].size() * seqs[g].size();
+      if (refs && g < (int)refs->size()) rids.insert(rids.end(), (*refs)[g].begin(), (*refs)[g].end());
+      roff.push_back((int)rids.size());
+    }
+    ids.push_back(0); rids.push_back(0);
+    const bool with_refs = refs != NULL && ref_dist != NULL;
+    std::vector<int32> p(pair ? n2 + 1 : 1), rd(toff.size());
+    HipCheck(eesen_edit_distance_parallel(h_, G, soff.data(), toff.data(), ids.data(), with_refs ? roff.data() : NULL, with_refs ? rids.data() : NULL,
+                                          pair ? p.data() : NULL, with_refs ? rd.data() : NULL));
+    if (pair) pair->assign(G, std::vector<int32>());
+    if (ref_dist) ref_dist->assign(G, std::vector<int32>());
+    size_t at = 0;
+    for (int g = 0; g < G; ++g) {
+      const size_t n = seqs[g].size();
+      if (pair) (*pair)[g].assign(p.begin() + at, p.begin() + at + n * n);
+      at += n * n;
+      if (with_refs) (*ref_dist)[g].assign(rd.begin() + soff[g], rd.begin() + soff[g + 1]);
+    }
+  }
+  /* Minimum Bayes risk over the entries the LAST DecodeParallel returned (any overload), eesen_ctc_decode_mbr: dist[s] the nbest x nbest
+   * distances (row-major, -1 where an entry does not count), posterior / risk [s][i] (-1e30 there), order[s] the first-pass ranks by
+   * risk ascending (ties: the larger score, then the smaller rank; the entries that do not count last), ref_dist[s][i] the distance to
+   * refs[s] (empty without refs).  level 0: over the mode's LM tokens, 1: over labels.  totals: z of every entry, S rows of nbest
+   * (RescoreNbest's totals padded with -1e30), or NULL for the decode call's scores.  S: that call's. */
+  struct Mbr {
+    std::vector<std::vector<int32> > dist, ref_dist, order;
+    std::vector<std::vector<double> > posterior, risk;
+  };
+  void MbrNbest(int32 S, Mbr* out, int level = 0, double scale = 1.0, const std::vector<std::vector<BaseFloat> >* totals = NULL,
+                const std::vector<std::vector<int32> >* refs = NULL) {
+    const int nbest = last_nbest_;
+    const size_t n = (size_t)S * nbest;
+    std::vector<BaseFloat> z(n + 1, -1e30f);
+    if (totals)
+      for (int s = 0; s < S && s < (int)totals->size(); ++s)
+        for (int i = 0; i < nbest && i < (int)(*totals)[s].size(); ++i) z[(size_t)s * nbest + i] = (*totals)[s][i];
+    std::vector<int> roff(1, 0), rids;
+    for (int s = 0; s < S; ++s) {
+      if (refs && s < (int)refs->size()) rids.insert(rids.end(), (*refs)[s].begin(), (*refs)[s].end());
+      roff.push_back((int)rids.size());
+    }
+    rids.push_back(0);
+    std::vector<int32> d(n * nbest + 1), rd(n + 1), ord(n + 1);
+    std::vector<double> post(n + 1), risk(n + 1);
+    HipCheck(eesen_ctc_decode_mbr(h_, S, level, scale, totals ? z.data() : NULL, refs ? roff.data() : NULL, refs ? rids.data() : NULL, d.data(),
+                                  refs ? rd.data() : NULL, post.data(), risk.data(), ord.data()));
+    out->dist.assign(S, std::vector<int32>());
+    out->ref_dist = out->order = out->dist;
+    out->posterior.assign(S, std::vector<double>());
+    out->risk = out->posterior;
+    for (int s = 0; s < S; ++s) {
+      const size_t e = (size_t)s * nbest;
+      out->dist[s].assign(d.begin() + e * nbest, d.begin() + (e + nbest) * nbest);
+      out->order[s].assign(ord.begin() + e, ord.begin() + e + nbest);
+      out->posterior[s].assign(post.begin() + e, post.begin() + e + nbest);
+      out->risk[s].assign(risk.begin() + e, risk.begin() + e + nbest);
+      if (refs) out->ref_dist[s].assign(rd.begin() + e, rd.begin() + e + nbest);
+    }
+  }
   void SetReportStep(int32 s) { report_step_ = s; }
   void SetFramesPerSec(float f) { frames_per_sec_ = f; }
   float NumErrorTokens() const { long e = 0; HipCheck(eesen_ctc_stats(h_, NULL, NULL, NULL, &e, NULL)); return (float)e; }   /* ctc-loss.h:62 */
