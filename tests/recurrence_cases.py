@@ -13,6 +13,10 @@ layer per case, at a shape and with the switches at which rec_plan.cpp takes a g
 
 Every row of the table is in exactly one of HELD_ELSEWHERE, UNREACHED and the rows only CASES names (tests/test_recurrence_cases.py);
 a case whose other pass runs a row that another module holds (the narrow plane tile at 320 cells) leaves that row with its module.
+
+Every case here runs on a whole device.  What the planner answers on a SHARED one (EESEN_GPU_SHARE > 1: sequence windows of 2, 4 and
+8 launches, other tiles, per-step kernels at shapes that are persistent here) is tests/share_cases.py's table, run by
+tests/test_gpu_recurrence_share.py.
 """
 from tests import dropout_cases as dc
 from tests.dropout_cases import D, oracle_run, seq_worst  # noqa: F401  (the metrics and the oracle are that module's)
@@ -183,6 +187,11 @@ def top_gradients(name, lens):
 
 def layer(name):
     return dc.shape_layer(ALL[name]["kind"], ALL[name]["H"])
+
+
+def masks(name):
+    """No case of this table has dropout (tests/dropout_cases.py holds those rows; tests/share_cases.py runs two under a share)."""
+    return None
 
 
 def line_aligned(name):

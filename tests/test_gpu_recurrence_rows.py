@@ -61,20 +61,22 @@ def bar(yardstick, factor):
     return max(factor * yardstick, FLOOR)
 
 
+# `cases`: the module that holds the case table and its generators -- tests/recurrence_cases.py, or tests/share_cases.py for
+# tests/test_gpu_recurrence_share.py, which runs these same functions on its own table
 @functools.lru_cache(maxsize=None)
-def _inputs(name):
+def _inputs(name, cases=rc):
     """(lengths, features, [(profile, od)], zero sequences) of a case: computed once, shared by the arms and the oracles, never written."""
-    lens = rc.lengths(name)
-    ods, zero = rc.top_gradients(name, lens)
-    x = rc.features(name, lens)
+    lens = cases.lengths(name)
+    ods, zero = cases.top_gradients(name, lens)
+    x = cases.features(name, lens)
     for a in [lens, x] + [od for _, od in ods]:
         a.setflags(write=False)
     return lens, x, ods, zero
 
 
-def _oracle(name, prec):
-    lens, x, ods, _ = _inputs(name)
-    return rc.oracle_run(rc.layer(name), x, lens, ods, prec)
+def _oracle(name, prec, cases=rc):
+    lens, x, ods, _ = _inputs(name, cases)
+    return cases.oracle_run(cases.layer(name), x, lens, ods, prec, cases.masks(name))
 
 
 @pytest.fixture(scope="module")
@@ -103,26 +105,30 @@ def report():
         pass
 
 
-def _arm(monkeypatch, env, name, runs=1):
-    """One fresh Net through Propagate and Backpropagate for every od, `runs` times over.
+def _arm(monkeypatch, env, name, runs=1, cases=rc):
+    """One fresh Net through Propagate and Backpropagate for every od, `runs` times over (a case with recurrent dropout: its masks
+    injected before every Propagate -- they are one-shot).
     Returns (plan, info, recoveries, [(out, [(in_diff, grads) per od]) per run])."""
     from eesen_amd.api import Net, CuMatrix
-    c = rc.ALL[name]; S, T = c["S"], c["T"]
-    lens, x, ods, _ = _inputs(name)
+    c = cases.ALL[name]; S, T = c["S"], c["T"]
+    lens, x, ods, _ = _inputs(name, cases)
+    mk = cases.masks(name)
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    net = Net.from_layers(rc.layer(name))
+    net = Net.from_layers(cases.layer(name))
     passes = []
     for _ in range(runs):
         out, back = None, []
         for _, od in ods:
+            if mk is not None:
+                net.SetDropoutMasks(0, fwd=mk["fwd"], rec=mk["rec"])
             net.SetSeqLengths(lens)
             o = net.Propagate(x).numpy()
             assert out is None or np.array_equal(o, out), "the same input gave another output"
             out = o
-            idf = CuMatrix(T * S, rc.D)
+            idf = CuMatrix(T * S, cases.D)
             net.BackpropagateNoUpdate(CuMatrix.from_numpy(od), idf)
             back.append((idf.numpy(), net.GetGrads()))
         passes.append((out, back))
@@ -151,9 +157,9 @@ def _what_ran(tag, plan, info, recoveries, fwd, bwd, launches, fails):
                 workgroups=[f.get("workgroups", 0), b.get("workgroups", 0)], recoveries=recoveries)
 
 
-def _exact(tag, name, passes, fails):
-    c = rc.ALL[name]; H, S, T, nd = c["H"], c["S"], c["T"], rc.ndir(name)
-    lens, _, ods, zero = _inputs(name)
+def _exact(tag, name, passes, fails, cases=rc):
+    c = cases.ALL[name]; H, S, T, nd = c["H"], c["S"], c["T"], cases.ndir(name)
+    lens, _, ods, zero = _inputs(name, cases)
     pad = np.arange(T)[:, None] >= lens[None, :]
     for out, back in passes:
         o = out.reshape(T, S, nd * H)
@@ -162,7 +168,7 @@ def _exact(tag, name, passes, fails):
         if not np.all(o[pad] == 0):
             fails.append(f"{tag}: padding rows of the output are not zero")
         for (prof, _), (ind, g) in zip(ods, back):
-            i = ind.reshape(T, S, rc.D)
+            i = ind.reshape(T, S, cases.D)
             if not (np.isfinite(i).all() and np.isfinite(g).all()):
                 fails.append(f"{tag} {prof}: in_diff or a gradient is not finite")
             if not np.all(i[pad] == 0):
@@ -175,10 +181,10 @@ def _exact(tag, name, passes, fails):
             fails.append(f"{tag}: the second run on the same Net gave other bits")
 
 
-def _accuracy(name, arms, oracles, report, fails):
+def _accuracy(name, arms, oracles, report, fails, cases=rc):
     """arms: tag -> (out, back) of the arm's first run; each held to the bar of every quantity."""
-    c = rc.ALL[name]; H, S, T, nd = c["H"], c["S"], c["T"], rc.ndir(name)
-    lens, _, ods, _ = _inputs(name)
+    c = cases.ALL[name]; H, S, T, nd = c["H"], c["S"], c["T"], cases.ndir(name)
+    lens, _, ods, _ = _inputs(name, cases)
     ref_out, ref_back = oracles[(name, "f64")].result()
     f32_out, f32_back = oracles[(name, "f32")].result()
 
@@ -198,13 +204,13 @@ def _accuracy(name, arms, oracles, report, fails):
         report(row)
 
     r3 = lambda v, w: np.asarray(v).reshape(T, S, w)
-    hold("out", {**{a: rc.seq_worst(r3(out, nd * H), r3(ref_out, nd * H), lens, nd) for a, (out, _) in arms.items()},
-                 "O": rc.seq_worst(r3(f32_out, nd * H), r3(ref_out, nd * H), lens, nd)})
-    L = rc.layer(name)
+    hold("out", {**{a: cases.seq_worst(r3(out, nd * H), r3(ref_out, nd * H), lens, nd) for a, (out, _) in arms.items()},
+                 "O": cases.seq_worst(r3(f32_out, nd * H), r3(ref_out, nd * H), lens, nd)})
+    L = cases.layer(name)
     names = lambda flat: {n: v for _, n, v in split_params(L, np.asarray(flat))}
     for k, (prof, _) in enumerate(ods):
-        hold(f"in_diff/{prof}", {**{a: rc.seq_worst(r3(back[k][0], rc.D), r3(ref_back[k][0], rc.D), lens) for a, (_, back) in arms.items()},
-                                 "O": rc.seq_worst(r3(f32_back[k][0], rc.D), r3(ref_back[k][0], rc.D), lens)})
+        hold(f"in_diff/{prof}", {**{a: cases.seq_worst(r3(back[k][0], cases.D), r3(ref_back[k][0], cases.D), lens) for a, (_, back) in arms.items()},
+                                 "O": cases.seq_worst(r3(f32_back[k][0], cases.D), r3(ref_back[k][0], cases.D), lens)})
         g = {**{a: names(back[k][1]) for a, (_, back) in arms.items()}, "O": names(f32_back[k][1])}
         ref = names(ref_back[k][1])
         for n in ref:

@@ -91,6 +91,11 @@ def test_the_case_table_is_well_formed():
 
 @pytest.mark.parametrize("name", list(rc.ALL))
 def test_lengths_features_and_top_gradients(name):
+    check_lengths_features_and_top_gradients(name)
+
+
+def check_lengths_features_and_top_gradients(name, rc=rc):
+    """(rc: the module of the case table -- tests/test_share_cases.py holds its own table's inputs to the same checks)"""
     c = rc.ALL[name]; S, T, H, nd = c["S"], c["T"], c["H"], rc.ndir(name)
     lens = rc.lengths(name)
     assert lens.shape == (S,) and lens.dtype == np.int32 and lens.min() >= 1 and lens.max() == T
@@ -134,11 +139,15 @@ def test_the_generalised_generators_are_the_dropout_modules():
 
 @pytest.mark.parametrize("name", SMALLEST)
 def test_the_fp32_oracle_is_a_yardstick_and_both_oracles_satisfy_the_exact_checks(name):
+    check_the_yardstick(name)
+
+
+def check_the_yardstick(name, rc=rc):
     c = rc.ALL[name]; S, T, H, nd = c["S"], c["T"], c["H"], rc.ndir(name)
     lens = rc.lengths(name); x = rc.features(name, lens); ods, zero = rc.top_gradients(name, lens)
     L = rc.layer(name)
-    out64, back64 = rc.oracle_run(L, x, lens, ods, "f64")
-    out32, back32 = rc.oracle_run(L, x, lens, ods, "f32")
+    out64, back64 = rc.oracle_run(L, x, lens, ods, "f64", rc.masks(name))
+    out32, back32 = rc.oracle_run(L, x, lens, ods, "f32", rc.masks(name))
     pad = np.arange(T)[:, None] >= lens[None, :]
     for out, back in ((out64, back64), (out32, back32)):
         o = out.reshape(T, S, nd * H)
