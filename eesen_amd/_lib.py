@@ -154,9 +154,17 @@ SIGNATURES = {
     "eesen_feeder_acquire": (_i, [_vp, _i, C.POINTER(_vp), _pi, _pi, _pi]),
     "eesen_feeder_release": (_i, [_vp, _i]),
     "eesen_feeder_set_pipeline": (_i, [_vp, _vp, _i]),
+    "eesen_feeder_set_fbank": (_i, [_vp, _vp]),
     "eesen_feeder_pipeline_shape": (_i, [_vp, _i, _i, _pi, _pi]),
     "eesen_feeder_submit_raw": (_i, [_vp, C.POINTER(_vp), _pi, _pi, C.POINTER(_vp), _i, _i, _pi]),
     "eesen_cmvn_norm": (_i, [_pd, _i, _i, _i, _pf]),
+    "eesen_fbank_opts_default": (_i, [_vp]),
+    "eesen_fbank_create": (_i, [_i, _vp, _vp, C.POINTER(_vp)]),
+    "eesen_fbank_destroy": (_i, [_vp]),
+    "eesen_fbank_shape": (_i, [_vp, _i, _pi, _pi]),
+    "eesen_fbank_compute": (_i, [_vp, C.POINTER(_vp), _pi, _vp, _i, C.POINTER(_vp)]),
+    "eesen_fbank_bench": (_i, [_vp, C.POINTER(_vp), _pi, _i, _i, _pf]),
+    "eesen_fbank_mel_banks": (_i, [_vp, _vp, _vp, _vp, _i, _pi]),
     "eesen_dev_alloc": (_i, [_i, _l, C.POINTER(_vp)]),
     "eesen_dev_free": (_i, [_i, _vp]),
     "eesen_dev_copy": (_i, [_i, _vp, _vp, _l, _i]),
@@ -166,6 +174,18 @@ SIGNATURES = {
     "eesen_op_gemm": (_i, [_i, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _f, _vp, _i, _vp]),
     "eesen_op_gemm_async": (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, C.c_long, _i]),
 }
+
+
+class FbankOpts(C.Structure):
+    """eesen_fbank_opts_t of include/eesen_hip.h, field for field."""
+    _fields_ = [("samp_freq", _f), ("frame_shift_ms", _f), ("frame_length_ms", _f), ("dither", _f), ("preemph_coeff", _f),
+                ("remove_dc_offset", _i), ("window_type", _i), ("round_to_power_of_two", _i), ("snip_edges", _i),
+                ("num_bins", _i), ("low_freq", _f), ("high_freq", _f), ("vtln_low", _f), ("vtln_high", _f), ("htk_mode", _i),
+                ("use_energy", _i), ("energy_floor", _f), ("raw_energy", _i), ("htk_compat", _i), ("use_log_fbank", _i),
+                ("vtln_warp", _f), ("dither_seed", C.c_ulonglong)]
+
+
+WINDOW_TYPES = {"hamming": 0, "hanning": 1, "povey": 2, "rectangular": 3}
 
 
 class EesenError(RuntimeError):

@@ -1128,6 +1128,12 @@ class Feeder:
         check(self.lib.eesen_feeder_set_pipeline(self.h, C.cast(arr, C.c_void_p), len(stages)))
         self._has_pipeline = len(stages) > 0
 
+    def set_fbank(self, **opts):
+        """Options of the filterbank head stage (`eesen_feeder_set_fbank`; keywords as for `Fbank`), to be called before a
+        set_pipeline whose first stage is EESEN_FEAT_FBANK: submit_raw then takes waveforms as [samples x 1] matrices."""
+        self._fbank_opts = fbank_opts(**opts)
+        check(self.lib.eesen_feeder_set_fbank(self.h, C.byref(self._fbank_opts)))
+
     def pipeline_shape(self, D_in: int, frames_in: int) -> Tuple[int, int]:
         """(frames, feature dimension) behind the pipeline for an utterance of [frames_in x D_in]."""
         d, t = C.c_int(), C.c_int()
@@ -1189,6 +1195,87 @@ class Feeder:
 
     def release(self, slot: int):
         check(self.lib.eesen_feeder_release(self.h, slot))
+
+
+def fbank_opts(**kw) -> "_lib.FbankOpts":
+    """The defaults of FbankOptions / FrameExtractionOptions / MelBanksOptions (`eesen_fbank_opts_default`) with `kw` on top:
+    field names of eesen_fbank_opts_t; `window_type` by name ("povey", ...); booleans as bool or int."""
+    o = _lib.FbankOpts()
+    check(_lib.load().eesen_fbank_opts_default(C.byref(o)))
+    names = {f[0] for f in _lib.FbankOpts._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise EesenError(-1, f"unknown fbank option {k}")
+        if k == "window_type" and isinstance(v, str):
+            if v not in _lib.WINDOW_TYPES:
+                raise EesenError(-1, f"Invalid window type {v}")
+            v = _lib.WINDOW_TYPES[v]
+        setattr(o, k, int(v) if isinstance(v, (bool, np.bool_)) else v)
+    return o
+
+
+class Fbank:
+    """Log-mel filterbank features from waveforms on the device (include/eesen_hip.h `eesen_fbank_*`; the reference's
+    compute-fbank-feats, src/feat/feature-fbank.cc).  Waveforms are 1-d arrays in int16 scale.
+
+        fb = Fbank(num_bins=40, dither=0.0)
+        frames, dim = fb.shape(len(wave))
+        feats = fb.compute([wave_a, wave_b])     # one launch for the minibatch; list of [frames x dim] float32
+    """
+
+    def __init__(self, device: int = 0, stream: Optional[int] = None, **opts):
+        self.lib = _lib.load()
+        self.opts = fbank_opts(**opts)
+        self.h = C.c_void_p()
+        check(self.lib.eesen_fbank_create(device, C.c_void_p(stream) if stream else None, C.byref(self.opts), C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h:
+            try:
+                self.lib.eesen_fbank_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def shape(self, nsamp: int) -> Tuple[int, int]:
+        """(frames, dim) for a waveform of nsamp samples: NumFrames in the extractor's edge mode, num_bins + use_energy."""
+        t, d = C.c_int(), C.c_int()
+        check(self.lib.eesen_fbank_shape(self.h, int(nsamp), C.byref(t), C.byref(d)))
+        return t.value, d.value
+
+    def compute(self, waves: Sequence[np.ndarray], utt_ids: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+        if not len(waves):
+            raise EesenError(-1, "empty minibatch")
+        waves = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in waves]
+        S = len(waves)
+        outs = [np.zeros(self.shape(len(w)), np.float32) for w in waves]
+        wp = (C.c_void_p * S)(*[w.ctypes.data for w in waves])
+        op = (C.c_void_p * S)(*[o.ctypes.data for o in outs])
+        ns = np.array([len(w) for w in waves], np.int32)
+        ids = None
+        if utt_ids is not None:
+            if len(utt_ids) != S:
+                raise EesenError(-1, "one utterance id per waveform")
+            ids = np.array(utt_ids, np.uint64)
+        check(self.lib.eesen_fbank_compute(self.h, wp, ns.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data if ids is not None else None, S, op))
+        return outs
+
+    def mel_banks(self):
+        return mel_banks(self.opts)
+
+
+def mel_banks(opts: "_lib.FbankOpts"):
+    """(first_index [num_bins], size [num_bins], list of weight vectors) of the reference's MelBanks for `opts` (vtln_warp
+    included); host only, no device needed (`eesen_fbank_mel_banks`)."""
+    lib = _lib.load()
+    nb = max(int(opts.num_bins), 0)
+    first, size = np.zeros(nb, np.int32), np.zeros(nb, np.int32)
+    n = C.c_int()
+    check(lib.eesen_fbank_mel_banks(C.byref(opts), first.ctypes.data, size.ctypes.data, None, 0, C.byref(n)))
+    w = np.zeros(n.value, np.float32)
+    check(lib.eesen_fbank_mel_banks(C.byref(opts), None, None, w.ctypes.data, n.value, None))
+    cuts = np.cumsum(size)[:-1]
+    return first, size, np.split(w, cuts)
 
 
 def train_step(net: Net, ctc: Ctc, batch, error_rate: bool = False) -> dict:

@@ -12,9 +12,11 @@
 // same kernel, so the output needs no memset.
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "fbank.h"
 #include "guard.h"
 
 namespace eesen {
@@ -143,10 +145,18 @@ struct Feeder {
     PinBuf cmvn_h;
     DevBuf<long> offs_d;
     DevBuf<int> frs_d;
+    // filterbank head stage: the frame prefix (S + 1) and the dither keys of the batch
+    PinBuf fb_meta_h;
+    DevBuf<int> fb_prefix_d;
+    DevBuf<unsigned long long> fb_ids_d;
   };
   struct Stage { int kind, a, b; size_t scale_off; };
   std::vector<Stage> pipe;
   DevBuf<float> scales_d;
+  // EESEN_FEAT_FBANK, the head stage that turns waveforms into features (fbank.hip); every waveform submitted gets a dither key of its own
+  std::unique_ptr<FbankPlan> fb_plan;
+  FbankDev fb_dev;
+  unsigned long long fb_next_id = 0;
   int device;
   hipStream_t compute;
   DevStream copy;
@@ -241,6 +251,10 @@ struct Feeder {
     for (int k = 0; k < n; ++k) {
       Stage g{st[k].kind, st[k].a, st[k].b, 0};
       switch (g.kind) {
+        case EESEN_FEAT_FBANK:
+          EESEN_REQUIRE(k == 0, EESEN_ERR_INVALID, "the filterbank stage reads waveforms: it must be the first stage");
+          EESEN_REQUIRE(fb_plan != nullptr, EESEN_ERR_STATE, "the filterbank stage needs its options first (eesen_feeder_set_fbank)");
+          break;
         case EESEN_FEAT_CMVN: ++n_cmvn; break;
         case EESEN_FEAT_SPLICE:   // KALDI_ASSERT(left_context >= 0 && right_context >= 0), feature-functions.cc:398
           EESEN_REQUIRE(g.a >= 0 && g.b >= 0 && g.a + g.b <= 64, EESEN_ERR_INVALID, "splice-feats: context must be 0..64 frames");
@@ -269,12 +283,25 @@ struct Feeder {
     }
     pipe.swap(np);
   }
-  static int stage_dim(const Stage& g, int D) {
+  void set_fbank(const eesen_fbank_opts_t& o) {
+    std::unique_ptr<FbankPlan> np(new FbankPlan(o));
+    EESEN_HIP_CHECK(hipSetDevice(device));
+    for (auto& s : slots)  // batches in flight still read the old tables
+      if (s.in_flight) s.ready.wait();
+    fb_dev.upload(*np);
+    fb_plan.swap(np);
+  }
+  int stage_dim(const Stage& g, int D) const {
+    if (g.kind == EESEN_FEAT_FBANK) {
+      EESEN_REQUIRE(D == 1, EESEN_ERR_INVALID, "the filterbank stage takes waveforms as [samples x 1] matrices");
+      return fb_plan->dim;
+    }
     if (g.kind == EESEN_FEAT_SPLICE) return D * (1 + g.a + g.b);
     if (g.kind == EESEN_FEAT_DELTAS) return D * (1 + g.a);
     return D;
   }
-  static int stage_frames(const Stage& g, int T) {
+  int stage_frames(const Stage& g, int T) const {
+    if (g.kind == EESEN_FEAT_FBANK) return fb_plan->num_frames(T);
     if (g.kind != EESEN_FEAT_SUBSAMPLE) return T;
     if (g.a < 0) return T * (-g.a);
     return T > g.b ? (T - g.b + g.a - 1) / g.a : 0;   // number of k = offset, offset + n, ... < T (subsample-feats.cc:82-84)
@@ -348,6 +375,24 @@ struct Feeder {
       float* dst = k % 2 ? sl.packed.p : sl.packed2.p;
       long biggest = 0;
       for (int s = 0; s < S; ++s) biggest = std::max(biggest, (long)fr_h[(size_t)(k + 1) * S + s] * dims[k + 1]);
+      if (pipe[k].kind == EESEN_FEAT_FBANK) {   // k == 0: the samples are boundary 0, the kernel writes boundary 1 where the next stage reads
+        int* prefix_h = static_cast<int*>(sl.fb_meta_h.reserve((size_t)(S + 2) * sizeof(int) + (size_t)S * sizeof(unsigned long long)));
+        unsigned long long* ids_h = reinterpret_cast<unsigned long long*>(prefix_h + (S + 2) / 2 * 2);
+        long frames_all = 0;
+        for (int s = 0; s < S; ++s) {
+          prefix_h[s] = (int)frames_all;
+          frames_all += fr_h[(size_t)S + s];
+          EESEN_REQUIRE(frames_all < (1L << 30), EESEN_ERR_INVALID, "too many frames in one batch");
+          ids_h[s] = fb_next_id++;
+        }
+        prefix_h[S] = (int)frames_all;
+        sl.fb_prefix_d.reserve((size_t)S + 1);
+        sl.fb_ids_d.reserve((size_t)S);
+        EESEN_HIP_CHECK(hipMemcpyAsync(sl.fb_prefix_d.p, prefix_h, (size_t)(S + 1) * sizeof(int), hipMemcpyHostToDevice, copy));
+        EESEN_HIP_CHECK(hipMemcpyAsync(sl.fb_ids_d.p, ids_h, (size_t)S * sizeof(unsigned long long), hipMemcpyHostToDevice, copy));
+        fbank_launch(*fb_plan, fb_dev, src, sl.offs_d.p, sl.frs_d.p, sl.fb_prefix_d.p, sl.fb_ids_d.p, S, (int)frames_all, dst, sl.offs_d.p + S, copy);
+        continue;
+      }
       const int bx = (int)std::min<long>(std::max<long>(cdivl(biggest, 256), 1), 2048);   // one element per thread: the stage is latency-bound otherwise
       const StageDev sd{pipe[k].kind, pipe[k].a, pipe[k].b};
       hipLaunchKernelGGL(feat_stage_kernel, dim3(bx, S), dim3(256), 0, copy, sd, scales_d.p ? scales_d.p + pipe[k].scale_off : nullptr, src,
@@ -415,6 +460,12 @@ int eesen_feeder_set_pipeline(eesen_feeder_t* f, const eesen_feat_stage_t* stage
     REQ_PTR(f);
     if (n_stages > 0) REQ_PTR(stages);
     f->set_pipeline(stages, n_stages);
+  });
+}
+int eesen_feeder_set_fbank(eesen_feeder_t* f, const eesen_fbank_opts_t* opts) {
+  return guard([&] {
+    REQ_PTR(f); REQ_PTR(opts);
+    f->set_fbank(*opts);
   });
 }
 int eesen_feeder_pipeline_shape(eesen_feeder_t* f, int D_in, int frames_in, int* D_out, int* frames_out) {

@@ -80,11 +80,11 @@ int main(int argc, char** argv) {
     const bool piped = !getenv("EESEN_HOST_FEATURE_PIPES") && parse_feature_pipeline(args[1], &pipe);
     std::unique_ptr<CmvnTable> cmvn_table;
     if (piped) {
-      ck(eesen_feeder_set_pipeline(feeder, pipe.stages.data(), (int)pipe.stages.size()));
+      ck(pipe.configure(feeder));
       if (!pipe.cmvn.empty()) cmvn_table.reset(new CmvnTable(pipe.cmvn, pipe.utt2spk, pipe.norm_vars));
     }
     const std::map<std::string, std::vector<int32_t>> labels = read_targets(args[2]);
-    FeatureReader reader(piped ? pipe.source : args[1]);
+    FeatureReader reader(piped ? pipe.source : args[1], piped ? pipe.wave_mode() : nullptr);
     IntVectorWriter writer(args[3]);
     std::unique_ptr<IntVectorWriter> pos_writer;
     if (!positions_wspecifier.empty()) pos_writer.reset(new IntVectorWriter(positions_wspecifier));
@@ -147,7 +147,7 @@ int main(int argc, char** argv) {
         if (cmvn_table) {
           const std::vector<float>* n = cmvn_table->lookup(utt);
           if (!n) { std::cerr << "WARNING (ctc-align:main()) No normalization statistics available for key " << utt << ", producing no output for this utterance" << std::endl; continue; }
-          if (CmvnTable::dim(*n) != m.cols)
+          if (CmvnTable::dim(*n) != pipe.cmvn_dim(m.cols))
             throw std::runtime_error("Dim mismatch in ApplyCmvn: cmvn 2x" + std::to_string(CmvnTable::dim(*n) + 1) + ", feats " + std::to_string(m.rows) + "x" + std::to_string(m.cols));
           cm = n->data();
         }

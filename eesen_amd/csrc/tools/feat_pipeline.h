@@ -9,6 +9,11 @@
 // subsample-feats,add-deltas}.cc); the tool then reads the RAW table itself, looks the CMVN statistics up per utterance, and the
 // filters run on the GPU inside the batch assembly.  Anything else (another tool, an option not implemented, e.g. --skip-dims)
 // is left to the shell: the rspecifier is opened as the pipe it is.  Same logic as eesen_amd/frontend.py.
+//
+// The pipe may start at the audio: `compute-fbank-feats [options] scp:wav.scp ark:- | apply-cmvn ... ark:- ark:- | add-deltas ark:- ark:- |`.
+// The tool then reads the wav table itself (FeatureReader in wave mode) and the features are computed on the device as well
+// (EESEN_FEAT_FBANK, the head stage); an option the device extractor does not implement (--vtln-map, --subtract-mean, htk output,
+// --round-to-power-of-two=false ...) leaves the rspecifier unrecognised.
 #pragma once
 #include <cmath>
 #include <map>
@@ -25,6 +30,16 @@ struct Pipeline {
   std::vector<eesen_feat_stage_t> stages;   // in order
   std::string cmvn, utt2spk;                // statistics rspecifier / rxfilename ("" = no CMVN stage), utt2spk rspecifier
   bool norm_vars = false;
+  // with a compute-fbank-feats head: `source` is the wav table
+  bool has_fbank = false;
+  eesen_fbank_opts_t fbank;
+  WaveSelect wave;
+  const WaveSelect* wave_mode() const { return has_fbank ? &wave : nullptr; }
+  int cmvn_dim(int raw_cols) const { return has_fbank ? fbank.num_bins + (fbank.use_energy ? 1 : 0) : raw_cols; }   // in front of the CMVN stage
+  int configure(eesen_feeder_t* feeder) const {   // the filterbank options first, then the stages
+    if (has_fbank) { const int rc = eesen_feeder_set_fbank(feeder, &fbank); if (rc != EESEN_OK) return rc; }
+    return eesen_feeder_set_pipeline(feeder, stages.data(), (int)stages.size());
+  }
 };
 
 inline bool shell_split(const std::string& s, std::vector<std::string>* out) {  // whitespace-separated words, '...' and "..." quoting
@@ -64,6 +79,52 @@ inline bool to_int(const std::string& v, int* x) {
   if (*end) return false;
   *x = (int)r;
   return true;
+}
+
+inline bool to_float(const std::string& v, float* x) {
+  if (v.empty()) return false;
+  char* end = nullptr;
+  const double r = strtod(v.c_str(), &end);
+  if (*end) return false;
+  *x = (float)r;
+  return true;
+}
+
+// compute-fbank-feats' options onto eesen_fbank_opts_t (FrameExtractionOptions / MelBanksOptions / FbankOptions::Register, --vtln-warp of
+// the tool, --dither-seed of this project); false: an unknown name or a value that does not parse
+inline bool set_fbank_option(const std::string& name, const std::string& v, eesen_fbank_opts_t* o) {
+  auto b = [&](int* dst) { bool x; if (!to_bool(v, &x)) return false; *dst = x ? 1 : 0; return true; };
+  if (name == "sample-frequency") return to_float(v, &o->samp_freq);
+  if (name == "frame-length") return to_float(v, &o->frame_length_ms);
+  if (name == "frame-shift") return to_float(v, &o->frame_shift_ms);
+  if (name == "preemphasis-coefficient") return to_float(v, &o->preemph_coeff);
+  if (name == "remove-dc-offset") return b(&o->remove_dc_offset);
+  if (name == "dither") return to_float(v, &o->dither);
+  if (name == "window-type") {
+    const char* names[] = {"hamming", "hanning", "povey", "rectangular"};
+    for (int i = 0; i < 4; ++i) if (v == names[i]) { o->window_type = i; return true; }
+    return false;
+  }
+  if (name == "round-to-power-of-two") return b(&o->round_to_power_of_two);
+  if (name == "snip-edges") return b(&o->snip_edges);
+  if (name == "num-mel-bins") return to_int(v, &o->num_bins);
+  if (name == "low-freq") return to_float(v, &o->low_freq);
+  if (name == "high-freq") return to_float(v, &o->high_freq);
+  if (name == "vtln-low") return to_float(v, &o->vtln_low);
+  if (name == "vtln-high") return to_float(v, &o->vtln_high);
+  if (name == "use-energy") return b(&o->use_energy);
+  if (name == "energy-floor") return to_float(v, &o->energy_floor);
+  if (name == "raw-energy") return b(&o->raw_energy);
+  if (name == "htk-compat") return b(&o->htk_compat);
+  if (name == "use-log-fbank") return b(&o->use_log_fbank);
+  if (name == "vtln-warp") return to_float(v, &o->vtln_warp);
+  if (name == "dither-seed") {
+    if (v.empty()) return false;
+    char* end = nullptr;
+    o->dither_seed = strtoull(v.c_str(), &end, 10);
+    return !*end;
+  }
+  return false;
 }
 
 // `--name=value` options (names with '_' for '-' accepted, as ParseOptions does) and positional arguments
@@ -119,6 +180,39 @@ inline bool parse_feature_pipeline(const std::string& rspecifier, Pipeline* out)
       for (const auto& kv : o) { bool ok = false; for (const char* n : names) ok = ok || kv.first == n; if (!ok) return false; }
       return true;
     };
+    if (si == 0 && tool == "compute-fbank-feats") {       // featbin/compute-fbank-feats.cc: the pipe starts at the audio
+      if (pos.size() != 2 || pos[1] != "ark:-") return false;
+      eesen_fbank_opts_default(&p.fbank);
+      for (const auto& kv : o) {
+        if (kv.first == "channel") { if (!to_int(kv.second, &p.wave.channel)) return false; }
+        else if (kv.first == "min-duration") { if (!to_float(kv.second, &p.wave.min_duration)) return false; }
+        else if (kv.first == "output-format") { if (kv.second != "kaldi") return false; }
+        else if (!set_fbank_option(kv.first, kv.second, &p.fbank)) return false;
+      }
+      if (!p.fbank.round_to_power_of_two) return false;
+      std::string src = pos[0];
+      while (!src.empty() && isspace((unsigned char)src.back())) src.pop_back();
+      if (!table_kind(src) || src.back() == '|') return false;
+      p.source = pos[0];
+      p.has_fbank = true;
+      p.wave.samp_freq = p.fbank.samp_freq;
+      p.stages.push_back({EESEN_FEAT_FBANK, 0, 0});
+      continue;
+    }
+    if (si == 1 && p.has_fbank && tool == "apply-cmvn") {  // reads the head's output: ark:-
+      if (!only({"utt2spk", "norm-vars", "norm-means"}) || pos.size() != 3 || pos[1] != "ark:-" || pos[2] != "ark:-") return false;
+      bool norm_means = true, norm_vars = false;
+      if (o.count("norm-means") && !to_bool(o["norm-means"], &norm_means)) return false;
+      if (o.count("norm-vars") && !to_bool(o["norm-vars"], &norm_vars)) return false;
+      if (norm_vars && !norm_means) return false;
+      if (norm_means) {
+        p.cmvn = pos[0];
+        p.utt2spk = o.count("utt2spk") ? o["utt2spk"] : "";
+        p.norm_vars = norm_vars;
+        p.stages.push_back({EESEN_FEAT_CMVN, norm_vars ? 1 : 0, 0});
+      }
+      continue;
+    }
     if (si == 0) {
       if (tool == "apply-cmvn") {                         // featbin/apply-cmvn.cc:36-47
         if (!only({"utt2spk", "norm-vars", "norm-means"}) || pos.size() != 3 || pos[2] != "ark:-") return false;

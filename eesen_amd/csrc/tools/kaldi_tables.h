@@ -2,7 +2,8 @@
 // train_ctc_parallel.cc and net_output_extract.cc).  Formats follow the reference: archive entry = key + space + object
 // (src/util/kaldi-table-inl.h), binary objects start with \0B (src/base/io-funcs-inl.h:183-187), float matrix FM
 // (src/cpucompute/matrix.cc:968-994), compressed CM / CM2 (src/cpucompute/compressed-matrix.cc:437-520), int32 vectors
-// (src/util/kaldi-holder-inl.h:190-260), script files `key path[:offset]` (src/util/kaldi-table.h).
+// (src/util/kaldi-holder-inl.h:190-260), script files `key path[:offset]` (src/util/kaldi-table.h), and RIFF/WAVE files with 16-bit
+// PCM samples (src/feat/wave-reader.cc) for the tools that start at the audio.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -216,6 +217,65 @@ inline std::vector<int32_t> read_int_vector(std::istream& is) {
   while (ls >> x) v.push_back(x);
   return v;
 }
+// WaveData::Read (src/feat/wave-reader.cc) for what the recipes feed it: RIFF/WAVE, PCM (format 1), 16 bits per sample, any channel
+// count -> [samples x channels] floats in int16 scale (the file's own interleaving) and the sample rate.  Chunks between `fmt ` and
+// `data` are skipped; a data chunk size of 0 or 0xFFFFFFFF (what sox and ffmpeg write into a pipe) means "read to the end", and a
+// data chunk cut short gives the samples that are there.  8- and 32-bit samples, RIFX and non-PCM formats are refused.
+struct Wave { Mat data; float samp_freq = 0.f; };
+inline Wave read_wave(std::istream& is) {
+  auto rd = [&](void* dst, size_t n, const char* what) {
+    is.read(static_cast<char*>(dst), (std::streamsize)n);
+    if (!is) throw std::runtime_error(std::string("WaveData: unexpected end of file (") + what + ")");
+  };
+  auto u32 = [&](const char* what) { unsigned char b[4]; rd(b, 4, what); return (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24; };
+  auto u16 = [&](const char* what) { unsigned char b[2]; rd(b, 2, what); return (uint32_t)b[0] | (uint32_t)b[1] << 8; };
+  char tag[5] = {0, 0, 0, 0, 0};
+  rd(tag, 4, "RIFF tag");
+  if (std::strcmp(tag, "RIFF")) throw std::runtime_error(std::string("WaveData: expected RIFF, got ") + tag);
+  u32("RIFF chunk size");
+  rd(tag, 4, "WAVE tag");
+  if (std::strcmp(tag, "WAVE")) throw std::runtime_error("WaveData: expected WAVE");
+  rd(tag, 4, "fmt tag");
+  if (std::strcmp(tag, "fmt ")) throw std::runtime_error("WaveData: expected the fmt chunk");
+  const uint32_t fmt_size = u32("fmt chunk size");
+  if (fmt_size < 16) throw std::runtime_error("WaveData: expect PCM format data to have fmt chunk of at least size 16.");
+  const uint32_t audio_format = u16("fmt"), channels = u16("fmt"), rate = u32("fmt"), byte_rate = u32("fmt"), block_align = u16("fmt"), bits = u16("fmt");
+  if (audio_format != 1) throw std::runtime_error("WaveData: can read only PCM data, format id in file is: " + std::to_string(audio_format));
+  for (uint32_t i = 16; i < fmt_size; ++i) { char c; rd(&c, 1, "fmt chunk"); }
+  if (channels == 0) throw std::runtime_error("WaveData: no channels present");
+  if (bits != 16) throw std::runtime_error("WaveData: only 16-bit samples are supported, bits_per_sample is " + std::to_string(bits));
+  if (byte_rate != rate * 2 * channels) throw std::runtime_error("Unexpected byte rate " + std::to_string(byte_rate) + " vs. " + std::to_string(rate) + " * 2 * " + std::to_string(channels));
+  if (block_align != 2 * channels) throw std::runtime_error("Unexpected block_align: " + std::to_string(block_align) + " vs. " + std::to_string(channels) + " * 2");
+  uint32_t size = 0;
+  for (;;) {
+    rd(tag, 4, "chunk name");
+    size = u32("chunk size");
+    if (!std::strcmp(tag, "data")) break;
+    for (uint32_t i = 0; i < size; ++i) { char c; rd(&c, 1, "chunk"); }
+  }
+  std::string raw;
+  if (size == 0 || size == 0xFFFFFFFFu) {
+    raw.assign(std::istreambuf_iterator<char>(is), std::istreambuf_iterator<char>());
+  } else {
+    raw.resize(size);
+    is.read(&raw[0], (std::streamsize)size);
+    raw.resize((size_t)is.gcount());
+    is.clear();
+    if (raw.empty()) throw std::runtime_error("WaveData: failed to read data chunk (read no bytes)");
+  }
+  Wave w;
+  w.samp_freq = (float)rate;
+  w.data.cols = (int)channels;
+  w.data.rows = (int)(raw.size() / block_align);
+  w.data.v.resize((size_t)w.data.rows * channels);
+  const unsigned char* b = reinterpret_cast<const unsigned char*>(raw.data());
+  for (size_t i = 0; i < w.data.v.size(); ++i) w.data.v[i] = (float)(int16_t)((uint16_t)b[2 * i] | (uint16_t)b[2 * i + 1] << 8);
+  return w;
+}
+// What compute-fbank-feats does with a wave file before the features (compute-fbank-feats.cc:97-139): a FeatureReader given one of
+// these reads a wav table and yields the chosen channel as a [samples x 1] matrix.
+struct WaveSelect { float samp_freq = 16000.f; int channel = -1; float min_duration = 0.f; std::string tool = "compute-fbank-feats"; };
+
 struct Spec { std::string kind, path; };
 inline Spec parse_spec(const std::string& s) {
   const size_t c = s.find(':');
@@ -227,16 +287,53 @@ inline Spec parse_spec(const std::string& s) {
 // SequentialBaseFloatMatrixReader (train-ctc-parallel.cc:124)
 class FeatureReader {
  public:
-  explicit FeatureReader(const std::string& rspecifier) : sp_(parse_spec(rspecifier)), in_(sp_.path), f_(in_.get()) { Next(); }
+  explicit FeatureReader(const std::string& rspecifier, const WaveSelect* wave = nullptr)
+      : sp_(parse_spec(rspecifier)), in_(sp_.path), f_(in_.get()), wave_(wave ? new WaveSelect(*wave) : nullptr) { Next(); }
+  long NumRead() const { return num_read_; }   // table entries seen, skipped ones included
   bool Done() const { return done_; }
   const std::string& Key() const { return key_; }
   Mat& Value() { return val_; }
   void Next() {
+    do { skip_ = false; Advance(); } while (!done_ && skip_);
+  }
+ private:
+  // a matrix, or in wave mode the chosen channel of a wave file; skip_ is set for an utterance the tool writes nothing for
+  Mat read_obj(std::istream& is) {
+    ++num_read_;
+    if (!wave_) return read_matrix(is);
+    Wave w = read_wave(is);
+    const std::string warn = "WARNING (" + wave_->tool + ":main()) ";
+    const double dur = w.data.rows / (double)w.samp_freq;
+    if (dur < wave_->min_duration) {
+      std::cerr << warn << "File: " << key_ << " is too short (" << dur << " sec): producing no output." << std::endl;
+      skip_ = true;
+      return Mat();
+    }
+    const int nch = w.data.cols;
+    int ch = wave_->channel;
+    if (ch == -1) {
+      ch = 0;
+      if (nch != 1) std::cerr << warn << "Channel not specified but you have data with " << nch << " channels; defaulting to zero" << std::endl;
+    } else if (ch >= nch) {
+      std::cerr << warn << "File with id " << key_ << " has " << nch << " channels but you specified channel " << ch << ", producing no output." << std::endl;
+      skip_ = true;
+      return Mat();
+    }
+    if (w.samp_freq != wave_->samp_freq)
+      throw std::runtime_error("Sample frequency mismatch: you specified " + std::to_string(wave_->samp_freq) + " but data has " + std::to_string(w.samp_freq) +
+                               " (use --sample-frequency option).  Utterance is " + key_);
+    Mat m;
+    m.rows = w.data.rows; m.cols = 1;
+    m.v.resize((size_t)m.rows);
+    for (int i = 0; i < m.rows; ++i) m.v[i] = w.data.v[(size_t)i * nch + ch];
+    return m;
+  }
+  void Advance() {
     if (done_) return;
     if (sp_.kind == "ark") {
       key_ = read_key(f_);
       if (key_.empty()) { done_ = true; in_.CloseChecked(); return; }
-      val_ = read_matrix(f_);
+      val_ = read_obj(f_);
       return;
     }
     std::string line;
@@ -261,24 +358,25 @@ class FeatureReader {
       // a script entry may itself be a command: `key cmd args |`
       if (!whole.empty() && whole.find_last_not_of(" \t") != std::string::npos && whole[whole.find_last_not_of(" \t")] == '|') {
         InStream a(whole);
-        val_ = read_matrix(a.get());
+        val_ = read_obj(a.get());
         return;
       }
       std::ifstream a(loc, std::ios::binary);
       if (!a) throw std::runtime_error("cannot open " + loc);
       a.seekg(off);
-      val_ = read_matrix(a);
+      val_ = read_obj(a);
       return;
     }
     done_ = true;
   }
- private:
   Spec sp_;
   InStream in_;
   std::istream& f_;
+  std::unique_ptr<WaveSelect> wave_;
   std::string key_;
   Mat val_;
-  bool done_ = false;
+  bool done_ = false, skip_ = false;
+  long num_read_ = 0;
 };
 // RandomAccessInt32VectorReader (train-ctc-parallel.cc:125): the whole table in memory
 inline std::map<std::string, std::vector<int32_t>> read_targets(const std::string& rspecifier) {
@@ -297,17 +395,38 @@ inline std::map<std::string, std::vector<int32_t>> read_targets(const std::strin
 }
 
 
-// BaseFloatMatrixWriter to `ark:file` (binary) or `ark,t:file` (text)
+// BaseFloatMatrixWriter to `ark:file` (binary), `ark,t:file` (text) or `ark,scp:file.ark,file.scp` (the archive and a script of
+// `key file.ark:offset` lines, the offset pointing at the object behind the key)
 class MatrixWriter {
  public:
   explicit MatrixWriter(const std::string& wspecifier) {
-    const Spec sp = parse_spec(wspecifier);
-    if (sp.kind != "ark") throw std::runtime_error("only ark: output is supported");
-    text_ = wspecifier.substr(0, wspecifier.find(':')).find(",t") != std::string::npos;
-    out_.reset(new OutStream(sp.path));
+    const size_t colon = wspecifier.find(':');
+    if (colon == std::string::npos) throw std::runtime_error("bad table specifier '" + wspecifier + "' (expected ark:... or ark,scp:...)");
+    std::vector<std::string> opts;
+    std::istringstream hs(wspecifier.substr(0, colon));
+    for (std::string o; std::getline(hs, o, ',');) opts.push_back(o);
+    int i_ark = -1, i_scp = -1;
+    for (size_t i = 0; i < opts.size(); ++i) { if (opts[i] == "ark") i_ark = (int)i; if (opts[i] == "scp") i_scp = (int)i; if (opts[i] == "t") text_ = true; }
+    if (i_ark < 0) throw std::runtime_error("only ark: output is supported");
+    std::string path = wspecifier.substr(colon + 1);
+    if (i_scp >= 0) {
+      const size_t comma = path.find(',');
+      if (comma == std::string::npos) throw std::runtime_error("wspecifier '" + wspecifier + "' names one file for an archive and a script");
+      std::string a = path.substr(0, comma), b = path.substr(comma + 1);
+      if (i_scp < i_ark) std::swap(a, b);
+      path = a;
+      scp_.reset(new std::ofstream(b));
+      if (!*scp_) throw std::runtime_error("cannot open " + b + " for writing");
+    }
+    ark_path_ = path;
+    out_.reset(new OutStream(path));
   }
   void Write(const std::string& key, const float* data, int rows, int cols, int ld) {
     std::ostream& f_ = out_->get();
+    if (scp_) {   // the offset points behind `key `; text entries have no fixed size, so the stream says how far it got
+      *scp_ << key << ' ' << ark_path_ << ':' << (long)f_.tellp() + (long)key.size() + 1 << "\n";
+      scp_->flush();
+    }
     f_ << key << ' ';
     if (text_) {
       f_ << " [";
@@ -329,6 +448,8 @@ class MatrixWriter {
   }
  private:
   std::unique_ptr<OutStream> out_;
+  std::unique_ptr<std::ofstream> scp_;
+  std::string ark_path_;
   bool text_ = false;
 };
 

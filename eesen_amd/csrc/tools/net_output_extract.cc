@@ -78,10 +78,10 @@ int main(int argc, char** argv) {
     const bool piped = !getenv("EESEN_HOST_FEATURE_PIPES") && parse_feature_pipeline(args[1], &pipe);
     std::unique_ptr<CmvnTable> cmvn_table;
     if (piped) {
-      ck(eesen_feeder_set_pipeline(feeder, pipe.stages.data(), (int)pipe.stages.size()));
+      ck(pipe.configure(feeder));
       if (!pipe.cmvn.empty()) cmvn_table.reset(new CmvnTable(pipe.cmvn, pipe.utt2spk, pipe.norm_vars));
     }
-    FeatureReader reader(piped ? pipe.source : args[1]);
+    FeatureReader reader(piped ? pipe.source : args[1], piped ? pipe.wave_mode() : nullptr);
     MatrixWriter writer(args[2]);
     const auto t0 = std::chrono::steady_clock::now();
     long num_done = 0;
@@ -127,7 +127,7 @@ int main(int argc, char** argv) {
         if (cmvn_table) {
           const std::vector<float>* n = cmvn_table->lookup(utt);
           if (!n) { std::cerr << "WARNING (net-output-extract:main()) No normalization statistics available for key " << utt << ", producing no output for this utterance" << std::endl; continue; }
-          if (CmvnTable::dim(*n) != m.cols)
+          if (CmvnTable::dim(*n) != pipe.cmvn_dim(m.cols))
             throw std::runtime_error("Dim mismatch in ApplyCmvn: cmvn 2x" + std::to_string(CmvnTable::dim(*n) + 1) + ", feats " + std::to_string(m.rows) + "x" + std::to_string(m.cols));
           cm = n->data();
         }

@@ -211,10 +211,10 @@ int main(int argc, char** argv) {
     const bool piped = !getenv("EESEN_HOST_FEATURE_PIPES") && parse_feature_pipeline(feature_rspecifier, &pipe);
     std::unique_ptr<CmvnTable> cmvn_table;
     if (piped) {
-      ck(eesen_feeder_set_pipeline(feeder, pipe.stages.data(), (int)pipe.stages.size()));
+      ck(pipe.configure(feeder));
       if (!pipe.cmvn.empty()) cmvn_table.reset(new CmvnTable(pipe.cmvn, pipe.utt2spk, pipe.norm_vars));
     }
-    FeatureReader feature_reader(piped ? pipe.source : feature_rspecifier);
+    FeatureReader feature_reader(piped ? pipe.source : feature_rspecifier, piped ? pipe.wave_mode() : nullptr);
     const std::map<std::string, std::vector<int32_t>> targets_reader = read_targets(targets_rspecifier);
     log_line("LOG", std::string(o.cross_validate ? "CROSS-VALIDATION" : "TRAINING") + " STARTED");   // :133
     const auto t0 = std::chrono::steady_clock::now();
@@ -247,7 +247,7 @@ int main(int argc, char** argv) {
           if (cmvn_table) {
             const std::vector<float>* n = cmvn_table->lookup(utt);
             if (!n) { warnings.push_back("No normalization statistics available for key " + utt + ", producing no output for this utterance"); continue; }
-            if (CmvnTable::dim(*n) != mat.cols)
+            if (CmvnTable::dim(*n) != pipe.cmvn_dim(mat.cols))
               throw std::runtime_error("Dim mismatch in ApplyCmvn: cmvn 2x" + std::to_string(CmvnTable::dim(*n) + 1) + ", feats " + std::to_string(mat.rows) + "x" + std::to_string(mat.cols));
             cm = n->data();
           }

@@ -79,7 +79,7 @@ def main(argv=None) -> int:
         if pipe is not None:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
-            feeder.set_pipeline(pipe.stages)
+            pipe.configure(feeder)
         n = dict(done=0, no_labels=0, infeasible=0, frames=0, score=0.0)
         positions = []              # (key, positions) of the utterances written, for --positions-wspecifier
 

@@ -279,7 +279,7 @@ def main(argv=None) -> int:
         if pipe is not None:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
-            feeder.set_pipeline(pipe.stages)
+            pipe.configure(feeder)
         n = dict(done=0, empty=0, dead=0, frames=0, score=0.0, tok_err=0, tok_ref=0, scored=0, lm=0.0, labels=0, word_err=0, word_ref=0, word_scored=0, ctm=0, reranked=0, tok_oracle=0, word_oracle=0, mbr_moved=0)
         scores = open(o.scores_out, "w") if o.scores_out else None
         lib = _lib.load()

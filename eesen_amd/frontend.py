@@ -13,6 +13,11 @@ trainers then read the RAW table themselves (here `scp:exp/train.scp`), look the
 the filters run on the GPU inside the batch assembly -- same command line, no filter processes.  Anything it does not
 recognise (another tool, an option it does not implement such as --skip-dims) returns None and the rspecifier is opened
 as the pipe it is.
+
+The pipe may start at the audio: `compute-fbank-feats [options] scp:wav.scp ark:- | apply-cmvn ... ark:- ark:- | add-deltas ark:- ark:- |`.
+The tools then read the wav table themselves and the features are computed on the device too (EESEN_FEAT_FBANK, the head stage of
+the feeder's pipeline); options the device extractor does not implement (--vtln-map, --subtract-mean, htk output, ...) leave the
+rspecifier unrecognised.
 """
 from __future__ import annotations
 
@@ -25,7 +30,33 @@ import numpy as np
 
 from . import kaldi_io
 
-CMVN, SPLICE, SUBSAMPLE, DELTAS = 1, 2, 3, 4    # EESEN_FEAT_* of include/eesen_hip.h
+CMVN, SPLICE, SUBSAMPLE, DELTAS, FBANK = 1, 2, 3, 4, 5    # EESEN_FEAT_* of include/eesen_hip.h
+
+# compute-fbank-feats' options that map onto eesen_fbank_opts_t: flag -> (field, type); FrameExtractionOptions / MelBanksOptions /
+# FbankOptions::Register, plus --vtln-warp of the tool and --dither-seed of this project
+FBANK_OPTIONS = {"sample-frequency": ("samp_freq", float), "frame-length": ("frame_length_ms", float), "frame-shift": ("frame_shift_ms", float),
+                 "preemphasis-coefficient": ("preemph_coeff", float), "remove-dc-offset": ("remove_dc_offset", bool), "dither": ("dither", float),
+                 "window-type": ("window_type", str), "round-to-power-of-two": ("round_to_power_of_two", bool), "snip-edges": ("snip_edges", bool),
+                 "num-mel-bins": ("num_bins", int), "low-freq": ("low_freq", float), "high-freq": ("high_freq", float),
+                 "vtln-low": ("vtln_low", float), "vtln-high": ("vtln_high", float), "use-energy": ("use_energy", bool),
+                 "energy-floor": ("energy_floor", float), "raw-energy": ("raw_energy", bool), "htk-compat": ("htk_compat", bool),
+                 "use-log-fbank": ("use_log_fbank", bool), "vtln-warp": ("vtln_warp", float), "dither-seed": ("dither_seed", int)}
+WINDOW_TYPES = ("hamming", "hanning", "povey", "rectangular")
+
+
+def fbank_geometry(opts: dict) -> Tuple[int, int]:
+    """(WindowShift, WindowSize) in samples (feature-functions.h:119-124: a double product of the float options, truncated)."""
+    sf = float(np.float32(opts.get("samp_freq", 16000.0)))
+    return (int(sf * 0.001 * float(np.float32(opts.get("frame_shift_ms", 10.0)))),
+            int(sf * 0.001 * float(np.float32(opts.get("frame_length_ms", 25.0)))))
+
+
+def fbank_num_frames(nsamp: int, opts: dict) -> int:
+    """NumFrames (feature-functions.cc:29-48); equals eesen_fbank_shape."""
+    shift, length = fbank_geometry(opts)
+    if opts.get("snip_edges", True):
+        return 0 if nsamp < length else 1 + (nsamp - length) // shift
+    return int(np.float32(np.float32(nsamp) / np.float32(shift)) + np.float32(0.5))
 
 
 def _bool(v: str) -> Optional[bool]:
@@ -57,6 +88,11 @@ def _options(argv: List[str], known: Dict[str, type]):
                     opts[name] = int(val)
                 except ValueError:
                     return None
+            elif known[name] is float:
+                try:
+                    opts[name] = float(val)
+                except ValueError:
+                    return None
             else:
                 opts[name] = val
         else:
@@ -71,10 +107,26 @@ class FeaturePipeline:
     cmvn: Optional[str] = None                    # stats rspecifier (per utterance / speaker) or rxfilename (global)
     utt2spk: Optional[str] = None
     norm_vars: bool = False
+    # with a compute-fbank-feats head: `source` is the wav table, `fbank` the extractor's options (fields of eesen_fbank_opts_t)
+    fbank: Optional[dict] = None
+    channel: int = -1
+    min_duration: float = 0.0
+
+    def configure(self, feeder) -> None:
+        """Sets this pipeline on an api.Feeder (the filterbank options first, when it starts at the audio)."""
+        if self.fbank is not None:
+            feeder.set_fbank(**self.fbank)
+        feeder.set_pipeline(self.stages)
+
+    def cmvn_dim(self, D: int) -> int:
+        """Feature dimension in front of the CMVN stage."""
+        return self.fbank.get("num_bins", 23) + int(self.fbank.get("use_energy", False)) if self.fbank is not None else D
 
     def out_dim(self, D: int) -> int:
         for k, a, b in self.stages:
-            if k == SPLICE:
+            if k == FBANK:
+                D = self.fbank.get("num_bins", 23) + int(self.fbank.get("use_energy", False))
+            elif k == SPLICE:
                 D *= 1 + a + b
             elif k == DELTAS:
                 D *= 1 + a
@@ -82,7 +134,9 @@ class FeaturePipeline:
 
     def out_frames(self, T: int) -> int:
         for k, a, b in self.stages:
-            if k == SUBSAMPLE:
+            if k == FBANK:
+                T = fbank_num_frames(T, self.fbank)
+            elif k == SUBSAMPLE:
                 T = T * -a if a < 0 else (max(0, (T - b + a - 1) // a) if T > b else 0)
         return T
 
@@ -101,6 +155,33 @@ def parse_feature_pipeline(rspecifier: str) -> Optional[FeaturePipeline]:
         except ValueError:
             return None
         tool, argv = os.path.basename(argv[0]), argv[1:]
+        if i == 0 and tool == "compute-fbank-feats":      # featbin/compute-fbank-feats.cc: the pipe starts at the audio
+            known = {k: t for k, (_, t) in FBANK_OPTIONS.items()}
+            known.update({"channel": int, "min-duration": float, "output-format": str})
+            r = _options(argv, known)
+            if r is None or len(r[1]) != 2 or r[1][1] != "ark:-":
+                return None
+            o, (src, _) = r
+            if o.get("output-format", "kaldi") != "kaldi" or not o.get("round-to-power-of-two", True) or o.get("window-type", "povey") not in WINDOW_TYPES:
+                return None
+            if src.partition(":")[0].split(",")[0] not in ("ark", "scp") or ":" not in src or src.rstrip().endswith("|"):
+                return None
+            pipe = FeaturePipeline(source=src, fbank={FBANK_OPTIONS[k][0]: v for k, v in o.items() if k in FBANK_OPTIONS},
+                                   channel=o.get("channel", -1), min_duration=o.get("min-duration", 0.0))
+            pipe.stages.append((FBANK, 0, 0))
+            continue
+        if i == 1 and pipe is not None and pipe.fbank is not None and tool == "apply-cmvn":     # reads the head's output: ark:-
+            r = _options(argv, {"utt2spk": str, "norm-vars": bool, "norm-means": bool})
+            if r is None or len(r[1]) != 3 or r[1][1] != "ark:-" or r[1][2] != "ark:-":
+                return None
+            o = r[0]
+            norm_means, norm_vars = o.get("norm-means", True), o.get("norm-vars", False)
+            if norm_vars and not norm_means:
+                return None
+            if norm_means:
+                pipe.cmvn, pipe.utt2spk, pipe.norm_vars = r[1][0], o.get("utt2spk") or None, norm_vars
+                pipe.stages.append((CMVN, int(norm_vars), 0))
+            continue
         if i == 0:
             if tool == "apply-cmvn":        # featbin/apply-cmvn.cc:36-47
                 r = _options(argv, {"utt2spk": str, "norm-vars": bool, "norm-means": bool})
@@ -209,20 +290,35 @@ class CmvnTable:
         return self.cache[key]
 
 
+def _read_waves(pipe: FeaturePipeline, source: str, warn) -> Iterator[Tuple[str, np.ndarray]]:
+    """The wav table as [samples x 1] matrices, with compute-fbank-feats' own checks (compute-fbank-feats.cc:97-139)."""
+    want = float(np.float32(pipe.fbank.get("samp_freq", 16000.0)))
+    for key, (rate, data) in kaldi_io.read_wav_table(source):
+        if data.shape[1] / rate < pipe.min_duration:
+            warn(f"File: {key} is too short ({data.shape[1] / rate:g} sec): producing no output.")
+            continue
+        chan = kaldi_io.select_channel(key, data, pipe.channel, warn)
+        if chan is None:
+            continue
+        if rate != want:
+            raise kaldi_io.KaldiIOError(f"Sample frequency mismatch: you specified {want:g} but data has {rate:g} (use --sample-frequency option).  Utterance is {key}")
+        yield key, np.ascontiguousarray(chan, np.float32).reshape(-1, 1)
+
+
 def read_raw(pipe: FeaturePipeline, source: Optional[str] = None, warn=None) -> Iterator[Tuple[str, RawUtt]]:
     """The raw table as (key, RawUtt).  Utterances the reference's filters would not have passed on are dropped the same
     way: no CMVN statistics (apply-cmvn.cc:87-92), no rows (add-deltas.cc:55-58), no frame left by the subsampling
     (subsample-feats.cc:87-92)."""
     warn = warn or (lambda msg: None)
     table = CmvnTable(pipe.cmvn, pipe.utt2spk, pipe.norm_vars) if pipe.cmvn else None
-    for key, mat in kaldi_io.read_mat_table(source or pipe.source):
+    for key, mat in (_read_waves(pipe, source or pipe.source, warn) if pipe.fbank is not None else kaldi_io.read_mat_table(source or pipe.source)):
         vec = None
         if table is not None:
             vec = table.lookup(key)
             if vec is None:
                 warn(f"No normalization statistics available for key {key}, producing no output for this utterance")
                 continue
-            if vec.shape[1] != mat.shape[1]:
+            if vec.shape[1] != pipe.cmvn_dim(mat.shape[1]):
                 raise kaldi_io.KaldiIOError(f"Dim mismatch in ApplyCmvn: cmvn 2x{vec.shape[1] + 1}, feats {mat.shape[0]}x{mat.shape[1]}")
         if mat.shape[0] == 0:
             warn(f"Empty feature matrix for key {key}")

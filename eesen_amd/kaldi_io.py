@@ -284,6 +284,86 @@ def read_mat_table(spec: str) -> Iterator[Tuple[str, np.ndarray]]:
     return _iter_table(spec, _read_matrix)
 
 
+def _read_exact(f: BinaryIO, n: int, what: str) -> bytes:
+    b = f.read(n)
+    while len(b) < n:                    # a pipe may return short reads
+        more = f.read(n - len(b))
+        if not more:
+            raise KaldiIOError(f"WaveData: unexpected end of file ({what})")
+        b += more
+    return b
+
+
+def read_wave(f: BinaryIO) -> Tuple[float, np.ndarray]:
+    """WaveData::Read (src/feat/wave-reader.cc) for what the recipes feed it: RIFF/WAVE, PCM (format 1), 16 bits per sample, any
+    channel count -> (sample rate, [channels x samples] float32 in int16 scale).  Chunks between `fmt ` and `data` are skipped; a
+    data chunk size of 0 or 0xFFFFFFFF (what sox and ffmpeg write into a pipe) means "read to the end", and a data chunk cut short
+    gives the samples that are there.  8- and 32-bit samples, RIFX and non-PCM formats are refused."""
+    tag = _read_exact(f, 4, "RIFF tag")
+    if tag != b"RIFF":
+        raise KaldiIOError(f"WaveData: expected RIFF, got {tag!r}")
+    _read_exact(f, 4, "RIFF chunk size")
+    if _read_exact(f, 4, "WAVE tag") != b"WAVE":
+        raise KaldiIOError("WaveData: expected WAVE")
+    if _read_exact(f, 4, "fmt tag") != b"fmt ":
+        raise KaldiIOError("WaveData: expected the fmt chunk")
+    fmt_size = struct.unpack("<I", _read_exact(f, 4, "fmt chunk size"))[0]
+    if fmt_size < 16:
+        raise KaldiIOError("WaveData: expect PCM format data to have fmt chunk of at least size 16.")
+    audio_format, channels, rate, byte_rate, block_align, bits = struct.unpack("<HHIIHH", _read_exact(f, 16, "fmt chunk"))
+    if audio_format != 1:
+        raise KaldiIOError(f"WaveData: can read only PCM data, format id in file is: {audio_format}")
+    _read_exact(f, fmt_size - 16, "fmt chunk")
+    if channels <= 0:
+        raise KaldiIOError("WaveData: no channels present")
+    if bits != 16:
+        raise KaldiIOError(f"WaveData: only 16-bit samples are supported, bits_per_sample is {bits}")
+    if byte_rate != rate * 2 * channels:
+        raise KaldiIOError(f"Unexpected byte rate {byte_rate} vs. {rate} * 2 * {channels}")
+    if block_align != 2 * channels:
+        raise KaldiIOError(f"Unexpected block_align: {block_align} vs. {channels} * 2")
+    while True:
+        name = _read_exact(f, 4, "chunk name")
+        size = struct.unpack("<I", _read_exact(f, 4, "chunk size"))[0]
+        if name == b"data":
+            break
+        _read_exact(f, size, "chunk " + name.decode(errors="replace"))
+    if size in (0, 0xFFFFFFFF):
+        raw = f.read()
+    else:
+        raw = f.read(size)
+        while len(raw) < size:
+            more = f.read(size - len(raw))
+            if not more:
+                break
+            raw += more
+        if not raw:
+            raise KaldiIOError("WaveData: failed to read data chunk (read no bytes)")
+    n = len(raw) // block_align
+    data = np.frombuffer(raw[: n * block_align], "<i2").reshape(n, channels).T.astype(np.float32)
+    return float(rate), data
+
+
+def read_wav_table(spec: str) -> Iterator[Tuple[str, Tuple[float, np.ndarray]]]:
+    """SequentialTableReader<WaveHolder>: `scp:wav.scp` with `key file.wav` or `key command |` lines, or an archive of wave files."""
+    return _iter_table(spec, read_wave)
+
+
+def select_channel(key: str, data: np.ndarray, channel: int = -1, warn=None):
+    """compute-fbank-feats.cc:106-123: -1 takes channel 0 (with a warning when there are several); a channel the file does not have
+    gives None (the tool warns and writes nothing for the utterance)."""
+    warn = warn or (lambda m: print("WARNING " + m, file=sys.stderr))
+    nch = data.shape[0]
+    if channel == -1:
+        if nch != 1:
+            warn(f"Channel not specified but you have data with {nch} channels; defaulting to zero")
+        return data[0]
+    if channel >= nch:
+        warn(f"File with id {key} has {nch} channels but you specified channel {channel}, producing no output.")
+        return None
+    return data[channel]
+
+
 def read_mat64_table(spec: str) -> Iterator[Tuple[str, np.ndarray]]:
     """RandomAccessDoubleMatrixReader (featbin/apply-cmvn.cc:80): CMVN statistics per utterance or speaker."""
     return _iter_table(spec, _read_matrix64)

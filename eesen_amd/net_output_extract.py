@@ -85,7 +85,7 @@ def main(argv=None) -> int:
         if pipe is not None:
             from eesen_amd.api import Feeder
             feeder = Feeder(o.device, slots=1)
-            feeder.set_pipeline(pipe.stages)
+            pipe.configure(feeder)
 
         def flush(group):
             """Propagates one group and returns its (key, matrix) results: the writer streams them out as they are produced

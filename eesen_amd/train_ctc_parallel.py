@@ -186,7 +186,7 @@ def main(argv=None) -> int:
         # add-deltas, train_ctc_parallel.sh:95-110): read the raw table here and run the filters on the device
         pipe = frontend.parse_feature_pipeline(feature_rspecifier) if not os.environ.get("EESEN_HOST_FEATURE_PIPES") else None
         if pipe is not None:
-            feeder.set_pipeline(pipe.stages)
+            pipe.configure(feeder)
             table = frontend.read_raw(pipe, warn=lambda m: log(m, "WARNING"))
         else:
             table = kaldi_io.read_mat_table(feature_rspecifier)

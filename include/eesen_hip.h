@@ -735,8 +735,16 @@ int eesen_feeder_release(eesen_feeder_t* f, int slot);
 #define EESEN_FEAT_SPLICE 2
 #define EESEN_FEAT_SUBSAMPLE 3
 #define EESEN_FEAT_DELTAS 4
+/* compute-fbank-feats in front of the filters (see "log-mel filterbank features" below): legal only as stage 0, configured beforehand by
+ * eesen_feeder_set_fbank; a and b are unused.  submit_raw then takes waveforms as [samples x 1] matrices (D_in = 1, frames[s] = the
+ * sample count), eesen_feeder_pipeline_shape(f, 1, nsamp, ...) answers through it, and the CMVN vectors have the filterbank dimension.
+ * The kernel writes straight into the packed buffer the next stage reads.  Every waveform submitted gets a fresh dither key (a counter
+ * per feeder), so an epoch's noise differs from the last one's while a feeder fed the same sequence reproduces its batches. */
+#define EESEN_FEAT_FBANK 5
 typedef struct eesen_feat_stage { int kind, a, b; } eesen_feat_stage_t;
 int eesen_feeder_set_pipeline(eesen_feeder_t* f, const eesen_feat_stage_t* stages, int n_stages); /* 0 stages: plain submit */
+struct eesen_fbank_opts;
+int eesen_feeder_set_fbank(eesen_feeder_t* f, const struct eesen_fbank_opts* opts);   /* before a pipeline that starts with EESEN_FEAT_FBANK */
 /* feature dimension / frame count behind the pipeline for an utterance of [frames_in x D_in] (either output may be NULL) */
 int eesen_feeder_pipeline_shape(eesen_feeder_t* f, int D_in, int frames_in, int* D_out, int* frames_out);
 /* cmvn[s] -> 2 x Dc floats (offsets, then scales), Dc = the dimension in front of the CMVN stage; NULL without such a stage */
@@ -745,6 +753,52 @@ int eesen_feeder_submit_raw(eesen_feeder_t* f, const float* const* utts, const i
 /* ApplyCmvn's normaliser (src/feat/cmvn.cc:78-108) on the host: stats = [rows x cols] doubles as apply-cmvn reads them
  * (row 0: sums and, last, the count; row 1: sums of squares), cols = dim + 1 -> offset_scale[2 x dim] */
 int eesen_cmvn_norm(const double* stats, int rows, int cols, int norm_vars, float* offset_scale);
+
+/* ---- log-mel filterbank features from waveforms (compute-fbank-feats; INTEGRATION.md "Fbank") ------------------
+ * Fbank::ComputeInternal (src/feat/feature-fbank.cc:104-183) over a minibatch of ragged waveforms in ONE launch: per frame
+ * ExtractWindow (src/feat/feature-functions.cc:91-167: cut [reflected without snip_edges], dither, DC removal, raw log
+ * energy, pre-emphasis, window function, zero padding), a real FFT of N = 256 / 512 / 1024 / 2048 points, the power spectrum
+ * of bins 0 .. N/2-1, the triangular mel filters of MelBanks (src/feat/mel-computations.cc:32-135) as a CSR table, floor at
+ * FLT_MIN and log, and the optional energy column (first; last with htk_compat).  Samples are in int16 scale, as floats.
+ * The struct carries the fields and defaults of FbankOptions, FrameExtractionOptions and MelBanksOptions.
+ * Deviations: dither is a counter-based generator keyed by (dither_seed, utterance id, frame, sample) with Box-Muller, so a
+ * seed reproduces its result (the reference draws from rand()); dither = 0 is the path held to the reference.  Refused with
+ * EESEN_ERR_INVALID: round_to_power_of_two = 0, a padded window outside 256 .. 2048, htk_mode. */
+#define EESEN_WINDOW_HAMMING 0
+#define EESEN_WINDOW_HANNING 1
+#define EESEN_WINDOW_POVEY 2
+#define EESEN_WINDOW_RECTANGULAR 3
+typedef struct eesen_fbank_opts {
+  float samp_freq, frame_shift_ms, frame_length_ms, dither, preemph_coeff;           /* 16000, 10, 25, 1.0, 0.97 */
+  int remove_dc_offset, window_type, round_to_power_of_two, snip_edges;              /* 1, POVEY, 1, 1 */
+  int num_bins;                                                                      /* 23 */
+  float low_freq, high_freq, vtln_low, vtln_high;                                    /* 20, 0, 100, -500 */
+  int htk_mode;                                                                      /* 0 (refused otherwise) */
+  int use_energy;                                                                    /* 0 */
+  float energy_floor;                                                                /* 0 */
+  int raw_energy, htk_compat, use_log_fbank;                                         /* 1, 0, 1 */
+  float vtln_warp;                                                                   /* 1.0: one factor per extractor */
+  unsigned long long dither_seed;                                                    /* 0 */
+} eesen_fbank_opts_t;
+typedef struct eesen_fbank eesen_fbank_t;
+int eesen_fbank_opts_default(eesen_fbank_opts_t* opts);
+/* create checks the options and builds the host tables; the device is first touched by eesen_fbank_compute (so shapes can be asked
+ * for, and options refused, on a host without one) */
+int eesen_fbank_create(int device, void* stream, const eesen_fbank_opts_t* opts, eesen_fbank_t** out);
+int eesen_fbank_destroy(eesen_fbank_t* fb);
+/* NumFrames (feature-functions.cc:29-48) in both edge modes, and num_bins + use_energy; either output may be NULL */
+int eesen_fbank_shape(eesen_fbank_t* fb, int nsamp, int* frames, int* dim);
+/* waves[s] -> nsamp[s] samples; utt_ids (NULL: 0 .. S-1) key the dither; out_host[s] -> [frames x dim] row-major (may be NULL
+ * for an utterance without frames).  Synchronises. */
+int eesen_fbank_compute(eesen_fbank_t* fb, const float* const* waves, const int* nsamp, const unsigned long long* utt_ids, int S,
+                        float* const* out_host);
+/* Average milliseconds (HIP events) of `iters` back-to-back launches of the kernel on these waveforms, after one warm-up launch and
+ * without the copies; microbenchmark entry point used by scripts/fbank_probe.py. */
+int eesen_fbank_bench(eesen_fbank_t* fb, const float* const* waves, const int* nsamp, int S, int iters, float* avg_ms);
+/* The filter table of MelBanks for opts (vtln_warp included), host only: first[num_bins], size[num_bins], and the weights of all
+ * bins back to back (*n_weights of them; written when weights != NULL and weights_cap suffices).  Carries the reference's
+ * option checks: at least 3 bins, the frequency and VTLN ranges, "num-mel-bins too large". */
+int eesen_fbank_mel_banks(const eesen_fbank_opts_t* opts, int* first, int* size, float* weights, int weights_cap, int* n_weights);
 
 /* ---- raw device helpers for hosts that own no GPU allocator --------------------------------- */
 int eesen_dev_alloc(int device, long bytes, void** dev_ptr);

@@ -1,0 +1,326 @@
+"""-m gpu: log-mel filterbank features from waveforms on the device (eesen_fbank_*, csrc/fbank.hip).
+
+* every case of tests/fbank_cases.py through eesen_fbank_compute, one launch per option set, dither 0: per case the largest distance
+  from the float64 restatement is at most 3 x the case's reference floor -- the distance of the reference tool's own output
+  (tests/golden/fbank.npz) from the same restatement, so a figure of the fixture and not of the code under test; 3 is the project's
+  factor for a different but equally valid float32 summation order.  White-noise cases also meet the project's own bound 1e-4, and
+  silence gives exactly logf(FLT_MIN) in every bin;
+* dither: the mean filterbank energy of dithered silence against its expectation, determinism per seed, and that seed and utterance
+  id both change the noise;
+* options the extractor does not support are refused.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from tests import fbank_cases as fc
+from tests import fbank_restatement as fr
+
+pytestmark = pytest.mark.gpu
+GOLD = fc.load_golden()
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name):
+    c = GOLD[name]
+    return tuple(fr.compute(w, c["opts"]) for w in c["waves"])
+
+
+@functools.lru_cache(maxsize=None)
+def floor_of(name):
+    c = GOLD[name]
+    return max([fr.distance(r, m, c["opts"]) for r, m in zip(c["refs"], restated(name)) if r is not None] + [0.0])
+
+
+@pytest.mark.parametrize("name", fc.CASE_NAMES)
+def test_case_against_restatement(gpu, name):
+    from eesen_amd.api import Fbank
+    c = GOLD[name]
+    fb = Fbank(**c["opts"])
+    got = fb.compute(c["waves"])                     # one launch for the whole case
+    want = restated(name)
+    assert len(got) == len(want)
+    worst = 0.0
+    for g, m, w in zip(got, want, c["waves"]):
+        assert g.dtype == np.float32 and g.shape == m.shape == fb.shape(len(w)), (g.shape, m.shape)
+        assert np.all(np.isfinite(g))
+        worst = max(worst, fr.distance(g, m, c["opts"]))
+    floor = floor_of(name)
+    print(f"fbank case {name}: S {len(got)}, frames {sum(m.shape[0] for m in want)}, device {worst:.3e}, reference floor {floor:.3e}")
+    assert worst <= 3.0 * floor, (name, worst, floor)
+    if c["kind"] == "noise":
+        assert worst <= fc.NOISE_BOUND, (name, worst)
+    if c["kind"] == "zero":
+        for g in got:
+            assert np.all(g == np.log(np.float32(np.finfo(np.float32).tiny))), g
+
+
+def test_golden_tolerance_directly(gpu):
+    """The device against the reference tool's matrices themselves: within 4 floors (its own distance plus three)."""
+    from eesen_amd.api import Fbank
+    for name in ("n512_bins40_s3", "tone_povey", "reflect"):
+        c = GOLD[name]
+        got = Fbank(**c["opts"]).compute(c["waves"])
+        d = max(fr.distance(g, r, c["opts"]) for g, r in zip(got, c["refs"]) if r is not None)
+        assert d <= 4.0 * floor_of(name), (name, d, floor_of(name))
+
+
+DITHER = dict(num_bins=23, use_log_fbank=False, remove_dc_offset=False, preemph_coeff=0.0, dither=2.0)
+F_DITHER = 4096
+
+
+@pytest.fixture(scope="module")
+def dithered(gpu):
+    from eesen_amd.api import Fbank
+    n = fc.nsamp_for(F_DITHER, DITHER)
+    z = np.zeros(n, np.float32)
+    fb = Fbank(dither_seed=7, **DITHER)
+    a = fb.compute([z], utt_ids=[3])[0]
+    return fb, z, a
+
+
+def test_dither_mean_energy(dithered):
+    """E |X_k|^2 = d^2 sum_n w_n^2 for every k > 0, so a bin's mean over frames tends to d^2 sum w^2 sum_k filt_j[k]; a bin's relative
+    standard deviation per frame is at most 1 and frames draw independent noise, hence 6 / sqrt(F)."""
+    _, _, a = dithered
+    assert a.shape == (F_DITHER, 23)
+    w = fr.window_function(DITHER)
+    expect = DITHER["dither"] ** 2 * np.sum(w * w) * fr.mel_filters(DITHER).sum(axis=1)
+    rel = np.abs(a.astype(np.float64).mean(axis=0) / expect - 1.0)
+    print("dither: worst relative deviation of a bin's mean energy", rel.max(), "allowed", 6.0 / np.sqrt(F_DITHER))
+    assert rel.max() <= 6.0 / np.sqrt(F_DITHER)
+
+
+def test_dither_keys(dithered):
+    from eesen_amd.api import Fbank
+    fb, z, a = dithered
+    short = z[: fc.nsamp_for(9, DITHER)]
+    a9 = fb.compute([short], utt_ids=[3])[0]
+    assert np.array_equal(a9, a[:9])                                     # same (seed, id, frame, sample): same noise
+    assert np.array_equal(fb.compute([short], utt_ids=[3])[0], a9)       # and again
+    b = Fbank(dither_seed=8, **DITHER).compute([short], utt_ids=[3])[0]
+    assert not np.array_equal(b, a9)
+    two = fb.compute([short, short], utt_ids=[3, 4])
+    assert np.array_equal(two[0], a9) and not np.array_equal(two[1], a9)
+    dflt = fb.compute([short, short])                                    # ids default to 0 .. S-1
+    assert not np.array_equal(dflt[0], dflt[1])
+    assert not np.array_equal(a9[0], a9[1])                              # neighbouring frames share samples, not noise
+
+
+def test_refused_options(gpu):
+    from eesen_amd.api import Fbank, EesenError
+    for bad in (dict(round_to_power_of_two=False), dict(htk_mode=True), dict(frame_length_ms=5.0), dict(samp_freq=96000.0),
+                dict(num_bins=2), dict(num_bins=400), dict(low_freq=9000.0), dict(vtln_warp=1.1, vtln_low=10.0)):
+        with pytest.raises(EesenError):
+            Fbank(**bad)
+
+
+# ------------------------------------------------------------------------------------------------ the feeder's head stage
+FEEDER_CASE = "n512_bins40_s3"
+NAMED = [("cmvn", True), ("splice", 1, 1), ("subsample", 3, 0), ("deltas", 2, 2)]
+
+
+def _stats(mats):
+    d = mats[0].shape[1]
+    st = np.zeros((2, d + 1))
+    for m in mats:
+        m = np.asarray(m, np.float64)
+        st[0, :d] += m.sum(0)
+        st[1, :d] += (m * m).sum(0)
+        st[0, d] += m.shape[0]
+    return st
+
+
+def test_feeder_fbank_head_stage(gpu):
+    """FBANK -> CMVN(norm_vars) -> SPLICE(1,1) -> SUBSAMPLE(3,0) -> DELTAS(2,2) on S = 3 ragged waveforms against the float64
+    restatement followed by the front end's own restatement (oracle/frontend.py).  The bound is the case's filterbank floor carried
+    through the stages: CMVN multiplies an error by its largest scale, splicing and subsampling copy, the deltas of order o multiply it
+    by at most the sum of the magnitudes of their window; times 3."""
+    from eesen_amd import frontend as fe
+    from eesen_amd.api import Feeder
+    from oracle import frontend as ofe
+    c = GOLD[FEEDER_CASE]
+    want_fb = restated(FEEDER_CASE)
+    st = _stats(want_fb)
+    f = Feeder()
+    f.set_fbank(**c["opts"])
+    f.set_pipeline([(fe.FBANK, 0, 0), (fe.CMVN, 1, 0), (fe.SPLICE, 1, 1), (fe.SUBSAMPLE, 3, 0), (fe.DELTAS, 2, 2)])
+    waves = [np.asarray(w, np.float32).reshape(-1, 1) for w in c["waves"]]
+    norm = fe.cmvn_norm(st, True)
+    shapes = [f.pipeline_shape(1, len(w)) for w in waves]
+    want = [ofe.run_pipeline(NAMED, m, st) for m in want_fb]
+    assert shapes == [w.shape for w in want] and shapes[0][1] == 40 * 3 * 3
+    slot = f.submit_raw(waves, [norm] * len(waves))
+    got = f.acquire(slot)
+    T, S = max(t for t, _ in shapes), len(waves)
+    assert (got.rows, got.cols) == (T * S, shapes[0][1])
+    host = got.numpy().reshape(T, S, -1)
+    f.release(slot)
+    amp = float(np.max(np.abs(norm[1]))) * max(float(np.sum(np.abs(s))) for s in ofe.delta_scales(2, 2))
+    bound = 3.0 * floor_of(FEEDER_CASE) * amp
+    worst = max(float(np.max(np.abs(host[:t, s, :] - want[s]))) for s, (t, _) in enumerate(shapes))
+    print(f"feeder head stage: worst {worst:.3e}, bound {bound:.3e} (amplification {amp:.3f})")
+    assert worst <= bound
+    for s, (t, _) in enumerate(shapes):
+        assert not host[t:, s, :].any(), "rows beyond an utterance's end are zero"
+
+
+def test_feeder_fbank_stage_errors(gpu):
+    from eesen_amd import frontend as fe
+    from eesen_amd.api import Feeder, EesenError
+    f = Feeder()
+    with pytest.raises(EesenError, match="eesen_feeder_set_fbank"):
+        f.set_pipeline([(fe.FBANK, 0, 0)])
+    f.set_fbank(num_bins=23, dither=0.0)
+    with pytest.raises(EesenError, match="first stage"):
+        f.set_pipeline([(fe.SPLICE, 1, 1), (fe.FBANK, 0, 0)])
+    f.set_pipeline([(fe.FBANK, 0, 0), (fe.DELTAS, 2, 2)])
+    assert f.pipeline_shape(1, 16000) == (98, 69)
+    with pytest.raises(EesenError, match="samples x 1"):
+        f.submit_raw([np.zeros((1000, 2), np.float32)])
+    with pytest.raises(EesenError):
+        f.set_fbank(round_to_power_of_two=False)
+
+
+# ------------------------------------------------------------------------------------------------ the tools
+import os
+import struct
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENV = dict(os.environ, PATH="/usr/bin:/bin")       # no featbin tool on PATH: a pipe can only have run on the device
+
+
+def _wav_scp(tmp_path, case):
+    c = GOLD[case]
+    scp = str(tmp_path / "wav.scp")
+    with open(scp, "w") as f:
+        for i, w in enumerate(c["waves"]):
+            p = str(tmp_path / f"u{i}.wav")
+            fc.write_wav(p, w, fr.full(c["opts"])["samp_freq"])
+            f.write(f"utt{i} cat {p} |\n" if i == 1 else f"utt{i} {p}\n")    # one entry as a command
+    return scp
+
+
+def test_compute_fbank_feats_tools(gpu, tmp_path):
+    """Three tiny wavs in a wav.scp: the native tool and the Python mirror equal api.Fbank.compute bit for bit, with ark and with
+    ark,scp output, and hold the case's bound against the restatement."""
+    from eesen_amd import kaldi_io
+    from eesen_amd.api import Fbank
+    c = GOLD[FEEDER_CASE]
+    scp = _wav_scp(tmp_path, FEEDER_CASE)
+    direct = Fbank(**c["opts"]).compute(c["waves"])
+    flags = fc.flags(c["opts"])
+    for tag, cmd in (("cc", [os.path.join(ROOT, "bin", "compute-fbank-feats")]), ("py", [sys.executable, "-m", "eesen_amd.compute_fbank_feats"])):
+        ark, ark2, scp2 = str(tmp_path / f"{tag}.ark"), str(tmp_path / f"{tag}2.ark"), str(tmp_path / f"{tag}2.scp")
+        for wspec in ("ark:" + ark, f"ark,scp:{ark2},{scp2}"):
+            r = subprocess.run(cmd + flags + ["scp:" + scp, wspec], capture_output=True, text=True, cwd=ROOT, timeout=300, env=ENV)
+            assert r.returncode == 0, r.stderr[-2000:]
+            assert "Done 3 out of 3 utterances" in r.stderr
+        for spec in ("ark:" + ark, "scp:" + scp2):
+            got = list(kaldi_io.read_mat_table(spec))
+            assert [k for k, _ in got] == ["utt0", "utt1", "utt2"]
+            for (_, m), d, w in zip(got, direct, restated(FEEDER_CASE)):
+                assert np.array_equal(m, d), (tag, spec)
+                assert fr.distance(m, w, c["opts"]) <= 3.0 * floor_of(FEEDER_CASE)
+    # nothing succeeds: exit status 1, as the reference; a sample-rate mismatch is an error
+    r = subprocess.run([os.path.join(ROOT, "bin", "compute-fbank-feats"), "--dither=0", "--min-duration=5", "scp:" + scp, "ark:" + str(tmp_path / "none.ark")],
+                       capture_output=True, text=True, cwd=ROOT, timeout=300, env=ENV)
+    assert r.returncode == 1 and "is too short" in r.stderr and "Done 0 out of 3" in r.stderr
+    for cmd in ([os.path.join(ROOT, "bin", "compute-fbank-feats")], [sys.executable, "-m", "eesen_amd.compute_fbank_feats"]):
+        r = subprocess.run(cmd + ["--dither=0", "--sample-frequency=8000", "scp:" + scp, "ark:" + str(tmp_path / "none.ark")],
+                           capture_output=True, text=True, cwd=ROOT, timeout=300, env=ENV)
+        assert r.returncode not in (0, 1) and "Sample frequency mismatch" in r.stderr
+
+
+def test_net_output_extract_from_audio(gpu, tmp_path):
+    """net-output-extract handed `ark:compute-fbank-feats --dither=0 ... scp:wav.scp ark:- | apply-cmvn ... ark:- ark:- | add-deltas ark:- ark:- |`
+    against the same net fed the reference tool's features (golden) as an archive.  Allowed: 3 x the posterior difference between
+    feeding the golden float32 features and feeding the float64 restatement's features rounded to float32 -- the reference's own spread,
+    measured here."""
+    from eesen_amd import kaldi_io, nnet_io, synth
+    from oracle import frontend as ofe
+    c = GOLD[FEEDER_CASE]
+    scp = _wav_scp(tmp_path, FEEDER_CASE)
+    gold = [np.asarray(r, np.float32) for r in c["refs"]]
+    rest = [np.asarray(m, np.float32) for m in restated(FEEDER_CASE)]
+    st = _stats(gold)
+    with open(tmp_path / "cmvn.mat", "wb") as f:       # Matrix<double>, binary: apply-cmvn's global (rxfilename) form
+        f.write(b"\x00BDM \x04" + struct.pack("<i", 2) + b"\x04" + struct.pack("<i", st.shape[1]) + st.astype("<f8").tobytes())
+    named = [("cmvn", True), ("deltas", 2, 2)]
+    keys = [f"utt{i}" for i in range(len(gold))]
+    for tag, feats in (("gold", gold), ("rest", rest)):
+        kaldi_io.write_mat_ark(str(tmp_path / f"{tag}.ark"), [(k, ofe.run_pipeline(named, m, st)) for k, m in zip(keys, feats)])
+    K = 9
+    cfg = synth.config("tiny_bi"); cfg.update(D=40 * 3, K=K)
+    net = str(tmp_path / "net.nnet")
+    nnet_io.write_nnet(net, synth.make_model(**cfg), binary=True)
+    pipe = (f"ark:compute-fbank-feats {' '.join(fc.flags(c['opts']))} scp:{scp} ark:- | apply-cmvn --norm-vars=true {tmp_path}/cmvn.mat ark:- ark:- | "
+            "add-deltas ark:- ark:- |")
+    exe = os.path.join(ROOT, "eesen_amd", "bin", "net-output-extract")
+    outs = {}
+    for tag, cmd, spec in (("gold", [exe], f"ark:{tmp_path}/gold.ark"), ("rest", [exe], f"ark:{tmp_path}/rest.ark"), ("cc", [exe], pipe),
+                           ("py", [sys.executable, "-m", "eesen_amd.net_output_extract"], pipe)):
+        out = str(tmp_path / f"post_{tag}.ark")
+        r = subprocess.run(cmd + ["--num-sequence=3", net, spec, "ark:" + out], capture_output=True, text=True, cwd=ROOT, timeout=300, env=ENV)
+        assert r.returncode == 0, r.stderr[-2000:]
+        outs[tag] = dict(kaldi_io.read_mat_table("ark:" + out))
+        assert sorted(outs[tag]) == keys
+    spread = max(float(np.max(np.abs(outs["gold"][k] - outs["rest"][k]))) for k in keys)
+    for tag in ("cc", "py"):
+        d = max(float(np.max(np.abs(outs[tag][k] - outs["gold"][k]))) for k in keys)
+        print(f"net-output-extract from audio ({tag}): posterior difference {d:.3e}, the reference's own spread {spread:.3e}")
+        assert d <= 3.0 * spread
+    assert all(np.array_equal(outs["cc"][k], outs["py"][k]) for k in keys)
+
+
+def test_trainer_aligner_decoder_from_audio(gpu, tmp_path):
+    """train-ctc-parallel (native and Python), ctc-align and ctc-decode handed the rspecifier that starts at the audio equal themselves
+    handed an archive of the same features (api.Fbank, then the front end's restatement of apply-cmvn and add-deltas, which the device
+    reproduces bit for bit): byte-identical models, alignments and hypotheses -- the head stage is the extractor, and nothing else changed."""
+    from eesen_amd import kaldi_io, nnet_io, synth
+    from eesen_amd.api import Fbank
+    from oracle import frontend as ofe
+    c = GOLD["n256_8k_bins23_s33"]
+    waves = [w for w, t in zip(c["waves"], fc.frames_of(c)) if t >= 4][:8]
+    scp = str(tmp_path / "wav.scp")
+    keys = [f"utt{i:02d}" for i in range(len(waves))]
+    with open(scp, "w") as f:
+        for k, w in zip(keys, waves):
+            fc.write_wav(str(tmp_path / f"{k}.wav"), w, 8000)
+            f.write(f"{k} {tmp_path}/{k}.wav\n")
+    feats = Fbank(**c["opts"]).compute(waves)
+    st = _stats(feats)
+    with open(tmp_path / "cmvn.mat", "wb") as f:
+        f.write(b"\x00BDM \x04" + struct.pack("<i", 2) + b"\x04" + struct.pack("<i", st.shape[1]) + st.astype("<f8").tobytes())
+    named = [("cmvn", False), ("deltas", 2, 2)]
+    kaldi_io.write_mat_ark(str(tmp_path / "pre.ark"), [(k, ofe.run_pipeline(named, m, st)) for k, m in zip(keys, feats)])
+    K = 7
+    rng = np.random.default_rng(5)
+    kaldi_io.write_vec_int_ark(str(tmp_path / "lab.ark"), [(k, rng.integers(1, K, size=max(1, m.shape[0] // 3)).astype(np.int32)) for k, m in zip(keys, feats)])
+    cfg = synth.config("tiny_bi"); cfg.update(D=23 * 3, K=K)
+    m_in = str(tmp_path / "init.nnet")
+    nnet_io.write_nnet(m_in, synth.make_model(max_grad=50.0, **cfg), binary=True)
+    pipe = (f"ark,s,cs:compute-fbank-feats {' '.join(fc.flags(c['opts']))} scp:{scp} ark:- | apply-cmvn {tmp_path}/cmvn.mat ark:- ark:- | add-deltas ark:- ark:- |")
+    pre = f"ark:{tmp_path}/pre.ark"
+    bindir = os.path.join(ROOT, "eesen_amd", "bin")
+
+    def run(cmd, out):
+        r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=300, env=ENV)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return open(out, "rb").read()
+
+    models = {}
+    for tag, cmd in (("cc", [os.path.join(bindir, "train-ctc-parallel")]), ("py", [sys.executable, "-m", "eesen_amd.train_ctc_parallel"])):
+        for src, spec in (("pipe", pipe), ("pre", pre)):
+            out = str(tmp_path / f"{tag}_{src}.nnet")
+            models[(tag, src)] = run(cmd + ["--learn-rate=0.01", "--num-sequence=4", "--frame-limit=100", spec, f"ark:{tmp_path}/lab.ark", m_in, out], out)
+    assert models[("cc", "pipe")] == models[("cc", "pre")] == models[("py", "pipe")] == models[("py", "pre")]
+    assert models[("cc", "pipe")] != open(m_in, "rb").read()
+    for tool, args in (("ctc-align", lambda spec, out: [m_in, spec, f"ark:{tmp_path}/lab.ark", "ark:" + out]),
+                       ("ctc-decode", lambda spec, out: ["--beam=4", m_in, spec, "ark:" + out])):
+        got = {src: run([os.path.join(bindir, tool)] + args(spec, str(tmp_path / f"{tool}_{src}.ark")), str(tmp_path / f"{tool}_{src}.ark"))
+               for src, spec in (("pipe", pipe), ("pre", pre))}
+        assert got["pipe"] == got["pre"] and len(got["pipe"]) > 0, tool
