@@ -165,6 +165,15 @@ SIGNATURES = {
     "eesen_fbank_compute": (_i, [_vp, C.POINTER(_vp), _pi, _vp, _i, C.POINTER(_vp)]),
     "eesen_fbank_bench": (_i, [_vp, C.POINTER(_vp), _pi, _i, _i, _pf]),
     "eesen_fbank_mel_banks": (_i, [_vp, _vp, _vp, _vp, _i, _pi]),
+    "eesen_pitch_opts_default": (_i, [_vp]),
+    "eesen_pitch_create": (_i, [_i, _vp, _vp, C.POINTER(_vp)]),
+    "eesen_pitch_destroy": (_i, [_vp]),
+    "eesen_pitch_shape": (_i, [_vp, _i, _pi, _pi, _pi]),
+    "eesen_pitch_compute": (_i, [_vp, C.POINTER(_vp), _pi, _vp, _i, _i, C.POINTER(_vp), _vp, _vp]),
+    "eesen_pitch_process": (_i, [_vp, C.POINTER(_vp), _pi, _vp, _i, C.POINTER(_vp), _vp, _vp]),
+    "eesen_pitch_nccf": (_i, [_vp, _vp, _i] + [_vp] * 12),
+    "eesen_pitch_lags": (_i, [_vp, _vp, _i, _pi]),
+    "eesen_pitch_bench": (_i, [_vp, C.POINTER(_vp), _pi, _i, _i, _pf]),
     "eesen_dev_alloc": (_i, [_i, _l, C.POINTER(_vp)]),
     "eesen_dev_free": (_i, [_i, _vp]),
     "eesen_dev_copy": (_i, [_i, _vp, _vp, _l, _i]),
@@ -183,6 +192,20 @@ class FbankOpts(C.Structure):
                 ("num_bins", _i), ("low_freq", _f), ("high_freq", _f), ("vtln_low", _f), ("vtln_high", _f), ("htk_mode", _i),
                 ("use_energy", _i), ("energy_floor", _f), ("raw_energy", _i), ("htk_compat", _i), ("use_log_fbank", _i),
                 ("vtln_warp", _f), ("dither_seed", C.c_ulonglong)]
+
+
+class PitchOpts(C.Structure):
+    """eesen_pitch_opts_t of include/eesen_hip.h, field for field."""
+    _fields_ = [("samp_freq", _f), ("frame_shift_ms", _f), ("frame_length_ms", _f), ("preemph_coeff", _f),
+                ("min_f0", _f), ("max_f0", _f), ("soft_min_f0", _f), ("penalty_factor", _f),
+                ("lowpass_cutoff", _f), ("resample_freq", _f), ("delta_pitch", _f), ("nccf_ballast", _f),
+                ("lowpass_filter_width", _i), ("upsample_filter_width", _i),
+                ("max_frames_latency", _i), ("frames_per_chunk", _i), ("simulate_first_pass_online", _i),
+                ("recompute_frame", _i), ("nccf_ballast_online", _i), ("snip_edges", _i),
+                ("pitch_scale", _f), ("pov_scale", _f), ("pov_offset", _f), ("delta_pitch_scale", _f), ("delta_pitch_noise_stddev", _f),
+                ("normalization_left_context", _i), ("normalization_right_context", _i), ("delta_window", _i), ("delay", _i),
+                ("add_pov_feature", _i), ("add_normalized_log_pitch", _i), ("add_delta_pitch", _i), ("add_raw_log_pitch", _i),
+                ("noise_seed", C.c_ulonglong)]
 
 
 WINDOW_TYPES = {"hamming": 0, "hanning": 1, "povey": 2, "rectangular": 3}

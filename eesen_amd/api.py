@@ -1278,6 +1278,134 @@ def mel_banks(opts: "_lib.FbankOpts"):
     return first, size, np.split(w, cuts)
 
 
+def pitch_opts(**kw) -> "_lib.PitchOpts":
+    """The defaults of PitchExtractionOptions and ProcessPitchOptions (`eesen_pitch_opts_default`) with `kw` on top: field names of
+    eesen_pitch_opts_t; booleans as bool or int."""
+    o = _lib.PitchOpts()
+    check(_lib.load().eesen_pitch_opts_default(C.byref(o)))
+    names = {f[0] for f in _lib.PitchOpts._fields_}
+    for k, v in kw.items():
+        if k not in names:
+            raise EesenError(-1, f"unknown pitch option {k}")
+        setattr(o, k, int(v) if isinstance(v, (bool, np.bool_)) else v)
+    return o
+
+
+def pitch_lags(opts: "_lib.PitchOpts") -> np.ndarray:
+    """The geometric lag grid of SelectLags for `opts`, in seconds; host only (`eesen_pitch_lags`)."""
+    lib = _lib.load()
+    n = C.c_int()
+    check(lib.eesen_pitch_lags(C.byref(opts), None, 0, C.byref(n)))
+    lags = np.zeros(n.value, np.float32)
+    check(lib.eesen_pitch_lags(C.byref(opts), lags.ctypes.data, n.value, None))
+    return lags
+
+
+class Pitch:
+    """Kaldi pitch features from waveforms on the device (include/eesen_hip.h `eesen_pitch_*`; the reference's
+    compute-kaldi-pitch-feats and process-kaldi-pitch-feats, src/feat/pitch-functions.cc).  Waveforms are 1-d arrays in int16 scale.
+
+        pt = Pitch(samp_freq=8000.0, delta_pitch_noise_stddev=0.0)
+        frames, raw_dim, processed_dim = pt.shape(len(wave))
+        raw = pt.compute([wave_a, wave_b])                  # one minibatch; list of [frames x 2] (NCCF, pitch in Hz)
+        feats = pt.compute([wave_a, wave_b], process=True)  # post-processed on the device: [frames + delay x processed_dim]
+        feats = pt.process(raw)                             # the post-processing alone
+    """
+
+    def __init__(self, device: int = 0, stream: Optional[int] = None, **opts):
+        self.lib = _lib.load()
+        self.opts = pitch_opts(**opts)
+        self.h = C.c_void_p()
+        check(self.lib.eesen_pitch_create(device, C.c_void_p(stream) if stream else None, C.byref(self.opts), C.byref(self.h)))
+
+    def __del__(self):
+        if getattr(self, "h", None) and self.h:
+            try:
+                self.lib.eesen_pitch_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    def shape(self, nsamp: int) -> Tuple[int, int, int]:
+        """(frames, 2, processed columns) for a waveform of nsamp samples; the processed matrix has frames + delay rows."""
+        t, r, d = C.c_int(), C.c_int(), C.c_int()
+        check(self.lib.eesen_pitch_shape(self.h, int(nsamp), C.byref(t), C.byref(r), C.byref(d)))
+        return t.value, r.value, d.value
+
+    def _ids(self, utt_ids, S):
+        if utt_ids is None:
+            return None
+        if len(utt_ids) != S:
+            raise EesenError(-1, "one utterance id per waveform")
+        return np.array(utt_ids, np.uint64)
+
+    def _rows(self, frames: int, process: bool) -> Tuple[int, int]:
+        if not frames:
+            return 0, 0
+        return (frames + int(self.opts.delay), self.shape(0)[2]) if process else (frames, 2)
+
+    def compute(self, waves: Sequence[np.ndarray], process: bool = False, utt_ids: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+        if not len(waves):
+            raise EesenError(-1, "empty minibatch")
+        waves = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in waves]
+        S = len(waves)
+        outs = [np.zeros(self._rows(self.shape(len(w))[0], process), np.float32) for w in waves]
+        wp = (C.c_void_p * S)(*[w.ctypes.data for w in waves])
+        op = (C.c_void_p * S)(*[o.ctypes.data for o in outs])
+        ns = np.array([len(w) for w in waves], np.int32)
+        caps = np.array([o.size for o in outs], np.int64)
+        ids = self._ids(utt_ids, S)
+        check(self.lib.eesen_pitch_compute(self.h, wp, ns.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data if ids is not None else None, S,
+                                           int(bool(process)), op, caps.ctypes.data, None))
+        return outs
+
+    def process(self, raw: Sequence[np.ndarray], utt_ids: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+        if not len(raw):
+            raise EesenError(-1, "empty minibatch")
+        raw = [np.ascontiguousarray(m, np.float32).reshape(-1, 2) for m in raw]
+        S = len(raw)
+        outs = [np.zeros(self._rows(m.shape[0], True), np.float32) for m in raw]
+        rp = (C.c_void_p * S)(*[m.ctypes.data for m in raw])
+        op = (C.c_void_p * S)(*[o.ctypes.data for o in outs])
+        fr = np.array([m.shape[0] for m in raw], np.int32)
+        caps = np.array([o.size for o in outs], np.int64)
+        ids = self._ids(utt_ids, S)
+        check(self.lib.eesen_pitch_process(self.h, rp, fr.ctypes.data_as(C.POINTER(C.c_int)), ids.ctypes.data if ids is not None else None, S,
+                                           op, caps.ctypes.data, None))
+        return outs
+
+    def stages(self, wave: np.ndarray) -> dict:
+        """DIAGNOSTIC (`eesen_pitch_nccf`): every stage output of one waveform -- down, nccf_pitch, nccf_pov, lags, avg_norm_prod,
+        mean_square, fwd, backptr, track, raw, taken, and the counts frames, first_pass_frames, states."""
+        wave = np.ascontiguousarray(wave, np.float32).reshape(-1)
+        counts = np.zeros(5, np.int32)
+        nul = [None] * 11
+        check(self.lib.eesen_pitch_nccf(self.h, wave.ctypes.data, len(wave), counts.ctypes.data, *nul))
+        F, f1, ns, n2, n1 = (int(v) for v in counts)
+        r = dict(frames=F, first_pass_frames=f1, states=ns, down=np.zeros(n2, np.float32), nccf_pitch=np.zeros((F, ns), np.float32),
+                 nccf_pov=np.zeros((F, ns), np.float32), lags=np.zeros(ns, np.float32), avg_norm_prod=np.zeros(F, np.float32),
+                 mean_square=np.zeros(2, np.float64), fwd=np.zeros(ns, np.float32), backptr=np.zeros((F, ns), np.uint16),
+                 track=np.zeros(F, np.int32), raw=np.zeros((F, 2), np.float32), first_pass_samples=n1)
+        taken = C.c_int()
+        check(self.lib.eesen_pitch_nccf(self.h, wave.ctypes.data, len(wave), counts.ctypes.data, *[r[k].ctypes.data for k in (
+            "down", "nccf_pitch", "nccf_pov", "lags", "avg_norm_prod", "mean_square", "fwd", "backptr", "track", "raw")], C.addressof(taken)))
+        r["taken"] = bool(taken.value)
+        return r
+
+    def lags(self) -> np.ndarray:
+        return pitch_lags(self.opts)
+
+    def bench(self, waves: Sequence[np.ndarray], iters: int = 10) -> np.ndarray:
+        """Milliseconds per repetition without the copies: [all four launches, down-sampler, NCCF, search, post-processing]."""
+        waves = [np.ascontiguousarray(w, np.float32).reshape(-1) for w in waves]
+        S = len(waves)
+        wp = (C.c_void_p * S)(*[w.ctypes.data for w in waves])
+        ns = np.array([len(w) for w in waves], np.int32)
+        ms = np.zeros(5, np.float32)
+        check(self.lib.eesen_pitch_bench(self.h, wp, ns.ctypes.data_as(C.POINTER(C.c_int)), S, int(iters), ms.ctypes.data_as(C.POINTER(C.c_float))))
+        return ms
+
+
 def train_step(net: Net, ctc: Ctc, batch, error_rate: bool = False) -> dict:
     """One pass of the trainer's inner loop (train-ctc-parallel.cc:195-207) on a eesen_amd.synth.Batch."""
     net.SetSeqLengths(batch.lens)

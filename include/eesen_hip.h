@@ -800,6 +800,66 @@ int eesen_fbank_bench(eesen_fbank_t* fb, const float* const* waves, const int* n
  * option checks: at least 3 bins, the frequency and VTLN ranges, "num-mel-bins too large". */
 int eesen_fbank_mel_banks(const eesen_fbank_opts_t* opts, int* first, int* size, float* weights, int weights_cap, int* n_weights);
 
+/* ---- Kaldi pitch features from waveforms (compute-kaldi-pitch-feats | process-kaldi-pitch-feats; INTEGRATION.md "Pitch") ------
+ * The offline path of ComputeKaldiPitch (src/feat/pitch-functions.cc:1244-1280) and ProcessPitch (:1536-1549) over a minibatch of
+ * ragged waveforms, four launches: the Hann-windowed-sinc down-sampler of LinearResample to resample_freq with the fp64 sums of the
+ * signal, the NCCF of every frame on the integer lags with and without the ballast and its up-sampling to the geometric lag grid
+ * (ArbitraryResample as a CSR table), the Viterbi search over the lag states with the energy re-estimate of RecomputeBacktraces at
+ * its head and the traceback at its end, and the post-processing.  The search takes the exact minimum over all predecessor states,
+ * ties to the lowest (the reference's pitch_use_naive_search branch); its arithmetic is float32 in a fixed order without fused
+ * multiply-add (csrc/pitch.hip's header).  The struct carries the fields and defaults of PitchExtractionOptions and
+ * ProcessPitchOptions.  Deviations: the delta-pitch noise is the fbank dither's counter-based generator keyed by (noise_seed,
+ * utterance id, frame), so a seed reproduces (the reference draws RandGauss()); delta_pitch_noise_stddev = 0 is the path held to
+ * the reference.  Refused with EESEN_ERR_INVALID: preemph_coeff != 0, frames_per_chunk != 0, simulate_first_pass_online,
+ * nccf_ballast_online, resample_freq <= 2 * lowpass_cutoff, soft_min_f0 > min_f0, more than 1024 lag states, no output column.
+ * max_frames_latency is accepted and has no effect offline, as in the reference. */
+typedef struct eesen_pitch_opts {
+  float samp_freq, frame_shift_ms, frame_length_ms, preemph_coeff;                    /* 16000, 10, 25, 0 (refused otherwise) */
+  float min_f0, max_f0, soft_min_f0, penalty_factor;                                  /* 50, 400, 10, 0.1 */
+  float lowpass_cutoff, resample_freq, delta_pitch, nccf_ballast;                     /* 1000, 4000, 0.005, 7000 */
+  int lowpass_filter_width, upsample_filter_width;                                    /* 1, 5 */
+  int max_frames_latency, frames_per_chunk, simulate_first_pass_online;               /* 0, 0 (refused otherwise), 0 (refused) */
+  int recompute_frame, nccf_ballast_online, snip_edges;                               /* 500, 0 (refused otherwise), 1 */
+  float pitch_scale, pov_scale, pov_offset, delta_pitch_scale, delta_pitch_noise_stddev;   /* 2, 2, 0, 10, 0.005 */
+  int normalization_left_context, normalization_right_context, delta_window, delay;   /* 75, 75, 2, 0 */
+  int add_pov_feature, add_normalized_log_pitch, add_delta_pitch, add_raw_log_pitch;  /* 1, 1, 1, 0 */
+  unsigned long long noise_seed;                                                      /* 0 */
+} eesen_pitch_opts_t;
+typedef struct eesen_pitch eesen_pitch_t;
+int eesen_pitch_opts_default(eesen_pitch_opts_t* opts);
+/* create checks the options and builds the host tables (filter phases, lag grid, up-sampling CSR); the device is first touched by a
+ * compute call, so shapes can be asked for, and options refused, on a host without one */
+int eesen_pitch_create(int device, void* stream, const eesen_pitch_opts_t* opts, eesen_pitch_t** out);
+int eesen_pitch_destroy(eesen_pitch_t* p);
+/* frames of a waveform of nsamp samples (NumFramesAvailable after InputFinished, pitch-functions.cc:760-775; NOT the filterbank's
+ * count), 2, and the number of selected post-processing columns; the processed matrix has frames + delay rows.  Outputs may be NULL */
+int eesen_pitch_shape(eesen_pitch_t* p, int nsamp, int* frames, int* raw_dim, int* processed_dim);
+/* waves[s] -> nsamp[s] samples in int16 scale; utt_ids (NULL: 0 .. S-1) key the noise.  process = 0: out[s] <- [frames x 2] (NCCF at
+ * the chosen lag without ballast, pitch in Hz); process = 1: the post-processing runs on them in the same call, without a copy back in
+ * between, and out[s] <- [frames + delay x processed_dim].  out_cap[s]: floats out[s] holds (NULL: trusted); out[s] may be NULL for a
+ * waveform without a frame.  frames_out (may be NULL) <- rows written per waveform.  Synchronises. */
+int eesen_pitch_compute(eesen_pitch_t* p, const float* const* waves, const int* nsamp, const unsigned long long* utt_ids, int S,
+                        int process, float* const* out, const long* out_cap, int* frames_out);
+/* the post-processing alone, for raw pairs that come from a table: raw[s] -> [frames[s] x 2] */
+int eesen_pitch_process(eesen_pitch_t* p, const float* const* raw, const int* frames, const unsigned long long* utt_ids, int S,
+                        float* const* out, const long* out_cap, int* frames_out);
+/* DIAGNOSTIC: the stage outputs of one waveform, which the tests hold one by one.  counts[5] <- frames, frames of the first pass
+ * (those that see window + last lag samples before the flush), lag states, down-sampled samples, of which before the flush.  Every
+ * other output may be NULL and is sized by the caller from counts (ask once with NULLs): down [samples], nccf_pitch and nccf_pov
+ * [frames x states] (up-sampled; nccf_pitch BEFORE the re-estimate's scaling), lags [states], avg_norm_prod [frames], mean_square
+ * [2] (without and with the flushed tail), fwd [states] (forward costs after the last frame), backptr [frames x states], track
+ * [frames], raw [frames x 2], taken <- whether the energy re-estimate was applied. */
+int eesen_pitch_nccf(eesen_pitch_t* p, const float* wave, int nsamp, int* counts, float* down, float* nccf_pitch, float* nccf_pov,
+                     float* lags, float* avg_norm_prod, double* mean_square, float* fwd, unsigned short* backptr, int* track,
+                     float* raw, int* taken);
+/* The lag grid of SelectLags (pitch-functions.cc:155-165) in seconds, host only: *n <- its size; written when lags != NULL and cap
+ * suffices */
+int eesen_pitch_lags(const eesen_pitch_opts_t* opts, float* lags, int cap, int* n);
+/* Average milliseconds (HIP events) over `iters` repetitions of the launches on these waveforms, after one warm-up pass and without
+ * the copies: avg_ms[5] <- all four launches back to back, then the down-sampler, the NCCF, the search and the post-processing
+ * alone; microbenchmark entry point used by scripts/pitch_probe.py. */
+int eesen_pitch_bench(eesen_pitch_t* p, const float* const* waves, const int* nsamp, int S, int iters, float* avg_ms);
+
 /* ---- raw device helpers for hosts that own no GPU allocator --------------------------------- */
 int eesen_dev_alloc(int device, long bytes, void** dev_ptr);
 int eesen_dev_free(int device, void* dev_ptr);
