@@ -544,10 +544,7 @@ int eesen_ctc_dropped(eesen_ctc_t* ctc, long* minibatches) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(minibatches); ctc->flush(); *minibatches = ctc->guard.dropped; });
 }
 int eesen_ctc_set_profiling(eesen_ctc_t* ctc, int mode) {
-  return guard([&] { REQ_PTR(ctc); ctc->timer.enable(mode == 2); ctc->timer.set_accumulate(mode == 2); ctc->align_timer.enable(mode == 2); ctc->align_timer.set_accumulate(mode == 2);
-                     ctc->decode_timer.enable(mode == 2); ctc->decode_timer.set_accumulate(mode == 2);
-                     ctc->stamp_timer.enable(mode == 2); ctc->stamp_timer.set_accumulate(mode == 2);
-                     ctc->mbr_accumulate = mode == 2; ctc->mbr_t[0] = ctc->mbr_t[1] = ctc->mbr_t[2] = 0; });
+  return guard([&] { REQ_PTR(ctc); ctc->set_profiling(mode); });
 }
 int eesen_ctc_get_phase_times(eesen_ctc_t* ctc, float* out3) {
   return guard([&] { REQ_PTR(ctc); REQ_PTR(out3); ctc->phase_times(out3); });
@@ -610,7 +607,7 @@ int eesen_ce_dropped(eesen_ce_t* ce, long* minibatches) {
   return guard([&] { REQ_PTR(ce); REQ_PTR(minibatches); ce->flush(); *minibatches = ce->guard.dropped; });
 }
 int eesen_ce_set_profiling(eesen_ce_t* ce, int mode) {
-  return guard([&] { REQ_PTR(ce); ce->timer.enable(mode == 2); ce->timer.set_accumulate(mode == 2); });
+  return guard([&] { REQ_PTR(ce); ce->clock.set_mode(mode == 2); });
 }
 int eesen_ce_get_phase_times(eesen_ce_t* ce, float* out1) {
   return guard([&] { REQ_PTR(ce); REQ_PTR(out1); ce->phase_times(out1); });

@@ -25,7 +25,7 @@ void CeLoss::fold(Pending& q, double* obj_out) {
   q.pin.wait();
   q.active = false;
   const CeSums* r = q.pin.as<CeSums>();
-  if (*reinterpret_cast<const unsigned*>(r + 1) != 0) {  // computed from a timed-out forward pass (StatGuard): not a statistic
+  if (StatGuard::raised(r, sizeof(CeSums))) {  // computed from a timed-out forward pass (StatGuard): not a statistic
     if (obj_out) *obj_out = std::numeric_limits<double>::quiet_NaN();
     guard.note_dropped("CE");
     return;
@@ -64,12 +64,9 @@ void CeLoss::flush() {
 
 void CeLoss::eval_parallel(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld, const int* targets,
                            float* diff, int ldd, double* obj_host) {
-  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
-  EESEN_REQUIRE(K > 0, EESEN_ERR_INVALID, "no classes");
-  EESEN_REQUIRE(ld >= K && ldd >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  check_shape(frame_num_utt, S, rows, K, ld, 1);
+  EESEN_REQUIRE(ldd >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
   const int T = rows / S;
-  for (int s = 0; s < S; ++s)
-    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
   // ce-loss.cc:106-113 checks every row's id (an id of a padded row is 0 there); only the valid rows' ids are read here, and a
   // negative one -- an out-of-bounds write in the reference -- is refused as well
   for (int t = 0; t < T; ++t)
@@ -82,34 +79,26 @@ void CeLoss::eval_parallel(const int* frame_num_utt, int S, const float* net_out
     }
   EESEN_HIP_CHECK(hipSetDevice(device));
 
-  // lens + targets: one stream-ordered upload through a pinned slot (the slot written here was last read two calls ago)
+  // lens + targets: one stream-ordered upload (StageSlots)
   const size_t n = (size_t)S + rows;
   const int nb = ce_eval_blocks(rows);
   if (tg.cap < n || part.cap < (size_t)nb || res.cap < 1) EESEN_HIP_CHECK(hipStreamSynchronize(st));  // reallocation frees what queued kernels may read
   tg.reserve(n);
   part.reserve(nb);
   res.reserve(1);
-  PinBuf& sp = stage[stage_idx++ & 1];
-  int* pinned = static_cast<int*>(loss_slot(sp, n * sizeof(int)));
-  std::copy(frame_num_utt, frame_num_utt + S, pinned);
-  std::copy(targets, targets + rows, pinned + S);
-  EESEN_HIP_CHECK(hipMemcpyAsync(tg.p, pinned, n * sizeof(int), hipMemcpyHostToDevice, st));
-  sp.used(st);
+  stage.upload(st, tg.p, n, [&](int* pinned) {
+    std::copy(frame_num_utt, frame_num_utt + S, pinned);
+    std::copy(targets, targets + rows, pinned + S);
+  });
 
-  const bool acc = timer.enabled();
-  int sp0 = -1;
-  if (acc) sp0 = timer.begin(st, 0); else ev[0].record(st);
+  clock.mark(st, 0);
   ce_eval(st, net_out, ld, rows, K, S, tg.p, tg.p + S, diff, ldd, part.p, res.p);
-  if (acc) timer.end(st, sp0); else ev[1].record(st);
+  clock.stop(st);
 
   // the sums (and the guard word's value when they were computed) back through a pinned slot
   Pending& q = pend[pend_idx++ & 1];
   fold(q, nullptr);
-  CeSums* r = static_cast<CeSums*>(loss_slot(q.pin, sizeof(CeSums) + sizeof(unsigned)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(r, res.p, sizeof(CeSums), hipMemcpyDeviceToHost, st));
-  *reinterpret_cast<unsigned*>(r + 1) = 0;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(r + 1, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  q.pin.used(st);
+  guard.read_back(q.pin, res.p, sizeof(CeSums), st);
   q.S = S; q.rows = rows; q.active = true;
   if (obj_host) {
     fold(pend[pend_idx & 1], nullptr);   // the older one first: totals accumulate in call order
@@ -124,14 +113,6 @@ std::string CeLoss::report() {
   std::ostringstream oss;
   oss << "\nFRAME_ACCURACY >> " << 100.0 * (double(correct) / double(frames)) << "% <<";
   return oss.str();
-}
-
-void CeLoss::phase_times(float* out1) {
-  if (timer.enabled()) { timer.collect(out1, 1); return; }   // sums since the last read
-  ev[1].wait();
-  float ms = 0.f;
-  EESEN_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-  out1[0] = ms * 1e-3f;
 }
 
 }  // namespace eesen

@@ -28,7 +28,7 @@ void Ctc::flush_pzx(PendingPzx& q) {
   q.pin.wait();
   const float* pz = q.pin.as<float>();
   q.active = false;
-  if (reinterpret_cast<const unsigned*>(pz)[q.S] != 0) {  // computed from a timed-out forward pass (see StatGuard): not a statistic
+  if (StatGuard::raised(pz, q.S * sizeof(float))) {  // computed from a timed-out forward pass (see StatGuard): not a statistic
     sequences -= q.S;
     frames -= q.nframes;
     guard.note_dropped("CTC");
@@ -45,14 +45,27 @@ void Ctc::flush() {
   for (unsigned k = 0; k < 2; ++k) flush_err(perr[(perr_idx + k) & 1], nullptr, nullptr);
 }
 
-static void check_batch(const int* frame_num_utt, int S, int rows, int K, const int* label_ids, const int* label_off) {
+void Ctc::set_profiling(int mode) {
+  for (PhaseClock* c : {&clock, &align_clock, &decode_clock, &stamp_clock}) c->set_mode(mode == 2);   // (rescore_clock: always the last call's)
+  mbr_accumulate = mode == 2;
+  mbr_t[0] = mbr_t[1] = mbr_t[2] = 0;
+}
+
+void check_shape(const int* frame_num_utt, int S, int rows, int K, int ld, int min_K) {
   EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
-  EESEN_REQUIRE(K > 0, EESEN_ERR_INVALID, "no classes");
+  if (min_K >= 2) EESEN_REQUIRE(K >= 2, EESEN_ERR_INVALID, "decoding needs the blank and at least one other class (K >= 2)");
+  else if (min_K == 1) EESEN_REQUIRE(K > 0, EESEN_ERR_INVALID, "no classes");
+  EESEN_REQUIRE(K > 0 && ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
   const int T = rows / S;
-  for (int s = 0; s < S; ++s) {
+  for (int s = 0; s < S; ++s)
     EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
+}
+
+// the shape and the labels of eval_parallel, align_parallel and error_rate_mseq
+static void check_batch(const int* frame_num_utt, int S, int rows, int K, int ld, const int* label_ids, const int* label_off) {
+  check_shape(frame_num_utt, S, rows, K, ld, 1);
+  for (int s = 0; s < S; ++s)
     EESEN_REQUIRE(label_off[s + 1] >= label_off[s], EESEN_ERR_INVALID, "label offsets must be non-decreasing");
-  }
   for (int i = label_off[0]; i < label_off[S]; ++i)
     EESEN_REQUIRE(label_ids[i] >= 0 && label_ids[i] < K, EESEN_ERR_INVALID, "label id outside [0, K)");
 }
@@ -68,43 +81,26 @@ Ctc::Lattices Ctc::upload_lattices(const int* frame_num_utt, int S, const int* l
     maxU = std::max(maxU, U);
   }
   const int Lprime = 2 * maxU + 1;  // ctc-loss.cc:118
-  int PL = 1;
-  while (64 * PL < Lprime) PL *= 2;
-  EESEN_REQUIRE(PL <= 64, EESEN_ERR_INVALID, "expanded label length above 4096 (2047 labels per utterance) is not supported");
-  const int Lpad = 64 * PL;
+  const int Lpad = lattice_pad(maxU);
+  EESEN_REQUIRE(Lpad > 0, EESEN_ERR_INVALID, "expanded label length above 4096 (2047 labels per utterance) is not supported");
 
-  // label expansion (ctc-loss.cc:116-129), sequence and expanded-label lengths: one staging vector
-  const size_t n_labx = (size_t)S * Lpad;
-  std::vector<int> h(n_labx + 2 * (size_t)S);
-  int* labx_h = h.data();
-  int* lens_h = labx_h + n_labx;
-  int* ll_h = lens_h + S;
-  std::fill(labx_h, labx_h + n_labx, -1);
-  for (int s = 0; s < S; ++s) {
-    const int U = label_off[s + 1] - label_off[s];
-    const int* lab = label_ids + label_off[s];
-    int* lx = labx_h + (size_t)s * Lpad;
-    for (int l = 0; l < U; ++l) { lx[2 * l] = 0; lx[2 * l + 1] = lab[l]; }
-    lx[2 * U] = 0;
-    lens_h[s] = frame_num_utt[s];
-    ll_h[s] = 2 * U + 1;
-  }
-  // Stream-ordered upload through a pinned slot: kernels of the previous call that still read labx are ahead of this copy on
-  // the stream, and the slot written here was last read by the copy of two calls ago -- nothing drains the stream.
-  if (labx.cap < h.size()) EESEN_HIP_CHECK(hipStreamSynchronize(st));  // reallocation frees what queued kernels may still read
-  labx.reserve(h.size());
-  PinBuf& sp = stage[stage_idx++ & 1];
-  int* pinned = static_cast<int*>(loss_slot(sp, h.size() * sizeof(int)));
-  std::copy(h.begin(), h.end(), pinned);
-  EESEN_HIP_CHECK(hipMemcpyAsync(labx.p, pinned, h.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  sp.used(st);
+  // label expansion, sequence and expanded-label lengths: one stream-ordered upload (StageSlots)
+  const size_t n_labx = (size_t)S * Lpad, n = n_labx + 2 * (size_t)S;
+  if (labx.cap < n) EESEN_HIP_CHECK(hipStreamSynchronize(st));  // reallocation frees what queued kernels may still read
+  labx.reserve(n);
+  stage.upload(st, labx.p, n, [&](int* h) {
+    for (int s = 0; s < S; ++s) {
+      h[n_labx + s] = frame_num_utt[s];
+      h[n_labx + S + s] = expand_labels(label_ids + label_off[s], label_off[s + 1] - label_off[s], h + (size_t)s * Lpad, Lpad);
+    }
+  });
   return Lattices{labx.p, labx.p + n_labx, labx.p + n_labx + S, Lpad, Lprime};
 }
 
 void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld, const int* label_ids,
                         const int* label_off, float* diff, int ldd, float* pzx_host) {
-  check_batch(frame_num_utt, S, rows, K, label_ids, label_off);
-  EESEN_REQUIRE(ld >= K && ldd >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  check_batch(frame_num_utt, S, rows, K, ld, label_ids, label_off);
+  EESEN_REQUIRE(ldd >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
   EESEN_HIP_CHECK(hipSetDevice(device));
   const int T = rows / S;
   const Lattices lat = upload_lattices(frame_num_utt, S, label_ids, label_off);
@@ -119,25 +115,19 @@ void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, i
   beta.reserve((size_t)S * T * Lpad);
   pzx_d.reserve(S);
 
-  const bool acc = timer.enabled();
-  int sp0 = -1, sp1 = -1, sp2 = -1;
-  if (acc) sp0 = timer.begin(st, 0); else ev[0].record(st);
+  clock.mark(st, 0);
   log_rows(st, net_out, ld, logp.p, K, rows, K);                                               // ctc-loss.cc:132-133
-  if (acc) { timer.end(st, sp0); sp1 = timer.begin(st, 1); } else ev[1].record(st);
+  clock.mark(st, 1);
   ctc_alpha_beta(st, logp.p, K, T, S, Lpad, labx_d, lens_dd, ll_d, alpha.p, beta.p, pzx_d.p, sweep_waves);  // :136-153
-  if (acc) { timer.end(st, sp1); sp2 = timer.begin(st, 2); } else ev[2].record(st);
+  clock.mark(st, 2);
   ctc_error_diff(st, net_out, ld, T, S, K, Lpad, Lprime, lens_dd, ll_d, labx_d, alpha.p, beta.p, pzx_d.p, diff, ldd);  // :156-168
-  if (acc) timer.end(st, sp2); else ev[3].record(st);
+  clock.stop(st);
 
   // ln p(z|x) per sequence (ctc-loss.cc:146-153 reads it element by element): back through a pinned slot.  A caller that wants
   // the values now waits for them; otherwise they join the objective sum when the next call needs the slot or the statistics.
   PendingPzx& q = ppzx[ppzx_idx++ & 1];
   flush_pzx(q);
-  float* pz = static_cast<float*>(loss_slot(q.pin, (size_t)(S + 1) * sizeof(float)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(pz, pzx_d.p, S * sizeof(float), hipMemcpyDeviceToHost, st));
-  reinterpret_cast<unsigned*>(pz)[S] = 0;   // the guard word's value when these ln p were computed
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(pz + S, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  q.pin.used(st);
+  const float* pz = static_cast<const float*>(guard.read_back(q.pin, pzx_d.p, S * sizeof(float), st));
   q.S = S; q.active = true;
   q.nframes = 0;
   for (int s = 0; s < S; ++s) q.nframes += frame_num_utt[s];
@@ -146,29 +136,18 @@ void Ctc::eval_parallel(const int* frame_num_utt, int S, const float* net_out, i
   if (pzx_host) {
     flush();  // keeps the accumulation order of the calls
     // a minibatch computed from a timed-out forward pass (guard word set) has no ln p: NaN, never garbage with status OK
-    const bool bad = reinterpret_cast<const unsigned*>(pz)[S] != 0;
+    const bool bad = StatGuard::raised(pz, S * sizeof(float));
     for (int s = 0; s < S; ++s) pzx_host[s] = bad ? std::numeric_limits<float>::quiet_NaN() : pz[s];
   }
   last_lens.assign(frame_num_utt, frame_num_utt + S);
   last_T = T; last_S = S; last_Lpad = Lpad; last_Lprime = Lprime;
 }
 
-void Ctc::phase_times(float* out3) {
-  if (timer.enabled()) { timer.collect(out3, 3); return; }   // sums since the last read
-  ev[3].wait();
-  for (int i = 0; i < 3; ++i) {
-    float ms = 0.f;
-    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-    out3[i] = ms * 1e-3f;
-  }
-}
-
 // Best-path alignment of every utterance against its labels.  The delta rows borrow `alpha`, the logarithms `logp`; the statistics
 // and the accessors of the last EvalParallel (last_*) are left alone.
 void Ctc::align_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* label_ids,
                          const int* label_off, int* ali_host, int* pos_host, float* score_host) {
-  check_batch(frame_num_utt, S, rows, K, label_ids, label_off);
-  EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  check_batch(frame_num_utt, S, rows, K, ld, label_ids, label_off);
   EESEN_HIP_CHECK(hipSetDevice(device));
   const int T = rows / S;
   const Lattices lat = upload_lattices(frame_num_utt, S, label_ids, label_off);
@@ -181,25 +160,17 @@ void Ctc::align_parallel(const int* frame_num_utt, int S, const float* scores, i
   int* pos_dev = ali_dev + rows;
   float* score_dev = reinterpret_cast<float*>(pos_dev + rows);
 
-  const bool acc = align_timer.enabled();
-  int sp0 = -1, sp1 = -1, sp2 = -1;
-  if (acc) sp0 = align_timer.begin(st, 0); else aev[0].record(st);
+  align_clock.mark(st, 0);
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
-  if (acc) { align_timer.end(st, sp0); sp1 = align_timer.begin(st, 1); } else aev[1].record(st);
+  align_clock.mark(st, 1);
   ctc_best_path(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, lat.Lpad, lat.labx, lat.lens, lat.lablens, alpha.p, sweep_waves);
-  if (acc) { align_timer.end(st, sp1); sp2 = align_timer.begin(st, 2); } else aev[2].record(st);
+  align_clock.mark(st, 2);
   ctc_traceback(st, alpha.p, T, S, lat.Lpad, lat.labx, lat.lens, lat.lablens, ali_dev, pos_dev, score_dev);
-  if (acc) align_timer.end(st, sp2); else aev[3].record(st);
+  align_clock.stop(st);
 
-  // results and the guard word's value when they were computed, through one pinned slot
-  int* out = static_cast<int*>(loss_slot(align_pin, (n_out + 1) * sizeof(int)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(out, ali_dev, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
-  out[n_out] = 0;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_out, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  align_pin.used(st);
+  const int* out = static_cast<const int*>(guard.read_back(align_pin, ali_dev, n_out * sizeof(int), st));
   align_pin.wait();
-  // computed from a timed-out forward pass (guard word set): no alignment -- NaN and -1, never garbage with status OK
-  const bool bad = out[n_out] != 0;
+  const bool bad = StatGuard::raised(out, n_out * sizeof(int));   // no alignment: NaN and -1
   for (int r = 0; r < rows; ++r) {
     ali_host[r] = bad ? -1 : out[r];
     if (pos_host) pos_host[r] = bad ? -1 : out[rows + r];
@@ -208,20 +179,11 @@ void Ctc::align_parallel(const int* frame_num_utt, int S, const float* scores, i
   for (int s = 0; s < S; ++s) score_host[s] = bad ? std::numeric_limits<float>::quiet_NaN() : sc[s];
 }
 
-void Ctc::align_times(float* out3) {
-  if (align_timer.enabled()) { align_timer.collect(out3, 3); return; }
-  aev[3].wait();
-  for (int i = 0; i < 3; ++i) {
-    float ms = 0.f;
-    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, aev[i], aev[i + 1]));
-    out3[i] = ms * 1e-3f;
-  }
-}
-
 // Prefix beam search of every utterance (INTEGRATION.md "Decoding").  The logarithms borrow `logp`; everything else is this call's own.
 void Ctc::decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                           int nbest, int* hyp_host, int* hyp_len_host, float* score_host) {
-  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, nullptr, 0.f, 0.f, false, hyp_host, hyp_len_host, score_host, nullptr);
+  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, nullptr, 0.f, 0.f, false, hyp_host, hyp_len_host, score_host,
+               nullptr, nullptr, nullptr, nullptr);
 }
 
 // With a token LM fused into the beam (INTEGRATION.md "LM fusion"): ctc_prefix_beam with the tables, inside the same phase.  The
@@ -234,7 +196,18 @@ void Ctc::decode_parallel_lm(const int* frame_num_utt, int S, const float* score
   EESEN_REQUIRE(!use_eos || lm->has_eos, EESEN_ERR_INVALID, "use_eos on an LM whose file has no </s>");
   EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(insertion_bonus), EESEN_ERR_INVALID, "lm_weight and insertion_bonus must be finite");
   decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, nullptr, lm, lm_weight, insertion_bonus, use_eos, hyp_host,
-               hyp_len_host, score_host, lm_score_host);
+               hyp_len_host, score_host, lm_score_host, nullptr, nullptr, nullptr);
+}
+
+// what the two lexicon searches ask of their lexicon and its word LM
+static void check_lexicon(const Lexicon* lex, bool unspaced, const TokenLm* lm, int K, bool use_eos, float lm_weight, float word_bonus) {
+  EESEN_REQUIRE(lex != nullptr, EESEN_ERR_INVALID, "decoding with a lexicon: the lexicon handle is null");
+  if (unspaced) EESEN_REQUIRE(lex->unspaced, EESEN_ERR_INVALID, "a lexicon with a space class (eesen_lex_create) is decoded with eesen_ctc_decode_parallel_lex");
+  else EESEN_REQUIRE(!lex->unspaced, EESEN_ERR_INVALID, "an unspaced lexicon (eesen_lex_create_unspaced) is decoded with eesen_ctc_decode_parallel_words");
+  EESEN_REQUIRE(lex->K == K, EESEN_ERR_INVALID, "the lexicon was built for another class count K than the scores have");
+  EESEN_REQUIRE(lm == nullptr || lm->K == lex->V() + 1, EESEN_ERR_INVALID, "the word LM's K must be the lexicon's word count + 1 (build it over eesen_lex_write_words' table)");
+  EESEN_REQUIRE(!use_eos || (lm != nullptr && lm->has_eos), EESEN_ERR_INVALID, "use_eos without a word LM, or on one whose file has no </s>");
+  EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_bonus), EESEN_ERR_INVALID, "lm_weight and word_bonus must be finite");
 }
 
 // Along a lexicon trie, with or without an LM over its words (INTEGRATION.md "Lexicon"): the same three launches; the lexicon's
@@ -243,14 +216,9 @@ void Ctc::decode_parallel_lm(const int* frame_num_utt, int S, const float* score
 void Ctc::decode_parallel_lex(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                               int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
                               int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host) {
-  EESEN_REQUIRE(lex != nullptr, EESEN_ERR_INVALID, "decoding with a lexicon: the lexicon handle is null");
-  EESEN_REQUIRE(!lex->unspaced, EESEN_ERR_INVALID, "an unspaced lexicon (eesen_lex_create_unspaced) is decoded with eesen_ctc_decode_parallel_words");
-  EESEN_REQUIRE(lex->K == K, EESEN_ERR_INVALID, "the lexicon was built for another class count K than the scores have");
-  EESEN_REQUIRE(lm == nullptr || lm->K == lex->V() + 1, EESEN_ERR_INVALID, "the word LM's K must be the lexicon's word count + 1 (build it over eesen_lex_write_words' table)");
-  EESEN_REQUIRE(!use_eos || (lm != nullptr && lm->has_eos), EESEN_ERR_INVALID, "use_eos without a word LM, or on one whose file has no </s>");
-  EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_bonus), EESEN_ERR_INVALID, "lm_weight and word_bonus must be finite");
+  check_lexicon(lex, false, lm, K, use_eos, lm_weight, word_bonus);
   decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, lex, lm, lm_weight, word_bonus, use_eos, hyp_host, hyp_len_host,
-               score_host, lm_score_host);
+               score_host, lm_score_host, nullptr, nullptr, nullptr);
   // (kept for decode_stamps, which speaks of these words and may run after the lexicon is gone: segmented whether asked for or not)
   const int T = rows / S;
   std::vector<int> w((size_t)T / 2 + 1);
@@ -331,198 +299,95 @@ void Ctc::upload_lm(const TokenLm& lm) {
   lm_serial = lm.serial;
 }
 
+// Every decode call: the checks, the buffers (DecodeLayout), the lengths, the logarithm and the top-C phase in front, the read-back
+// behind.  In between the plain / fused search and its hypothesis kernel or, along an unspaced lexicon, the word search's, whose trie
+// holds a third array and whose words, word ends and word counts come back behind the labels (the three hosts may be null).
 void Ctc::decode_batch(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
-                       int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host,
-                       int* hyp_len_host, float* score_host, float* lm_score_host) {
-  const bool fused = lm != nullptr || lex != nullptr;   // the beam carries LM sums (all 0 under a lexicon without an LM)
-  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
-  EESEN_REQUIRE(K >= 2, EESEN_ERR_INVALID, "decoding needs the blank and at least one other class (K >= 2)");
-  EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+                       int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
+                       float* score_host, float* lm_score_host, int* word_host, int* word_len_host, int* word_end_host) {
+  const bool words = lex && lex->unspaced;
+  check_shape(frame_num_utt, S, rows, K, ld, words ? 0 : 2);   // (words: the lexicon's K is the scores', which its caller held)
   EESEN_REQUIRE(beam >= 1 && beam <= 64, EESEN_ERR_INVALID, "beam outside [1, 64]");
   EESEN_REQUIRE(max_classes >= 1 && max_classes <= 64, EESEN_ERR_INVALID, "max_classes outside [1, 64]");
-  EESEN_REQUIRE(beam * max_classes <= 2048, EESEN_ERR_INVALID, "beam * max_classes above 2048 (the candidate keys of a frame live in LDS)");
+  if (!words) EESEN_REQUIRE(beam * max_classes <= 2048, EESEN_ERR_INVALID, "beam * max_classes above 2048 (the candidate keys of a frame live in LDS)");
+  else {
+    const int H = lex->max_homophones;
+    EESEN_REQUIRE((long)beam * (1 + (long)max_classes * (1 + H)) <= 4096, EESEN_ERR_INVALID,
+                  "beam * (1 + max_classes * (1 + H)) above 4096, H = " + std::to_string(H) + " the lexicon's largest homophone set (the successor keys of a frame live in LDS)");
+  }
   EESEN_REQUIRE(nbest >= 1 && nbest <= beam, EESEN_ERR_INVALID, "nbest outside [1, beam]");
-  const int T = rows / S;
-  for (int s = 0; s < S; ++s)
-    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
   EESEN_HIP_CHECK(hipSetDevice(device));
-  const int B = beam, N = nbest, Cc = std::min(max_classes, K - 1);
-  const size_t n_cand = (size_t)rows * Cc, n_beam = (size_t)S * B, n_trie = (size_t)S * (1 + (size_t)T * B);
-  const size_t n_f = n_cand + rows + n_beam + (fused ? n_beam : 0), n_i = n_cand + S + 2 * n_beam + S;
-  const size_t n_hyp = (size_t)S * N * T, n_out = n_hyp + (fused ? 3 : 2) * (size_t)S * N;   // labels, lengths, scores (, LM sums)
-  EESEN_REQUIRE(n_trie <= ((size_t)1 << 30), EESEN_ERR_INVALID, "decoding: more than 2^30 trie nodes (S * (1 + T * beam)): decode fewer utterances together");
-  if ((!is_log && logp.cap < (size_t)rows * K) || dec_f.cap < n_f || dec_i.cap < n_i || dec_trie.cap < 2 * n_trie || dec_out.cap < n_out)
+  const DecodeLayout L = decode_layout(rows, S, K, beam, max_classes, nbest, words ? kDecodeWords : lm || lex ? kDecodeFused : kDecodePlain);
+  const bool fused = L.fused();   // the beam carries LM sums (all 0 under a lexicon without an LM)
+  EESEN_REQUIRE(L.n_trie <= ((size_t)1 << 30), EESEN_ERR_INVALID, "decoding: more than 2^30 trie nodes (S * (1 + T * beam)): decode fewer utterances together");
+  if ((!is_log && logp.cap < (size_t)rows * K) || dec_f.cap < L.n_f || dec_i.cap < L.n_i || dec_trie.cap < L.n_t || dec_out.cap < L.n_out)
     EESEN_HIP_CHECK(hipStreamSynchronize(st));
   if (!is_log) logp.reserve((size_t)rows * K);
-  dec_f.reserve(n_f);
-  dec_i.reserve(n_i);
-  dec_trie.reserve(2 * n_trie);
-  dec_out.reserve(n_out);
-  float* csc = dec_f.p;
-  float* sblank = csc + n_cand;
-  float* fscore = sblank + rows;
-  int* cid = dec_i.p;
-  int* lens_d = cid + n_cand;
-  int* fnode = lens_d + S;
-  int* flen = fnode + n_beam;
-  int* count = flen + n_beam;
-  int* hyp_d = dec_out.p;
-  int* len_d = hyp_d + n_hyp;
-  float* score_d = reinterpret_cast<float*>(len_d + (size_t)S * N);
-  float* flm = fscore + n_beam;             // (with an LM only)
-  float* lmsum_d = score_d + (size_t)S * N;
+  dec_f.reserve(L.n_f);
+  dec_i.reserve(L.n_i);
+  dec_trie.reserve(L.n_t);
+  dec_out.reserve(L.n_out);
+  float *csc = dec_f.p + L.csc, *sblank = dec_f.p + L.sblank, *fscore = dec_f.p + L.fscore, *flm = fused ? dec_f.p + L.flm : nullptr;
+  int *cid = dec_i.p + L.cid, *lens_d = dec_i.p + L.lens, *fnode = dec_i.p + L.fnode, *flen = dec_i.p + L.flen, *count = dec_i.p + L.count;
+  int *trie0 = dec_trie.p + L.trie[0], *trie1 = dec_trie.p + L.trie[1], *out_d = dec_out.p;
+  float* score_d = reinterpret_cast<float*>(out_d + L.score);
+  float* lmsum_d = fused ? reinterpret_cast<float*>(out_d + L.lmsum) : nullptr;
   if (lm) upload_lm(*lm);
   if (lex) upload_lex(*lex);
   const float* la = lex ? upload_lookahead(lex, lm) : nullptr;   // (the plain and the token-LM search ignore the mode)
-
-  PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
-  int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
-  std::copy(frame_num_utt, frame_num_utt + S, pinned);
-  EESEN_HIP_CHECK(hipMemcpyAsync(lens_d, pinned, S * sizeof(int), hipMemcpyHostToDevice, st));
-  sp.used(st);
+  stage.upload(st, lens_d, S, [&](int* pinned) { std::copy(frame_num_utt, frame_num_utt + S, pinned); });
 
   const float* sc = is_log ? scores : logp.p;
-  const int sld = is_log ? ld : K;
-  const bool acc = decode_timer.enabled();
-  int sp0 = -1, sp1 = -1, sp2 = -1;
-  if (acc) sp0 = decode_timer.begin(st, 0); else dev[0].record(st);
+  const int sld = is_log ? ld : K, T = L.T, B = L.B, N = L.N;
+  decode_clock.mark(st, 0);
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
-  ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
-  if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
-  ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, lex ? &lex_tab : nullptr, la, la ? la + lex->nodes() : nullptr, lm_weight, insertion_bonus, use_eos, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, fused ? flm : nullptr, count);
-  if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
-  ctc_hyp(st, dec_trie.p, dec_trie.p + n_trie, fnode, flen, fscore, fused ? flm : nullptr, count, T, S, B, N, hyp_d, len_d, score_d, fused ? lmsum_d : nullptr);
-  if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
-  dec_rows = rows; dec_S = S; dec_C = Cc;
+  ctc_row_topc(st, sc, sld, rows, K, S, lens_d, L.C, cid, csc, sblank);
+  decode_clock.mark(st, 1);
+  if (words)
+    ctc_word_beam(st, sc, sld, T, S, lens_d, B, L.C, cid, csc, sblank, lm ? &lm_tab : nullptr, word_tab, la, lm_weight, bonus, use_eos, trie0, trie1,
+                  dec_trie.p + L.trie[2], fnode, flen, fscore, flm, dec_i.p + L.fword, dec_i.p + L.fnw, count);
+  else
+    ctc_prefix_beam(st, sc, sld, T, S, lens_d, B, L.C, cid, csc, sblank, lm ? &lm_tab : nullptr, lex ? &lex_tab : nullptr, la, la ? la + lex->nodes() : nullptr,
+                    lm_weight, bonus, use_eos, trie0, trie1, fnode, flen, fscore, flm, count);
+  decode_clock.mark(st, 2);
+  if (words)
+    ctc_word_hyp(st, trie0, trie1, dec_trie.p + L.trie[2], fnode, flen, fscore, flm, dec_i.p + L.fword, dec_i.p + L.fnw, count, T, S, B, N, out_d + L.hyp,
+                 out_d + L.len, score_d, lmsum_d, out_d + L.words, out_d + L.ends, out_d + L.wlen);
+  else
+    ctc_hyp(st, trie0, trie1, fnode, flen, fscore, flm, count, T, S, B, N, out_d + L.hyp, out_d + L.len, score_d, lmsum_d);
+  decode_clock.stop(st);
+  dec = L;   // (decode_stamps, decode_rescore, decode_mbr: the hypotheses stay in dec_out and decode_pin)
   dec_lens.assign(frame_num_utt, frame_num_utt + S);
-  dec_N = N; dec_T = T; dec_mode = lex ? 1 : 0; dec_fused = fused;   // (decode_stamps: the hypotheses stay in dec_out and decode_pin)
-  dec_space = lex ? lex->space : -1;
+  dec_space = lex && !words ? lex->space : -1;
   dec_V = lex ? lex->V() : 0;
 
-  // results and the guard word's value when they were computed, through one pinned slot
-  int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(out, hyp_d, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
-  out[n_out] = 0;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_out, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  decode_pin.used(st);
+  const int* out = static_cast<const int*>(guard.read_back(decode_pin, out_d, L.n_out * sizeof(int), st));
   decode_pin.wait();
-  // computed from a timed-out forward pass (guard word set): no hypotheses -- NaN and -1, never garbage with status OK
-  const bool bad = out[n_out] != 0;
-  for (size_t i = 0; i < n_hyp; ++i) hyp_host[i] = bad ? -1 : out[i];
-  const float* scr = reinterpret_cast<const float*>(out + n_hyp + (size_t)S * N);
-  for (size_t i = 0; i < (size_t)S * N; ++i) {
-    hyp_len_host[i] = bad ? -1 : out[n_hyp + i];
-    score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
-    if (fused && lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[(size_t)S * N + i];
+  const bool bad = StatGuard::raised(out, L.n_out * sizeof(int));   // no hypotheses: NaN and -1
+  const float* outf = reinterpret_cast<const float*>(out);
+  const float kNaN = std::numeric_limits<float>::quiet_NaN();
+  for (size_t i = 0; i < L.n_hyp; ++i) {
+    hyp_host[i] = bad ? -1 : out[L.hyp + i];
+    if (word_host) word_host[i] = bad ? -1 : out[L.words + i];
+    if (word_end_host) word_end_host[i] = bad ? -1 : out[L.ends + i];
+  }
+  for (size_t i = 0; i < L.NL; ++i) {
+    hyp_len_host[i] = bad ? -1 : out[L.len + i];
+    score_host[i] = bad ? kNaN : outf[L.score + i];
+    if (fused && lm_score_host) lm_score_host[i] = bad ? kNaN : outf[L.lmsum + i];
+    if (word_len_host) word_len_host[i] = bad ? -1 : out[L.wlen + i];
   }
 }
 
-// Along an unspaced lexicon (INTEGRATION.md "Words without a boundary unit"): the candidate selection of decode_batch, then the word
-// beam and its hypothesis kernel, in decode_batch's buffers, phases and conventions.  The trie holds a third array (the word closed
-// in front of a node's label) and the final beam a word and a word count per hypothesis; nothing is segmented on the host.
+// Along an unspaced lexicon (INTEGRATION.md "Words without a boundary unit"): decode_batch with the word beam and its hypothesis kernel.
+// The final beam holds a word and a word count per hypothesis; nothing is segmented on the host.
 void Ctc::decode_parallel_words(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam,
                                 int max_classes, int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos,
                                 int* hyp_host, int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host,
                                 int* word_end_host) {
-  EESEN_REQUIRE(lex != nullptr, EESEN_ERR_INVALID, "decoding with a lexicon: the lexicon handle is null");
-  EESEN_REQUIRE(lex->unspaced, EESEN_ERR_INVALID, "a lexicon with a space class (eesen_lex_create) is decoded with eesen_ctc_decode_parallel_lex");
-  EESEN_REQUIRE(lex->K == K, EESEN_ERR_INVALID, "the lexicon was built for another class count K than the scores have");
-  EESEN_REQUIRE(lm == nullptr || lm->K == lex->V() + 1, EESEN_ERR_INVALID, "the word LM's K must be the lexicon's word count + 1 (build it over eesen_lex_write_words' table)");
-  EESEN_REQUIRE(!use_eos || (lm != nullptr && lm->has_eos), EESEN_ERR_INVALID, "use_eos without a word LM, or on one whose file has no </s>");
-  EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(word_bonus), EESEN_ERR_INVALID, "lm_weight and word_bonus must be finite");
-  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
-  EESEN_REQUIRE(ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
-  EESEN_REQUIRE(beam >= 1 && beam <= 64, EESEN_ERR_INVALID, "beam outside [1, 64]");
-  EESEN_REQUIRE(max_classes >= 1 && max_classes <= 64, EESEN_ERR_INVALID, "max_classes outside [1, 64]");
-  const int H = lex->max_homophones;
-  EESEN_REQUIRE((long)beam * (1 + (long)max_classes * (1 + H)) <= 4096, EESEN_ERR_INVALID,
-                "beam * (1 + max_classes * (1 + H)) above 4096, H = " + std::to_string(H) + " the lexicon's largest homophone set (the successor keys of a frame live in LDS)");
-  EESEN_REQUIRE(nbest >= 1 && nbest <= beam, EESEN_ERR_INVALID, "nbest outside [1, beam]");
-  const int T = rows / S;
-  for (int s = 0; s < S; ++s)
-    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
-  EESEN_HIP_CHECK(hipSetDevice(device));
-  const int B = beam, N = nbest, Cc = std::min(max_classes, K - 1);
-  const size_t n_cand = (size_t)rows * Cc, n_beam = (size_t)S * B, n_trie = (size_t)S * (1 + (size_t)T * B), SN = (size_t)S * N;
-  const size_t n_f = n_cand + rows + 2 * n_beam, n_i = n_cand + S + 4 * n_beam + S;
-  const size_t n_hyp = SN * T, n_out = 3 * n_hyp + 4 * SN;   // labels, lengths, scores, LM sums, words, word ends, word counts
-  EESEN_REQUIRE(n_trie <= ((size_t)1 << 30), EESEN_ERR_INVALID, "decoding: more than 2^30 trie nodes (S * (1 + T * beam)): decode fewer utterances together");
-  if ((!is_log && logp.cap < (size_t)rows * K) || dec_f.cap < n_f || dec_i.cap < n_i || dec_trie.cap < 3 * n_trie || dec_out.cap < n_out)
-    EESEN_HIP_CHECK(hipStreamSynchronize(st));
-  if (!is_log) logp.reserve((size_t)rows * K);
-  dec_f.reserve(n_f);
-  dec_i.reserve(n_i);
-  dec_trie.reserve(3 * n_trie);
-  dec_out.reserve(n_out);
-  float* csc = dec_f.p;
-  float* sblank = csc + n_cand;
-  float* fscore = sblank + rows;
-  float* flm = fscore + n_beam;
-  int* cid = dec_i.p;
-  int* lens_d = cid + n_cand;
-  int* fnode = lens_d + S;
-  int* flen = fnode + n_beam;
-  int* fword = flen + n_beam;
-  int* fnw = fword + n_beam;
-  int* count = fnw + n_beam;
-  int* hyp_d = dec_out.p;
-  int* len_d = hyp_d + n_hyp;
-  float* score_d = reinterpret_cast<float*>(len_d + SN);
-  float* lmsum_d = score_d + SN;
-  int* words_d = reinterpret_cast<int*>(lmsum_d + SN);
-  int* ends_d = words_d + n_hyp;
-  int* wlen_d = ends_d + n_hyp;
-  if (lm) upload_lm(*lm);
-  upload_lex(*lex);
-  const float* la = upload_lookahead(lex, lm);
-
-  PinBuf& sp = stage[stage_idx++ & 1];   // the lengths, in stream order (see upload_lattices)
-  int* pinned = static_cast<int*>(loss_slot(sp, S * sizeof(int)));
-  std::copy(frame_num_utt, frame_num_utt + S, pinned);
-  EESEN_HIP_CHECK(hipMemcpyAsync(lens_d, pinned, S * sizeof(int), hipMemcpyHostToDevice, st));
-  sp.used(st);
-
-  const float* sc = is_log ? scores : logp.p;
-  const int sld = is_log ? ld : K;
-  const bool acc = decode_timer.enabled();
-  int sp0 = -1, sp1 = -1, sp2 = -1;
-  if (acc) sp0 = decode_timer.begin(st, 0); else dev[0].record(st);
-  if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
-  ctc_row_topc(st, sc, sld, rows, K, S, lens_d, Cc, cid, csc, sblank);
-  if (acc) { decode_timer.end(st, sp0); sp1 = decode_timer.begin(st, 1); } else dev[1].record(st);
-  ctc_word_beam(st, sc, sld, T, S, lens_d, B, Cc, cid, csc, sblank, lm ? &lm_tab : nullptr, word_tab, la, lm_weight, word_bonus, use_eos, dec_trie.p,
-                dec_trie.p + n_trie, dec_trie.p + 2 * n_trie, fnode, flen, fscore, flm, fword, fnw, count);
-  if (acc) { decode_timer.end(st, sp1); sp2 = decode_timer.begin(st, 2); } else dev[2].record(st);
-  ctc_word_hyp(st, dec_trie.p, dec_trie.p + n_trie, dec_trie.p + 2 * n_trie, fnode, flen, fscore, flm, fword, fnw, count, T, S, B, N, hyp_d, len_d,
-               score_d, lmsum_d, words_d, ends_d, wlen_d);
-  if (acc) decode_timer.end(st, sp2); else dev[3].record(st);
-  dec_rows = rows; dec_S = S; dec_C = Cc;
-  dec_lens.assign(frame_num_utt, frame_num_utt + S);
-  dec_N = N; dec_T = T; dec_mode = 2; dec_fused = true;
-  dec_V = lex->V();
-
-  // results and the guard word's value when they were computed, through one pinned slot
-  int* out = static_cast<int*>(loss_slot(decode_pin, (n_out + 1) * sizeof(int)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(out, hyp_d, n_out * sizeof(int), hipMemcpyDeviceToHost, st));
-  out[n_out] = 0;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_out, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  decode_pin.used(st);
-  decode_pin.wait();
-  // computed from a timed-out forward pass (guard word set): no hypotheses -- NaN and -1, never garbage with status OK
-  const bool bad = out[n_out] != 0;
-  const int* w_out = out + n_hyp + 3 * SN;
-  for (size_t i = 0; i < n_hyp; ++i) {
-    hyp_host[i] = bad ? -1 : out[i];
-    if (word_host) word_host[i] = bad ? -1 : w_out[i];
-    if (word_end_host) word_end_host[i] = bad ? -1 : w_out[n_hyp + i];
-  }
-  const float* scr = reinterpret_cast<const float*>(out + n_hyp + SN);
-  for (size_t i = 0; i < SN; ++i) {
-    hyp_len_host[i] = bad ? -1 : out[n_hyp + i];
-    score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[i];
-    if (lm_score_host) lm_score_host[i] = bad ? std::numeric_limits<float>::quiet_NaN() : scr[SN + i];
-    if (word_len_host) word_len_host[i] = bad ? -1 : w_out[2 * n_hyp + i];
-  }
+  check_lexicon(lex, true, lm, K, use_eos, lm_weight, word_bonus);
+  decode_batch(frame_num_utt, S, scores, rows, K, ld, is_log, beam, max_classes, nbest, lex, lm, lm_weight, word_bonus, use_eos, hyp_host, hyp_len_host,
+               score_host, lm_score_host, word_host, word_len_host, word_end_host);
 }
 
 // N-best posterior word confidences (INTEGRATION.md "Time stamps and CTM"): lattice-to-ctm-conf's idea on a list instead of a lattice.
@@ -574,20 +439,19 @@ void word_confidence(int n, const double* scores, const int* word_len, const int
 // align_parallel's do, the logarithms `logp`.
 void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, double conf_scale,
                         int* lstart_host, int* lend_host, int* wstart_host, int* wend_host, float* wconf_host, float* path_score_host) {
-  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "time stamps: no decode call on this Ctc yet");
-  EESEN_REQUIRE(S == dec_S && rows == dec_rows, EESEN_ERR_STATE, "time stamps: S or rows differ from the last decode call's");
+  EESEN_REQUIRE(dec.rows > 0, EESEN_ERR_STATE, "time stamps: no decode call on this Ctc yet");
+  EESEN_REQUIRE(S == dec.S && rows == dec.rows, EESEN_ERR_STATE, "time stamps: S or rows differ from the last decode call's");
   EESEN_REQUIRE(K > 0 && ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
   EESEN_REQUIRE(std::isfinite(conf_scale) && conf_scale >= 0, EESEN_ERR_INVALID, "conf_scale must be finite and >= 0");
   for (int s = 0; s < S; ++s)
     EESEN_REQUIRE(frame_num_utt[s] == dec_lens[s], EESEN_ERR_STATE, "time stamps: frame_num_utt differs from the last decode call's");
   EESEN_HIP_CHECK(hipSetDevice(device));
-  const int T = dec_T, N = dec_N;
-  const size_t NL = (size_t)S * N, n_hyp = NL * T;
-  const size_t n_dec = dec_mode == 2 ? 3 * n_hyp + 4 * NL : n_hyp + (dec_fused ? 3 : 2) * NL;
+  const int T = dec.T, N = dec.N, tokens = dec_tokens();
+  const size_t NL = dec.NL, n_hyp = dec.n_hyp;
   const int* dout = decode_pin.as<int>();
-  const int* hyp_h = dout;
-  const int* hlen = dout + n_hyp;
-  const float* z = reinterpret_cast<const float*>(hlen + NL);
+  const int* hyp_h = dout + dec.hyp;
+  const int* hlen = dout + dec.len;
+  const float* z = reinterpret_cast<const float*>(dout) + dec.score;
   const float kNaN = std::numeric_limits<float>::quiet_NaN();
   auto fill = [&](int* p, size_t n, int v) { if (p) std::fill(p, p + n, v); };
   auto fillf = [&](float* p, size_t n, float v) { if (p) std::fill(p, p + n, v); };
@@ -595,15 +459,13 @@ void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, in
     fill(lstart_host, n_hyp, -1); fill(lend_host, n_hyp, -1); fill(wstart_host, n_hyp, -1); fill(wend_host, n_hyp, -1);
     fillf(wconf_host, n_hyp, kNaN); fillf(path_score_host, NL, kNaN);
   };
-  if (dout[n_dec] != 0) { all_bad(); return; }
+  if (StatGuard::raised(dout, dec.n_out * sizeof(int))) { all_bad(); return; }
 
-  constexpr int kMaxLabels = 2047;   // L' <= 4096
+  constexpr int kMaxLabels = kMaxLatticeLabels;   // an entry beyond has no lattice (ctc_hyp_lattices) and no stamps
   int maxU = 0;
   for (size_t i = 0; i < NL; ++i)
     if (hlen[i] <= kMaxLabels) maxU = std::max(maxU, hlen[i]);
-  int PL = 1;
-  while (64 * PL < 2 * maxU + 1) PL *= 2;
-  const int Lpad = 64 * PL;
+  const int Lpad = lattice_pad(maxU);
   const size_t per_lattice = (size_t)T * Lpad;
   size_t G = stamp_group > 0 ? (size_t)stamp_group : std::max<size_t>(1, kStampDeltaBytes / (per_lattice * sizeof(float)));
   G = std::min(G, NL);
@@ -622,37 +484,29 @@ void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, in
   int* lstart_d = ali_d2 + n_hyp;
   int* lend_d = lstart_d + n_hyp;
   float* score_d = reinterpret_cast<float*>(lend_d + n_hyp);
-  const int* lens_d = dec_i.p + (size_t)dec_rows * dec_C;
 
-  const bool acc = stamp_timer.enabled();
-  int sp0 = -1, sp1 = -1, sp2 = -1;
-  if (acc) sp0 = stamp_timer.begin(st, 0); else sev[0].record(st);
+  stamp_clock.mark(st, 0);
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
-  ctc_hyp_lattices(st, dec_out.p, dec_out.p + n_hyp, lens_d, T, (int)NL, N, Lpad, labx_d, ll_d, lens_l);
-  if (acc) { stamp_timer.end(st, sp0); sp1 = stamp_timer.begin(st, 1); } else sev[1].record(st);
+  ctc_hyp_lattices(st, dec_out.p + dec.hyp, dec_out.p + dec.len, dec_i.p + dec.lens, T, (int)NL, N, Lpad, labx_d, ll_d, lens_l);
+  stamp_clock.mark(st, 1);
   for (size_t g0 = 0; g0 < NL; g0 += G) {   // groups of lattices: the delta rows stay within their budget
     const int gc = (int)std::min(G, NL - g0);
     ctc_best_path(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, Lpad, labx_d + g0 * Lpad, lens_l + g0, ll_d + g0, alpha.p, sweep_waves, gc,
                   (int)g0, N);
     ctc_traceback(st, alpha.p, T, gc, Lpad, labx_d + g0 * Lpad, lens_l + g0, ll_d + g0, ali_d2 + g0 * T, pos_d + g0 * T, score_d + g0);
   }
-  if (acc) { stamp_timer.end(st, sp1); sp2 = stamp_timer.begin(st, 2); } else sev[2].record(st);
+  stamp_clock.mark(st, 2);
   ctc_stamp(st, pos_d, T, (int)NL, (int)G, lens_l, lstart_d, lend_d);
-  if (acc) stamp_timer.end(st, sp2); else sev[3].record(st);
+  stamp_clock.stop(st);
 
-  int* out = static_cast<int*>(loss_slot(stamp_pin, (n_res + 1) * sizeof(int)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(out, lstart_d, n_res * sizeof(int), hipMemcpyDeviceToHost, st));
-  out[n_res] = 0;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + n_res, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  stamp_pin.used(st);
+  const int* out = static_cast<const int*>(guard.read_back(stamp_pin, lstart_d, n_res * sizeof(int), st));
   stamp_pin.wait();
-  if (out[n_res] != 0) { all_bad(); return; }
+  if (StatGuard::raised(out, n_res * sizeof(int))) { all_bad(); return; }
   const int* ls = out;
   const int* le = out + n_hyp;
   const float* ps = reinterpret_cast<const float*>(out + 2 * n_hyp);
 
   // words: runs of labels [a, b] with an id, per entry; then the confidences per utterance
-  const int* w_out = dout + n_hyp + 3 * NL;   // (unspaced mode: words, ends [NL][T], counts [NL])
   std::vector<int> wid((size_t)N * T), wb((size_t)N * T), we((size_t)N * T), wl(N);
   std::vector<double> zz(N), conf((size_t)N * T);
   const bool want_words = wstart_host || wend_host || wconf_host;   // (a caller after the label intervals alone pays for neither)
@@ -679,9 +533,9 @@ void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, in
         ++nw;
       };
       const int* h = hyp_h + i * T;
-      if (dec_mode == 0) {
+      if (tokens == 0) {
         for (int u = 0; u < U; ++u) word(h[u], u, u);
-      } else if (dec_mode == 1) {
+      } else if (tokens == 1) {
         const int want = dec_word_len[i];   // the runs between the space labels, whose frames belong to no word
         int first = 0;
         for (int u = 0; u <= U && U > 0; ++u) {
@@ -692,12 +546,12 @@ void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, in
         }
         EESEN_REQUIRE(nw == want, EESEN_ERR_STATE, "time stamps: the labelling's spaces do not match its words");
       } else {
-        const int want = w_out[2 * n_hyp + i];
+        const int want = dout[dec.wlen + i];
         int first = 0;
         for (int j = 0; j < want && j < T; ++j) {
-          const int end = w_out[n_hyp + i * T + j];
+          const int end = dout[dec.ends + i * T + j];
           EESEN_REQUIRE(end > first && end <= U, EESEN_ERR_STATE, "time stamps: word ends outside the labelling");
-          word(w_out[i * T + j], first, end - 1);
+          word(dout[dec.words + i * T + j], first, end - 1);
           first = end;
         }
       }
@@ -721,51 +575,26 @@ void Ctc::decode_stamps(const int* frame_num_utt, int S, const float* scores, in
 // upload_lattices does, into buffers of this call's own: labx, alpha and the last_* accessors of eval_parallel stay as they are.
 void Ctc::score_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* hyp_off,
                          const int* label_off, const int* label_ids, float* score_host) {
-  EESEN_REQUIRE(S > 0 && rows > 0 && rows % S == 0, EESEN_ERR_INVALID, "rows must be a positive multiple of the sequence count");
-  EESEN_REQUIRE(K > 0 && ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
+  check_shape(frame_num_utt, S, rows, K, ld, 0);
   const int T = rows / S;
   EESEN_REQUIRE(hyp_off[0] == 0, EESEN_ERR_INVALID, "hyp_off must start at 0");
-  for (int s = 0; s < S; ++s) {
-    EESEN_REQUIRE(frame_num_utt[s] >= 0 && frame_num_utt[s] <= T, EESEN_ERR_INVALID, "frame_num_utt out of range");
+  for (int s = 0; s < S; ++s)
     EESEN_REQUIRE(hyp_off[s + 1] >= hyp_off[s], EESEN_ERR_INVALID, "labelling offsets must be non-decreasing");
-  }
   const int NH = hyp_off[S];
-  constexpr int kMaxLabels = 2047;   // L' <= 4096
   int maxU = 0;
   for (int h = 0; h < NH; ++h) {
-    const int U = label_off[h + 1] - label_off[h];
-    EESEN_REQUIRE(U >= 0, EESEN_ERR_INVALID, "label offsets must be non-decreasing");
-    EESEN_REQUIRE(U <= kMaxLabels, EESEN_ERR_INVALID, "expanded label length above 4096 (2047 labels per labelling) is not supported");
-    maxU = std::max(maxU, U);
+    EESEN_REQUIRE(label_off[h + 1] >= label_off[h], EESEN_ERR_INVALID, "label offsets must be non-decreasing");
+    maxU = std::max(maxU, label_off[h + 1] - label_off[h]);
   }
+  const int Lpad = lattice_pad(maxU);
+  EESEN_REQUIRE(Lpad > 0, EESEN_ERR_INVALID, "expanded label length above 4096 (2047 labels per labelling) is not supported");
   if (NH > 0)
     for (int i = label_off[0]; i < label_off[NH]; ++i)
       EESEN_REQUIRE(label_ids[i] >= 1 && label_ids[i] < K, EESEN_ERR_INVALID, "label id outside [1, K)");
   if (NH == 0) return;
   EESEN_HIP_CHECK(hipSetDevice(device));
-  int PL = 1;
-  while (64 * PL < 2 * maxU + 1) PL *= 2;
-  const int Lpad = 64 * PL;
 
   const size_t n_labx = (size_t)NH * Lpad, n_in = n_labx + 3 * (size_t)NH, n_int = n_in + NH;
-  std::vector<int> hbuf(n_in);
-  int* labx_h = hbuf.data();
-  int* ll_h = labx_h + n_labx;
-  int* lens_h = ll_h + NH;
-  int* utt_h = lens_h + NH;
-  std::fill(labx_h, labx_h + n_labx, -1);
-  for (int s = 0; s < S; ++s) {
-    for (int h = hyp_off[s]; h < hyp_off[s + 1]; ++h) {
-      const int U = label_off[h + 1] - label_off[h];
-      const int* lab = label_ids + label_off[h];
-      int* lx = labx_h + (size_t)h * Lpad;
-      for (int l = 0; l < U; ++l) { lx[2 * l] = 0; lx[2 * l + 1] = lab[l]; }
-      lx[2 * U] = 0;
-      ll_h[h] = 2 * U + 1;
-      lens_h[h] = frame_num_utt[s];
-      utt_h[h] = s;
-    }
-  }
   if ((!is_log && logp.cap < (size_t)rows * K) || score_i.cap < n_int) EESEN_HIP_CHECK(hipStreamSynchronize(st));
   if (!is_log) logp.reserve((size_t)rows * K);
   score_i.reserve(n_int);
@@ -774,27 +603,25 @@ void Ctc::score_parallel(const int* frame_num_utt, int S, const float* scores, i
   int* lens_l = ll_d + NH;
   int* utt_d = lens_l + NH;
   float* score_d = reinterpret_cast<float*>(utt_d + NH);
-  PinBuf& sp = stage[stage_idx++ & 1];   // in stream order (see upload_lattices)
-  int* pinned = static_cast<int*>(loss_slot(sp, n_in * sizeof(int)));
-  std::copy(hbuf.begin(), hbuf.end(), pinned);
-  EESEN_HIP_CHECK(hipMemcpyAsync(labx_d, pinned, n_in * sizeof(int), hipMemcpyHostToDevice, st));
-  sp.used(st);
+  stage.upload(st, labx_d, n_in, [&](int* h) {   // every labelling's lattice, expanded length, frame count and utterance
+    for (int s = 0; s < S; ++s)
+      for (int q = hyp_off[s]; q < hyp_off[s + 1]; ++q) {
+        h[n_labx + q] = expand_labels(label_ids + label_off[q], label_off[q + 1] - label_off[q], h + (size_t)q * Lpad, Lpad);
+        h[n_labx + NH + q] = frame_num_utt[s];
+        h[n_labx + 2 * (size_t)NH + q] = s;
+      }
+  });
 
-  rev[0].record(st);
+  rescore_clock.mark(st, 0);
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
-  rev[1].record(st);
+  rescore_clock.mark(st, 1);
   ctc_score(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, NH, Lpad, labx_d, lens_l, ll_d, utt_d, score_d, sweep_waves);
-  rev[2].record(st);
+  rescore_clock.stop(st);
   rescore_host_s = 0;
 
-  float* out = static_cast<float*>(loss_slot(score_pin, ((size_t)NH + 1) * sizeof(float)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(out, score_d, (size_t)NH * sizeof(float), hipMemcpyDeviceToHost, st));
-  reinterpret_cast<unsigned*>(out)[NH] = 0;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + NH, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  score_pin.used(st);
+  const float* out = static_cast<const float*>(guard.read_back(score_pin, score_d, (size_t)NH * sizeof(float), st));
   score_pin.wait();
-  // computed from a timed-out forward pass (guard word set): NaN, never garbage with status OK
-  const bool bad = reinterpret_cast<const unsigned*>(out)[NH] != 0;
+  const bool bad = StatGuard::raised(out, (size_t)NH * sizeof(float));   // no scores: NaN
   if (score_host)
     for (int h = 0; h < NH; ++h) score_host[h] = bad ? std::numeric_limits<float>::quiet_NaN() : out[h];
 }
@@ -803,25 +630,23 @@ void Ctc::score_parallel(const int* frame_num_utt, int S, const float* scores, i
 // the device (ctc_hyp_lattices in its scoring form) and swept in one launch; the LM scores and the ranking are the host's.
 void Ctc::decode_rescore(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const TokenLm* lm,
                          float lm_weight, float bonus, bool use_eos, float* am_host, float* lm_host, float* total_host, int* order_host) {
-  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "rescoring: no decode call on this Ctc yet");
-  EESEN_REQUIRE(S == dec_S && rows == dec_rows, EESEN_ERR_STATE, "rescoring: S or rows differ from the last decode call's");
+  EESEN_REQUIRE(dec.rows > 0, EESEN_ERR_STATE, "rescoring: no decode call on this Ctc yet");
+  EESEN_REQUIRE(S == dec.S && rows == dec.rows, EESEN_ERR_STATE, "rescoring: S or rows differ from the last decode call's");
   EESEN_REQUIRE(K > 0 && ld >= K, EESEN_ERR_INVALID, "leading dimension smaller than the class count");
   EESEN_REQUIRE(std::isfinite(lm_weight) && std::isfinite(bonus), EESEN_ERR_INVALID, "lm_weight and bonus must be finite");
   if (lm) {
     EESEN_REQUIRE(!use_eos || lm->has_eos, EESEN_ERR_INVALID, "use_eos on an LM whose file has no </s>");
-    if (dec_mode == 0) EESEN_REQUIRE(lm->K == K, EESEN_ERR_INVALID, "the rescoring LM was built for another class count K than the scores have");
+    if (dec_tokens() == 0) EESEN_REQUIRE(lm->K == K, EESEN_ERR_INVALID, "the rescoring LM was built for another class count K than the scores have");
     else EESEN_REQUIRE(lm->K == dec_V + 1, EESEN_ERR_INVALID, "the rescoring word LM's K must be the lexicon's word count + 1");
   }
   for (int s = 0; s < S; ++s)
     EESEN_REQUIRE(frame_num_utt[s] == dec_lens[s], EESEN_ERR_STATE, "rescoring: frame_num_utt differs from the last decode call's");
   EESEN_HIP_CHECK(hipSetDevice(device));
-  const int T = dec_T, N = dec_N;
-  const size_t NL = (size_t)S * N, n_hyp = NL * T;
-  const size_t n_dec = dec_mode == 2 ? 3 * n_hyp + 4 * NL : n_hyp + (dec_fused ? 3 : 2) * NL;
+  const int T = dec.T, N = dec.N, tokens = dec_tokens();
+  const size_t NL = dec.NL;
   const int* dout = decode_pin.as<int>();
-  const int* hyp_h = dout;
-  const int* hlen = dout + n_hyp;
-  const float* z = reinterpret_cast<const float*>(hlen + NL);   // totals, then (fused) the LM sums
+  const int* hlen = dout + dec.len;
+  const float* lmsum = reinterpret_cast<const float*>(dout) + dec.lmsum;   // (fused: the first pass's LM sums)
   const float kNaN = std::numeric_limits<float>::quiet_NaN();
   auto all_bad = [&] {   // decoded or scored from a timed-out forward pass (guard word set): NaN and -1, never garbage with status OK
     if (am_host) std::fill(am_host, am_host + NL, kNaN);
@@ -829,15 +654,12 @@ void Ctc::decode_rescore(const int* frame_num_utt, int S, const float* scores, i
     if (total_host) std::fill(total_host, total_host + NL, kNaN);
     if (order_host) std::fill(order_host, order_host + NL, -1);
   };
-  if (dout[n_dec] != 0) { all_bad(); return; }
+  if (StatGuard::raised(dout, dec.n_out * sizeof(int))) { all_bad(); return; }
 
-  constexpr int kMaxLabels = 2047;   // L' <= 4096; an entry beyond has no lattice (ctc_hyp_lattices) and reads as infeasible
-  int maxU = 0;
+  int maxU = 0;   // (an entry beyond kMaxLatticeLabels has no lattice (ctc_hyp_lattices) and reads as infeasible)
   for (size_t i = 0; i < NL; ++i)
-    if (hlen[i] <= kMaxLabels) maxU = std::max(maxU, hlen[i]);
-  int PL = 1;
-  while (64 * PL < 2 * maxU + 1) PL *= 2;
-  const int Lpad = 64 * PL;
+    if (hlen[i] <= kMaxLatticeLabels) maxU = std::max(maxU, hlen[i]);
+  const int Lpad = lattice_pad(maxU);
   const size_t n_int = NL * Lpad + 4 * NL;
   if ((!is_log && logp.cap < (size_t)rows * K) || score_i.cap < n_int) EESEN_HIP_CHECK(hipStreamSynchronize(st));
   if (!is_log) logp.reserve((size_t)rows * K);
@@ -847,25 +669,19 @@ void Ctc::decode_rescore(const int* frame_num_utt, int S, const float* scores, i
   int* lens_l = ll_d + NL;
   int* utt_d = lens_l + NL;
   float* score_d = reinterpret_cast<float*>(utt_d + NL);
-  const int* lens_d = dec_i.p + (size_t)dec_rows * dec_C;
 
-  rev[0].record(st);
+  rescore_clock.mark(st, 0);
   if (!is_log) log_rows(st, scores, ld, logp.p, K, rows, K);
-  ctc_hyp_lattices(st, dec_out.p, dec_out.p + n_hyp, lens_d, T, (int)NL, N, Lpad, labx_d, ll_d, lens_l, utt_d);
-  rev[1].record(st);
+  ctc_hyp_lattices(st, dec_out.p + dec.hyp, dec_out.p + dec.len, dec_i.p + dec.lens, T, (int)NL, N, Lpad, labx_d, ll_d, lens_l, utt_d);
+  rescore_clock.mark(st, 1);
   ctc_score(st, is_log ? scores : logp.p, is_log ? ld : K, T, S, (int)NL, Lpad, labx_d, lens_l, ll_d, utt_d, score_d, sweep_waves);
-  rev[2].record(st);
+  rescore_clock.stop(st);
 
-  float* out = static_cast<float*>(loss_slot(score_pin, (NL + 1) * sizeof(float)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(out, score_d, NL * sizeof(float), hipMemcpyDeviceToHost, st));
-  reinterpret_cast<unsigned*>(out)[NL] = 0;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(out + NL, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  score_pin.used(st);
+  const float* out = static_cast<const float*>(guard.read_back(score_pin, score_d, NL * sizeof(float), st));
   score_pin.wait();
-  if (reinterpret_cast<const unsigned*>(out)[NL] != 0) { all_bad(); return; }
+  if (StatGuard::raised(out, NL * sizeof(float))) { all_bad(); return; }
 
   const auto t0 = std::chrono::steady_clock::now();
-  const int* w_out = dout + n_hyp + 3 * NL;   // (unspaced mode: words, ends [NL][T], counts [NL])
   std::vector<float> tot(N);
   std::vector<int> ord(N);
   for (int s = 0; s < S; ++s) {
@@ -878,9 +694,9 @@ void Ctc::decode_rescore(const int* frame_num_utt, int S, const float* scores, i
       float g32 = -1e30f;
       tot[r] = -1e30f;
       if (feasible) {
-        const int* tok = dec_mode == 0 ? hyp_h + i * T : dec_mode == 1 ? dec_word.data() + i * T : w_out + i * T;
-        const int n = dec_mode == 0 ? U : dec_mode == 1 ? dec_word_len[i] : w_out[2 * n_hyp + i];
-        const double g = lm ? lm->score(tok, n, use_eos, nullptr) : dec_fused ? (double)z[NL + i] : 0.0;
+        const int* tok = tokens == 0 ? dout + dec.hyp + i * T : tokens == 1 ? dec_word.data() + i * T : dout + dec.words + i * T;
+        const int n = tokens == 0 ? U : tokens == 1 ? dec_word_len[i] : dout[dec.wlen + i];
+        const double g = lm ? lm->score(tok, n, use_eos, nullptr) : dec.fused() ? (double)lmsum[i] : 0.0;
         g32 = (float)g;
         tot[r] = (float)((double)a + (double)lm_weight * g + (double)bonus * n);
         ord[nf++] = r;
@@ -900,22 +716,11 @@ void Ctc::decode_rescore(const int* frame_num_utt, int S, const float* scores, i
   rescore_host_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-void Ctc::rescore_times(float* out3) {
-  rev[2].wait();
-  for (int i = 0; i < 2; ++i) {
-    float ms = 0.f;
-    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, rev[i], rev[i + 1]));
-    out3[i] = ms * 1e-3f;
-  }
-  out3[2] = (float)rescore_host_s;
-}
-
 namespace {
 double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 }  // namespace
 
 const int* Ctc::ed_run(const int* tok_h, size_t n_tok, const int* dev_tok, const std::vector<int>& jobs, size_t n_same, int max_len, bool* bad) {
-  const bool guarded = bad != nullptr && guard.word != nullptr;   // (bad == null: the tokens are the caller's, no forward pass to guard)
   const auto t0 = std::chrono::steady_clock::now();
   const size_t nj = jobs.size() / 4, n_in = n_tok + 4 * nj, n_all = n_in + nj;
   EESEN_REQUIRE(n_all < ((size_t)1 << 31), EESEN_ERR_INVALID, "edit distances: more than 2^31 tokens and jobs in one call");
@@ -925,14 +730,11 @@ const int* Ctc::ed_run(const int* tok_h, size_t n_tok, const int* dev_tok, const
   int* tok_d = ed_i.p;
   int* jobs_d = tok_d + n_tok;
   int* out_d = jobs_d + 4 * nj;
-  if (n_in > 0) {
-    PinBuf& sp = stage[stage_idx++ & 1];   // in stream order (see upload_lattices)
-    int* pinned = static_cast<int*>(loss_slot(sp, n_in * sizeof(int)));
-    if (n_tok > 0) std::copy(tok_h, tok_h + n_tok, pinned);
-    std::copy(jobs.begin(), jobs.end(), pinned + n_tok);
-    EESEN_HIP_CHECK(hipMemcpyAsync(tok_d, pinned, n_in * sizeof(int), hipMemcpyHostToDevice, st));
-    sp.used(st);
-  }
+  if (n_in > 0)
+    stage.upload(st, tok_d, n_in, [&](int* pinned) {
+      if (n_tok > 0) std::copy(tok_h, tok_h + n_tok, pinned);
+      std::copy(jobs.begin(), jobs.end(), pinned + n_tok);
+    });
   const double build_s = seconds_since(t0);
   if (nj > 0) {
     const int* first = dev_tok ? dev_tok : tok_d;
@@ -945,12 +747,10 @@ const int* Ctc::ed_run(const int* tok_h, size_t n_tok, const int* dev_tok, const
     }
     mev[1].record(st);
   }
-  int* out = static_cast<int*>(loss_slot(ed_pin, (nj + 1) * sizeof(int)));
-  if (nj > 0) EESEN_HIP_CHECK(hipMemcpyAsync(out, out_d, nj * sizeof(int), hipMemcpyDeviceToHost, st));
-  out[nj] = 0;
-  if (guarded) EESEN_HIP_CHECK(hipMemcpyAsync(out + nj, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  if (nj > 0 || guarded) { ed_pin.used(st); ed_pin.wait(); }
-  if (bad) *bad = out[nj] != 0;
+  // (bad == null: the tokens are the caller's, no forward pass to guard)
+  const int* out = static_cast<const int*>(guard.read_back(ed_pin, out_d, nj * sizeof(int), st, bad != nullptr));
+  ed_pin.wait();
+  if (bad) *bad = StatGuard::raised(out, nj * sizeof(int));
   float ms = 0.f;
   if (nj > 0) EESEN_HIP_CHECK(hipEventElapsedTime(&ms, mev[0], mev[1]));
   mbr_t[0] += build_s;
@@ -1032,8 +832,8 @@ void Ctc::edit_distance_parallel(int G, const int* seq_off, const int* tok_off, 
 void Ctc::decode_mbr(int S, int level, double scale, const float* total_host, const int* ref_off, const int* ref_ids, int* dist_host,
                      int* ref_dist_host, double* post_host, double* risk_host, int* order_host) {
   const auto t0 = std::chrono::steady_clock::now();
-  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "MBR: no decode call on this Ctc yet");
-  EESEN_REQUIRE(S == dec_S, EESEN_ERR_STATE, "MBR: S differs from the last decode call's");
+  EESEN_REQUIRE(dec.rows > 0, EESEN_ERR_STATE, "MBR: no decode call on this Ctc yet");
+  EESEN_REQUIRE(S == dec.S, EESEN_ERR_STATE, "MBR: S differs from the last decode call's");
   EESEN_REQUIRE(level == 0 || level == 1, EESEN_ERR_INVALID, "MBR: level must be 0 (LM tokens) or 1 (labels)");
   EESEN_REQUIRE(std::isfinite(scale) && scale >= 0, EESEN_ERR_INVALID, "MBR: scale must be finite and >= 0");
   const bool refs = ref_off != nullptr;
@@ -1048,13 +848,11 @@ void Ctc::decode_mbr(int S, int level, double scale, const float* total_host, co
     EESEN_REQUIRE(ref_off[S] == ref_off[0] || ref_ids != nullptr, EESEN_ERR_INVALID, "ref_ids is null");
   }
   if (!mbr_accumulate) mbr_t[0] = mbr_t[1] = mbr_t[2] = 0;
-  const int T = dec_T, N = dec_N;
-  const size_t NL = (size_t)S * N, n_hyp = NL * T;
-  const size_t n_dec = dec_mode == 2 ? 3 * n_hyp + 4 * NL : n_hyp + (dec_fused ? 3 : 2) * NL;
+  const int T = dec.T, N = dec.N;
+  const size_t NL = dec.NL;
   const int* dout = decode_pin.as<int>();
-  const int* hlen = dout + n_hyp;
-  const float* z32 = total_host ? total_host : reinterpret_cast<const float*>(hlen + NL);
-  const int* w_out = dout + n_hyp + 3 * NL;   // (unspaced mode: words, ends [NL][T], counts [NL])
+  const int* hlen = dout + dec.len;
+  const float* z32 = total_host ? total_host : reinterpret_cast<const float*>(dout) + dec.score;
   const double kNaN = std::numeric_limits<double>::quiet_NaN();
   auto all_bad = [&] {   // decoded from a timed-out forward pass (guard word set): -1 and NaN, never garbage with status OK
     if (dist_host) std::fill(dist_host, dist_host + NL * N, -1);
@@ -1063,14 +861,14 @@ void Ctc::decode_mbr(int S, int level, double scale, const float* total_host, co
     if (risk_host) std::fill(risk_host, risk_host + NL, kNaN);
     if (order_host) std::fill(order_host, order_host + NL, -1);
   };
-  if (dout[n_dec] != 0) { all_bad(); return; }
+  if (StatGuard::raised(dout, dec.n_out * sizeof(int))) { all_bad(); return; }
 
   // every entry's tokens: where they are and how many; the entries that count
-  const int kind = level == 1 ? 0 : dec_mode;   // 0 labels, 1 the spaced mode's words, 2 the unspaced mode's
+  const int kind = level == 1 ? 0 : dec_tokens();   // 0 labels, 1 the spaced mode's words, 2 the unspaced mode's
   std::vector<int> off(NL), len(NL), tok;       // (tok: the uploaded tokens -- the spaced mode's words, then the references)
   std::vector<char> counts(NL);
   for (size_t i = 0; i < NL; ++i) {
-    const int n = hlen[i] < 0 ? -1 : kind == 0 ? hlen[i] : kind == 1 ? dec_word_len[i] : w_out[2 * n_hyp + i];
+    const int n = hlen[i] < 0 ? -1 : kind == 0 ? hlen[i] : kind == 1 ? dec_word_len[i] : dout[dec.wlen + i];
     const float z = z32[i];
     counts[i] = n >= 0 && n <= kEditDistanceMaxLen && z > -1e29f && !std::isnan(z);
     len[i] = n;
@@ -1078,12 +876,12 @@ void Ctc::decode_mbr(int S, int level, double scale, const float* total_host, co
       off[i] = (int)tok.size();
       if (counts[i]) tok.insert(tok.end(), dec_word.begin() + i * T, dec_word.begin() + i * T + n);
     } else {
-      EESEN_REQUIRE(i * T + (kind == 2 ? n_hyp + 3 * NL : 0) < ((size_t)1 << 31), EESEN_ERR_INVALID, "MBR: hypothesis buffer beyond 2^31 ints");
+      EESEN_REQUIRE(i * T + (kind == 2 ? dec.words : 0) < ((size_t)1 << 31), EESEN_ERR_INVALID, "MBR: hypothesis buffer beyond 2^31 ints");
       off[i] = (int)(i * T);
     }
     if (counts[i]) max_len = std::max(max_len, n);
   }
-  const int* dev_tok = kind == 0 ? dec_out.p : kind == 2 ? dec_out.p + n_hyp + 3 * NL : nullptr;
+  const int* dev_tok = kind == 0 ? dec_out.p + dec.hyp : kind == 2 ? dec_out.p + dec.words : nullptr;
   const int ref_base = (int)tok.size();
   if (refs && ref_off[S] > ref_off[0]) tok.insert(tok.end(), ref_ids + ref_off[0], ref_ids + ref_off[S]);
   const bool need_pairs = dist_host || risk_host || order_host, need_ref = refs && ref_dist_host;
@@ -1159,40 +957,19 @@ void Ctc::mbr_times(float* out3) {
   if (mbr_accumulate) mbr_t[0] = mbr_t[1] = mbr_t[2] = 0;
 }
 
-void Ctc::stamp_times(float* out3) {
-  if (stamp_timer.enabled()) { stamp_timer.collect(out3, 3); return; }
-  sev[3].wait();
-  for (int i = 0; i < 3; ++i) {
-    float ms = 0.f;
-    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, sev[i], sev[i + 1]));
-    out3[i] = ms * 1e-3f;
-  }
-}
-
-void Ctc::decode_times(float* out3) {
-  if (decode_timer.enabled()) { decode_timer.collect(out3, 3); return; }
-  dev[3].wait();
-  for (int i = 0; i < 3; ++i) {
-    float ms = 0.f;
-    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, dev[i], dev[i + 1]));
-    out3[i] = ms * 1e-3f;
-  }
-}
-
 void Ctc::get_decode_candidates(int* ids_host, float* scores_host, float* blank_host, int* Cc) {
-  EESEN_REQUIRE(dec_rows > 0, EESEN_ERR_STATE, "no DecodeParallel yet");
+  EESEN_REQUIRE(dec.rows > 0, EESEN_ERR_STATE, "no DecodeParallel yet");
   EESEN_HIP_CHECK(hipSetDevice(device));
   EESEN_HIP_CHECK(hipStreamSynchronize(st));
-  const size_t n_cand = (size_t)dec_rows * dec_C;
-  if (Cc) *Cc = dec_C;
-  if (ids_host) EESEN_HIP_CHECK(hipMemcpy(ids_host, dec_i.p, n_cand * sizeof(int), hipMemcpyDeviceToHost));
-  if (scores_host) EESEN_HIP_CHECK(hipMemcpy(scores_host, dec_f.p, n_cand * sizeof(float), hipMemcpyDeviceToHost));
-  if (blank_host) EESEN_HIP_CHECK(hipMemcpy(blank_host, dec_f.p + n_cand, (size_t)dec_rows * sizeof(float), hipMemcpyDeviceToHost));
-  for (int r = 0; r < dec_rows; ++r) {   // rows the selection never visits
-    if (r / dec_S < dec_lens[r % dec_S]) continue;
-    for (int c = 0; c < dec_C; ++c) {
-      if (ids_host) ids_host[(size_t)r * dec_C + c] = -1;
-      if (scores_host) scores_host[(size_t)r * dec_C + c] = -1e30f;
+  if (Cc) *Cc = dec.C;
+  if (ids_host) EESEN_HIP_CHECK(hipMemcpy(ids_host, dec_i.p + dec.cid, dec.n_cand * sizeof(int), hipMemcpyDeviceToHost));
+  if (scores_host) EESEN_HIP_CHECK(hipMemcpy(scores_host, dec_f.p + dec.csc, dec.n_cand * sizeof(float), hipMemcpyDeviceToHost));
+  if (blank_host) EESEN_HIP_CHECK(hipMemcpy(blank_host, dec_f.p + dec.sblank, (size_t)dec.rows * sizeof(float), hipMemcpyDeviceToHost));
+  for (int r = 0; r < dec.rows; ++r) {   // rows the selection never visits
+    if (r / dec.S < dec_lens[r % dec.S]) continue;
+    for (int c = 0; c < dec.C; ++c) {
+      if (ids_host) ids_host[(size_t)r * dec.C + c] = -1;
+      if (scores_host) scores_host[(size_t)r * dec.C + c] = -1e30f;
     }
     if (blank_host) blank_host[r] = -1e30f;
   }
@@ -1246,7 +1023,7 @@ void Ctc::flush_err(PendingErr& q, int* num_err, int* num_ref) {
   const int* ids = q.pin.as<int>();
   const int S = q.S;
   int err = 0, ref = 0;
-  if (q.guarded && ids[(size_t)q.rows] != 0) {  // decoded from a timed-out forward pass (see StatGuard): not a statistic
+  if (StatGuard::raised(ids, (size_t)q.rows * sizeof(int))) {  // decoded from a timed-out forward pass (see StatGuard): not a statistic
     if (q.with_probs) q.probs.wait();
     if (num_err) *num_err = 0;
     if (num_ref) *num_ref = 0;
@@ -1292,19 +1069,15 @@ void Ctc::flush_err(PendingErr& q, int* num_err, int* num_ref) {
 // the device is busy with the backward pass, so neither side waits for the other.
 void Ctc::error_rate_mseq(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld,
                           const int* label_ids, const int* label_off, int* num_err, int* num_ref) {
-  check_batch(frame_num_utt, S, rows, K, label_ids, label_off);
+  check_batch(frame_num_utt, S, rows, K, /*ld=*/K, label_ids, label_off);   // (the argmax takes any stride)
   EESEN_HIP_CHECK(hipSetDevice(device));
   if (ids_d.cap < (size_t)rows) EESEN_HIP_CHECK(hipStreamSynchronize(st));
   ids_d.reserve(rows);
   PendingErr& q = perr[perr_idx++ & 1];
   flush_err(q, nullptr, nullptr);
   row_argmax(st, net_out, ld, rows, K, ids_d.p);  // FindRowMaxId, ctc-loss.cc:238-239
-  int* pinned = static_cast<int*>(loss_slot(q.pin, ((size_t)rows + 1) * sizeof(int)));
-  EESEN_HIP_CHECK(hipMemcpyAsync(pinned, ids_d.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, st));
-  pinned[rows] = 0;
-  q.rows = rows; q.guarded = guard.word != nullptr;
-  if (guard.word) EESEN_HIP_CHECK(hipMemcpyAsync(pinned + rows, guard.word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-  q.pin.used(st);
+  guard.read_back(q.pin, ids_d.p, (size_t)rows * sizeof(int), st);
+  q.rows = rows;
   q.S = S; q.K = K; q.active = true;
   q.with_probs = !seq_out.empty();
   if (q.with_probs) {  // "This is inefficient, but ok for now" (ctc-loss.cc:283): the whole posterior matrix comes back

@@ -53,6 +53,26 @@ int PhaseTimer::spans(int* phases, float* secs, int cap) {
   return (int)used_;
 }
 
+// ------------------------------------------------------------------------------------------ PhaseClock
+void PhaseClock::mark(hipStream_t st, int phase) {
+  phase_ = phase;
+  if (!spans_.enabled()) { ev_[phase].record(st); return; }
+  if (phase > 0) spans_.end(st, span_);
+  span_ = spans_.begin(st, phase);
+}
+void PhaseClock::stop(hipStream_t st) {
+  if (spans_.enabled()) spans_.end(st, span_); else ev_[phase_ + 1].record(st);
+}
+void PhaseClock::read(float* out, int nphase) {
+  if (spans_.enabled()) { spans_.collect(out, nphase); return; }   // sums since the last read
+  ev_[nphase].wait();
+  for (int i = 0; i < nphase; ++i) {
+    float ms = 0.f;
+    EESEN_HIP_CHECK(hipEventElapsedTime(&ms, ev_[i], ev_[i + 1]));
+    out[i] = ms * 1e-3f;
+  }
+}
+
 // ------------------------------------------------------------------------------------------ Layer
 long Layer::file_params() const {
   if (is_lstm()) return (long)ndir * ((long)4 * Hf * din_f + (long)4 * Hf * Hf + 4 * Hf + 3 * Hf);  // bilstm-layer.h:991-998
@@ -206,6 +226,22 @@ void StatGuard::unhook() {
   if (net) net->guards.erase(std::remove(net->guards.begin(), net->guards.end(), this), net->guards.end());
   word = nullptr;
   net = nullptr;
+}
+
+void* StatGuard::read_back(PinBuf& pin, const void* dev, size_t bytes, hipStream_t stream, bool guarded) {
+  char* host = static_cast<char*>(loss_slot(pin, bytes + sizeof(unsigned)));
+  if (bytes) EESEN_HIP_CHECK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, stream));
+  std::memset(host + bytes, 0, sizeof(unsigned));   // the guard word's value when these results were computed
+  guarded = guarded && word;
+  if (guarded) EESEN_HIP_CHECK(hipMemcpyAsync(host + bytes, word, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+  if (bytes || guarded) pin.used(stream);   // (nothing enqueued: nothing to wait for)
+  return host;
+}
+
+bool StatGuard::raised(const void* host, size_t bytes) {
+  unsigned w;
+  std::memcpy(&w, static_cast<const char*>(host) + bytes, sizeof w);
+  return w != 0;
 }
 
 void StatGuard::note_dropped(const char* what) {

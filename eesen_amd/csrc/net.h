@@ -3,6 +3,7 @@
 #include <string>
 #include <vector>
 
+#include "ctc_layout.h"
 #include "kernels.h"
 #include "lex.h"
 #include "lm.h"
@@ -84,6 +85,22 @@ class PhaseTimer {
   bool on_ = false, accumulate_ = false;
 };
 
+// The phase times of one entry point of a loss object, in the two modes of eesen_ctc_set_profiling / eesen_ce_set_profiling.  The
+// last call's (the default): one event per phase boundary, adjacent phases share one.  Accumulating (mode 2): a begin / end pair per
+// phase, summed over the calls since the last read and cleared by it -- no synchronisation per call.
+class PhaseClock {
+ public:
+  static constexpr int kMaxPhases = 3;
+  void set_mode(bool accumulate) { spans_.enable(accumulate); spans_.set_accumulate(accumulate); }
+  void mark(hipStream_t st, int phase);  // `phase` starts here (0 first, then in order); the one before it ends
+  void stop(hipStream_t st);             // the last phase ends
+  void read(float* out, int nphase);     // seconds per phase; waits for the recorded events
+ private:
+  DevEvent ev_[kMaxPhases + 1] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};
+  PhaseTimer spans_;
+  int phase_ = 0, span_ = -1;
+};
+
 struct Comm;  // comm.cpp: RCCL communicator (one rank per GPU)
 void comm_check_alive(const Comm* c);  // throws EESEN_ERR_COMM once the communicator's watchdog has aborted it (null: no-op)
 constexpr size_t kLiveWords = 4;       // floats behind the gradient buffer: [0] = the data-parallel liveness word (comm.cpp)
@@ -108,6 +125,12 @@ struct StatGuard {
   void hook(struct Net* n, int device, hipStream_t stream, const char* entry_point);   // n == nullptr: only unhooks
   void unhook();
   void note_dropped(const char* what);   // counts, and warns at the first and every hundredth
+  // A result's way back: `bytes` at `dev` into `pin` in stream order, a zero word behind them and -- hooked, and unless the caller
+  // opts out -- the guard word's value of that moment copied over it.  Returns the host block; pin.wait() before it is read.
+  void* read_back(PinBuf& pin, const void* dev, size_t bytes, hipStream_t stream, bool guarded = true);
+  // Was the word raised behind the `bytes` of a block read_back returned?  Then they were computed from a timed-out forward pass:
+  // NaN / -1 for the caller and nothing for the statistics, never garbage with status OK.
+  static bool raised(const void* host, size_t bytes);
 };
 
 struct Net {
@@ -264,6 +287,25 @@ struct Net {
 // a staging / result slot of the loss objects: twice what is asked for when it has to grow, at least a page
 inline void* loss_slot(PinBuf& pin, size_t bytes) { return pin.reserve(bytes, std::max<size_t>(bytes * 2, 4096)); }
 
+// Staging of the loss objects' small inputs (labels, lengths, targets): n ints, written by fill(pinned), to `dst` on the device through
+// two alternating pinned slots.  The upload is stream-ordered: kernels of the previous call that still read `dst` are ahead of this
+// copy on the stream, and the slot written here was last read by the copy of two calls ago -- nothing drains the stream.
+struct StageSlots {
+  PinBuf slot[2];
+  unsigned idx = 0;
+  template <class Fill> void upload(hipStream_t st, int* dst, size_t n, Fill&& fill) {
+    PinBuf& sp = slot[idx++ & 1];
+    int* pinned = static_cast<int*>(loss_slot(sp, n * sizeof(int)));
+    fill(pinned);
+    EESEN_HIP_CHECK(hipMemcpyAsync(dst, pinned, n * sizeof(int), hipMemcpyHostToDevice, st));
+    sp.used(st);
+  }
+};
+
+// The shape every entry point of the loss objects takes: rows = T * S, ld >= K, 0 <= frame_num_utt[s] <= T.  min_K: 2 the decoder, 1 the
+// losses and the alignment, 0 the callers that refuse K <= 0 as a short leading dimension.
+void check_shape(const int* frame_num_utt, int S, int rows, int K, int ld, int min_K);
+
 struct Ctc {
   int device = 0;
   hipStream_t st = nullptr;
@@ -274,34 +316,31 @@ struct Ctc {
   int sweep_waves = 0;   // EESEN_CTC_WAVES when this object was created (tuning.h): 0 = the default number of waves per lattice
   double obj_sum = 0;
   long sequences = 0, frames = 0, err_tokens = 0, ref_tokens = 0;
-  DevEvent ev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};   // phase_times without the timer
-  PhaseTimer timer;  // eesen_ctc_set_profiling(2): spans accumulate over many calls, read once (no per-call synchronisation)
-  DevEvent aev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};  // align_times without the timer
-  PhaseTimer align_timer;      // the same for align_parallel (phases: log, sweep, traceback)
+  PhaseClock clock;            // eval_parallel (phases: log, alpha / beta, error signal)
+  PhaseClock align_clock;      // align_parallel (phases: log, sweep, traceback)
   PinBuf align_pin;            // results of align_parallel (D2H)
   // decode_parallel (ctc_decode.hip): candidates of every frame and the final beam (floats, ints), the trie, the hypotheses
   DevBuf<float> dec_f;
   DevBuf<int> dec_i, dec_trie, dec_out;
-  DevEvent dev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};  // decode_times without the timer
-  PhaseTimer decode_timer;     // phases: top-C (with the logarithm), beam, hypotheses
-  PinBuf decode_pin;           // results of decode_parallel (D2H)
-  int dec_rows = 0, dec_S = 0, dec_C = 0;   // shape of the candidates the last decode_parallel left (get_decode_candidates)
+  PhaseClock decode_clock;     // phases: top-C (with the logarithm), beam, hypotheses
+  PinBuf decode_pin;           // results of decode_parallel (D2H): dec_out as it is, then the guard word
+  // What the last decode call left for get_decode_candidates, decode_stamps, decode_rescore and decode_mbr: where everything is (dec),
+  // the candidates in dec_f / dec_i, the hypotheses in dec_out (device) and in decode_pin (host), until the next decode call.
+  DecodeLayout dec;
   std::vector<int> dec_lens;
-  // What the last decode call left for decode_stamps: its hypotheses stay in dec_out (device) and in decode_pin (host) until the next
-  // decode call.  dec_mode: 0 labels are words (plain, token LM), 1 spaced lexicon (the words in dec_word / dec_word_len: the
-  // lexicon may be gone by then), 2 unspaced lexicon (words and word ends in the pinned results).
-  int dec_N = 0, dec_T = 0, dec_mode = 0, dec_space = -1;
-  bool dec_fused = false;
+  int dec_space = -1;          // the space class of a spaced lexicon, -1 in every other mode
+  // whose ids the LM tokens of an entry are: 0 its labels (plain, token LM), 1 a spaced lexicon's words (in dec_word / dec_word_len:
+  // the lexicon may be gone by then), 2 an unspaced lexicon's (words and word ends in dec_out)
+  int dec_tokens() const { return dec.mode == kDecodeWords ? 2 : dec_space >= 0 ? 1 : 0; }
   std::vector<int> dec_word, dec_word_len;   // [S * N * T], [S * N]
   DevBuf<int> stamp_i;         // decode_stamps: lattices, per-lattice lengths, positions, then the results (label starts, ends, path scores)
-  DevEvent sev[4] = {DevEvent(true), DevEvent(true), DevEvent(true), DevEvent(true)};  // stamp_times without the timer
-  PhaseTimer stamp_timer;      // phases: lattice build (with the logarithm), sweep + traceback, stamps
+  PhaseClock stamp_clock;      // phases: lattice build (with the logarithm), sweep + traceback, stamps
   PinBuf stamp_pin;            // results of decode_stamps (D2H)
   int stamp_group = 0;         // eesen_ctc_set_stamp_group: lattices per sweep launch, 0 = as many as kStampDeltaBytes holds (tuning.h)
   // score_parallel / decode_rescore (INTEGRATION.md "Rescoring"): lattices, expanded-label lengths, frame counts and utterance of
   // every lattice, then the scores.  Nothing else: the scoring sweep keeps no row
   DevBuf<int> score_i;
-  DevEvent rev[3] = {DevEvent(true), DevEvent(true), DevEvent(true)};   // rescore_times: lattice build (+ log), sweep
+  PhaseClock rescore_clock;    // rescore_times: lattice build (+ log), sweep; always the last call's
   double rescore_host_s = 0;   // ... and the host's LM scoring and ranking of the last decode_rescore
   PinBuf score_pin;            // results of the scoring sweep (D2H)
   int dec_V = 0;               // the lexicon's word count of the last decode call (0: none): what a second word LM must fit
@@ -329,10 +368,9 @@ struct Ctc {
   // Nothing in a training step has to stall the host: label staging goes through two alternating PinBufs, and the
   // per-sequence ln p / the greedy-decode ids of a call whose caller did not ask for them (NULL result pointers) come
   // back through PinBufs that are folded into the statistics at the next call that needs them ("deferred").
-  PinBuf stage[2];             // label expansion + class position lists (H2D)
-  unsigned stage_idx = 0;
+  StageSlots stage;            // label expansion, lengths, tokens and jobs (H2D)
   struct PendingPzx { PinBuf pin; int S = 0; long nframes = 0; bool active = false; } ppzx[2];
-  struct PendingErr { PinBuf pin, probs; int S = 0, K = 0, rows = 0; bool active = false, with_probs = false, guarded = false; std::vector<int> frames, ids, off; } perr[2];
+  struct PendingErr { PinBuf pin, probs; int S = 0, K = 0, rows = 0; bool active = false, with_probs = false; std::vector<int> frames, ids, off; } perr[2];
   StatGuard guard;             // eesen_ctc_set_guard
   std::string seq_out;         // --sequence-out-file of the trainer (ctc-loss.cc:247-250,282-291): decoded sequences are appended here
   unsigned ppzx_idx = 0, perr_idx = 0;
@@ -347,11 +385,12 @@ struct Ctc {
   void error_rate_mseq(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld,
                        const int* label_ids, const int* label_off, int* num_err, int* num_ref);
   void get_alpha_beta(float* alpha_host, float* beta_host, int* Lprime);
-  void phase_times(float* out3);
+  void set_profiling(int mode);   // eesen_ctc_set_profiling: 2 = the phase clocks and the MBR times accumulate until they are read
+  void phase_times(float* out3) { clock.read(out3, 3); }
   // Best-path alignment (ctc_best_path + ctc_traceback in ctc.hip); touches neither the objective nor the error statistics.
   void align_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const int* label_ids,
                       const int* label_off, int* ali_host, int* pos_host, float* score_host);
-  void align_times(float* out3);
+  void align_times(float* out3) { align_clock.read(out3, 3); }
   // Prefix beam search over the posteriors (ctc_row_topc + ctc_prefix_beam + ctc_hyp in ctc_decode.hip); touches neither the
   // objective nor the error statistics, and none of the buffers of eval_parallel / align_parallel but `logp`.
   void decode_parallel(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
@@ -371,13 +410,13 @@ struct Ctc {
   void decode_parallel_words(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
                              int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float word_bonus, bool use_eos, int* hyp_host,
                              int* hyp_len_host, float* score_host, float* lm_score_host, int* word_host, int* word_len_host, int* word_end_host);
-  void decode_times(float* out3);
+  void decode_times(float* out3) { decode_clock.read(out3, 3); }
   // Time stamps and confidences of the last decode call's entries (INTEGRATION.md "Time stamps and CTM"): ctc_hyp_lattices, then
   // ctc_best_path + ctc_traceback over all S * nbest lattices in groups, then ctc_stamp; words and confidences on the host.
   // lstart / lend / wstart / wend (int) and wconf (float) [S][nbest][T], path_score [S][nbest]; any may be null.
   void decode_stamps(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, double conf_scale,
                      int* lstart_host, int* lend_host, int* wstart_host, int* wend_host, float* wconf_host, float* path_score_host);
-  void stamp_times(float* out3);
+  void stamp_times(float* out3) { stamp_clock.read(out3, 3); }
   // Exact log-scores ln p(labels | x) (INTEGRATION.md "Rescoring"; ctc_score in ctc.hip): utterance s has the labellings
   // hyp_off[s] .. hyp_off[s + 1], labelling h the labels label_ids[label_off[h] .. label_off[h + 1]) (none: the empty labelling).
   // Touches neither the statistics nor the lattices of the last eval_parallel; the logarithms borrow `logp`.
@@ -388,7 +427,7 @@ struct Ctc {
   // any may be null.  Leaves what the decode call left untouched.
   void decode_rescore(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, const TokenLm* lm,
                       float lm_weight, float bonus, bool use_eos, float* am_host, float* lm_host, float* total_host, int* order_host);
-  void rescore_times(float* out3);
+  void rescore_times(float* out3) { rescore_clock.read(out3, 2); out3[2] = (float)rescore_host_s; }
   // Levenshtein distances on the device (edit_distance_jobs in edit_distance.hip), every integer equal to edit_distance() below.
   // Group g owns the sequences seq_off[g] .. seq_off[g + 1], sequence q the tokens tok_ids[tok_off[q] .. tok_off[q + 1]); pair_host:
   // n_g x n_g distances per group, packed; ref_dist_host [NQ]: every sequence against its group's reference.  No statistic touched.
@@ -406,8 +445,8 @@ struct Ctc {
   struct Lattices { const int *labx, *lens, *lablens; int Lpad, Lprime; };
   Lattices upload_lattices(const int* frame_num_utt, int S, const int* label_ids, const int* label_off);
   void decode_batch(const int* frame_num_utt, int S, const float* scores, int rows, int K, int ld, bool is_log, int beam, int max_classes,
-                    int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float insertion_bonus, bool use_eos, int* hyp_host,
-                    int* hyp_len_host, float* score_host, float* lm_score_host);
+                    int nbest, const Lexicon* lex, const TokenLm* lm, float lm_weight, float bonus, bool use_eos, int* hyp_host, int* hyp_len_host,
+                    float* score_host, float* lm_score_host, int* word_host, int* word_len_host, int* word_end_host);
   void upload_lm(const TokenLm& lm);
   void upload_lex(const Lexicon& lex);
   const float* upload_lookahead(const Lexicon* lex, const TokenLm* lm);   // null with the mode off; refuses a missing word LM
@@ -435,8 +474,7 @@ struct CeLoss {
   hipStream_t st = nullptr;
   DevBuf<int> tg;              // lens[S] then targets[rows] of the current call
   DevBuf<CeSums> part, res;    // workgroup partials, the call's sums
-  PinBuf stage[2];
-  unsigned stage_idx = 0;
+  StageSlots stage;
   struct Pending { PinBuf pin; int S = 0; long rows = 0; bool active = false; } pend[2];
   unsigned pend_idx = 0;
   // running totals and the *_progress_ counters of ce-loss.cc:144-167 (the reference's are int32; these are wide)
@@ -445,8 +483,7 @@ struct CeLoss {
   int report_step = 100;       // the trainer's default (train-ce-parallel.cc:52); the reference's CE leaves it uninitialised
   std::vector<std::string> progress;   // progress lines not yet handed out (eesen_ce_progress), oldest first
   StatGuard guard;             // eesen_ce_set_guard
-  DevEvent ev[2] = {DevEvent(true), DevEvent(true)};
-  PhaseTimer timer;
+  PhaseClock clock;            // one phase: ce_eval
 
   CeLoss(int device, void* stream);
   ~CeLoss();
@@ -455,7 +492,7 @@ struct CeLoss {
   void eval_parallel(const int* frame_num_utt, int S, const float* net_out, int rows, int K, int ld, const int* targets,
                      float* diff, int ldd, double* obj_host);
   std::string report();
-  void phase_times(float* out1);
+  void phase_times(float* out1) { clock.read(out1, 1); }
 };
 
 }  // namespace eesen

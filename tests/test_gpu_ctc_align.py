@@ -130,6 +130,27 @@ def test_conventions(ctc):
         assert e.value.code == -1      # EESEN_ERR_INVALID
 
 
+def test_guard_word_set_returns_nan_and_minus_one(gpu):
+    """Aligned from a timed-out forward pass (the guarded Net's error word raised): -1 and NaN, never garbage with status OK."""
+    from eesen_amd import synth
+    from eesen_amd.api import Net, Ctc
+    lens, probs, labels, T, S, _ = R.case("dense_3x12x7")
+    net = Net.from_layers(synth.make_model(**synth.config("tiny_bi")))
+    ctc = Ctc()
+    ctc.SetGuard(net)
+    ok = _align(ctc, lens, probs, labels)
+    for s in range(S):
+        assert np.all(ok[0][:int(lens[s]), s] >= 0) and np.all(ok[1][:int(lens[s]), s] >= 0)
+    assert np.all(np.isfinite(ok[2]))
+    net._raise_error_word(2)
+    ali, pos, score = _align(ctc, lens, probs, labels)
+    assert np.all(ali == -1) and np.all(pos == -1) and np.all(np.isnan(score))
+    net._raise_error_word(0)
+    again = _align(ctc, lens, probs, labels)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again, ok))
+    ctc.SetGuard(None)
+
+
 def test_statistics_and_eval_parallel_untouched(gpu):
     from eesen_amd.api import Ctc, CuMatrix
     lens, probs, labels, T, S, _ = R.case("dense_3x12x7")
