@@ -155,6 +155,9 @@ SIGNATURES = {
     "eesen_feeder_release": (_i, [_vp, _i]),
     "eesen_feeder_set_pipeline": (_i, [_vp, _vp, _i]),
     "eesen_feeder_set_fbank": (_i, [_vp, _vp]),
+    "eesen_feeder_set_pitch": (_i, [_vp, _vp]),
+    "eesen_feat_paste_frames": (_i, [_pi, _i, _i, _pi]),
+    "eesen_paste_feats": (_i, [_i, _vp, _vp, _pi, _i, _pi, _i, _i, _vp, _pi]),
     "eesen_feeder_pipeline_shape": (_i, [_vp, _i, _i, _pi, _pi]),
     "eesen_feeder_submit_raw": (_i, [_vp, C.POINTER(_vp), _pi, _pi, C.POINTER(_vp), _i, _i, _pi]),
     "eesen_cmvn_norm": (_i, [_pd, _i, _i, _i, _pf]),

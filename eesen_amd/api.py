@@ -1134,6 +1134,12 @@ class Feeder:
         self._fbank_opts = fbank_opts(**opts)
         check(self.lib.eesen_feeder_set_fbank(self.h, C.byref(self._fbank_opts)))
 
+    def set_pitch(self, **opts):
+        """Options of the pitch half of the filterbank + pitch head stage (`eesen_feeder_set_pitch`; keywords as for `Pitch`), to be
+        called, like set_fbank, before a set_pipeline whose first stage is EESEN_FEAT_FBANK_PITCH."""
+        self._pitch_opts = pitch_opts(**opts)
+        check(self.lib.eesen_feeder_set_pitch(self.h, C.byref(self._pitch_opts)))
+
     def pipeline_shape(self, D_in: int, frames_in: int) -> Tuple[int, int]:
         """(frames, feature dimension) behind the pipeline for an utterance of [frames_in x D_in]."""
         d, t = C.c_int(), C.c_int()
@@ -1195,6 +1201,35 @@ class Feeder:
 
     def release(self, slot: int):
         check(self.lib.eesen_feeder_release(self.h, slot))
+
+
+def paste_feats(inputs: Sequence[Sequence[np.ndarray]], tolerance: int = 0, device: int = 0, stream: Optional[int] = None) -> List[Optional[np.ndarray]]:
+    """paste-feats on the device (`eesen_paste_feats`): inputs[j][s] is utterance s of table j (2..4 tables, each of one width);
+    returns per utterance the matrices side by side, trimmed to the shortest, or None where the lengths differ by more than
+    `tolerance` or a table's matrix is empty (eesen_amd.frontend.paste_frames)."""
+    from .frontend import paste_frames
+    n = len(inputs)
+    if n < 2 or any(len(t) != len(inputs[0]) for t in inputs) or not len(inputs[0]):
+        raise EesenError(-1, "paste_feats: 2..4 tables of as many utterances each")
+    S = len(inputs[0])
+    tabs = [[np.ascontiguousarray(m, np.float32) for m in t] for t in inputs]
+    dims = np.zeros(n, np.int32)
+    for j, t in enumerate(tabs):
+        widths = {m.shape[1] for m in t if m.ndim == 2 and m.shape[0]}
+        if any(m.ndim != 2 for m in t) or len(widths) > 1:
+            raise EesenError(-1, f"paste_feats: table {j} must hold matrices of one width")
+        dims[j] = widths.pop() if widths else max(t[0].shape[1], 1)
+    frames = np.array([[m.shape[0] for m in t] for t in tabs], np.int32)
+    rows = [paste_frames(frames[:, s], tolerance) for s in range(S)]
+    outs = [np.zeros((r, int(dims.sum())), np.float32) if r else None for r in rows]
+    tp = [(C.c_void_p * S)(*[m.ctypes.data for m in t]) for t in tabs]
+    ip = (C.c_void_p * n)(*[C.cast(p, C.c_void_p).value for p in tp])
+    op = (C.c_void_p * S)(*[o.ctypes.data if o is not None else None for o in outs])
+    got = np.zeros(S, np.int32)
+    check(_lib.load().eesen_paste_feats(device, C.c_void_p(stream) if stream else None, C.cast(ip, C.c_void_p), dims.ctypes.data_as(C.POINTER(C.c_int)), n,
+                                        frames.ctypes.data_as(C.POINTER(C.c_int)), S, int(tolerance), C.cast(op, C.c_void_p), got.ctypes.data_as(C.POINTER(C.c_int))))
+    assert list(got) == rows
+    return outs
 
 
 def fbank_opts(**kw) -> "_lib.FbankOpts":

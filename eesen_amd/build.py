@@ -23,7 +23,7 @@ FILE_FLAGS = {"pitch.hip": ["-ffp-contract=off"]}
 
 BINDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin")
 TOOLS = {"train-ctc-parallel": "train_ctc_parallel.cc", "train-ce-parallel": "train_ce_parallel.cc", "net-output-extract": "net_output_extract.cc", "ctc-align": "ctc_align.cc", "ctc-decode": "ctc_decode.cc", "compute-fbank-feats": "compute_fbank_feats.cc",
-         "compute-kaldi-pitch-feats": "compute_kaldi_pitch_feats.cc", "process-kaldi-pitch-feats": "process_kaldi_pitch_feats.cc"}
+         "compute-kaldi-pitch-feats": "compute_kaldi_pitch_feats.cc", "process-kaldi-pitch-feats": "process_kaldi_pitch_feats.cc", "paste-feats": "paste_feats.cc"}
 
 
 def csrc_digest() -> str:

@@ -18,8 +18,25 @@
 
 #include "fbank.h"
 #include "guard.h"
+#include "pitch.h"
 
 namespace eesen {
+
+// AppendFeats' length rule (src/featbin/paste-feats.cc:35-56) on row counts alone: the shortest input's rows, or none when the
+// longest exceeds it by more than the tolerance or an input is empty.  The feeder's combined head, eesen_paste_feats and the tools
+// all decide through this one function.
+int paste_frames(const int* frames, int n_inputs, int tolerance) {
+  EESEN_REQUIRE(n_inputs >= 1, EESEN_ERR_INVALID, "paste-feats: need at least one input");
+  EESEN_REQUIRE(tolerance >= 0, EESEN_ERR_INVALID, "paste-feats: --length-tolerance must not be negative");
+  int min_len = frames[0], max_len = frames[0];
+  for (int i = 0; i < n_inputs; ++i) {
+    EESEN_REQUIRE(frames[i] >= 0, EESEN_ERR_INVALID, "negative frame count");
+    min_len = std::min(min_len, frames[i]);
+    max_len = std::max(max_len, frames[i]);
+  }
+  return (max_len - min_len > tolerance || min_len == 0) ? 0 : min_len;
+}
+
 namespace {
 
 template <int V>  // V = floats per thread (4: D % 4 == 0 and 16-byte aligned rows, else 1)
@@ -104,6 +121,49 @@ __global__ __launch_bounds__(256) void feat_stage_kernel(StageDev st, const floa
   }
 }
 
+// paste-feats (src/featbin/paste-feats.cc:56-63): utterance s of the output is [fr_out[s] x Dout], its row t the rows t of the 2..4
+// inputs side by side.  The inputs are ragged matrices packed back to back, each with its own width and per-utterance offsets, and
+// may hold MORE rows than the output (the join trims to the shortest).  One output element per thread, utterance = blockIdx.y, plain
+// float loads and stores: rows are 43 or 83 floats wide, so neither side is 16-byte aligned from one row to the next; consecutive
+// threads still write consecutive floats and read runs of dim[j] consecutive floats.  A dropped utterance has fr_out[s] = 0 and is
+// left alone.
+constexpr int kPasteMaxInputs = 4;
+struct PasteArgs {
+  const float* src[kPasteMaxInputs];
+  const long* off[kPasteMaxInputs];    // off[j][s]: floats in front of utterance s in input j
+  int dim[kPasteMaxInputs], start[kPasteMaxInputs];   // width of input j and its first output column
+  int n;
+};
+
+__global__ __launch_bounds__(256) void feat_paste_kernel(PasteArgs a, float* __restrict__ dst, const long* __restrict__ off_out,
+                                                        const int* __restrict__ fr_out, int Dout) {
+  const int s = blockIdx.y;
+  const long n = (long)fr_out[s] * Dout;
+  if (n == 0) return;
+  const float* x[kPasteMaxInputs];
+#pragma unroll
+  for (int j = 0; j < kPasteMaxInputs; ++j) x[j] = j < a.n ? a.src[j] + a.off[j][s] : nullptr;
+  float* y = dst + off_out[s];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const long t = i / Dout;
+    const int c = (int)(i - t * Dout);
+    const float* p = x[0];
+    int d = a.dim[0], c0 = 0;
+#pragma unroll
+    for (int j = 1; j < kPasteMaxInputs; ++j)
+      if (j < a.n && c >= a.start[j]) { p = x[j]; d = a.dim[j]; c0 = a.start[j]; }
+    y[i] = p[t * d + (c - c0)];
+  }
+}
+
+void paste_launch(PasteArgs a, float* dst, const long* off_out, const int* fr_out, int Dout, int S, long biggest, hipStream_t st) {
+  a.start[0] = 0;
+  for (int j = 1; j < kPasteMaxInputs; ++j) a.start[j] = j < a.n ? a.start[j - 1] + a.dim[j - 1] : 0;
+  const int bx = (int)std::min<long>(std::max<long>(cdivl(biggest, 256), 1), 2048);
+  hipLaunchKernelGGL(feat_paste_kernel, dim3(bx, S), dim3(256), 0, st, a, dst, off_out, fr_out, Dout);
+  check_launch("feat_paste_kernel");
+}
+
 // DeltaFeatures::DeltaFeatures, feat/feature-functions.cc:216-241, in the reference's float arithmetic
 std::vector<float> delta_scales(int order, int window) {
   std::vector<std::vector<float>> sc(order + 1);
@@ -149,6 +209,16 @@ struct Feeder {
     PinBuf fb_meta_h;
     DevBuf<int> fb_prefix_d;
     DevBuf<unsigned long long> fb_ids_d;
+    // filterbank + pitch head stage: the batch's tables in one pinned block and one device block (8-byte words: the PitchUtt table,
+    // the filterbank's and the processed pitch's offsets, the noise keys, the filterbank's frame prefix), the filterbank matrix
+    // before the join, and the pitch tracker's scratch
+    PinBuf fp_meta_h;
+    DevBuf<unsigned long long> fp_meta_d;
+    DevBuf<float> fp_fbank, pt_down, pt_nccf_pitch, pt_nccf_pov, pt_avg, pt_raw, pt_proc;
+    DevBuf<PitchSums> pt_sums;
+    DevBuf<unsigned short> pt_backptr;
+    DevBuf<int> pt_taken;
+    DevBuf<double> pt_scan;
   };
   struct Stage { int kind, a, b; size_t scale_off; };
   std::vector<Stage> pipe;
@@ -157,6 +227,9 @@ struct Feeder {
   std::unique_ptr<FbankPlan> fb_plan;
   FbankDev fb_dev;
   unsigned long long fb_next_id = 0;
+  // EESEN_FEAT_FBANK_PITCH adds the pitch tracker (pitch.hip) beside it; a waveform's key is the same for the dither and the delta-pitch noise
+  std::unique_ptr<PitchPlan> pt_plan;
+  PitchDev pt_dev;
   int device;
   hipStream_t compute;
   DevStream copy;
@@ -255,6 +328,13 @@ struct Feeder {
           EESEN_REQUIRE(k == 0, EESEN_ERR_INVALID, "the filterbank stage reads waveforms: it must be the first stage");
           EESEN_REQUIRE(fb_plan != nullptr, EESEN_ERR_STATE, "the filterbank stage needs its options first (eesen_feeder_set_fbank)");
           break;
+        case EESEN_FEAT_FBANK_PITCH:
+          EESEN_REQUIRE(k == 0, EESEN_ERR_INVALID, "the filterbank + pitch stage reads waveforms: it must be the first stage");
+          EESEN_REQUIRE(fb_plan != nullptr, EESEN_ERR_STATE, "the filterbank + pitch stage needs the filterbank options first (eesen_feeder_set_fbank)");
+          EESEN_REQUIRE(pt_plan != nullptr, EESEN_ERR_STATE, "the filterbank + pitch stage needs the pitch options first (eesen_feeder_set_pitch)");
+          require_same_rate();
+          EESEN_REQUIRE(g.a >= 0, EESEN_ERR_INVALID, "paste-feats: --length-tolerance must not be negative");
+          break;
         case EESEN_FEAT_CMVN: ++n_cmvn; break;
         case EESEN_FEAT_SPLICE:   // KALDI_ASSERT(left_context >= 0 && right_context >= 0), feature-functions.cc:398
           EESEN_REQUIRE(g.a >= 0 && g.b >= 0 && g.a + g.b <= 64, EESEN_ERR_INVALID, "splice-feats: context must be 0..64 frames");
@@ -291,7 +371,29 @@ struct Feeder {
     fb_dev.upload(*np);
     fb_plan.swap(np);
   }
+  void set_pitch(const eesen_pitch_opts_t& o) {
+    std::unique_ptr<PitchPlan> np(new PitchPlan(o));
+    EESEN_HIP_CHECK(hipSetDevice(device));
+    for (auto& s : slots)  // batches in flight still read the old tables
+      if (s.in_flight) s.ready.wait();
+    pt_dev.upload(*np);
+    pt_plan.swap(np);
+  }
+  void require_same_rate() const {
+    EESEN_REQUIRE(fb_plan->opts.samp_freq == pt_plan->opts.samp_freq, EESEN_ERR_INVALID,
+                  "the filterbank + pitch stage reads one waveform: the two --sample-frequency values differ (" +
+                      std::to_string(fb_plan->opts.samp_freq) + " vs. " + std::to_string(pt_plan->opts.samp_freq) + ")");
+  }
+  // rows of the processed pitch matrix of a waveform: frames + delay, none without a frame
+  int pitch_rows(int nsamp) const {
+    const int f = pt_plan->num_frames(nsamp);
+    return f ? f + pt_plan->opts.delay : 0;
+  }
   int stage_dim(const Stage& g, int D) const {
+    if (g.kind == EESEN_FEAT_FBANK_PITCH) {
+      EESEN_REQUIRE(D == 1, EESEN_ERR_INVALID, "the filterbank + pitch stage takes waveforms as [samples x 1] matrices");
+      return fb_plan->dim + pt_plan->proc_dim;
+    }
     if (g.kind == EESEN_FEAT_FBANK) {
       EESEN_REQUIRE(D == 1, EESEN_ERR_INVALID, "the filterbank stage takes waveforms as [samples x 1] matrices");
       return fb_plan->dim;
@@ -302,6 +404,10 @@ struct Feeder {
   }
   int stage_frames(const Stage& g, int T) const {
     if (g.kind == EESEN_FEAT_FBANK) return fb_plan->num_frames(T);
+    if (g.kind == EESEN_FEAT_FBANK_PITCH) {
+      const int fr[2] = {fb_plan->num_frames(T), pitch_rows(T)};
+      return paste_frames(fr, 2, g.a);
+    }
     if (g.kind != EESEN_FEAT_SUBSAMPLE) return T;
     if (g.a < 0) return T * (-g.a);
     return T > g.b ? (T - g.b + g.a - 1) / g.a : 0;   // number of k = offset, offset + n, ... < T (subsample-feats.cc:82-84)
@@ -311,6 +417,89 @@ struct Feeder {
   int cmvn_dim(int D) const {  // feature dimension in front of the CMVN stage (0: no such stage)
     for (const Stage& g : pipe) { if (g.kind == EESEN_FEAT_CMVN) return D; D = stage_dim(g, D); }
     return 0;
+  }
+
+  // EESEN_FEAT_FBANK_PITCH: what a batch may hold, checked before anything of it is staged -- fbank_launch's and Pitch::layout's bounds
+  void check_fbank_pitch(const int* frames, int S) const {
+    require_same_rate();
+    long fb_all = 0, pt_all = 0;
+    for (int s = 0; s < S; ++s) {
+      EESEN_REQUIRE(frames[s] >= 0, EESEN_ERR_INVALID, "negative frame count");
+      fb_all += fb_plan->num_frames(frames[s]);
+      pt_all += pt_plan->num_frames(frames[s]);
+      EESEN_REQUIRE(fb_all < (1L << 30) && pt_all < kPitchMaxFrames, EESEN_ERR_INVALID, "too many frames in one batch");
+    }
+  }
+  // The head stage over the slot's samples (boundary 0, already on their way): the filterbank into its scratch matrix, the four pitch
+  // launches into theirs, then the join into boundary 1.  Everything is enqueued on the copy stream; the batch's tables travel in the
+  // slot's pinned block, which the slot's `ready` event orders, so nothing here waits for the device.
+  void submit_fbank_pitch(Slot& sl, const int* fr_h, int S, const float* wave, float* dst, int Dout, long biggest) {
+    const PitchPlan& pp = *pt_plan;
+    const size_t words = (size_t)S * (sizeof(PitchUtt) / 8 + 3) + (size_t)(S + 2) / 2;
+    static_assert(sizeof(PitchUtt) % 8 == 0, "the PitchUtt table is laid out in 8-byte words");
+    unsigned long long* meta = static_cast<unsigned long long*>(sl.fp_meta_h.reserve(words * 8));
+    PitchUtt* utt_h = reinterpret_cast<PitchUtt*>(meta);
+    long* fb_off_h = reinterpret_cast<long*>(utt_h + S);
+    long* proc_off_h = fb_off_h + S;
+    unsigned long long* ids_h = reinterpret_cast<unsigned long long*>(proc_off_h + S);
+    int* prefix_h = reinterpret_cast<int*>(ids_h + S);
+    long fb_all = 0, pt_all = 0, samp_all = 0, down_all = 0, proc_all = 0;
+    for (int s = 0; s < S; ++s) {
+      PitchUtt u = PitchUtt();
+      u.nsamp = fr_h[s];
+      u.frames = pp.num_frames(u.nsamp, &u.f1, &u.n1, &u.n2);
+      u.wave_off = samp_all; u.down_off = down_all; u.proc_off = proc_all;
+      u.prefix = (int)pt_all;
+      u.id = ids_h[s] = fb_next_id++;
+      utt_h[s] = u;
+      proc_off_h[s] = proc_all;
+      fb_off_h[s] = fb_all * fb_plan->dim;
+      prefix_h[s] = (int)fb_all;
+      samp_all += u.nsamp;
+      down_all += u.n2;
+      proc_all += u.frames ? (long)(u.frames + pp.opts.delay) * pp.proc_dim : 0;
+      pt_all += u.frames;
+      fb_all += fb_plan->num_frames(u.nsamp);
+    }
+    prefix_h[S] = (int)fb_all;
+    sl.fp_meta_d.reserve(words);
+    EESEN_HIP_CHECK(hipMemcpyAsync(sl.fp_meta_d.p, meta, words * 8, hipMemcpyHostToDevice, copy));
+    const PitchUtt* utt_d = reinterpret_cast<const PitchUtt*>(sl.fp_meta_d.p);
+    const long* fb_off_d = reinterpret_cast<const long*>(utt_d + S);
+    const long* proc_off_d = fb_off_d + S;
+    const unsigned long long* ids_d = reinterpret_cast<const unsigned long long*>(proc_off_d + S);
+    const int* prefix_d = reinterpret_cast<const int*>(ids_d + S);
+
+    sl.fp_fbank.reserve((size_t)std::max(fb_all * fb_plan->dim, 1L));
+    fbank_launch(*fb_plan, fb_dev, wave, sl.offs_d.p, sl.frs_d.p, prefix_d, ids_d, S, (int)fb_all, sl.fp_fbank.p, fb_off_d, copy);
+
+    const size_t F = (size_t)std::max(pt_all, 1L), ns = (size_t)pp.states;   // as Pitch::bufs, without the diagnostics
+    sl.pt_down.reserve((size_t)std::max(down_all, 1L));
+    sl.pt_sums.reserve((size_t)S);
+    sl.pt_nccf_pitch.reserve(F * ns);
+    sl.pt_nccf_pov.reserve(F * ns);
+    sl.pt_avg.reserve(F);
+    sl.pt_backptr.reserve(F * ns);
+    sl.pt_raw.reserve(F * 2);
+    sl.pt_scan.reserve(2 * (F + S));
+    sl.pt_proc.reserve((size_t)std::max(proc_all, 1L));
+    sl.pt_taken.reserve((size_t)S);
+    PitchBufs b;
+    b.utt = utt_d; b.S = S; b.total_frames = (int)pt_all;
+    b.wave = wave; b.down = sl.pt_down.p; b.sums = sl.pt_sums.p;
+    b.nccf_pitch = sl.pt_nccf_pitch.p; b.nccf_pov = sl.pt_nccf_pov.p; b.avg_norm_prod = sl.pt_avg.p;
+    b.backptr = sl.pt_backptr.p; b.fwd = nullptr; b.track = nullptr; b.taken = sl.pt_taken.p;
+    b.raw = sl.pt_raw.p; b.scan = sl.pt_scan.p; b.proc = sl.pt_proc.p;
+    pitch_downsample_launch(pp, pt_dev, b, copy);
+    pitch_nccf_launch(pp, pt_dev, b, copy);
+    pitch_viterbi_launch(pp, pt_dev, b, copy);
+    pitch_process_launch(pp, b, copy);
+
+    PasteArgs pa = PasteArgs();
+    pa.n = 2;
+    pa.src[0] = sl.fp_fbank.p; pa.off[0] = fb_off_d; pa.dim[0] = fb_plan->dim;
+    pa.src[1] = sl.pt_proc.p; pa.off[1] = proc_off_d; pa.dim[1] = pp.proc_dim;
+    paste_launch(pa, dst, sl.offs_d.p + S, sl.frs_d.p + S, Dout, S, biggest, copy);
   }
 
   int submit_raw(const float* const* utts, const int* frames, const int* strides, const float* const* cmvn, int S, int D) {
@@ -324,6 +513,7 @@ struct Feeder {
     std::vector<int> dims(nb);
     dims[0] = D;
     for (int k = 0; k < nst; ++k) dims[k + 1] = stage_dim(pipe[k], dims[k]);
+    if (pipe[0].kind == EESEN_FEAT_FBANK_PITCH) check_fbank_pitch(frames, S);
     int id = 0;
     Slot& sl = next_slot(&id);
     long* off_h = static_cast<long*>(sl.meta_h.reserve((size_t)nb * S * (sizeof(long) + sizeof(int))));
@@ -391,6 +581,10 @@ struct Feeder {
         EESEN_HIP_CHECK(hipMemcpyAsync(sl.fb_prefix_d.p, prefix_h, (size_t)(S + 1) * sizeof(int), hipMemcpyHostToDevice, copy));
         EESEN_HIP_CHECK(hipMemcpyAsync(sl.fb_ids_d.p, ids_h, (size_t)S * sizeof(unsigned long long), hipMemcpyHostToDevice, copy));
         fbank_launch(*fb_plan, fb_dev, src, sl.offs_d.p, sl.frs_d.p, sl.fb_prefix_d.p, sl.fb_ids_d.p, S, (int)frames_all, dst, sl.offs_d.p + S, copy);
+        continue;
+      }
+      if (pipe[k].kind == EESEN_FEAT_FBANK_PITCH) {   // k == 0, as above; both extractors read boundary 0, the join writes boundary 1
+        submit_fbank_pitch(sl, fr_h, S, src, dst, dims[1], biggest);
         continue;
       }
       const int bx = (int)std::min<long>(std::max<long>(cdivl(biggest, 256), 1), 2048);   // one element per thread: the stage is latency-bound otherwise
@@ -466,6 +660,88 @@ int eesen_feeder_set_fbank(eesen_feeder_t* f, const eesen_fbank_opts_t* opts) {
   return guard([&] {
     REQ_PTR(f); REQ_PTR(opts);
     f->set_fbank(*opts);
+  });
+}
+int eesen_feeder_set_pitch(eesen_feeder_t* f, const eesen_pitch_opts_t* opts) {
+  return guard([&] {
+    REQ_PTR(f); REQ_PTR(opts);
+    f->set_pitch(*opts);
+  });
+}
+int eesen_feat_paste_frames(const int* frames, int n_inputs, int tolerance, int* out) {
+  return guard([&] {
+    REQ_PTR(frames); REQ_PTR(out);
+    *out = paste_frames(frames, n_inputs, tolerance);
+  });
+}
+// paste-feats on host matrices through feat_paste_kernel: every input packed back to back, one upload, one launch, one copy back
+int eesen_paste_feats(int device, void* stream, const float* const* const* inputs, const int* dims, int n_inputs, const int* frames,
+                      int S, int tolerance, float* const* out, int* frames_out) {
+  return guard([&] {
+    REQ_PTR(inputs); REQ_PTR(dims); REQ_PTR(frames);
+    EESEN_REQUIRE(n_inputs >= 2 && n_inputs <= kPasteMaxInputs, EESEN_ERR_INVALID, "paste-feats on the device joins 2..4 inputs");
+    EESEN_REQUIRE(S > 0 && S <= 65535, EESEN_ERR_INVALID, "1..65535 utterances per call");
+    long Dout = 0;
+    for (int j = 0; j < n_inputs; ++j) {
+      REQ_PTR(inputs[j]);
+      EESEN_REQUIRE(dims[j] > 0, EESEN_ERR_INVALID, "an input without columns");
+      Dout += dims[j];
+    }
+    EESEN_REQUIRE(Dout < (1L << 24), EESEN_ERR_INVALID, "too many columns");
+    // layout: the inputs' offsets [n x S], the output's offsets [S] and row counts [S]
+    std::vector<long> off((size_t)(n_inputs + 1) * S);
+    std::vector<int> rows(S);
+    std::vector<long> total(n_inputs + 1, 0);
+    long biggest = 0;
+    for (int s = 0; s < S; ++s) {
+      int fr[kPasteMaxInputs];
+      for (int j = 0; j < n_inputs; ++j) {
+        fr[j] = frames[(size_t)j * S + s];
+        EESEN_REQUIRE(fr[j] >= 0, EESEN_ERR_INVALID, "negative frame count");
+        EESEN_REQUIRE(fr[j] == 0 || inputs[j][s] != nullptr, EESEN_ERR_INVALID, "null input matrix");
+        off[(size_t)j * S + s] = total[j];
+      }
+      rows[s] = paste_frames(fr, n_inputs, tolerance);
+      for (int j = 0; j < n_inputs; ++j) total[j] += (long)rows[s] * dims[j];   // only the rows the join keeps go up
+      off[(size_t)n_inputs * S + s] = total[n_inputs];
+      total[n_inputs] += (long)rows[s] * Dout;
+      biggest = std::max(biggest, (long)rows[s] * Dout);
+      EESEN_REQUIRE(rows[s] == 0 || (out && out[s] != nullptr), EESEN_ERR_INVALID, "null output matrix");
+      if (frames_out) frames_out[s] = rows[s];
+    }
+    const long n_out = total[n_inputs];
+    if (!n_out) return;            // every utterance dropped: nothing to launch
+    require_device(device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PinBuf host, meta;
+    float* h = static_cast<float*>(host.reserve((size_t)n_out * sizeof(float)));   // the inputs side by side take as many floats as the output
+    long at = 0;
+    std::vector<long> base(n_inputs);
+    for (int j = 0; j < n_inputs; ++j) {
+      base[j] = at;
+      for (int s = 0; s < S; ++s)
+        if (rows[s]) std::memcpy(h + at + off[(size_t)j * S + s], inputs[j][s], (size_t)rows[s] * dims[j] * sizeof(float));
+      at += total[j];
+    }
+    const size_t meta_bytes = off.size() * sizeof(long) + (size_t)S * sizeof(int);
+    char* m = static_cast<char*>(meta.reserve(meta_bytes));
+    std::memcpy(m, off.data(), off.size() * sizeof(long));
+    std::memcpy(m + off.size() * sizeof(long), rows.data(), (size_t)S * sizeof(int));
+    DevBuf<float> in_d, out_d;
+    DevBuf<long> meta_d;
+    in_d.reserve((size_t)n_out);
+    out_d.reserve((size_t)n_out);
+    meta_d.reserve(off.size() + ((size_t)S + 1) / 2);
+    EESEN_HIP_CHECK(hipMemcpyAsync(in_d.p, h, (size_t)n_out * sizeof(float), hipMemcpyHostToDevice, st));
+    EESEN_HIP_CHECK(hipMemcpyAsync(meta_d.p, m, meta_bytes, hipMemcpyHostToDevice, st));
+    PasteArgs pa = PasteArgs();
+    pa.n = n_inputs;
+    for (int j = 0; j < n_inputs; ++j) { pa.src[j] = in_d.p + base[j]; pa.off[j] = meta_d.p + (size_t)j * S; pa.dim[j] = dims[j]; }
+    paste_launch(pa, out_d.p, meta_d.p + (size_t)n_inputs * S, reinterpret_cast<const int*>(meta_d.p + off.size()), (int)Dout, S, biggest, st);
+    EESEN_HIP_CHECK(hipMemcpyAsync(h, out_d.p, (size_t)n_out * sizeof(float), hipMemcpyDeviceToHost, st));   // (the staged inputs are consumed by then: one stream)
+    EESEN_HIP_CHECK(hipStreamSynchronize(st));
+    for (int s = 0; s < S; ++s)
+      if (rows[s]) std::memcpy(out[s], h + off[(size_t)n_inputs * S + s], (size_t)rows[s] * Dout * sizeof(float));
   });
 }
 int eesen_feeder_pipeline_shape(eesen_feeder_t* f, int D_in, int frames_in, int* D_out, int* frames_out) {

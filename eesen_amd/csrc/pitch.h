@@ -48,6 +48,7 @@ struct PitchDev {
 };
 constexpr int kPitchFramesPerBlock = 4;      // NCCF kernel: one wavefront per frame
 constexpr int kPitchMaxStates = 1024;        // search kernel: one thread per lag state, one workgroup per utterance
+constexpr long kPitchMaxFrames = (1L << 30) / kPitchMaxStates * 256;   // frames of one launch: [frames x states] offsets stay below 2^38
 
 struct PitchBufs {
   const PitchUtt* utt; int S; int total_frames;

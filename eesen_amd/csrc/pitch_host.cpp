@@ -196,7 +196,7 @@ struct Pitch {
       total_down += u.n2;
       total_proc += u.frames ? (long)(u.frames + plan.opts.delay) * plan.proc_dim : 0;
       frames_all += u.frames;
-      EESEN_REQUIRE(frames_all < (1L << 30) / kPitchMaxStates * 256, EESEN_ERR_INVALID, "too many frames in one call");
+      EESEN_REQUIRE(frames_all < kPitchMaxFrames, EESEN_ERR_INVALID, "too many frames in one call");
     }
     total_frames = (int)frames_all;
     utt_d.reserve((size_t)S);

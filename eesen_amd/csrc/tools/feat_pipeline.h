@@ -14,8 +14,16 @@
 // The tool then reads the wav table itself (FeatureReader in wave mode) and the features are computed on the device as well
 // (EESEN_FEAT_FBANK, the head stage); an option the device extractor does not implement (--vtln-map, --subtract-mean, htk output,
 // --round-to-power-of-two=false ...) leaves the rspecifier unrecognised.
+//
+// Or at the audio through both extractors, the tonal recipes' features (asr_egs/wsj/steps/make_fbank_pitch.sh:117-121):
+//   paste-feats --length-tolerance=2 "ark:compute-fbank-feats [options] scp,p:wav.scp ark:- |"
+//               "ark,s,cs:compute-kaldi-pitch-feats [options] scp,p:wav.scp ark:- | process-kaldi-pitch-feats [options] ark:- ark:- |" ark:- | ...
+// Both inner pipes must name the same wav table and every option must be one of the device extractors' (--config files are read as
+// the tools read them); the head stage is then EESEN_FEAT_FBANK_PITCH.  The inputs in the other order, a third input, --binary or
+// extract-segments leave the rspecifier unrecognised.
 #pragma once
 #include <cmath>
+#include <fstream>
 #include <map>
 #include <string>
 #include <vector>
@@ -34,10 +42,18 @@ struct Pipeline {
   bool has_fbank = false;
   eesen_fbank_opts_t fbank;
   WaveSelect wave;
+  // with a paste-feats head over compute-fbank-feats and the two pitch tools: the pitch options and paste-feats' --length-tolerance
+  bool has_pitch = false;
+  eesen_pitch_opts_t pitch;
+  int tolerance = 0;
   const WaveSelect* wave_mode() const { return has_fbank ? &wave : nullptr; }
-  int cmvn_dim(int raw_cols) const { return has_fbank ? fbank.num_bins + (fbank.use_energy ? 1 : 0) : raw_cols; }   // in front of the CMVN stage
-  int configure(eesen_feeder_t* feeder) const {   // the filterbank options first, then the stages
+  int pitch_dim() const { return (pitch.add_pov_feature != 0) + (pitch.add_normalized_log_pitch != 0) + (pitch.add_delta_pitch != 0) + (pitch.add_raw_log_pitch != 0); }
+  int cmvn_dim(int raw_cols) const {   // in front of the CMVN stage
+    return has_fbank ? fbank.num_bins + (fbank.use_energy ? 1 : 0) + (has_pitch ? pitch_dim() : 0) : raw_cols;
+  }
+  int configure(eesen_feeder_t* feeder) const {   // the extractors' options first, then the stages
     if (has_fbank) { const int rc = eesen_feeder_set_fbank(feeder, &fbank); if (rc != EESEN_OK) return rc; }
+    if (has_pitch) { const int rc = eesen_feeder_set_pitch(feeder, &pitch); if (rc != EESEN_OK) return rc; }
     return eesen_feeder_set_pipeline(feeder, stages.data(), (int)stages.size());
   }
 };
@@ -127,6 +143,55 @@ inline bool set_fbank_option(const std::string& name, const std::string& v, eese
   return false;
 }
 
+// compute-kaldi-pitch-feats' (which = 0: PitchExtractionOptions::Register) or process-kaldi-pitch-feats' (which = 1:
+// ProcessPitchOptions::Register, plus --noise-seed of this project) options onto eesen_pitch_opts_t
+inline bool set_pitch_option(int which, const std::string& name, const std::string& v, eesen_pitch_opts_t* o) {
+  auto b = [&](int* dst) { bool x; if (!to_bool(v, &x)) return false; *dst = x ? 1 : 0; return true; };
+  if (which == 0) {
+    if (name == "sample-frequency") return to_float(v, &o->samp_freq);
+    if (name == "frame-length") return to_float(v, &o->frame_length_ms);
+    if (name == "frame-shift") return to_float(v, &o->frame_shift_ms);
+    if (name == "preemphasis-coefficient") return to_float(v, &o->preemph_coeff);
+    if (name == "min-f0") return to_float(v, &o->min_f0);
+    if (name == "max-f0") return to_float(v, &o->max_f0);
+    if (name == "soft-min-f0") return to_float(v, &o->soft_min_f0);
+    if (name == "penalty-factor") return to_float(v, &o->penalty_factor);
+    if (name == "lowpass-cutoff") return to_float(v, &o->lowpass_cutoff);
+    if (name == "resample-frequency") return to_float(v, &o->resample_freq);
+    if (name == "delta-pitch") return to_float(v, &o->delta_pitch);
+    if (name == "nccf-ballast") return to_float(v, &o->nccf_ballast);
+    if (name == "nccf-ballast-online") return b(&o->nccf_ballast_online);
+    if (name == "lowpass-filter-width") return to_int(v, &o->lowpass_filter_width);
+    if (name == "upsample-filter-width") return to_int(v, &o->upsample_filter_width);
+    if (name == "frames-per-chunk") return to_int(v, &o->frames_per_chunk);
+    if (name == "simulate-first-pass-online") return b(&o->simulate_first_pass_online);
+    if (name == "recompute-frame") return to_int(v, &o->recompute_frame);
+    if (name == "max-frames-latency") return to_int(v, &o->max_frames_latency);
+    if (name == "snip-edges") return b(&o->snip_edges);
+    return false;
+  }
+  if (name == "pitch-scale") return to_float(v, &o->pitch_scale);
+  if (name == "pov-scale") return to_float(v, &o->pov_scale);
+  if (name == "pov-offset") return to_float(v, &o->pov_offset);
+  if (name == "delta-pitch-scale") return to_float(v, &o->delta_pitch_scale);
+  if (name == "delta-pitch-noise-stddev") return to_float(v, &o->delta_pitch_noise_stddev);
+  if (name == "normalization-left-context") return to_int(v, &o->normalization_left_context);
+  if (name == "normalization-right-context") return to_int(v, &o->normalization_right_context);
+  if (name == "delta-window") return to_int(v, &o->delta_window);
+  if (name == "delay") return to_int(v, &o->delay);
+  if (name == "add-pov-feature") return b(&o->add_pov_feature);
+  if (name == "add-normalized-log-pitch") return b(&o->add_normalized_log_pitch);
+  if (name == "add-delta-pitch") return b(&o->add_delta_pitch);
+  if (name == "add-raw-log-pitch") return b(&o->add_raw_log_pitch);
+  if (name == "noise-seed") {
+    if (v.empty()) return false;
+    char* end = nullptr;
+    o->noise_seed = strtoull(v.c_str(), &end, 10);
+    return !*end;
+  }
+  return false;
+}
+
 // `--name=value` options (names with '_' for '-' accepted, as ParseOptions does) and positional arguments
 inline bool split_options(const std::vector<std::string>& argv, size_t from, std::map<std::string, std::string>* opts,
                           std::vector<std::string>* pos) {
@@ -144,6 +209,86 @@ inline bool split_options(const std::vector<std::string>& argv, size_t from, std
   return true;
 }
 
+// --config=<file> as the tools read it (one --x=y per line, # comments; read first, so the command line overrides it): the file's
+// options in front of the others.  false: a file that cannot be read or a line that is no option
+inline bool with_config(const std::vector<std::string>& argv, std::vector<std::string>* out) {
+  std::vector<std::string> head, rest;
+  for (size_t i = 0; i < argv.size(); ++i) {
+    const std::string& a = argv[i];
+    if (i > 0 && a.rfind("--config=", 0) == 0) {
+      std::string path = a.substr(9);
+      while (!path.empty() && isspace((unsigned char)path.back())) path.pop_back();
+      while (!path.empty() && isspace((unsigned char)path.front())) path.erase(path.begin());
+      std::ifstream f(path);
+      if (!f) return false;
+      std::string line;
+      while (std::getline(f, line)) {
+        line = line.substr(0, line.find('#'));
+        while (!line.empty() && isspace((unsigned char)line.back())) line.pop_back();
+        while (!line.empty() && isspace((unsigned char)line.front())) line.erase(line.begin());
+        if (line.empty()) continue;
+        if (line.rfind("--", 0) != 0) return false;
+        head.push_back(line);
+      }
+    } else {
+      rest.push_back(a);
+    }
+  }
+  out->clear();
+  if (!rest.empty()) out->push_back(rest[0]);
+  out->insert(out->end(), head.begin(), head.end());
+  out->insert(out->end(), rest.begin() + (rest.empty() ? 0 : 1), rest.end());
+  return true;
+}
+
+// the commands of a pipe line, split at the `|` outside quotes; false when a quote is left open
+inline bool split_pipe(const std::string& cmd, std::vector<std::string>* segs) {
+  segs->clear();
+  size_t b = 0;
+  bool in_q = false;
+  char q = 0;
+  for (size_t i = 0; i <= cmd.size(); ++i) {
+    if (i < cmd.size() && (cmd[i] == '\'' || cmd[i] == '"')) { if (!in_q) { in_q = true; q = cmd[i]; } else if (q == cmd[i]) in_q = false; }
+    if (i == cmd.size() || (cmd[i] == '|' && !in_q)) { segs->push_back(cmd.substr(b, i - b)); b = i + 1; }
+  }
+  return !in_q;
+}
+
+// an input of paste-feats that is itself a pipe, "ark[,s,cs]:tool ... | tool ... |": the argument vectors of its commands
+inline bool inner_pipe(const std::string& spec, std::vector<std::vector<std::string>>* out) {
+  const size_t colon = spec.find(':');
+  if (colon == std::string::npos) return false;
+  std::string head = spec.substr(0, colon), cmd = spec.substr(colon + 1);
+  std::vector<std::string> hs;
+  for (size_t b = 0;;) { const size_t c = head.find(',', b); hs.push_back(head.substr(b, c == std::string::npos ? c : c - b)); if (c == std::string::npos) break; b = c + 1; }
+  if (hs[0] != "ark") return false;
+  for (size_t i = 1; i < hs.size(); ++i) if (hs[i] != "s" && hs[i] != "cs") return false;
+  while (!cmd.empty() && isspace((unsigned char)cmd.back())) cmd.pop_back();
+  if (cmd.empty() || cmd.back() != '|') return false;
+  cmd.pop_back();
+  std::vector<std::string> segs;
+  if (!split_pipe(cmd, &segs)) return false;
+  out->clear();
+  for (const std::string& s : segs) {
+    std::vector<std::string> argv;
+    if (!shell_split(s, &argv) || argv.empty()) return false;
+    out->push_back(argv);
+  }
+  return true;
+}
+
+// a wav table rspecifier without its options (scp,p:x -> scp:x); "" for anything that is not a plain table
+inline std::string wav_source(std::string src) {
+  while (!src.empty() && isspace((unsigned char)src.back())) src.pop_back();
+  const size_t c = src.find(':');
+  if (c == std::string::npos || src.empty() || src.back() == '|') return "";
+  const std::string k = src.substr(0, src.find_first_of(",:"));
+  if (k != "ark" && k != "scp") return "";
+  std::string path = src.substr(c + 1);
+  while (!path.empty() && isspace((unsigned char)path.front())) path.erase(path.begin());
+  return k + ":" + path;
+}
+
 inline bool table_kind(const std::string& spec) {  // ark:... / scp:... (with options), not itself a command
   const size_t c = spec.find(':');
   if (c == std::string::npos) return false;
@@ -159,15 +304,7 @@ inline bool parse_feature_pipeline(const std::string& rspecifier, Pipeline* out)
   if (cmd.empty() || cmd.back() != '|') return false;
   cmd.pop_back();
   std::vector<std::string> segs;
-  {
-    size_t b = 0;
-    bool in_q = false;
-    char q = 0;
-    for (size_t i = 0; i <= cmd.size(); ++i) {
-      if (i < cmd.size() && (cmd[i] == '\'' || cmd[i] == '"')) { if (!in_q) { in_q = true; q = cmd[i]; } else if (q == cmd[i]) in_q = false; }
-      if (i == cmd.size() || (cmd[i] == '|' && !in_q)) { segs.push_back(cmd.substr(b, i - b)); b = i + 1; }
-    }
-  }
+  if (!split_pipe(cmd, &segs)) return false;
   Pipeline p;
   for (size_t si = 0; si < segs.size(); ++si) {
     std::vector<std::string> argv, pos;
@@ -180,6 +317,50 @@ inline bool parse_feature_pipeline(const std::string& rspecifier, Pipeline* out)
       for (const auto& kv : o) { bool ok = false; for (const char* n : names) ok = ok || kv.first == n; if (!ok) return false; }
       return true;
     };
+    if (si == 0 && tool == "paste-feats") {               // featbin/paste-feats.cc over the two extractors: the pipe starts at the audio
+      if (!only({"length-tolerance"}) || pos.size() != 3 || pos[2] != "ark:-") return false;
+      if (o.count("length-tolerance") && (!to_int(o["length-tolerance"], &p.tolerance) || p.tolerance < 0)) return false;
+      std::vector<std::vector<std::string>> fb, pt;
+      if (!inner_pipe(pos[0], &fb) || !inner_pipe(pos[1], &pt) || fb.size() != 1 || pt.size() != 2) return false;
+      const char* tools[3] = {"compute-fbank-feats", "compute-kaldi-pitch-feats", "process-kaldi-pitch-feats"};
+      std::vector<std::string> args[3];
+      std::map<std::string, std::string> io[3];
+      std::vector<std::string> ipos[3];
+      for (int k = 0; k < 3; ++k) {
+        const std::vector<std::string>& av = k == 0 ? fb[0] : pt[k - 1];
+        std::string t = av[0];
+        if (t.find('/') != std::string::npos) t = t.substr(t.rfind('/') + 1);
+        if (t != tools[k] || !with_config(av, &args[k])) return false;
+        split_options(args[k], 1, &io[k], &ipos[k]);
+      }
+      if (ipos[0].size() != 2 || ipos[0][1] != "ark:-" || ipos[1].size() != 2 || ipos[1][1] != "ark:-") return false;
+      if (ipos[2].size() != 2 || ipos[2][0] != "ark:-" || ipos[2][1] != "ark:-") return false;
+      int verbose = 0;
+      eesen_fbank_opts_default(&p.fbank);
+      for (const auto& kv : io[0]) {
+        if (kv.first == "channel") { if (!to_int(kv.second, &p.wave.channel)) return false; }
+        else if (kv.first == "min-duration") { if (!to_float(kv.second, &p.wave.min_duration)) return false; }
+        else if (kv.first == "output-format") { if (kv.second != "kaldi") return false; }
+        else if (kv.first == "verbose") { if (!to_int(kv.second, &verbose)) return false; }
+        else if (!set_fbank_option(kv.first, kv.second, &p.fbank)) return false;
+      }
+      if (!p.fbank.round_to_power_of_two) return false;
+      eesen_pitch_opts_default(&p.pitch);
+      for (int k = 1; k < 3; ++k)
+        for (const auto& kv : io[k]) {
+          if (kv.first == "verbose" || (k == 2 && kv.first == "srand")) { if (!to_int(kv.second, &verbose)) return false; }
+          else if (!set_pitch_option(k - 1, kv.first, kv.second, &p.pitch)) return false;
+        }
+      // what the device extractor refuses (eesen_pitch_create) stays with the reference's tool
+      if (p.pitch.preemph_coeff != 0.f || p.pitch.frames_per_chunk != 0 || p.pitch.simulate_first_pass_online || p.pitch.nccf_ballast_online) return false;
+      const std::string src = wav_source(ipos[0][0]);
+      if (src.empty() || src != wav_source(ipos[1][0])) return false;
+      p.source = ipos[0][0];
+      p.has_fbank = p.has_pitch = true;
+      p.wave.samp_freq = p.fbank.samp_freq;
+      p.stages.push_back({EESEN_FEAT_FBANK_PITCH, p.tolerance, 0});
+      continue;
+    }
     if (si == 0 && tool == "compute-fbank-feats") {       // featbin/compute-fbank-feats.cc: the pipe starts at the audio
       if (pos.size() != 2 || pos[1] != "ark:-") return false;
       eesen_fbank_opts_default(&p.fbank);

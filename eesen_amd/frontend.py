@@ -18,6 +18,13 @@ The pipe may start at the audio: `compute-fbank-feats [options] scp:wav.scp ark:
 The tools then read the wav table themselves and the features are computed on the device too (EESEN_FEAT_FBANK, the head stage of
 the feeder's pipeline); options the device extractor does not implement (--vtln-map, --subtract-mean, htk output, ...) leave the
 rspecifier unrecognised.
+
+Or at the audio through both extractors, the tonal recipes' features (asr_egs/wsj/steps/make_fbank_pitch.sh:117-121):
+`paste-feats --length-tolerance=2 "ark:compute-fbank-feats [options] scp,p:wav.scp ark:- |" "ark,s,cs:compute-kaldi-pitch-feats [options]
+scp,p:wav.scp ark:- | process-kaldi-pitch-feats [options] ark:- ark:- |" ark:- | apply-cmvn ... ark:- ark:- | ...`.  Both inner pipes must name
+the same wav table and every option must be one of the device extractors' (--config files are read as the tools read them); the head
+stage is then EESEN_FEAT_FBANK_PITCH and `paste_frames` the row count of an utterance.  The inputs in the other order, a third input,
+--binary or extract-segments leave the rspecifier unrecognised (INTEGRATION.md "Fbank + pitch").
 """
 from __future__ import annotations
 
@@ -31,6 +38,7 @@ import numpy as np
 from . import kaldi_io
 
 CMVN, SPLICE, SUBSAMPLE, DELTAS, FBANK = 1, 2, 3, 4, 5    # EESEN_FEAT_* of include/eesen_hip.h
+FBANK_PITCH = 6
 
 # compute-fbank-feats' options that map onto eesen_fbank_opts_t: flag -> (field, type); FrameExtractionOptions / MelBanksOptions /
 # FbankOptions::Register, plus --vtln-warp of the tool and --dither-seed of this project
@@ -57,6 +65,81 @@ def fbank_num_frames(nsamp: int, opts: dict) -> int:
     if opts.get("snip_edges", True):
         return 0 if nsamp < length else 1 + (nsamp - length) // shift
     return int(np.float32(np.float32(nsamp) / np.float32(shift)) + np.float32(0.5))
+
+
+def paste_frames(frames, tolerance: int = 0) -> int:
+    """Rows of an utterance behind paste-feats, from its row counts in the inputs (AppendFeats, paste-feats.cc:35-56): the shortest,
+    or 0 -- no output -- when the longest exceeds it by more than `tolerance` or an input is empty; equals eesen_feat_paste_frames."""
+    frames = [int(f) for f in frames]
+    if not frames or tolerance < 0 or min(frames) < 0:
+        raise ValueError("paste_frames: at least one row count, none of them negative, and a tolerance >= 0")
+    lo, hi = min(frames), max(frames)
+    return 0 if hi - lo > tolerance or lo == 0 else lo
+
+
+def _pitch_flags():
+    """(compute-kaldi-pitch-feats', process-kaldi-pitch-feats'): flag -> (field of eesen_pitch_opts_t, type), as the tools register them."""
+    from .compute_kaldi_pitch_feats import PITCH_OPTIONS
+    from .process_kaldi_pitch_feats import PROCESS_OPTIONS
+    return ({k: (f, type(d)) for k, (f, d, _) in PITCH_OPTIONS.items()}, {k: (f, type(d)) for k, (f, d, _) in PROCESS_OPTIONS.items()})
+
+
+def _split_pipe(cmd: str) -> Optional[List[str]]:
+    """The commands of a shell pipe line, split at the `|` that stand outside quotes (an inner rspecifier such as
+    "ark:compute-fbank-feats ... |" keeps its own); None when a quote is left open."""
+    segs, cur, quote, i = [], [], None, 0
+    while i < len(cmd):
+        ch = cmd[i]
+        if quote is None and ch == "\\" and i + 1 < len(cmd):
+            cur.append(cmd[i:i + 2])
+            i += 2
+            continue
+        if quote is None and ch in "'\"":
+            quote = ch
+        elif quote == ch:
+            quote = None
+        elif quote == '"' and ch == "\\" and i + 1 < len(cmd):
+            cur.append(cmd[i:i + 2])
+            i += 2
+            continue
+        elif quote is None and ch == "|":
+            segs.append("".join(cur))
+            cur, ch = [], ""
+        cur.append(ch)
+        i += 1
+    if quote is not None:
+        return None
+    segs.append("".join(cur))
+    return segs
+
+
+def _with_config(argv: List[str]) -> Optional[List[str]]:
+    """--config=<file> as the tools read it (one --x=y per line, # comments; read first, so the command line overrides it): the
+    file's options in front of the others.  None when a file cannot be read or a line is no option."""
+    head, rest = [], []
+    for a in argv:
+        if a.startswith("--config="):
+            try:
+                lines = open(a[len("--config="):].strip()).read().splitlines()
+            except OSError:
+                return None
+            for line in lines:
+                line = line.split("#", 1)[0].strip()
+                if line and not line.startswith("--"):
+                    return None
+                if line:
+                    head.append(line)
+        else:
+            rest.append(a)
+    return head + rest
+
+
+def _wav_source(src: str) -> Optional[str]:
+    """A wav table rspecifier without its options (scp,p:x -> scp:x); None for anything that is not a plain table."""
+    head, sep, path = src.partition(":")
+    if not sep or head.split(",")[0] not in ("ark", "scp") or src.rstrip().endswith("|"):
+        return None
+    return head.split(",")[0] + ":" + path.strip()
 
 
 def _bool(v: str) -> Optional[bool]:
@@ -111,21 +194,43 @@ class FeaturePipeline:
     fbank: Optional[dict] = None
     channel: int = -1
     min_duration: float = 0.0
+    # with a paste-feats head over compute-fbank-feats and the two pitch tools: `pitch` holds fields of eesen_pitch_opts_t and
+    # `tolerance` paste-feats' --length-tolerance (the stage is (FBANK_PITCH, tolerance, 0))
+    pitch: Optional[dict] = None
+    tolerance: int = 0
+    _pitch_shape: object = field(default=None, compare=False, repr=False)
 
     def configure(self, feeder) -> None:
-        """Sets this pipeline on an api.Feeder (the filterbank options first, when it starts at the audio)."""
+        """Sets this pipeline on an api.Feeder (the extractors' options first, when it starts at the audio)."""
         if self.fbank is not None:
             feeder.set_fbank(**self.fbank)
+        if self.pitch is not None:
+            feeder.set_pitch(**self.pitch)
         feeder.set_pipeline(self.stages)
+
+    def _fbank_dim(self) -> int:
+        return self.fbank.get("num_bins", 23) + int(self.fbank.get("use_energy", False))
+
+    def pitch_rows(self, nsamp: int) -> Tuple[int, int]:
+        """(rows, columns) of the processed pitch matrix of a waveform: eesen_pitch_shape (host only), frames + delay rows."""
+        if self._pitch_shape is None:
+            from .api import Pitch
+            self._pitch_shape = Pitch(**self.pitch)       # no device is touched before a compute call
+        frames, _, dim = self._pitch_shape.shape(nsamp)
+        return (frames + int(self.pitch.get("delay", 0)) if frames else 0), dim
 
     def cmvn_dim(self, D: int) -> int:
         """Feature dimension in front of the CMVN stage."""
-        return self.fbank.get("num_bins", 23) + int(self.fbank.get("use_energy", False)) if self.fbank is not None else D
+        if self.pitch is not None:
+            return self._fbank_dim() + self.pitch_rows(0)[1]
+        return self._fbank_dim() if self.fbank is not None else D
 
     def out_dim(self, D: int) -> int:
         for k, a, b in self.stages:
             if k == FBANK:
-                D = self.fbank.get("num_bins", 23) + int(self.fbank.get("use_energy", False))
+                D = self._fbank_dim()
+            elif k == FBANK_PITCH:
+                D = self._fbank_dim() + self.pitch_rows(0)[1]
             elif k == SPLICE:
                 D *= 1 + a + b
             elif k == DELTAS:
@@ -136,16 +241,77 @@ class FeaturePipeline:
         for k, a, b in self.stages:
             if k == FBANK:
                 T = fbank_num_frames(T, self.fbank)
+            elif k == FBANK_PITCH:
+                T = paste_frames([fbank_num_frames(T, self.fbank), self.pitch_rows(T)[0]], a)
             elif k == SUBSAMPLE:
                 T = T * -a if a < 0 else (max(0, (T - b + a - 1) // a) if T > b else 0)
         return T
+
+
+def _inner_pipe(spec: str) -> Optional[List[List[str]]]:
+    """The argument vectors of an input of paste-feats that is itself a pipe, "ark[,s,cs]:tool ... | tool ... |"; None otherwise."""
+    head, sep, cmd = spec.partition(":")
+    if not sep or head.split(",")[0] != "ark" or any(o not in ("s", "cs") for o in head.split(",")[1:]) or not cmd.rstrip().endswith("|"):
+        return None
+    segs = _split_pipe(cmd.rstrip()[:-1])
+    if segs is None or any(not s.strip() for s in segs):
+        return None
+    try:
+        return [shlex.split(s) for s in segs]
+    except ValueError:
+        return None
+
+
+def _parse_paste_head(argv: List[str]) -> Optional[FeaturePipeline]:
+    """paste-feats [--length-tolerance=N] "<fbank pipe>" "<pitch pipe>" ark:- (asr_egs/wsj/steps/make_fbank_pitch.sh:117-121): both
+    inner pipes over one wav table, every option one of the device extractors'.  None leaves the rspecifier to the shell."""
+    r = _options(argv, {"length-tolerance": int})
+    if r is None or len(r[1]) != 3 or r[1][2] != "ark:-" or r[0].get("length-tolerance", 0) < 0:
+        return None
+    fb, pt = _inner_pipe(r[1][0]), _inner_pipe(r[1][1])
+    if fb is None or pt is None or len(fb) != 1 or len(pt) != 2:
+        return None
+    if [os.path.basename(a[0]) for a in fb + pt] != ["compute-fbank-feats", "compute-kaldi-pitch-feats", "process-kaldi-pitch-feats"]:
+        return None
+    args = [_with_config(a[1:]) for a in fb + pt]
+    if any(a is None for a in args):
+        return None
+    known = {k: t for k, (_, t) in FBANK_OPTIONS.items()}
+    known.update({"channel": int, "min-duration": float, "output-format": str, "verbose": int})
+    rf = _options(args[0], known)
+    if rf is None or len(rf[1]) != 2 or rf[1][1] != "ark:-":
+        return None
+    o = rf[0]
+    if o.get("output-format", "kaldi") != "kaldi" or not o.get("round-to-power-of-two", True) or o.get("window-type", "povey") not in WINDOW_TYPES:
+        return None
+    compute_flags, process_flags = _pitch_flags()
+    rc = _options(args[1], {**{k: t for k, (_, t) in compute_flags.items()}, "verbose": int})
+    rp = _options(args[2], {**{k: t for k, (_, t) in process_flags.items()}, "verbose": int, "srand": int})
+    if rc is None or rp is None or len(rc[1]) != 2 or rc[1][1] != "ark:-" or rp[1] != ["ark:-", "ark:-"]:
+        return None
+    oc = rc[0]   # what the device extractor refuses (eesen_pitch_create) stays with the reference's tool
+    if oc.get("preemphasis-coefficient", 0.0) != 0.0 or oc.get("frames-per-chunk", 0) != 0 or oc.get("simulate-first-pass-online", False) or oc.get("nccf-ballast-online", False):
+        return None
+    src = _wav_source(rf[1][0])
+    if src is None or src != _wav_source(rc[1][0]):
+        return None
+    pitch = {compute_flags[k][0]: v for k, v in oc.items() if k in compute_flags}
+    pitch.update({process_flags[k][0]: v for k, v in rp[0].items() if k in process_flags})
+    tol = r[0].get("length-tolerance", 0)
+    pipe = FeaturePipeline(source=rf[1][0], fbank={FBANK_OPTIONS[k][0]: v for k, v in o.items() if k in FBANK_OPTIONS}, pitch=pitch, tolerance=tol,
+                           channel=o.get("channel", -1), min_duration=o.get("min-duration", 0.0))
+    pipe.stages.append((FBANK_PITCH, tol, 0))
+    return pipe
 
 
 def parse_feature_pipeline(rspecifier: str) -> Optional[FeaturePipeline]:
     head, sep, cmd = rspecifier.partition(":")
     if not sep or head.split(",")[0] != "ark" or not cmd.rstrip().endswith("|"):
         return None
-    segs = [s.strip() for s in cmd.rstrip().rstrip("|").split("|")]
+    segs = _split_pipe(cmd.rstrip().rstrip("|"))       # quote-aware: an input of paste-feats may be a pipe of its own
+    if segs is None:
+        return None
+    segs = [s.strip() for s in segs]
     if not segs or any(not s for s in segs):
         return None
     pipe = None
@@ -155,6 +321,11 @@ def parse_feature_pipeline(rspecifier: str) -> Optional[FeaturePipeline]:
         except ValueError:
             return None
         tool, argv = os.path.basename(argv[0]), argv[1:]
+        if i == 0 and tool == "paste-feats":              # featbin/paste-feats.cc over the two extractors: the pipe starts at the audio
+            pipe = _parse_paste_head(argv)
+            if pipe is None:
+                return None
+            continue
         if i == 0 and tool == "compute-fbank-feats":      # featbin/compute-fbank-feats.cc: the pipe starts at the audio
             known = {k: t for k, (_, t) in FBANK_OPTIONS.items()}
             known.update({"channel": int, "min-duration": float, "output-format": str})
@@ -323,6 +494,11 @@ def read_raw(pipe: FeaturePipeline, source: Optional[str] = None, warn=None) -> 
         if mat.shape[0] == 0:
             warn(f"Empty feature matrix for key {key}")
             continue
+        if pipe.pitch is not None:      # paste-feats' own warning (paste-feats.cc:44-49) where the two extractors' lengths do not meet
+            counts = [fbank_num_frames(mat.shape[0], pipe.fbank), pipe.pitch_rows(mat.shape[0])[0]]
+            if paste_frames(counts, pipe.tolerance) == 0:
+                warn(f"Length mismatch {max(counts)} vs. {min(counts)} for utt {key} exceeds tolerance {pipe.tolerance}")
+                continue
         frames = pipe.out_frames(mat.shape[0])
         if frames == 0:
             warn(f"For utterance {key}, output would have no rows, producing no output.")

@@ -381,6 +381,31 @@ def read_mat64_file(rxfilename: str) -> np.ndarray:
         return _read_matrix64(f)
 
 
+def read_mat_file(rxfilename: str) -> np.ndarray:
+    """ReadKaldiObject(rxfilename, Matrix<BaseFloat>*): `file`, `file:offset` or `cmd |`."""
+    loc, off = rxfilename, 0
+    if not loc.rstrip().endswith("|") and ":" in loc and loc.rsplit(":", 1)[1].isdigit():
+        loc, o = loc.rsplit(":", 1)
+        off = int(o)
+    with _open(loc) as f:
+        if off:
+            f.seek(off)
+        return np.asarray(_read_matrix(f), np.float32)
+
+
+def _matrix_bytes(m: np.ndarray, text: bool) -> bytes:
+    if text:
+        return b" [" + b"".join(b"\n  " + " ".join(repr(float(np.float32(v))) for v in r).encode() + b" " for r in m) + b"]\n"
+    return b"\x00BFM " + b"\x04" + struct.pack("<i", m.shape[0]) + b"\x04" + struct.pack("<i", m.shape[1]) + m.tobytes()
+
+
+def write_mat_file(wxfilename: str, m: np.ndarray, binary: bool = True) -> None:
+    """WriteKaldiObject(Matrix<BaseFloat>, wxfilename, binary): `file`, `-` or `| cmd`."""
+    with _open_out(wxfilename) as f:
+        f.write(_matrix_bytes(np.ascontiguousarray(m, np.float32), not binary))
+        f.flush()
+
+
 def read_token_map(spec: str) -> Dict[str, str]:
     """The utt2spk map behind RandomAccessTableReaderMapped (util/kaldi-table.h): a text archive of `utt spk` lines."""
     kind, path, _ = _parse_specifier(spec)
@@ -414,10 +439,7 @@ def write_mat_ark(path: str, items, text: bool = False, scp_path: str = None):
             pos += len(key.encode()) + 1
             if scp:
                 scp.write(f"{key} {path}:{pos}\n")
-            if text:
-                body = b" [" + b"".join(b"\n  " + " ".join(repr(float(np.float32(v))) for v in r).encode() + b" " for r in m) + b"]\n"
-            else:
-                body = b"\x00BFM " + b"\x04" + struct.pack("<i", m.shape[0]) + b"\x04" + struct.pack("<i", m.shape[1]) + m.tobytes()
+            body = _matrix_bytes(m, text)
             f.write(body)
             pos += len(body)
             f.flush()

@@ -741,10 +741,30 @@ int eesen_feeder_release(eesen_feeder_t* f, int slot);
  * The kernel writes straight into the packed buffer the next stage reads.  Every waveform submitted gets a fresh dither key (a counter
  * per feeder), so an epoch's noise differs from the last one's while a feeder fed the same sequence reproduces its batches. */
 #define EESEN_FEAT_FBANK 5
+/* paste-feats --length-tolerance=a "compute-fbank-feats ..." "compute-kaldi-pitch-feats ... | process-kaldi-pitch-feats ..." in front of
+ * the filters (the tonal recipes' features, asr_egs/wsj/steps/make_fbank_pitch.sh:117-121; INTEGRATION.md "Fbank + pitch"): legal only
+ * as stage 0, configured beforehand by eesen_feeder_set_fbank AND eesen_feeder_set_pitch, whose samp_freq must agree; a = the length
+ * tolerance (>= 0), b is unused.  Input as for EESEN_FEAT_FBANK ([samples x 1], D_in = 1).  The samples go up once; the filterbank,
+ * the four pitch launches (post-processing included) and the join run back to back on the feeder's stream.  Output columns: the
+ * filterbank's, then the processed pitch's.  Rows: eesen_feat_paste_frames of the filterbank's frame count and the processed pitch
+ * matrix's row count (frames + delay, 0 without a frame) -- an utterance it leaves without rows is dropped as above.  A waveform's
+ * key (the feeder's counter) is the same for the dither and for the delta-pitch noise.  A batch beyond 2^30 filterbank frames or 2^28
+ * pitch frames is EESEN_ERR_INVALID. */
+#define EESEN_FEAT_FBANK_PITCH 6
 typedef struct eesen_feat_stage { int kind, a, b; } eesen_feat_stage_t;
 int eesen_feeder_set_pipeline(eesen_feeder_t* f, const eesen_feat_stage_t* stages, int n_stages); /* 0 stages: plain submit */
 struct eesen_fbank_opts;
 int eesen_feeder_set_fbank(eesen_feeder_t* f, const struct eesen_fbank_opts* opts);   /* before a pipeline that starts with EESEN_FEAT_FBANK */
+struct eesen_pitch_opts;
+int eesen_feeder_set_pitch(eesen_feeder_t* f, const struct eesen_pitch_opts* opts);   /* and before one that starts with EESEN_FEAT_FBANK_PITCH; carries eesen_pitch_create's refusals */
+/* AppendFeats' length rule (src/featbin/paste-feats.cc:35-56) on the row counts of one utterance in n_inputs (>= 1) tables, host only:
+ * *out <- the shortest count, or 0 (the utterance is dropped) when the longest exceeds it by more than tolerance or an input is empty */
+int eesen_feat_paste_frames(const int* frames, int n_inputs, int tolerance, int* out);
+/* paste-feats for callers that hold tables: inputs[j][s] -> host matrix [frames[j * S + s] x dims[j]] row-major of input j (2..4
+ * inputs), out[s] -> host room for [rows x sum of dims] (may be NULL for a dropped utterance), frames_out[s] (may be NULL) <- rows by the
+ * rule above.  One upload, the feeder's join kernel, one copy back on `stream`.  Synchronises. */
+int eesen_paste_feats(int device, void* stream, const float* const* const* inputs, const int* dims, int n_inputs, const int* frames,
+                      int S, int tolerance, float* const* out, int* frames_out);
 /* feature dimension / frame count behind the pipeline for an utterance of [frames_in x D_in] (either output may be NULL) */
 int eesen_feeder_pipeline_shape(eesen_feeder_t* f, int D_in, int frames_in, int* D_out, int* frames_out);
 /* cmvn[s] -> 2 x Dc floats (offsets, then scales), Dc = the dimension in front of the CMVN stage; NULL without such a stage */
