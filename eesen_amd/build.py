@@ -15,7 +15,7 @@ CSRC = os.path.join(_DIR, "csrc")
 LIBDIR = os.path.join(_DIR, "lib")
 LIB = os.path.join(LIBDIR, "libeesen_hip.so")
 SOURCES = ["gemm.hip", "lstm.hip", "lstm_persistent.hip", "rec_plan.cpp", "ctc.hip", "ctc_decode.hip", "edit_distance.hip", "ce.hip", "optim.hip", "feeder.hip", "fbank.hip", "fbank_host.cpp", "pitch.hip", "pitch_host.cpp", "net.cpp", "ctc_host.cpp", "ce_host.cpp", "nnet_format.cpp", "lm.cpp", "lex.cpp", "capi.cpp", "comm.cpp"]
-HEADERS = ["common.h", "guard.h", "kernels.h", "rec_kernels.h", "net.h", "lm.h", "lex.h", "handles.h", "fbank.h", "pitch.h", "dither.h", "tuning.h", "lstm_fwd_bf_step.inc", "ctc_word_beam.inc", os.path.join("..", "..", "include", "eesen_hip.h")]
+HEADERS = ["common.h", "guard.h", "kernels.h", "rec_kernels.h", "net.h", "lm.h", "lex.h", "handles.h", "fbank.h", "pitch.h", "feat_layout.h", "dither.h", "tuning.h", "lstm_fwd_bf_step.inc", "ctc_word_beam.inc", os.path.join("..", "..", "include", "eesen_hip.h")]
 FLAGS = (os.environ.get("EESEN_BUILD_DEFS", "").split()) + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # pitch.hip's search is float32 in a fixed order that a numpy restatement reproduces bit for bit: no fused multiply-add anywhere in that
 # file, the bodies of __fmul_rn / __fadd_rn in the HIP headers included (a pragma in the file does not reach those)

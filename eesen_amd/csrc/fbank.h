@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.h"
+#include "feat_layout.h"
 
 namespace eesen {
 

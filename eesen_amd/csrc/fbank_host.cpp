@@ -158,11 +158,9 @@ struct Fbank {
   FbankDev dev;
   int device;
   hipStream_t stream;
-  PinBuf wave_h, out_h, meta_h;
+  PinBuf wave_h, out_h, tab_h;
   DevBuf<float> wave_d, out_d;
-  DevBuf<long> off_d;           // off | out_off
-  DevBuf<int> cnt_d;            // nsamp | prefix (S + 1)
-  DevBuf<unsigned long long> ids_d;
+  DevBuf<long> tab_d;           // the batch's tables (feat_layout.h)
 
   bool on_device = false;       // the tables go up with the first compute(): options, shapes and filters need no device
 
@@ -186,51 +184,33 @@ struct Fbank {
       on_device = true;
     }
     EESEN_HIP_CHECK(hipSetDevice(device));
-    // S offsets in, S offsets out, S ids, then S sample counts and S + 1 frame prefixes
-    const size_t meta_bytes = (size_t)S * (2 * sizeof(long) + sizeof(unsigned long long)) + (size_t)(2 * S + 1) * sizeof(int);
-    long* off_h = static_cast<long*>(meta_h.reserve(meta_bytes));
-    long* out_off_h = off_h + S;
-    unsigned long long* ids_h = reinterpret_cast<unsigned long long*>(out_off_h + S);
-    int* nsamp_h = reinterpret_cast<int*>(ids_h + S);
-    int* prefix_h = nsamp_h + S;
-    long total = 0, total_out = 0;
-    long frames_all = 0;
+    // the batch's tables as the feeder's filterbank head lays them out: one boundary (the samples), one block, one upload
+    const size_t words = batch_words(1, S, kHeadFbank);
+    const BatchTables h = batch_carve(tab_h.reserve(words * 8), 1, S, kHeadFbank);
+    const FbankTotals tot = fbank_layout(nsamp, S, plan.dim, [this](int n) { return plan.num_frames(n); }, h.off, h.prefix, h.fb_off);
     for (int s = 0; s < S; ++s) {
-      EESEN_REQUIRE(nsamp[s] >= 0, EESEN_ERR_INVALID, "negative sample count");
       EESEN_REQUIRE(nsamp[s] == 0 || waves[s] != nullptr, EESEN_ERR_INVALID, "null waveform");
-      const int fr = plan.num_frames(nsamp[s]);
-      EESEN_REQUIRE(fr == 0 || bench_iters > 0 || (out_host && out_host[s] != nullptr), EESEN_ERR_INVALID, "null output matrix");
-      off_h[s] = total;
-      out_off_h[s] = total_out;
-      nsamp_h[s] = nsamp[s];
-      prefix_h[s] = (int)frames_all;
-      ids_h[s] = utt_ids ? utt_ids[s] : (unsigned long long)s;
-      total += nsamp[s];
-      total_out += (long)fr * plan.dim;
-      frames_all += fr;
-      EESEN_REQUIRE(frames_all < (1L << 30), EESEN_ERR_INVALID, "too many frames in one call");
+      EESEN_REQUIRE(h.prefix[s + 1] == h.prefix[s] || bench_iters > 0 || (out_host && out_host[s] != nullptr), EESEN_ERR_INVALID, "null output matrix");
+      h.frames[s] = nsamp[s];
+      h.ids[s] = key_of(utt_ids, 0, s);
     }
-    prefix_h[S] = (int)frames_all;
-    if (!frames_all) return;
-    float* wh = static_cast<float*>(wave_h.reserve((size_t)total * sizeof(float)));
+    if (!tot.frames) return;
+    float* wh = static_cast<float*>(wave_h.reserve((size_t)tot.samp * sizeof(float)));
     for (int s = 0; s < S; ++s)
-      if (nsamp[s]) std::memcpy(wh + off_h[s], waves[s], (size_t)nsamp[s] * sizeof(float));
-    float* oh = static_cast<float*>(out_h.reserve((size_t)total_out * sizeof(float)));
-    wave_d.reserve((size_t)total);
-    out_d.reserve((size_t)total_out);
-    off_d.reserve((size_t)2 * S);
-    cnt_d.reserve((size_t)2 * S + 1);
-    ids_d.reserve((size_t)S);
-    EESEN_HIP_CHECK(hipMemcpyAsync(wave_d.p, wh, (size_t)total * sizeof(float), hipMemcpyHostToDevice, stream));
-    EESEN_HIP_CHECK(hipMemcpyAsync(off_d.p, off_h, (size_t)2 * S * sizeof(long), hipMemcpyHostToDevice, stream));
-    EESEN_HIP_CHECK(hipMemcpyAsync(cnt_d.p, nsamp_h, (size_t)(2 * S + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
-    EESEN_HIP_CHECK(hipMemcpyAsync(ids_d.p, ids_h, (size_t)S * sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    fbank_launch(plan, dev, wave_d.p, off_d.p, cnt_d.p, cnt_d.p + S, ids_d.p, S, (int)frames_all, out_d.p, off_d.p + S, stream);
+      if (nsamp[s]) std::memcpy(wh + h.off[s], waves[s], (size_t)nsamp[s] * sizeof(float));
+    float* oh = static_cast<float*>(out_h.reserve((size_t)tot.out * sizeof(float)));
+    wave_d.reserve((size_t)tot.samp);
+    out_d.reserve((size_t)tot.out);
+    tab_d.reserve(words);
+    const BatchTables d = batch_carve(tab_d.p, 1, S, kHeadFbank);
+    EESEN_HIP_CHECK(hipMemcpyAsync(wave_d.p, wh, (size_t)tot.samp * sizeof(float), hipMemcpyHostToDevice, stream));
+    EESEN_HIP_CHECK(hipMemcpyAsync(tab_d.p, h.off, words * 8, hipMemcpyHostToDevice, stream));
+    auto launch = [&] { fbank_launch(plan, dev, wave_d.p, d.off, d.frames, d.prefix, d.ids, S, tot.frames, out_d.p, d.fb_off, stream); };
+    launch();
     if (bench_iters > 0) {
       DevEvent t0(true), t1(true);
       t0.record(stream);
-      for (int i = 0; i < bench_iters; ++i)
-        fbank_launch(plan, dev, wave_d.p, off_d.p, cnt_d.p, cnt_d.p + S, ids_d.p, S, (int)frames_all, out_d.p, off_d.p + S, stream);
+      for (int i = 0; i < bench_iters; ++i) launch();
       t1.record(stream);
       t1.wait();
       float ms = 0.f;
@@ -238,11 +218,11 @@ struct Fbank {
       *avg_ms = ms / bench_iters;
       return;
     }
-    EESEN_HIP_CHECK(hipMemcpyAsync(oh, out_d.p, (size_t)total_out * sizeof(float), hipMemcpyDeviceToHost, stream));
+    EESEN_HIP_CHECK(hipMemcpyAsync(oh, out_d.p, (size_t)tot.out * sizeof(float), hipMemcpyDeviceToHost, stream));
     EESEN_HIP_CHECK(hipStreamSynchronize(stream));
     for (int s = 0; s < S; ++s) {
-      const long n = (long)(prefix_h[s + 1] - prefix_h[s]) * plan.dim;
-      if (n) std::memcpy(out_host[s], oh + out_off_h[s], (size_t)n * sizeof(float));
+      const long n = (long)(h.prefix[s + 1] - h.prefix[s]) * plan.dim;
+      if (n) std::memcpy(out_host[s], oh + h.fb_off[s], (size_t)n * sizeof(float));
     }
   }
 };

@@ -21,22 +21,6 @@
 #include "pitch.h"
 
 namespace eesen {
-
-// AppendFeats' length rule (src/featbin/paste-feats.cc:35-56) on row counts alone: the shortest input's rows, or none when the
-// longest exceeds it by more than the tolerance or an input is empty.  The feeder's combined head, eesen_paste_feats and the tools
-// all decide through this one function.
-int paste_frames(const int* frames, int n_inputs, int tolerance) {
-  EESEN_REQUIRE(n_inputs >= 1, EESEN_ERR_INVALID, "paste-feats: need at least one input");
-  EESEN_REQUIRE(tolerance >= 0, EESEN_ERR_INVALID, "paste-feats: --length-tolerance must not be negative");
-  int min_len = frames[0], max_len = frames[0];
-  for (int i = 0; i < n_inputs; ++i) {
-    EESEN_REQUIRE(frames[i] >= 0, EESEN_ERR_INVALID, "negative frame count");
-    min_len = std::min(min_len, frames[i]);
-    max_len = std::max(max_len, frames[i]);
-  }
-  return (max_len - min_len > tolerance || min_len == 0) ? 0 : min_len;
-}
-
 namespace {
 
 template <int V>  // V = floats per thread (4: D % 4 == 0 and 16-byte aligned rows, else 1)
@@ -156,11 +140,14 @@ __global__ __launch_bounds__(256) void feat_paste_kernel(PasteArgs a, float* __r
   }
 }
 
+// the grid of a launch with utterance = blockIdx.y over an output whose largest utterance holds `biggest` floats: one element per
+// thread (a stage is latency-bound otherwise), at most 2048 blocks along x
+dim3 stage_grid(long biggest, int S) { return dim3((unsigned)std::min<long>(std::max<long>(cdivl(biggest, 256), 1), 2048), S); }
+
 void paste_launch(PasteArgs a, float* dst, const long* off_out, const int* fr_out, int Dout, int S, long biggest, hipStream_t st) {
   a.start[0] = 0;
   for (int j = 1; j < kPasteMaxInputs; ++j) a.start[j] = j < a.n ? a.start[j - 1] + a.dim[j - 1] : 0;
-  const int bx = (int)std::min<long>(std::max<long>(cdivl(biggest, 256), 1), 2048);
-  hipLaunchKernelGGL(feat_paste_kernel, dim3(bx, S), dim3(256), 0, st, a, dst, off_out, fr_out, Dout);
+  hipLaunchKernelGGL(feat_paste_kernel, dim3(stage_grid(biggest, S)), dim3(256), 0, st, a, dst, off_out, fr_out, Dout);
   check_launch("feat_paste_kernel");
 }
 
@@ -192,36 +179,22 @@ struct Feeder {
   struct Slot {
     // Pinned staging, owned only: its reuse is ordered by `ready` (the slot's copies and kernels have run), not by a use of its own.
     PinBuf host;            // the utterance matrices back to back
-    PinBuf off_h;           // S offsets (floats) + S frame counts packed behind them as ints
+    PinBuf tab_h;           // the batch's tables (BatchTables, feat_layout.h): one block here, one on the device, one upload
+    DevBuf<long> tab_d;
     DevBuf<float> packed, out;
-    DevBuf<long> off_d;
-    DevBuf<int> frames_d;
     DevEvent ready, consumed;
     bool in_flight = false, has_consumer = false;
     int T = 0, S = 0, D = 0, ld = 0;
-    // feature front end: the second packed buffer of the stage ping-pong, per-boundary offsets / frame counts, CMVN vectors
+    // feature front end: the second packed buffer of the stage ping-pong, the CMVN vectors
     DevBuf<float> packed2, cmvn_d;
-    PinBuf meta_h;            // (n_stages + 1) x S offsets, then as many frame counts (ints)
     PinBuf cmvn_h;
-    DevBuf<long> offs_d;
-    DevBuf<int> frs_d;
-    // filterbank head stage: the frame prefix (S + 1) and the dither keys of the batch
-    PinBuf fb_meta_h;
-    DevBuf<int> fb_prefix_d;
-    DevBuf<unsigned long long> fb_ids_d;
-    // filterbank + pitch head stage: the batch's tables in one pinned block and one device block (8-byte words: the PitchUtt table,
-    // the filterbank's and the processed pitch's offsets, the noise keys, the filterbank's frame prefix), the filterbank matrix
-    // before the join, and the pitch tracker's scratch
-    PinBuf fp_meta_h;
-    DevBuf<unsigned long long> fp_meta_d;
-    DevBuf<float> fp_fbank, pt_down, pt_nccf_pitch, pt_nccf_pov, pt_avg, pt_raw, pt_proc;
-    DevBuf<PitchSums> pt_sums;
-    DevBuf<unsigned short> pt_backptr;
-    DevBuf<int> pt_taken;
-    DevBuf<double> pt_scan;
+    // filterbank + pitch head stage: the filterbank matrix before the join, and the pitch tracker's scratch
+    DevBuf<float> fbank;
+    PitchScratch pitch;
   };
   struct Stage { int kind, a, b; size_t scale_off; };
   std::vector<Stage> pipe;
+  std::vector<long> tab;    // a batch's tables while it can still be refused: no slot is taken before they are complete
   DevBuf<float> scales_d;
   // EESEN_FEAT_FBANK, the head stage that turns waveforms into features (fbank.hip); every waveform submitted gets a dither key of its own
   std::unique_ptr<FbankPlan> fb_plan;
@@ -257,6 +230,10 @@ struct Feeder {
     sl.in_flight = sl.has_consumer = false;
     return sl;
   }
+  void drain() {   // batches in flight still read the tables a set_* call is about to replace
+    for (auto& s : slots)
+      if (s.in_flight) s.ready.wait();
+  }
   // the raw matrices back to back in the slot's pinned staging (a quarter more when it has to grow), rows made contiguous
   static float* pack(Slot& sl, const float* const* utts, const int* frames, const int* strides, const long* off, int S, int D, long total) {
     float* host = static_cast<float*>(sl.host.reserve((size_t)total * sizeof(float), ((size_t)total + (size_t)total / 4) * sizeof(float)));
@@ -266,52 +243,6 @@ struct Feeder {
       else for (int t = 0; t < frames[s]; ++t) std::memcpy(host + off[s] + (long)t * D, utts[s] + (long)t * st, (size_t)D * sizeof(float));
     }
     return host;
-  }
-
-  int submit(const float* const* utts, const int* frames, const int* strides, int S, int D) {
-    EESEN_REQUIRE(S > 0 && D > 0, EESEN_ERR_INVALID, "need at least one utterance and one feature column");
-    EESEN_HIP_CHECK(hipSetDevice(device));
-    long total = 0;
-    int T = 0;
-    for (int s = 0; s < S; ++s) {
-      EESEN_REQUIRE(frames[s] >= 0, EESEN_ERR_INVALID, "negative frame count");
-      EESEN_REQUIRE(frames[s] == 0 || utts[s] != nullptr, EESEN_ERR_INVALID, "null utterance matrix");
-      EESEN_REQUIRE(!strides || frames[s] == 0 || strides[s] >= D, EESEN_ERR_INVALID, "row stride smaller than the feature dimension");
-      total += (long)frames[s] * D;
-      T = std::max(T, frames[s]);
-    }
-    EESEN_REQUIRE(T > 0, EESEN_ERR_INVALID, "every utterance is empty");
-    int id = 0;
-    Slot& sl = next_slot(&id);
-    long* off_h = static_cast<long*>(sl.off_h.reserve((size_t)S * (sizeof(long) + sizeof(int))));
-    int* frames_h = reinterpret_cast<int*>(off_h + S);
-    long o = 0;
-    for (int s = 0; s < S; ++s) {
-      off_h[s] = o;
-      frames_h[s] = frames[s];
-      o += (long)frames[s] * D;
-    }
-    const float* host = pack(sl, utts, frames, strides, off_h, S, D, total);
-    const int ld = (D + 3) / 4 * 4;  // rows of the assembled matrix start on 16 bytes (GEMM operand alignment)
-    sl.packed.reserve((size_t)total);
-    sl.off_d.reserve((size_t)S);
-    sl.frames_d.reserve((size_t)S);
-    const bool fresh = sl.out.reserve((size_t)T * S * ld);
-    if (ld != D && fresh) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, sl.out.cap * sizeof(float), copy));  // pad columns stay zero
-    else if (ld != D) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, (size_t)T * S * ld * sizeof(float), copy));
-    if (total) EESEN_HIP_CHECK(hipMemcpyAsync(sl.packed.p, host, (size_t)total * sizeof(float), hipMemcpyHostToDevice, copy));
-    EESEN_HIP_CHECK(hipMemcpyAsync(sl.off_d.p, off_h, (size_t)S * sizeof(long), hipMemcpyHostToDevice, copy));
-    EESEN_HIP_CHECK(hipMemcpyAsync(sl.frames_d.p, frames_h, (size_t)S * sizeof(int), hipMemcpyHostToDevice, copy));
-    const bool vec = D % 4 == 0;  // then every packed frame and every output row is 16-byte aligned
-    const long n = (long)T * S * (vec ? D / 4 : D);
-    const int blocks = (int)std::min<long>(cdivl(n, 256), 256L * 32);
-    if (vec) interleave_kernel<4><<<blocks, 256, 0, copy>>>(sl.packed.p, sl.off_d.p, sl.frames_d.p, sl.out.p, T, S, D, ld);
-    else interleave_kernel<1><<<blocks, 256, 0, copy>>>(sl.packed.p, sl.off_d.p, sl.frames_d.p, sl.out.p, T, S, D, ld);
-    check_launch("interleave_kernel");
-    sl.ready.record(copy);
-    sl.in_flight = true;
-    sl.T = T; sl.S = S; sl.D = D; sl.ld = ld;
-    return id;
   }
 
   // ---- feature front end (see feat_stage_kernel) ----
@@ -355,8 +286,7 @@ struct Feeder {
       np.push_back(g);
     }
     EESEN_REQUIRE(n_cmvn <= 1, EESEN_ERR_INVALID, "at most one CMVN stage");
-    for (auto& s : slots)  // batches in flight still read the old scale table
-      if (s.in_flight) s.ready.wait();
+    drain();
     if (!scales.empty()) {
       scales_d.reserve(scales.size());
       EESEN_HIP_CHECK(hipMemcpy(scales_d.p, scales.data(), scales.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -366,16 +296,14 @@ struct Feeder {
   void set_fbank(const eesen_fbank_opts_t& o) {
     std::unique_ptr<FbankPlan> np(new FbankPlan(o));
     EESEN_HIP_CHECK(hipSetDevice(device));
-    for (auto& s : slots)  // batches in flight still read the old tables
-      if (s.in_flight) s.ready.wait();
+    drain();
     fb_dev.upload(*np);
     fb_plan.swap(np);
   }
   void set_pitch(const eesen_pitch_opts_t& o) {
     std::unique_ptr<PitchPlan> np(new PitchPlan(o));
     EESEN_HIP_CHECK(hipSetDevice(device));
-    for (auto& s : slots)  // batches in flight still read the old tables
-      if (s.in_flight) s.ready.wait();
+    drain();
     pt_dev.upload(*np);
     pt_plan.swap(np);
   }
@@ -408,134 +336,91 @@ struct Feeder {
       const int fr[2] = {fb_plan->num_frames(T), pitch_rows(T)};
       return paste_frames(fr, 2, g.a);
     }
-    if (g.kind != EESEN_FEAT_SUBSAMPLE) return T;
-    if (g.a < 0) return T * (-g.a);
-    return T > g.b ? (T - g.b + g.a - 1) / g.a : 0;   // number of k = offset, offset + n, ... < T (subsample-feats.cc:82-84)
+    return g.kind == EESEN_FEAT_SUBSAMPLE ? subsample_frames(T, g.a, g.b) : T;
   }
   int pipeline_dim(int D) const { for (const Stage& g : pipe) D = stage_dim(g, D); return D; }
   int pipeline_frames(int T) const { for (const Stage& g : pipe) T = stage_frames(g, T); return T; }
-  int cmvn_dim(int D) const {  // feature dimension in front of the CMVN stage (0: no such stage)
-    for (const Stage& g : pipe) { if (g.kind == EESEN_FEAT_CMVN) return D; D = stage_dim(g, D); }
-    return 0;
-  }
 
-  // EESEN_FEAT_FBANK_PITCH: what a batch may hold, checked before anything of it is staged -- fbank_launch's and Pitch::layout's bounds
-  void check_fbank_pitch(const int* frames, int S) const {
-    require_same_rate();
-    long fb_all = 0, pt_all = 0;
-    for (int s = 0; s < S; ++s) {
-      EESEN_REQUIRE(frames[s] >= 0, EESEN_ERR_INVALID, "negative frame count");
-      fb_all += fb_plan->num_frames(frames[s]);
-      pt_all += pt_plan->num_frames(frames[s]);
-      EESEN_REQUIRE(fb_all < (1L << 30) && pt_all < kPitchMaxFrames, EESEN_ERR_INVALID, "too many frames in one batch");
+  // What the head stage of a batch needs beyond its tables: the totals of the two layouts.
+  struct Head { int kind = kHeadNone; FbankTotals fb; PitchTotals pt; };
+
+  // The head stage over the slot's samples (boundary 0, already on their way): the filterbank alone writes boundary 1; with the pitch
+  // tracker beside it the filterbank writes its scratch matrix, the tracker its own, and the join writes boundary 1.  Everything is
+  // enqueued on the copy stream and reads the batch's tables from the slot's device block (`d`).
+  void head_stage(Slot& sl, const Head& h, const BatchTables& d, int S, const float* wave, float* dst, int Dout, long biggest) {
+    float* fb_out = dst;
+    if (h.kind == kHeadFbankPitch) {
+      sl.fbank.reserve((size_t)std::max(h.fb.out, 1L));
+      fb_out = sl.fbank.p;
     }
-  }
-  // The head stage over the slot's samples (boundary 0, already on their way): the filterbank into its scratch matrix, the four pitch
-  // launches into theirs, then the join into boundary 1.  Everything is enqueued on the copy stream; the batch's tables travel in the
-  // slot's pinned block, which the slot's `ready` event orders, so nothing here waits for the device.
-  void submit_fbank_pitch(Slot& sl, const int* fr_h, int S, const float* wave, float* dst, int Dout, long biggest) {
-    const PitchPlan& pp = *pt_plan;
-    const size_t words = (size_t)S * (sizeof(PitchUtt) / 8 + 3) + (size_t)(S + 2) / 2;
-    static_assert(sizeof(PitchUtt) % 8 == 0, "the PitchUtt table is laid out in 8-byte words");
-    unsigned long long* meta = static_cast<unsigned long long*>(sl.fp_meta_h.reserve(words * 8));
-    PitchUtt* utt_h = reinterpret_cast<PitchUtt*>(meta);
-    long* fb_off_h = reinterpret_cast<long*>(utt_h + S);
-    long* proc_off_h = fb_off_h + S;
-    unsigned long long* ids_h = reinterpret_cast<unsigned long long*>(proc_off_h + S);
-    int* prefix_h = reinterpret_cast<int*>(ids_h + S);
-    long fb_all = 0, pt_all = 0, samp_all = 0, down_all = 0, proc_all = 0;
-    for (int s = 0; s < S; ++s) {
-      PitchUtt u = PitchUtt();
-      u.nsamp = fr_h[s];
-      u.frames = pp.num_frames(u.nsamp, &u.f1, &u.n1, &u.n2);
-      u.wave_off = samp_all; u.down_off = down_all; u.proc_off = proc_all;
-      u.prefix = (int)pt_all;
-      u.id = ids_h[s] = fb_next_id++;
-      utt_h[s] = u;
-      proc_off_h[s] = proc_all;
-      fb_off_h[s] = fb_all * fb_plan->dim;
-      prefix_h[s] = (int)fb_all;
-      samp_all += u.nsamp;
-      down_all += u.n2;
-      proc_all += u.frames ? (long)(u.frames + pp.opts.delay) * pp.proc_dim : 0;
-      pt_all += u.frames;
-      fb_all += fb_plan->num_frames(u.nsamp);
-    }
-    prefix_h[S] = (int)fb_all;
-    sl.fp_meta_d.reserve(words);
-    EESEN_HIP_CHECK(hipMemcpyAsync(sl.fp_meta_d.p, meta, words * 8, hipMemcpyHostToDevice, copy));
-    const PitchUtt* utt_d = reinterpret_cast<const PitchUtt*>(sl.fp_meta_d.p);
-    const long* fb_off_d = reinterpret_cast<const long*>(utt_d + S);
-    const long* proc_off_d = fb_off_d + S;
-    const unsigned long long* ids_d = reinterpret_cast<const unsigned long long*>(proc_off_d + S);
-    const int* prefix_d = reinterpret_cast<const int*>(ids_d + S);
-
-    sl.fp_fbank.reserve((size_t)std::max(fb_all * fb_plan->dim, 1L));
-    fbank_launch(*fb_plan, fb_dev, wave, sl.offs_d.p, sl.frs_d.p, prefix_d, ids_d, S, (int)fb_all, sl.fp_fbank.p, fb_off_d, copy);
-
-    const size_t F = (size_t)std::max(pt_all, 1L), ns = (size_t)pp.states;   // as Pitch::bufs, without the diagnostics
-    sl.pt_down.reserve((size_t)std::max(down_all, 1L));
-    sl.pt_sums.reserve((size_t)S);
-    sl.pt_nccf_pitch.reserve(F * ns);
-    sl.pt_nccf_pov.reserve(F * ns);
-    sl.pt_avg.reserve(F);
-    sl.pt_backptr.reserve(F * ns);
-    sl.pt_raw.reserve(F * 2);
-    sl.pt_scan.reserve(2 * (F + S));
-    sl.pt_proc.reserve((size_t)std::max(proc_all, 1L));
-    sl.pt_taken.reserve((size_t)S);
-    PitchBufs b;
-    b.utt = utt_d; b.S = S; b.total_frames = (int)pt_all;
-    b.wave = wave; b.down = sl.pt_down.p; b.sums = sl.pt_sums.p;
-    b.nccf_pitch = sl.pt_nccf_pitch.p; b.nccf_pov = sl.pt_nccf_pov.p; b.avg_norm_prod = sl.pt_avg.p;
-    b.backptr = sl.pt_backptr.p; b.fwd = nullptr; b.track = nullptr; b.taken = sl.pt_taken.p;
-    b.raw = sl.pt_raw.p; b.scan = sl.pt_scan.p; b.proc = sl.pt_proc.p;
-    pitch_downsample_launch(pp, pt_dev, b, copy);
-    pitch_nccf_launch(pp, pt_dev, b, copy);
-    pitch_viterbi_launch(pp, pt_dev, b, copy);
-    pitch_process_launch(pp, b, copy);
-
+    fbank_launch(*fb_plan, fb_dev, wave, d.off, d.frames, d.prefix, d.ids, S, h.fb.frames, fb_out, d.fb_off, copy);
+    if (h.kind != kHeadFbankPitch) return;
+    pitch_track_launch(*pt_plan, pt_dev, sl.pitch.reserve(*pt_plan, h.pt, S, d.utt, wave), true, copy);
     PasteArgs pa = PasteArgs();
     pa.n = 2;
-    pa.src[0] = sl.fp_fbank.p; pa.off[0] = fb_off_d; pa.dim[0] = fb_plan->dim;
-    pa.src[1] = sl.pt_proc.p; pa.off[1] = proc_off_d; pa.dim[1] = pp.proc_dim;
-    paste_launch(pa, dst, sl.offs_d.p + S, sl.frs_d.p + S, Dout, S, biggest, copy);
+    pa.src[0] = sl.fbank.p; pa.off[0] = d.fb_off; pa.dim[0] = fb_plan->dim;
+    pa.src[1] = sl.pitch.proc.p; pa.off[1] = d.proc_off; pa.dim[1] = pt_plan->proc_dim;
+    paste_launch(pa, dst, d.off + S, d.frames + S, Dout, S, biggest, copy);
   }
 
-  int submit_raw(const float* const* utts, const int* frames, const int* strides, const float* const* cmvn, int S, int D) {
-    if (pipe.empty()) return submit(utts, frames, strides, S, D);
+  // the zero-padded, time-major matrix of the slot from the packed utterances of the last boundary
+  void assemble(Slot& sl, const float* packed, const long* off, const int* frames, int T, int S, int D) {
+    const int ld = (D + 3) / 4 * 4;  // rows of the assembled matrix start on 16 bytes (GEMM operand alignment)
+    const bool fresh = sl.out.reserve((size_t)T * S * ld);
+    if (ld != D)  // pad columns stay zero
+      EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, (fresh ? sl.out.cap : (size_t)T * S * ld) * sizeof(float), copy));
+    const bool vec = D % 4 == 0;  // then every packed frame and every output row is 16-byte aligned
+    const long n = (long)T * S * (vec ? D / 4 : D);
+    const int blocks = (int)std::min<long>(cdivl(n, 256), 256L * 32);
+    if (vec) interleave_kernel<4><<<blocks, 256, 0, copy>>>(packed, off, frames, sl.out.p, T, S, D, ld);
+    else interleave_kernel<1><<<blocks, 256, 0, copy>>>(packed, off, frames, sl.out.p, T, S, D, ld);
+    check_launch("interleave_kernel");
+    sl.T = T; sl.S = S; sl.D = D; sl.ld = ld;
+  }
+
+  // One batch through the stages `pl` (none: the matrices as they are).  Two passes.  The first lays the batch out in `tab` and
+  // holds every refusal: it reads counts and compares pointers, takes no slot, waits for nothing and hands out no noise key.  The
+  // second takes the slot, packs, uploads (the payload and the tables: two copies) and enqueues the kernels; nothing synchronises.
+  int stage_batch(const std::vector<Stage>& pl, const float* const* utts, const int* frames, const int* strides, const float* const* cmvn, int S, int D) {
     EESEN_REQUIRE(S > 0 && D > 0, EESEN_ERR_INVALID, "need at least one utterance and one feature column");
-    EESEN_HIP_CHECK(hipSetDevice(device));
-    const int nst = (int)pipe.size(), nb = nst + 1;
-    const int Dc = cmvn_dim(D);
-    EESEN_REQUIRE(!Dc || cmvn, EESEN_ERR_INVALID, "the pipeline has a CMVN stage: per-utterance offset/scale vectors are required");
-    // dimensions and frame counts at every stage boundary
+    const int nst = (int)pl.size(), nb = nst + 1;
     std::vector<int> dims(nb);
     dims[0] = D;
-    for (int k = 0; k < nst; ++k) dims[k + 1] = stage_dim(pipe[k], dims[k]);
-    if (pipe[0].kind == EESEN_FEAT_FBANK_PITCH) check_fbank_pitch(frames, S);
-    int id = 0;
-    Slot& sl = next_slot(&id);
-    long* off_h = static_cast<long*>(sl.meta_h.reserve((size_t)nb * S * (sizeof(long) + sizeof(int))));
-    int* fr_h = reinterpret_cast<int*>(off_h + (size_t)nb * S);
-    std::vector<long> total(nb, 0);
-    int T = 0;
+    int Dc = 0;   // the feature dimension in front of the CMVN stage (0: no such stage)
+    for (int k = 0; k < nst; ++k) {
+      if (pl[k].kind == EESEN_FEAT_CMVN) Dc = dims[k];
+      dims[k + 1] = stage_dim(pl[k], dims[k]);
+    }
+    EESEN_REQUIRE(!Dc || cmvn, EESEN_ERR_INVALID, "the pipeline has a CMVN stage: per-utterance offset/scale vectors are required");
+    Head h;
+    if (nst) h.kind = pl[0].kind == EESEN_FEAT_FBANK ? kHeadFbank : pl[0].kind == EESEN_FEAT_FBANK_PITCH ? kHeadFbankPitch : kHeadNone;
+    tab.resize(batch_words(nb, S, h.kind));
+    const BatchTables t = batch_carve(tab.data(), nb, S, h.kind);
+    std::vector<long> total(nb);
+    const int T = boundary_layout(frames, S, dims.data(), nb, [&](int k, int f) { return stage_frames(pl[k], f); }, t.off, t.frames, total.data());
     for (int s = 0; s < S; ++s) {
-      EESEN_REQUIRE(frames[s] >= 0, EESEN_ERR_INVALID, "negative frame count");
       EESEN_REQUIRE(frames[s] == 0 || utts[s] != nullptr, EESEN_ERR_INVALID, "null utterance matrix");
       EESEN_REQUIRE(!strides || frames[s] == 0 || strides[s] >= D, EESEN_ERR_INVALID, "row stride smaller than the feature dimension");
       EESEN_REQUIRE(!Dc || frames[s] == 0 || cmvn[s] != nullptr, EESEN_ERR_INVALID, "null CMVN vectors");
-      int f = frames[s];
-      for (int b = 0; b < nb; ++b) {
-        if (b) f = stage_frames(pipe[b - 1], f);
-        off_h[(size_t)b * S + s] = total[b];
-        fr_h[(size_t)b * S + s] = f;
-        total[b] += (long)f * dims[b];
-      }
-      T = std::max(T, f);
     }
     EESEN_REQUIRE(T > 0, EESEN_ERR_INVALID, "every utterance is empty after the front end");
-    const float* host = pack(sl, utts, frames, strides, off_h, S, D, total[0]);   // (off_h[s]: the offsets at boundary 0)
+    if (h.kind) {   // the waveforms are [samples x 1]: their sample offsets are boundary 0's, written again as they are
+      h.fb = fbank_layout(frames, S, fb_plan->dim, [this](int n) { return fb_plan->num_frames(n); }, t.off, t.prefix, t.fb_off);
+      for (int s = 0; s < S; ++s) t.ids[s] = fb_next_id + s;
+    }
+    if (h.kind == kHeadFbankPitch) {
+      require_same_rate();
+      h.pt = pitch_layout(frames, nullptr, nullptr, fb_next_id, S, pt_plan->opts.delay, pt_plan->proc_dim,
+                          [this](int n, int* f1, int* n1, int* n2) { return pt_plan->num_frames(n, f1, n1, n2); }, t.utt);
+      for (int s = 0; s < S; ++s) t.proc_off[s] = t.utt[s].proc_off;
+    }
+
+    EESEN_HIP_CHECK(hipSetDevice(device));
+    if (h.kind) fb_next_id += S;   // every waveform submitted gets a key of its own
+    int id = 0;
+    Slot& sl = next_slot(&id);
+    std::memcpy(sl.tab_h.reserve(tab.size() * 8), tab.data(), tab.size() * 8);
+    const float* host = pack(sl, utts, frames, strides, t.off, S, D, total[0]);
     if (Dc) {
       float* cmvn_h = static_cast<float*>(sl.cmvn_h.reserve((size_t)S * 2 * Dc * sizeof(float)));
       for (int s = 0; s < S; ++s) {
@@ -546,65 +431,40 @@ struct Feeder {
       EESEN_HIP_CHECK(hipMemcpyAsync(sl.cmvn_d.p, cmvn_h, (size_t)S * 2 * Dc * sizeof(float), hipMemcpyHostToDevice, copy));
     }
     // even boundaries live in `packed`, odd ones in `packed2`
-    size_t cap_even = 0, cap_odd = 0;
-    for (int b = 0; b < nb; ++b) (b % 2 ? cap_odd : cap_even) = std::max(b % 2 ? cap_odd : cap_even, (size_t)total[b]);
-    sl.packed.reserve(std::max<size_t>(cap_even, 1));
-    sl.packed2.reserve(std::max<size_t>(cap_odd, 1));
-    sl.offs_d.reserve((size_t)nb * S);
-    sl.frs_d.reserve((size_t)nb * S);
-    const int Dout = dims[nst], ld = (Dout + 3) / 4 * 4;
-    const bool fresh = sl.out.reserve((size_t)T * S * ld);
-    if (ld != Dout && fresh) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, sl.out.cap * sizeof(float), copy));
-    else if (ld != Dout) EESEN_HIP_CHECK(hipMemsetAsync(sl.out.p, 0, (size_t)T * S * ld * sizeof(float), copy));
+    size_t cap[2] = {1, nst ? (size_t)1 : 0};
+    for (int b = 0; b < nb; ++b) cap[b % 2] = std::max(cap[b % 2], (size_t)total[b]);
+    sl.packed.reserve(cap[0]);
+    sl.packed2.reserve(cap[1]);
+    sl.tab_d.reserve(tab.size());
+    const BatchTables d = batch_carve(sl.tab_d.p, nb, S, h.kind);
     if (total[0]) EESEN_HIP_CHECK(hipMemcpyAsync(sl.packed.p, host, (size_t)total[0] * sizeof(float), hipMemcpyHostToDevice, copy));
-    EESEN_HIP_CHECK(hipMemcpyAsync(sl.offs_d.p, off_h, (size_t)nb * S * sizeof(long), hipMemcpyHostToDevice, copy));
-    EESEN_HIP_CHECK(hipMemcpyAsync(sl.frs_d.p, fr_h, (size_t)nb * S * sizeof(int), hipMemcpyHostToDevice, copy));
+    EESEN_HIP_CHECK(hipMemcpyAsync(sl.tab_d.p, sl.tab_h.p, tab.size() * 8, hipMemcpyHostToDevice, copy));
     for (int k = 0; k < nst; ++k) {
       if (!total[k + 1]) continue;
       const float* src = k % 2 ? sl.packed2.p : sl.packed.p;
       float* dst = k % 2 ? sl.packed.p : sl.packed2.p;
       long biggest = 0;
-      for (int s = 0; s < S; ++s) biggest = std::max(biggest, (long)fr_h[(size_t)(k + 1) * S + s] * dims[k + 1]);
-      if (pipe[k].kind == EESEN_FEAT_FBANK) {   // k == 0: the samples are boundary 0, the kernel writes boundary 1 where the next stage reads
-        int* prefix_h = static_cast<int*>(sl.fb_meta_h.reserve((size_t)(S + 2) * sizeof(int) + (size_t)S * sizeof(unsigned long long)));
-        unsigned long long* ids_h = reinterpret_cast<unsigned long long*>(prefix_h + (S + 2) / 2 * 2);
-        long frames_all = 0;
-        for (int s = 0; s < S; ++s) {
-          prefix_h[s] = (int)frames_all;
-          frames_all += fr_h[(size_t)S + s];
-          EESEN_REQUIRE(frames_all < (1L << 30), EESEN_ERR_INVALID, "too many frames in one batch");
-          ids_h[s] = fb_next_id++;
-        }
-        prefix_h[S] = (int)frames_all;
-        sl.fb_prefix_d.reserve((size_t)S + 1);
-        sl.fb_ids_d.reserve((size_t)S);
-        EESEN_HIP_CHECK(hipMemcpyAsync(sl.fb_prefix_d.p, prefix_h, (size_t)(S + 1) * sizeof(int), hipMemcpyHostToDevice, copy));
-        EESEN_HIP_CHECK(hipMemcpyAsync(sl.fb_ids_d.p, ids_h, (size_t)S * sizeof(unsigned long long), hipMemcpyHostToDevice, copy));
-        fbank_launch(*fb_plan, fb_dev, src, sl.offs_d.p, sl.frs_d.p, sl.fb_prefix_d.p, sl.fb_ids_d.p, S, (int)frames_all, dst, sl.offs_d.p + S, copy);
+      for (int s = 0; s < S; ++s) biggest = std::max(biggest, (long)t.frames[(size_t)(k + 1) * S + s] * dims[k + 1]);
+      if (k == 0 && h.kind) {
+        head_stage(sl, h, d, S, src, dst, dims[1], biggest);
         continue;
       }
-      if (pipe[k].kind == EESEN_FEAT_FBANK_PITCH) {   // k == 0, as above; both extractors read boundary 0, the join writes boundary 1
-        submit_fbank_pitch(sl, fr_h, S, src, dst, dims[1], biggest);
-        continue;
-      }
-      const int bx = (int)std::min<long>(std::max<long>(cdivl(biggest, 256), 1), 2048);   // one element per thread: the stage is latency-bound otherwise
-      const StageDev sd{pipe[k].kind, pipe[k].a, pipe[k].b};
-      hipLaunchKernelGGL(feat_stage_kernel, dim3(bx, S), dim3(256), 0, copy, sd, scales_d.p ? scales_d.p + pipe[k].scale_off : nullptr, src,
-                         sl.offs_d.p + (size_t)k * S, sl.frs_d.p + (size_t)k * S, dims[k], dst, sl.offs_d.p + (size_t)(k + 1) * S,
-                         sl.frs_d.p + (size_t)(k + 1) * S, dims[k + 1], sl.cmvn_d.p);
+      const StageDev sd{pl[k].kind, pl[k].a, pl[k].b};
+      hipLaunchKernelGGL(feat_stage_kernel, stage_grid(biggest, S), dim3(256), 0, copy, sd, scales_d.p ? scales_d.p + pl[k].scale_off : nullptr, src,
+                         d.off + (size_t)k * S, d.frames + (size_t)k * S, dims[k], dst, d.off + (size_t)(k + 1) * S,
+                         d.frames + (size_t)(k + 1) * S, dims[k + 1], sl.cmvn_d.p);
       check_launch("feat_stage_kernel");
     }
-    const float* last = nst % 2 ? sl.packed2.p : sl.packed.p;
-    const bool vec = Dout % 4 == 0;
-    const long n = (long)T * S * (vec ? Dout / 4 : Dout);
-    const int blocks = (int)std::min<long>(cdivl(n, 256), 256L * 32);
-    if (vec) interleave_kernel<4><<<blocks, 256, 0, copy>>>(last, sl.offs_d.p + (size_t)nst * S, sl.frs_d.p + (size_t)nst * S, sl.out.p, T, S, Dout, ld);
-    else interleave_kernel<1><<<blocks, 256, 0, copy>>>(last, sl.offs_d.p + (size_t)nst * S, sl.frs_d.p + (size_t)nst * S, sl.out.p, T, S, Dout, ld);
-    check_launch("interleave_kernel");
+    assemble(sl, nst % 2 ? sl.packed2.p : sl.packed.p, d.off + (size_t)nst * S, d.frames + (size_t)nst * S, T, S, dims[nst]);
     sl.ready.record(copy);
     sl.in_flight = true;
-    sl.T = T; sl.S = S; sl.D = Dout; sl.ld = ld;
     return id;
+  }
+  int submit(const float* const* utts, const int* frames, const int* strides, int S, int D) {
+    return stage_batch(std::vector<Stage>(), utts, frames, strides, nullptr, S, D);
+  }
+  int submit_raw(const float* const* utts, const int* frames, const int* strides, const float* const* cmvn, int S, int D) {
+    return stage_batch(pipe, utts, frames, strides, cmvn, S, D);
   }
 
   Slot& checked(int id) {

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "common.h"
+#include "feat_layout.h"   // PitchUtt, PitchTotals, kPitchMaxStates, kPitchMaxFrames
 
 namespace eesen {
 
@@ -30,15 +31,6 @@ struct PitchPlan {
 
 std::vector<float> pitch_lags(const eesen_pitch_opts_t& o);   // SelectLags in the reference's float arithmetic
 
-// One utterance of a launch, as the kernels see it.
-struct PitchUtt {
-  long wave_off, down_off;       // into the packed samples / down-sampled samples
-  long proc_off;                 // floats in front of its processed matrix
-  unsigned long long id;
-  int nsamp, n1, n2;
-  int f1, frames, prefix;        // prefix: frames in front of it in the launch
-  int pad;
-};
 struct PitchSums { double sum1, sq1, sum2, sq2; };   // of the down-sampled signal without and with the flushed tail
 
 struct PitchDev {
@@ -47,8 +39,6 @@ struct PitchDev {
   void upload(const PitchPlan& p);
 };
 constexpr int kPitchFramesPerBlock = 4;      // NCCF kernel: one wavefront per frame
-constexpr int kPitchMaxStates = 1024;        // search kernel: one thread per lag state, one workgroup per utterance
-constexpr long kPitchMaxFrames = (1L << 30) / kPitchMaxStates * 256;   // frames of one launch: [frames x states] offsets stay below 2^38
 
 struct PitchBufs {
   const PitchUtt* utt; int S; int total_frames;
@@ -64,5 +54,19 @@ void pitch_downsample_launch(const PitchPlan& p, const PitchDev& d, const PitchB
 void pitch_nccf_launch(const PitchPlan& p, const PitchDev& d, const PitchBufs& b, hipStream_t st);
 void pitch_viterbi_launch(const PitchPlan& p, const PitchDev& d, const PitchBufs& b, hipStream_t st);
 void pitch_process_launch(const PitchPlan& p, const PitchBufs& b, hipStream_t st);   // utt[s].frames rows of b.raw from row utt[s].prefix
+// down-sample, NCCF, Viterbi and, asked for, the post-processing, in that order on one stream
+void pitch_track_launch(const PitchPlan& p, const PitchDev& d, const PitchBufs& b, bool process, hipStream_t st);
+
+// The tracker's device buffers for one batch: the stand-alone extractor holds one set, the feeder one per staging slot.
+struct PitchScratch {
+  DevBuf<float> down, nccf_pitch, nccf_pov, avg, fwd, raw, proc;
+  DevBuf<PitchSums> sums;
+  DevBuf<unsigned short> backptr;
+  DevBuf<int> track, taken;
+  DevBuf<double> scan;
+  // sized for the batch and handed to the kernels; diag: the search's forward costs and track as well; search = false: the
+  // post-processing alone, which needs no NCCF
+  PitchBufs reserve(const PitchPlan& p, const PitchTotals& t, int S, const PitchUtt* utt_d, const float* wave, bool diag = false, bool search = true);
+};
 
 }  // namespace eesen

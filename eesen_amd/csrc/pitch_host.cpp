@@ -135,6 +135,35 @@ int PitchPlan::num_frames(int nsamp, int* f1_out, int* n1_out, int* n2_out) cons
   return std::max(fa, f1);
 }
 
+PitchBufs PitchScratch::reserve(const PitchPlan& p, const PitchTotals& t, int S, const PitchUtt* utt_d, const float* wave, bool diag, bool search) {
+  const size_t F = (size_t)std::max(t.frames, 1L), ns = search ? (size_t)p.states : 0;
+  down.reserve((size_t)std::max(t.down, 1L));
+  sums.reserve((size_t)S);
+  nccf_pitch.reserve(F * ns);
+  nccf_pov.reserve(F * ns);
+  avg.reserve(F);
+  backptr.reserve(F * ns);
+  raw.reserve(F * 2);
+  scan.reserve(2 * (F + S));
+  proc.reserve((size_t)std::max(t.proc, 1L));
+  taken.reserve((size_t)S);
+  if (diag) { fwd.reserve((size_t)S * ns); track.reserve(F); }
+  PitchBufs b;
+  b.utt = utt_d; b.S = S; b.total_frames = (int)t.frames;
+  b.wave = wave; b.down = down.p; b.sums = sums.p;
+  b.nccf_pitch = nccf_pitch.p; b.nccf_pov = nccf_pov.p; b.avg_norm_prod = avg.p;
+  b.backptr = backptr.p; b.fwd = diag ? fwd.p : nullptr; b.track = diag ? track.p : nullptr; b.taken = taken.p;
+  b.raw = raw.p; b.scan = scan.p; b.proc = proc.p;
+  return b;
+}
+
+void pitch_track_launch(const PitchPlan& p, const PitchDev& d, const PitchBufs& b, bool process, hipStream_t st) {
+  pitch_downsample_launch(p, d, b, st);
+  pitch_nccf_launch(p, d, b, st);
+  pitch_viterbi_launch(p, d, b, st);
+  if (process) pitch_process_launch(p, b, st);
+}
+
 // The stand-alone extractor: one staging area, synchronous per call.
 struct Pitch {
   PitchPlan plan;
@@ -144,14 +173,10 @@ struct Pitch {
   bool on_device = false;      // the tables go up with the first compute call: options, shapes and lags need no device
   PinBuf wave_h, out_h, diag_h;
   std::vector<PitchUtt> utts;
-  long total_samp = 0, total_down = 0, total_proc = 0;
-  int total_frames = 0;
+  PitchTotals tot;
   DevBuf<PitchUtt> utt_d;
-  DevBuf<float> wave_d, down_d, nccf_pitch_d, nccf_pov_d, avg_d, fwd_d, raw_d, proc_d;
-  DevBuf<PitchSums> sums_d;
-  DevBuf<unsigned short> backptr_d;
-  DevBuf<int> track_d, taken_d;
-  DevBuf<double> scan_d;
+  DevBuf<float> wave_d;
+  PitchScratch sc;
 
   Pitch(int dev_, void* st, const eesen_pitch_opts_t& o) : plan(o), device(dev_), stream(static_cast<hipStream_t>(st)) {
     EESEN_REQUIRE(dev_ >= 0, EESEN_ERR_INVALID, "device index out of range");
@@ -175,74 +200,32 @@ struct Pitch {
   void layout(const int* nsamp, const int* frames, const unsigned long long* ids, int S) {
     EESEN_REQUIRE(S > 0, EESEN_ERR_INVALID, "need at least one utterance");
     utts.assign(S, PitchUtt());
-    total_samp = total_down = total_proc = 0;
-    long frames_all = 0;
-    for (int s = 0; s < S; ++s) {
-      PitchUtt& u = utts[s];
-      if (frames) {
-        EESEN_REQUIRE(frames[s] >= 0, EESEN_ERR_INVALID, "negative frame count");
-        u.frames = frames[s];
-      } else {
-        EESEN_REQUIRE(nsamp[s] >= 0, EESEN_ERR_INVALID, "negative sample count");
-        u.nsamp = nsamp[s];
-        u.frames = plan.num_frames(nsamp[s], &u.f1, &u.n1, &u.n2);
-      }
-      u.wave_off = total_samp;
-      u.down_off = total_down;
-      u.proc_off = total_proc;
-      u.prefix = (int)frames_all;
-      u.id = ids ? ids[s] : (unsigned long long)s;
-      total_samp += u.nsamp;
-      total_down += u.n2;
-      total_proc += u.frames ? (long)(u.frames + plan.opts.delay) * plan.proc_dim : 0;
-      frames_all += u.frames;
-      EESEN_REQUIRE(frames_all < kPitchMaxFrames, EESEN_ERR_INVALID, "too many frames in one call");
-    }
-    total_frames = (int)frames_all;
+    tot = pitch_layout(nsamp, frames, ids, 0, S, plan.opts.delay, plan.proc_dim,
+                       [this](int n, int* f1, int* n1, int* n2) { return plan.num_frames(n, f1, n1, n2); }, utts.data());
     utt_d.reserve((size_t)S);
     EESEN_HIP_CHECK(hipMemcpyAsync(utt_d.p, utts.data(), (size_t)S * sizeof(PitchUtt), hipMemcpyHostToDevice, stream));
     EESEN_HIP_CHECK(hipStreamSynchronize(stream));      // utts is pageable and reused
   }
 
-  PitchBufs bufs(bool diag, bool search = true) {
-    const int S = (int)utts.size();
-    const size_t F = (size_t)std::max(total_frames, 1), ns = search ? (size_t)plan.states : 0;   // (the post-processing alone needs no NCCF)
-    down_d.reserve((size_t)std::max(total_down, 1L));
-    sums_d.reserve((size_t)S);
-    nccf_pitch_d.reserve(F * ns);
-    nccf_pov_d.reserve(F * ns);
-    avg_d.reserve(F);
-    backptr_d.reserve(F * ns);
-    raw_d.reserve(F * 2);
-    scan_d.reserve(2 * (F + S));
-    proc_d.reserve((size_t)std::max(total_proc, 1L));
-    taken_d.reserve((size_t)S);
-    if (diag) { fwd_d.reserve((size_t)S * ns); track_d.reserve(F); }
-    PitchBufs b;
-    b.utt = utt_d.p; b.S = S; b.total_frames = total_frames;
-    b.wave = wave_d.p; b.down = down_d.p; b.sums = sums_d.p;
-    b.nccf_pitch = nccf_pitch_d.p; b.nccf_pov = nccf_pov_d.p; b.avg_norm_prod = avg_d.p;
-    b.backptr = backptr_d.p; b.fwd = diag ? fwd_d.p : nullptr; b.track = diag ? track_d.p : nullptr; b.taken = taken_d.p;
-    b.raw = raw_d.p; b.scan = scan_d.p; b.proc = proc_d.p;
-    return b;
-  }
-
-  void upload_waves(const float* const* waves) {
-    const int S = (int)utts.size();
-    float* wh = static_cast<float*>(wave_h.reserve((size_t)std::max(total_samp, 1L) * sizeof(float)));
+  // a batch of waveforms laid out, on its way to the device, and the scratch sized for it
+  PitchBufs stage(const float* const* waves, const int* nsamp, const unsigned long long* ids, int S, bool diag = false) {
+    to_device();
+    layout(nsamp, nullptr, ids, S);
+    float* wh = static_cast<float*>(wave_h.reserve((size_t)std::max(tot.samp, 1L) * sizeof(float)));
     for (int s = 0; s < S; ++s) {
       EESEN_REQUIRE(utts[s].nsamp == 0 || waves[s] != nullptr, EESEN_ERR_INVALID, "null waveform");
       if (utts[s].nsamp) std::memcpy(wh + utts[s].wave_off, waves[s], (size_t)utts[s].nsamp * sizeof(float));
     }
-    wave_d.reserve((size_t)std::max(total_samp, 1L));
-    if (total_samp) EESEN_HIP_CHECK(hipMemcpyAsync(wave_d.p, wh, (size_t)total_samp * sizeof(float), hipMemcpyHostToDevice, stream));
+    wave_d.reserve((size_t)std::max(tot.samp, 1L));
+    if (tot.samp) EESEN_HIP_CHECK(hipMemcpyAsync(wave_d.p, wh, (size_t)tot.samp * sizeof(float), hipMemcpyHostToDevice, stream));
+    return sc.reserve(plan, tot, S, utt_d.p, wave_d.p, diag);
   }
 
   // rows and floats per row of utterance s in the matrices handed back
   void copy_out(bool process, float* const* out, const long* out_cap, int* frames_out) {
     const int S = (int)utts.size();
     const int dim = process ? plan.proc_dim : 2;
-    const long total = process ? total_proc : (long)total_frames * 2;
+    const long total = process ? tot.proc : tot.frames * 2;
     for (int s = 0; s < S; ++s) {
       const int rows = utts[s].frames ? utts[s].frames + (process ? plan.opts.delay : 0) : 0;
       EESEN_REQUIRE(rows == 0 || (out && out[s] != nullptr), EESEN_ERR_INVALID, "null output matrix");
@@ -251,7 +234,7 @@ struct Pitch {
     }
     if (!total) return;
     float* oh = static_cast<float*>(out_h.reserve((size_t)total * sizeof(float)));
-    EESEN_HIP_CHECK(hipMemcpyAsync(oh, process ? proc_d.p : raw_d.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, stream));
+    EESEN_HIP_CHECK(hipMemcpyAsync(oh, process ? sc.proc.p : sc.raw.p, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, stream));
     EESEN_HIP_CHECK(hipStreamSynchronize(stream));
     for (int s = 0; s < S; ++s) {
       if (!utts[s].frames) continue;
@@ -263,14 +246,7 @@ struct Pitch {
 
   void compute(const float* const* waves, const int* nsamp, const unsigned long long* ids, int S, bool process, float* const* out,
                const long* out_cap, int* frames_out) {
-    to_device();
-    layout(nsamp, nullptr, ids, S);
-    upload_waves(waves);
-    const PitchBufs b = bufs(false);
-    pitch_downsample_launch(plan, dev, b, stream);
-    pitch_nccf_launch(plan, dev, b, stream);
-    pitch_viterbi_launch(plan, dev, b, stream);
-    if (process) pitch_process_launch(plan, b, stream);
+    pitch_track_launch(plan, dev, stage(waves, nsamp, ids, S), process, stream);
     copy_out(process, out, out_cap, frames_out);
     EESEN_HIP_CHECK(hipStreamSynchronize(stream));
   }
@@ -279,15 +255,15 @@ struct Pitch {
                int* frames_out) {
     to_device();
     layout(nullptr, frames, ids, S);
-    const PitchBufs b = bufs(false, false);
-    float* rh = static_cast<float*>(wave_h.reserve((size_t)std::max(total_frames, 1) * 2 * sizeof(float)));
+    const PitchBufs b = sc.reserve(plan, tot, S, utt_d.p, nullptr, false, false);
+    float* rh = static_cast<float*>(wave_h.reserve((size_t)std::max(tot.frames, 1L) * 2 * sizeof(float)));
     for (int s = 0; s < S; ++s) {
       EESEN_REQUIRE(utts[s].frames == 0 || raw[s] != nullptr, EESEN_ERR_INVALID, "null input matrix");
       for (long k = 0; k < (long)utts[s].frames; ++k)
         EESEN_REQUIRE(raw[s][2 * k + 1] > 0.f, EESEN_ERR_INVALID, "pitch values must be positive");
       if (utts[s].frames) std::memcpy(rh + (long)utts[s].prefix * 2, raw[s], (size_t)utts[s].frames * 2 * sizeof(float));
     }
-    if (total_frames) EESEN_HIP_CHECK(hipMemcpyAsync(raw_d.p, rh, (size_t)total_frames * 2 * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (tot.frames) EESEN_HIP_CHECK(hipMemcpyAsync(sc.raw.p, rh, (size_t)tot.frames * 2 * sizeof(float), hipMemcpyHostToDevice, stream));
     pitch_process_launch(plan, b, stream);
     copy_out(true, out, out_cap, frames_out);
     EESEN_HIP_CHECK(hipStreamSynchronize(stream));
@@ -310,41 +286,32 @@ struct Pitch {
     if (counts) { counts[0] = frames; counts[1] = f1; counts[2] = plan.states; counts[3] = n2; counts[4] = n1; }
     if (lags) std::copy(plan.lags.begin(), plan.lags.end(), lags);
     if (!down && !nccf_pitch && !nccf_pov && !avg && !mean_square && !fwd && !backptr && !track && !raw && !taken) return;
-    to_device();
-    layout(&nsamp, nullptr, nullptr, 1);
-    upload_waves(&wave);
-    const PitchBufs b = bufs(true);
-    pitch_downsample_launch(plan, dev, b, stream);
-    pitch_nccf_launch(plan, dev, b, stream);
-    pitch_viterbi_launch(plan, dev, b, stream);
+    pitch_track_launch(plan, dev, stage(&wave, &nsamp, nullptr, 1, true), false, stream);
     EESEN_HIP_CHECK(hipStreamSynchronize(stream));
     const size_t F = (size_t)frames, ns = (size_t)plan.states;
-    fetch(down, down_d.p, (size_t)n2);
+    fetch(down, sc.down.p, (size_t)n2);
     PitchSums sm;
-    fetch(&sm, sums_d.p, 1);
+    fetch(&sm, sc.sums.p, 1);
     if (mean_square) {
       mean_square[0] = n1 ? sm.sq1 / n1 - (sm.sum1 / n1) * (sm.sum1 / n1) : 0.0;
       mean_square[1] = n2 ? sm.sq2 / n2 - (sm.sum2 / n2) * (sm.sum2 / n2) : 0.0;
     }
-    fetch(nccf_pitch, nccf_pitch_d.p, F * ns);
-    fetch(nccf_pov, nccf_pov_d.p, F * ns);
-    fetch(avg, avg_d.p, F);
-    fetch(backptr, backptr_d.p, F * ns);
-    fetch(track, track_d.p, F);
-    fetch(raw, raw_d.p, F * 2);
-    if (F) fetch(fwd, fwd_d.p, ns);
+    fetch(nccf_pitch, sc.nccf_pitch.p, F * ns);
+    fetch(nccf_pov, sc.nccf_pov.p, F * ns);
+    fetch(avg, sc.avg.p, F);
+    fetch(backptr, sc.backptr.p, F * ns);
+    fetch(track, sc.track.p, F);
+    fetch(raw, sc.raw.p, F * 2);
+    if (F) fetch(fwd, sc.fwd.p, ns);
     if (taken) {
       *taken = 0;
-      if (F) fetch(taken, taken_d.p, 1);
+      if (F) fetch(taken, sc.taken.p, 1);
     }
   }
 
   // avg_ms[5]: everything, then each launch alone; one warm-up pass first (it also fills what the later launches read)
   void bench(const float* const* waves, const int* nsamp, int S, int iters, float* avg_ms) {
-    to_device();
-    layout(nsamp, nullptr, nullptr, S);
-    upload_waves(waves);
-    const PitchBufs b = bufs(false);
+    const PitchBufs b = stage(waves, nsamp, nullptr, S);
     auto run = [&](int which) {
       if (which == 0 || which == 1) pitch_downsample_launch(plan, dev, b, stream);
       if (which == 0 || which == 2) pitch_nccf_launch(plan, dev, b, stream);

@@ -7,7 +7,9 @@
   silence gives exactly logf(FLT_MIN) in every bin;
 * dither: the mean filterbank energy of dithered silence against its expectation, determinism per seed, and that seed and utterance
   id both change the noise;
-* options the extractor does not support are refused.
+* options the extractor does not support are refused;
+* the feeder's filterbank head equals the extractor bit for bit, dither and keys included, and a batch it refuses takes no slot and
+  no key.
 """
 import functools
 
@@ -181,6 +183,78 @@ def test_feeder_fbank_stage_errors(gpu):
         f.submit_raw([np.zeros((1000, 2), np.float32)])
     with pytest.raises(EesenError):
         f.set_fbank(round_to_power_of_two=False)
+
+
+DITHERED_HEAD = dict(dither=1.0, dither_seed=5)
+
+
+def _head_feeder(opts, slots):
+    from eesen_amd import frontend as fe
+    from eesen_amd.api import Feeder
+    f = Feeder(slots=slots)
+    f.set_fbank(**opts)
+    f.set_pipeline([(fe.FBANK, 0, 0)])
+    return f
+
+
+def _slot_matrix(f, slot):
+    """The whole assembled matrix of a slot, pad columns included."""
+    from eesen_amd.api import CuMatrix
+    got = f.acquire(slot)
+    host = CuMatrix.view(got.ptr, got.rows, got.stride, got.stride, got.device, keepalive=f).numpy()
+    f.release(slot)
+    return host
+
+
+def _assembled(mats, ld):
+    """The feeder's [T*S x ld] matrix of these utterances: row t*S + s, zeros past an utterance's end and in the pad columns."""
+    T, S = max(m.shape[0] for m in mats), len(mats)
+    out = np.zeros((T, S, ld), np.float32)
+    for s, m in enumerate(mats):
+        out[:m.shape[0], s, :m.shape[1]] = m
+    return out.reshape(T * S, ld)
+
+
+def _same_bits(host, mats):
+    exp = _assembled(mats, host.shape[1])
+    return host.shape == exp.shape and np.array_equal(host.view(np.uint32), exp.view(np.uint32))
+
+
+def test_feeder_fbank_head_equals_the_extractor(gpu):
+    """The filterbank head alone, dither on, against api.Fbank.compute with the feeder's keys, bit for bit.  One slot, two batches: the
+    case's waveforms (keys 0 .. S-1), then two of them in another order (keys S, S + 1); the smaller batch shows nothing of the larger."""
+    from eesen_amd.api import Fbank
+    c = GOLD[FEEDER_CASE]
+    opts = dict(c["opts"], **DITHERED_HEAD)
+    f, fb = _head_feeder(opts, slots=1), Fbank(**opts)
+    S = len(c["waves"])
+    for waves, ids in ((c["waves"], list(range(S))), ([c["waves"][2], c["waves"][0]], [S, S + 1])):
+        want = fb.compute(waves, utt_ids=ids)
+        host = _slot_matrix(f, f.submit_raw([np.asarray(w, np.float32).reshape(-1, 1) for w in waves]))
+        assert _same_bits(host, want), ids
+    assert not np.array_equal(want[1], fb.compute([c["waves"][0]], utt_ids=[0])[0]), "the dither is on, and keyed"
+
+
+def test_feeder_refused_batch_leaves_no_trace(gpu):
+    """A batch refused on the host -- every waveform shorter than a window, then a [samples x 2] matrix -- takes no slot and no key: the
+    submits around the refusals get slots 0 and 1 and the keys 0 .. S-1 and S .. 2S-1."""
+    from eesen_amd.api import Fbank, EesenError
+    c = GOLD[FEEDER_CASE]
+    opts = dict(c["opts"], **DITHERED_HEAD)
+    f, fb = _head_feeder(opts, slots=2), Fbank(**opts)
+    cols = [np.asarray(w, np.float32).reshape(-1, 1) for w in c["waves"]]
+    S = len(cols)
+    first = f.submit_raw(cols)
+    assert first == 0
+    assert fb.shape(100)[0] == 0
+    with pytest.raises(EesenError, match="empty after the front end"):
+        f.submit_raw([np.ones((100, 1), np.float32)] * S)
+    with pytest.raises(EesenError, match="samples x 1"):
+        f.submit_raw([np.zeros((1000, 2), np.float32)])
+    second = f.submit_raw(cols[::-1])
+    assert second == 1
+    assert _same_bits(_slot_matrix(f, first), fb.compute(c["waves"], utt_ids=list(range(S))))
+    assert _same_bits(_slot_matrix(f, second), fb.compute(c["waves"][::-1], utt_ids=list(range(S, 2 * S))))
 
 
 # ------------------------------------------------------------------------------------------------ the tools

@@ -76,6 +76,21 @@ def test_training_from_feeder_equals_training_from_host_matrix(gpu):
     assert np.array_equal(outs[0][0], outs[1][0]) and np.array_equal(outs[0][1], outs[1][1])
 
 
+def test_refused_batch_takes_no_slot(gpu):
+    """A batch refused on the host (every utterance empty) between two submits: the slots are 0 and 1, both matrices intact."""
+    from eesen_amd.api import Feeder, EesenError
+    rng = np.random.default_rng(8)
+    f = Feeder(slots=2)
+    a, b = _mats(rng, [5, 9, 2], 13), _mats(rng, [4, 4], 13)
+    first = f.submit(a)
+    with pytest.raises(EesenError):
+        f.submit([np.zeros((0, 13), np.float32)] * 3)
+    second = f.submit(b)
+    assert (first, second) == (0, 1)
+    assert np.array_equal(f.acquire(first).numpy(), interleave(a, 13)[0])
+    assert np.array_equal(f.acquire(second).numpy(), interleave(b, 13)[0])
+
+
 def test_feeder_errors(gpu):
     from eesen_amd.api import Feeder, EesenError
     f = Feeder()
