@@ -6,10 +6,24 @@ a waveform without a frame), and whether its --verbose=3 log shows the energy re
 PROCESS_CASES are option sets of process-kaldi-pitch-feats (noise 0); the fixture holds that tool's output on the raw matrices of
 PROCESS_INPUTS.  SWEEP is a table of sample count -> frame count from the same tool on silent waveforms, per rate and edge mode.
 
-`write_golden(bindir)` is how the file was made.  The two tools were built out of tree, in a scratch directory that is not kept:
-the reference's base/, cpucompute/ and util/ sources, feat/{pitch-functions,resample,feature-functions,wave-reader,mel-computations,
-srfft}.cc and the two featbin sources, compiled where they lie with the flags of oracle/ref_build/Makefile (g++ -std=c++11 -O2,
--DHAVE_CLAPACK -DKALDI_DOUBLEPRECISION=0, blas_rename.h) and linked against the same SciPy OpenBLAS.
+`write_golden(bindir)` is how the file was made.  The two tools are `make -C oracle/ref_build pitchbin`: the reference's base/,
+cpucompute/ and util/ sources, feat/{pitch-functions,resample,feature-functions,wave-reader,mel-computations,srfft}.cc and the two
+featbin sources, compiled where they lie with that Makefile's flags (g++ -std=c++11 -O2, -DHAVE_CLAPACK -DKALDI_DOUBLEPRECISION=0,
+blas_rename.h) and linked against the same SciPy OpenBLAS, into oracle/_ref/pitchbin (the `bindir`; not kept in the repository).
+
+A second fixture, tests/golden/pitch_edges.npz (`write_golden_edges`, `load_golden_edges`; `python -m tests.pitch_cases` remakes it
+with the same two tools), holds what the first one's shapes leave out -- the sizes at which the kernels take another path:
+* GRID_STATES: lag grids of 63, 64, 65, 448, 449, 1023 and 1024 states (`delta_pitch_for` searches the option).  The search kernel
+  runs one thread per state in ceil(states / 64) wavefronts and reads the previous costs four at a time: one wavefront alone, a last
+  wavefront that is full (no +inf filler), one with a single state in it, states % 4 of 0, 1 and 3 next to a wavefront edge, and the
+  sixteen wavefronts of kPitchMaxStates.  One more state is refused;
+* RESAMPLE_OPTS: down-sampling ratios 16:3, 441:40 and 16:5 -- a few filter phases with more than one output sample per unit, where
+  the first fixture has 1 (16 and 8 kHz) or 160 (11025 Hz);
+* EDGE_LENGTHS: post-processing of the first 255, 256, 257, 512, 513 and 598 rows of the tool's own long_6s output, and of three
+  utterances of 598, 1 and 300 rows in one call.  pitch_process_kernel scans the pov-weighted prefix sums 256 frames at a time with a
+  carry between the chunks; the first fixture's utterances stay under 59 frames and never reach the carry or a default +-75 window
+  with both ends inside the utterance.
+The same condition holds: the float64 restatement picks the tool's lag on every frame of every edge case.
 
 A condition on the fixture (tests/test_pitch_cases.py): the float64 restatement picks the tool's lag on EVERY frame of every case.  A
 case that does not is a badly chosen input (clipping, exact ties) and is replaced, not tolerated.
@@ -18,6 +32,7 @@ Waveforms are at most 0.6 s but for one of 6 s (598 frames, past recompute_frame
 the NCCF kernel: the two S = 3 cases total one above a multiple of it, the S = 33 case one below.
 """
 import json
+import math
 import os
 import subprocess
 import tempfile
@@ -25,9 +40,10 @@ import tempfile
 import numpy as np
 
 from tests.fbank_cases import write_wav
-from tests.pitch_restatement import full, num_frames
+from tests.pitch_restatement import full, lags, num_frames
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pitch.npz")
+GOLDEN_EDGES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pitch_edges.npz")
 NCCF_FRAMES_PER_BLOCK = 4
 
 
@@ -131,6 +147,84 @@ SWEEP_LENGTHS = [399, 400, 401, 559, 560, 561, 720, 1000, 200, 275, 276, 300, 64
 SWEEP_RATES = [8000.0, 11025.0, 16000.0]
 
 
+# ---------------------------------------------------------------------------------------------- the edge cases (pitch_edges.npz)
+GRID_STATES = [63, 64, 65, 448, 449, 1023, 1024]
+GRID_NAMES = [f"grid_{ns}" for ns in GRID_STATES]
+MAX_STATES = 1024                                       # kPitchMaxStates
+RESAMPLE_OPTS = dict(resample_3000=dict(resample_freq=3000.0), rate_44100=dict(samp_freq=44100.0),
+                     resample_5000_cut1500=dict(resample_freq=5000.0, lowpass_cutoff=1500.0))
+RESAMPLE_OUT_UNITS = dict(resample_3000=3, rate_44100=40, resample_5000_cut1500=5)
+EDGE_SECONDS = (0.3, 0.2, 0.15)                         # two voiced glides and one of white noise per case
+
+
+def delta_pitch_for(states, opts=None):
+    """A delta_pitch of six decimals whose lag grid has exactly `states` states (searched for: the grid's values are float32
+    roundings, so the count is not a formula of the option).  Starts where the grid's last step would fall half a step short of
+    1 / min_f0 and walks in steps of 1e-6."""
+    o = dict(opts or {})
+    f = full(o)
+    d = round(math.expm1(math.log(f["max_f0"] / f["min_f0"]) / (states - 0.5)), 6)
+    for _ in range(2000):
+        n = len(lags(dict(o, delta_pitch=d)))
+        if n == states:
+            return d
+        d = round(d + (1e-6 if n > states else -1e-6), 6)
+    raise ValueError(f"no delta_pitch of six decimals gives {states} states")
+
+
+def _edge_cases():
+    cases = []
+
+    def three(sf):
+        # one generator per case, so that a case whose input has to be replaced (a float32 tie between two lag paths, say: see the
+        # condition in the docstring) gets another seed and leaves the others as they are
+        rng = np.random.default_rng([20240917, len(cases)])
+        n = [int(round(s * sf)) for s in EDGE_SECONDS]
+        up = voiced(rng, n[0], sf, float(rng.uniform(80.0, 160.0)), float(rng.uniform(220.0, 340.0)))
+        down = voiced(rng, n[1], sf, float(rng.uniform(220.0, 340.0)), float(rng.uniform(80.0, 160.0)))
+        return [up, down, white(rng, n[2], float(rng.uniform(1000.0, 3000.0)))]
+
+    for ns in GRID_STATES:
+        cases.append(dict(name=f"grid_{ns}", kind="mixed", opts=dict(delta_pitch=delta_pitch_for(ns)), waves=three(16000.0)))
+    for name, o in RESAMPLE_OPTS.items():
+        cases.append(dict(name=name, kind="mixed", opts=dict(o), waves=three(full(o)["samp_freq"])))
+    return cases
+
+
+EDGE_CASES = _edge_cases()
+EDGE_NAMES = [c["name"] for c in EDGE_CASES]
+
+EDGE_SOURCE = "long_6s"                                 # whose tool output (598 rows) the post-processing inputs are cut from
+EDGE_LENGTHS = [255, 256, 257, 512, 513, 598]
+EDGE_THREE = "three_598_1_300"
+SCAN_CHUNK = 256                                        # frames per LDS scan of pitch_process_kernel
+
+
+def edge_process_inputs(raw):
+    """{input name: [raw matrices of one call]} cut from the tool's [598 x 2] output on EDGE_SOURCE: its first T rows, and three
+    utterances of which the second and third start their prefix sums behind a long one."""
+    assert raw.shape == (598, 2)
+    ins = {f"rows{T}": [raw[:T]] for T in EDGE_LENGTHS}
+    ins[EDGE_THREE] = [raw, raw[100:101], raw[298:]]
+    return ins
+
+
+EDGE_INPUT_NAMES = [f"rows{T}" for T in EDGE_LENGTHS] + [EDGE_THREE]
+EDGE_PROCESS_PAIRS = ([(p, i) for p in ("defaults", "all_delay2", "ctx_10_3") for i in EDGE_INPUT_NAMES] +
+                      [("delta_window3", "rows598"), ("raw_only", "rows598")])
+
+
+def long_and_short():
+    """(options, waveforms): the 6 s waveform whole (598 frames), then behind it a one-frame slice, a slice without a frame and a
+    300-frame slice -- real utterance lengths and the shortest ones in one launch."""
+    c = next(c for c in CASES if c["name"] == EDGE_SOURCE)
+    w, o = c["waves"][0], c["opts"]
+    one, many = samples_for(1, o), samples_for(300, o)
+    waves = [w, w[16000:16000 + one], w[9000:9000 + one - 4], w[20000:20000 + many]]
+    assert [num_frames(len(x), o)[1] for x in waves] == [598, 1, 0, 300]
+    return o, waves
+
+
 def frames_of(case):
     return [num_frames(len(w), case["opts"])[1] for w in case["waves"]]
 
@@ -176,6 +270,19 @@ def flags(opts, table=OPTION_FLAGS):
     return ["--%s=%s" % (table[k], ("true" if v else "false") if isinstance(v, bool) else v) for k, v in opts.items() if k in table]
 
 
+def _run_compute(compute, tmp, tag, opts, waves, verbose=False):
+    """compute-kaldi-pitch-feats on `waves` written as wav files under `tmp`: (path of the archive, the tool's log)."""
+    scp, ark = os.path.join(tmp, tag + ".scp"), os.path.join(tmp, tag + ".ark")
+    with open(scp, "w") as f:
+        for i, w in enumerate(waves):
+            p = os.path.join(tmp, f"{tag}_{i}.wav")
+            write_wav(p, w, full(opts)["samp_freq"])
+            f.write(f"utt{i:03d} {p}\n")
+    r = subprocess.run([compute] + (["--verbose=3"] if verbose else []) + flags(opts) + ["scp:" + scp, "ark:" + ark], check=True,
+                       capture_output=True, text=True)
+    return ark, r.stderr
+
+
 def write_golden(bindir, path=GOLDEN):
     """Runs the reference's compute-kaldi-pitch-feats and process-kaldi-pitch-feats (in `bindir`) on every case."""
     from eesen_amd import kaldi_io
@@ -183,15 +290,7 @@ def write_golden(bindir, path=GOLDEN):
     data = {"names": json.dumps(CASE_NAMES), "process_names": json.dumps([p["name"] for p in PROCESS_CASES])}
     with tempfile.TemporaryDirectory() as tmp:
         def run_compute(tag, opts, waves, verbose=False):
-            scp, ark = os.path.join(tmp, tag + ".scp"), os.path.join(tmp, tag + ".ark")
-            with open(scp, "w") as f:
-                for i, w in enumerate(waves):
-                    p = os.path.join(tmp, f"{tag}_{i}.wav")
-                    write_wav(p, w, full(opts)["samp_freq"])
-                    f.write(f"utt{i:03d} {p}\n")
-            r = subprocess.run([compute] + (["--verbose=3"] if verbose else []) + flags(opts) + ["scp:" + scp, "ark:" + ark], check=True,
-                               capture_output=True, text=True)
-            return ark, r.stderr
+            return _run_compute(compute, tmp, tag, opts, waves, verbose)
 
         for c in CASES:
             name = c["name"]
@@ -223,3 +322,53 @@ def write_golden(bindir, path=GOLDEN):
                 rows += [(rate, int(snip), n, got.get(i, 0)) for i, n in enumerate(SWEEP_LENGTHS)]
         data["sweep"] = np.array(rows, np.float64)
     np.savez_compressed(path, **data)
+
+
+def load_golden_edges():
+    """({edge case: dict(opts, kind, waves, refs, taken)} as load_golden gives them,
+    {(process case, input name): ([raw matrices of the call], [the tool's output on each])})"""
+    z = np.load(GOLDEN_EDGES)
+    cases = {}
+    for name in json.loads(str(z["names"])):
+        n = int(z[name + "/count"])
+        cases[name] = dict(opts=json.loads(str(z[name + "/opts"])), kind=str(z[name + "/kind"]), taken=bool(z[name + "/taken"]),
+                           waves=[z[f"{name}/wave{i}"] for i in range(n)],
+                           refs=[z[f"{name}/ref{i}"] if f"{name}/ref{i}" in z.files else None for i in range(n)])
+    inputs = edge_process_inputs(np.load(GOLDEN)[EDGE_SOURCE + "/ref0"])
+    proc = {(p, src): (inputs[src], [z[f"process/{p}/{src}/{i}"] for i in range(len(inputs[src]))])
+            for p, src in (tuple(k) for k in json.loads(str(z["process_pairs"])))}
+    return cases, proc
+
+
+def write_golden_edges(bindir, path=GOLDEN_EDGES):
+    """Runs the two reference tools (in `bindir`) on every edge case.  The post-processing inputs come from pitch.npz."""
+    from eesen_amd import kaldi_io
+    compute, process = os.path.join(bindir, "compute-kaldi-pitch-feats"), os.path.join(bindir, "process-kaldi-pitch-feats")
+    data = {"names": json.dumps(EDGE_NAMES), "process_pairs": json.dumps(EDGE_PROCESS_PAIRS)}
+    with tempfile.TemporaryDirectory() as tmp:
+        for c in EDGE_CASES:
+            name = c["name"]
+            data[name + "/opts"] = json.dumps(c["opts"])
+            data[name + "/kind"] = c["kind"]
+            data[name + "/count"] = len(c["waves"])
+            for i, w in enumerate(c["waves"]):
+                data[f"{name}/wave{i}"] = w
+            ark, log = _run_compute(compute, tmp, name, c["opts"], c["waves"], verbose=True)
+            data[name + "/taken"] = "Forward-cost per frame changed from" in log
+            for key, m in kaldi_io.read_mat_table("ark:" + ark):
+                data[f"{name}/ref{int(key[3:])}"] = np.asarray(m, np.float32)
+        inputs = edge_process_inputs(np.load(GOLDEN)[EDGE_SOURCE + "/ref0"])
+        by_name = {p["name"]: p["opts"] for p in PROCESS_CASES}
+        for pname, src in EDGE_PROCESS_PAIRS:
+            raw, out = os.path.join(tmp, f"{pname}_{src}_in.ark"), os.path.join(tmp, f"{pname}_{src}.ark")
+            kaldi_io.write_mat_ark(raw, [(f"utt{i:03d}", np.asarray(m, np.float32)) for i, m in enumerate(inputs[src])])
+            subprocess.run([process] + flags(by_name[pname], PROCESS_FLAGS) + ["ark:" + raw, "ark:" + out], check=True, capture_output=True)
+            for key, m in kaldi_io.read_mat_table("ark:" + out):
+                data[f"process/{pname}/{src}/{int(key[3:])}"] = np.asarray(m, np.float32)
+    np.savez_compressed(path, **data)
+
+
+if __name__ == "__main__":      # python -m tests.pitch_cases [bindir]: remakes pitch_edges.npz after `make -C oracle/ref_build pitchbin`
+    import sys
+    write_golden_edges(sys.argv[1] if len(sys.argv) > 1 else
+                       os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "pitchbin"))

@@ -327,9 +327,21 @@ def process_dim(popts):
     return int(bool(p["add_pov_feature"])) + int(bool(p["add_normalized_log_pitch"])) + int(bool(p["add_delta_pitch"])) + int(bool(p["add_raw_log_pitch"]))
 
 
-def process(raw, popts, noise=None):
+def prefix_sums(v):
+    """P[t] = sum of v over frames < t, T + 1 entries."""
+    return np.concatenate([[0.0], np.cumsum(v)])
+
+
+def prefix_sums_without_carry(v, chunk=256):
+    """A WRONG prefix sum, for the tests' teeth: scanned `chunk` frames at a time as pitch_process_kernel does, but every chunk
+    starts again from zero.  Equal to prefix_sums up to `chunk` frames and on no longer input."""
+    v = np.asarray(v, np.float64)
+    return np.concatenate([[0.0]] + [np.cumsum(v[b:b + chunk]) for b in range(0, len(v), chunk)])
+
+
+def process(raw, popts, noise=None, prefix=prefix_sums):
     """Post-processing of a [T x 2] (NCCF, pitch) matrix in float64 -> [T + delay x columns].  `noise`: the per-frame standard
-    normal draws (None: zero)."""
+    normal draws (None: zero).  `prefix`: how the two pov-weighted prefix sums are formed."""
     p = full_process(popts)
     raw = np.asarray(raw, np.float64)
     T = raw.shape[0]
@@ -339,8 +351,8 @@ def process(raw, popts, noise=None):
         cols.append(p["pov_scale"] * ((1.0001 - np.clip(nc, -1.0, 1.0)) ** 0.15 - 1.0) + p["pov_offset"])
     if p["add_normalized_log_pitch"]:
         pov = nccf_to_pov(nc)
-        c1 = np.concatenate([[0.0], np.cumsum(pov)])
-        c2 = np.concatenate([[0.0], np.cumsum(pov * lp)])
+        c1 = prefix(pov)
+        c2 = prefix(pov * lp)
         t = np.arange(T)
         b = np.maximum(t - p["normalization_left_context"], 0)
         e = np.minimum(t + p["normalization_right_context"] + 1, T)

@@ -3,7 +3,8 @@ tests/golden/paste.npz, the two stand-alone extractors and numpy.
 
 * bit equality: the feeder with the combined head alone, read back through acquire, equals numpy.hstack of api.Fbank.compute and
   api.Pitch.compute(process=True) on the same waveforms and ids, trimmed by the row rule, on every case; a dropped utterance has no
-  rows, pad columns are zero, and a slot reused by a smaller batch shows nothing of the larger one;
+  rows, pad columns are zero, and a slot reused by a smaller batch shows nothing of the larger one; the same on a 6 s waveform with a
+  one-frame, a no-frame and a 300-frame slice behind it (the fixture's waveforms are at most 0.6 s);
 * against the reference's pasted matrices: rows and kept set exact.  Filterbank columns by the rule of tests/test_gpu_fbank.py: the
   distance from the float64 restatement is at most 3 x the case's reference floor (the reference tool's own distance from it).  Pitch
   columns by the rule of tests/test_gpu_pitch.py: the device picks the lag of the float64 restatement -- which picks the reference
@@ -100,6 +101,31 @@ def test_feeder_equals_the_two_extractors(gpu, name):
         assert f.pipeline_shape(1, len(w)) == (m.shape[0], D)
         assert (ref is None) == (m.shape[0] == 0), "the kept set is the reference's"
     host, cols = read_slot(f, f.submit_raw(as_columns(c["waves"])))
+    assert cols == D and host.shape[1] == (D + 3) // 4 * 4
+    exp = assembled(want, host.shape[1])
+    assert host.shape == exp.shape
+    assert np.array_equal(host.view(np.uint32), exp.view(np.uint32))
+
+
+def test_feeder_equals_the_two_extractors_at_utterance_length(gpu):
+    """The same equality at real lengths: the 6 s waveform of the pitch tests (598 frames, past the 256-frame chunks of the pitch
+    post-processing's scan) with a one-pitch-frame slice, a slice without a frame and a 300-frame slice behind it, at 8 kHz.  Device
+    against device, bit for bit, zero rows of the two dropped utterances and pad columns included."""
+    from eesen_amd.api import Fbank, Pitch
+    from tests import pitch_cases
+    popts, waves = pitch_cases.long_and_short()
+    c = dict(GOLD["s33_8k"], waves=waves)
+    assert pr.full(c["pitch"])["samp_freq"] == pr.full(popts)["samp_freq"] == 8000.0
+    assert [r[2] for r in pc.rows_of(c)] == [598, 0, 0, 299]
+    fb, pt = Fbank(**c["fbank"]).compute(waves), Pitch(**c["pitch"]).compute(waves, process=True)
+    assert [m.shape[0] for m in pt] == [598, 1, 0, 300]
+    want = pasted(fb, pt, c["tolerance"])
+    assert [m.shape[0] for m in want] == [598, 0, 0, 299]
+    f = head_feeder(c)
+    D = want[0].shape[1]
+    for w, m in zip(waves, want):
+        assert f.pipeline_shape(1, len(w)) == (m.shape[0], D)
+    host, cols = read_slot(f, f.submit_raw(as_columns(waves)))
     assert cols == D and host.shape[1] == (D + 3) // 4 * 4
     exp = assembled(want, host.shape[1])
     assert host.shape == exp.shape

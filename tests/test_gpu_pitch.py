@@ -13,6 +13,16 @@
   raw output exactly; the noise reproduces per seed and has the mean and deviation asked for; a launch of 33 equals 33 launches of 1;
 * both native tools and both Python mirrors against api.Pitch.
 
+The edge cases of tests/golden/pitch_edges.npz go through the same checks with the same bounds, at the sizes where the kernels take
+another path (tests/pitch_cases.py lists why each is there):
+* stages, search and end to end on lag grids of 63, 64, 65, 448, 449, 1023 and 1024 states -- one wavefront, a full last wavefront,
+  one state in the last wavefront, the sixteen-wavefront maximum -- and on down-sampling ratios 16:3, 441:40 and 16:5; 1025 states
+  are refused with EESEN_ERR_INVALID;
+* post-processing against the tool on 255, 256, 257, 512, 513 and 598 rows and on 598, 1 and 300 rows in one call: the prefix-sum
+  scan's chunks of 256 frames and the carry between them, and an utterance whose sums start behind a long one's;
+* the 6 s waveform with a one-frame, a no-frame and a 300-frame slice behind it in one launch: the same bits as each alone, raw and
+  processed, and process = 1 inside compute equals process on compute's raw output.
+
 Measured figures of one run are in profiles/pitch.md.
 """
 import functools
@@ -29,19 +39,22 @@ from tests import pitch_restatement as pr
 
 pytestmark = pytest.mark.gpu
 GOLD, PROC, SWEEP = pc.load_golden()
+EDGE, EDGE_PROC = pc.load_golden_edges()
+ALL = {**GOLD, **EDGE}
+COMPUTE_NAMES = pc.CASE_NAMES + pc.EDGE_NAMES
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @functools.lru_cache(maxsize=None)
 def restated(name, mode):
-    c = GOLD[name]
+    c = ALL[name]
     return tuple(pr.compute(w.astype(mode), c["opts"], mode) for w in c["waves"])
 
 
 @functools.lru_cache(maxsize=None)
 def device_stages(name):
     from eesen_amd.api import Pitch
-    c = GOLD[name]
+    c = ALL[name]
     pt = Pitch(**c["opts"])
     return tuple(pt.stages(w) for w in c["waves"])
 
@@ -54,14 +67,14 @@ def lag_index(mat, lags):
 @functools.lru_cache(maxsize=None)
 def nccf_floor(name):
     """The float64 restatement's distance from the reference tool in the NCCF column (the lags agree on every frame: CPU test)."""
-    c = GOLD[name]
+    c = ALL[name]
     return max([float(np.abs(ref[:, 0].astype(np.float64) - r["out"][:, 0]).max()) for ref, r in zip(c["refs"], restated(name, np.float64))
                 if ref is not None] + [0.0])
 
 
-@pytest.mark.parametrize("name", pc.CASE_NAMES)
+@pytest.mark.parametrize("name", COMPUTE_NAMES)
 def test_stages_against_restatement(gpu, name):
-    c = GOLD[name]
+    c = ALL[name]
     r64, r32, dev = restated(name, np.float64), restated(name, np.float32), device_stages(name)
     worst = dict(down=0.0, nccf_pitch=0.0, nccf_pov=0.0)
     own = dict(worst)
@@ -83,9 +96,9 @@ def test_stages_against_restatement(gpu, name):
         assert worst[k] <= 3.0 * own[k], (name, k, worst[k], own[k])
 
 
-@pytest.mark.parametrize("name", pc.CASE_NAMES)
+@pytest.mark.parametrize("name", COMPUTE_NAMES)
 def test_search_bit_for_bit(gpu, name):
-    c = GOLD[name]
+    c = ALL[name]
     taken_any = False
     for d in device_stages(name):
         if not d["frames"]:
@@ -101,10 +114,10 @@ def test_search_bit_for_bit(gpu, name):
     assert taken_any == c["taken"], (name, taken_any, c["taken"])
 
 
-@pytest.mark.parametrize("name", pc.CASE_NAMES)
+@pytest.mark.parametrize("name", COMPUTE_NAMES)
 def test_end_to_end_against_the_tool(gpu, name):
     from eesen_amd.api import Pitch
-    c = GOLD[name]
+    c = ALL[name]
     pt = Pitch(**c["opts"])
     got = pt.compute(c["waves"])                       # one launch for the whole case
     lags = pr.lags(c["opts"])
@@ -136,18 +149,69 @@ def test_process_against_the_tool(gpu, pname):
     from eesen_amd.api import Pitch
     popts = next(p["opts"] for p in pc.PROCESS_CASES if p["name"] == pname)
     pt = Pitch(**popts)
-    dim = pr.process_dim(popts)
     for src in pc.PROCESS_INPUTS:
         raws = [m for m in GOLD[src]["refs"] if m is not None]
         refs = [m for m in PROC[pname][src] if m is not None]
-        got = pt.process(raws)
-        worst, floor = np.zeros(dim), np.zeros(dim)
-        for raw, ref, g in zip(raws, refs, got):
-            assert g.shape == ref.shape == (raw.shape[0] + popts.get("delay", 0), dim)
-            worst = np.maximum(worst, np.abs(g.astype(np.float64) - ref).max(axis=0))
-            floor = np.maximum(floor, np.abs(pr.process(raw, popts) - ref).max(axis=0))
-        print(f"pitch process {pname} on {src}: device {worst}, reference floor {floor}")
-        assert np.all(worst <= 3.0 * floor), (pname, src, worst, floor)
+        check_process(pt, pname, popts, src, raws, refs)
+
+
+def check_process(pt, pname, popts, src, raws, refs):
+    """One call of eesen_pitch_process on `raws` against the tool's `refs`: per column within 3 x the reference floor."""
+    dim = pr.process_dim(popts)
+    got = pt.process(raws)
+    worst, floor = np.zeros(dim), np.zeros(dim)
+    for raw, ref, g in zip(raws, refs, got):
+        assert g.shape == ref.shape == (raw.shape[0] + popts.get("delay", 0), dim)
+        worst = np.maximum(worst, np.abs(g.astype(np.float64) - ref).max(axis=0))
+        floor = np.maximum(floor, np.abs(pr.process(raw, popts) - ref).max(axis=0))
+    print(f"pitch process {pname} on {src}: device {worst}, reference floor {floor}")
+    assert np.all(worst <= 3.0 * floor), (pname, src, worst, floor)
+
+
+@pytest.mark.parametrize("pname,src", pc.EDGE_PROCESS_PAIRS)
+def test_process_against_the_tool_at_length(gpu, pname, src):
+    """The same rule past the 256-frame chunk of the prefix-sum scan: 255 .. 598 rows, and 598, 1 and 300 rows in one call."""
+    from eesen_amd.api import Pitch
+    popts = next(p["opts"] for p in pc.PROCESS_CASES if p["name"] == pname)
+    raws, refs = EDGE_PROC[(pname, src)]
+    check_process(Pitch(**popts), pname, popts, src, raws, refs)
+
+
+def test_lag_grid_bound(gpu):
+    """1024 lag states (a workgroup of 16 wavefronts) are accepted and run; one more is refused."""
+    from eesen_amd.api import Pitch, EesenError, pitch_lags, pitch_opts
+    c = EDGE[f"grid_{pc.MAX_STATES}"]
+    pt = Pitch(**c["opts"])
+    assert len(pt.lags()) == pc.MAX_STATES and pt.compute(c["waves"][2:])[0].shape == c["refs"][2].shape
+    over = dict(delta_pitch=pc.delta_pitch_for(pc.MAX_STATES + 1))
+    assert len(pr.lags(over)) == pc.MAX_STATES + 1
+    for refused in (lambda: Pitch(**over), lambda: pitch_lags(pitch_opts(**over))):
+        with pytest.raises(EesenError, match="more than 1024 lag states") as e:
+            refused()
+        assert e.value.code == -1                       # EESEN_ERR_INVALID
+
+
+def test_long_and_short_in_one_launch(gpu):
+    """At lengths past the scan's chunk, with noise 0: compute(process=True) on the four together equals each alone bit for bit, so a
+    short utterance's prefix sums start clean behind a long one's; and process = 1 inside compute equals process on compute's raw
+    output bit for bit."""
+    from eesen_amd.api import Pitch
+    o, waves = pc.long_and_short()
+    for more in (dict(), dict(add_raw_log_pitch=True, delay=2), dict(normalization_left_context=10, normalization_right_context=3)):
+        pt = Pitch(delta_pitch_noise_stddev=0.0, **o, **more)
+        raw = pt.compute(waves)
+        both = pt.compute(waves, process=True)
+        assert [m.shape[0] for m in raw] == [598, 1, 0, 300]
+        for i, w in enumerate(waves):
+            for process, together in ((False, raw), (True, both)):
+                alone = pt.compute([w], process=process)[0]
+                assert alone.shape == together[i].shape and np.array_equal(alone.view(np.uint32), together[i].view(np.uint32)), (more, i, process)
+        keep = [i for i, m in enumerate(raw) if m.shape[0]]
+        after = pt.process([raw[i] for i in keep], utt_ids=keep)
+        for i, m in zip(keep, after):
+            assert m.shape == (raw[i].shape[0] + more.get("delay", 0), pt.shape(0)[2])
+            assert np.array_equal(both[i].view(np.uint32), m.view(np.uint32)), (more, i)
+        assert both[2].shape == (0, 0)
 
 
 def test_process_inside_compute(gpu):

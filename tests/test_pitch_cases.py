@@ -5,6 +5,11 @@ The fixture is the case list; the case list covers what the kernels can get wron
 lag on EVERY frame of every case, takes the energy re-estimate exactly where the tool's log says it did, and counts the tool's frames
 on the whole sweep.  Its remaining distance from the tool, in the NCCF column and in every processed column, is the case's REFERENCE
 FLOOR, printed here and listed in profiles/pitch.md; tests/test_gpu_pitch.py allows the device three of them.
+
+The edge fixture (tests/golden/pitch_edges.npz) is held to the same conditions, and its own promises are asserted: lag grids of exactly
+63 .. 1024 states, down-sampling units of 3, 40 and 5 output samples, post-processing inputs on both sides of 256 and of 512 rows, all
+long enough for an unclamped default window.  A post-processing that loses the carry between its 256-row scans is caught on every
+input past 256 rows and on none up to it, so those lengths test what they are there for.
 """
 import functools
 
@@ -15,6 +20,8 @@ from tests import pitch_cases as pc
 from tests import pitch_restatement as pr
 
 GOLD, PROC, SWEEP = pc.load_golden()
+EDGE, EDGE_PROC = pc.load_golden_edges()
+ALL = {**GOLD, **EDGE}
 
 
 def test_fixture_is_the_case_list():
@@ -65,15 +72,76 @@ def test_case_list_covers_what_the_kernels_can_get_wrong():
     assert any(0 < t < 14 for t in frames["s33_ragged"])                                        # an utterance shorter than that window
 
 
+def test_edge_fixture_is_the_edge_case_list():
+    import os
+    assert list(EDGE) == pc.EDGE_NAMES and not set(EDGE) & set(GOLD)
+    for c in pc.EDGE_CASES:
+        g = EDGE[c["name"]]
+        assert g["opts"] == c["opts"] and g["kind"] == c["kind"] and len(g["waves"]) == len(c["waves"]) == 3
+        for a, b, ref, t in zip(g["waves"], c["waves"], g["refs"], pc.frames_of(c)):
+            assert a.dtype == np.int16 and np.array_equal(a, b)
+            assert ref is not None and ref.shape == (t, 2) and ref.dtype == np.float32
+    assert sorted(EDGE_PROC) == sorted(pc.EDGE_PROCESS_PAIRS)
+    for (pname, src), (raws, refs) in EDGE_PROC.items():
+        popts = next(p["opts"] for p in pc.PROCESS_CASES if p["name"] == pname)
+        assert len(raws) == len(refs)
+        for raw, ref in zip(raws, refs):
+            assert ref.dtype == np.float32 and ref.shape == (raw.shape[0] + popts.get("delay", 0), pr.process_dim(popts))
+    assert os.path.getsize(pc.GOLDEN_EDGES) < 512 * 1024
+
+
+def test_edge_case_list_covers_the_sizes_the_kernels_branch_on():
+    by = {c["name"]: c for c in pc.EDGE_CASES}
+    # the search: one thread per state, ceil(states / 64) wavefronts of which the last is padded with +inf, float4 reads up to ns4
+    states = [len(pr.lags(by[n]["opts"])) for n in pc.GRID_NAMES]
+    assert states == pc.GRID_STATES == [63, 64, 65, 448, 449, 1023, 1024]
+    assert all(set(by[n]["opts"]) == {"delta_pitch"} for n in pc.GRID_NAMES)                     # the default 50 .. 400 Hz
+    assert [-(-s // 64) for s in states] == [1, 1, 2, 7, 8, 16, 16] and pc.MAX_STATES == 1024
+    assert {s % 64 for s in states} >= {0, 1, 63} and {s % 4 for s in states} == {0, 1, 3}
+    assert len(pr.lags(dict(delta_pitch=pc.delta_pitch_for(pc.MAX_STATES + 1)))) == pc.MAX_STATES + 1    # the refused grid exists
+    # the down-sampler: a few phases, more than one output sample per unit
+    for n, unit in pc.RESAMPLE_OUT_UNITS.items():
+        in_unit, out_unit, first, weights = pr.downsample_tables(by[n]["opts"])
+        assert out_unit == unit == len(first) == len(weights)
+    assert sorted(pc.RESAMPLE_OUT_UNITS.values()) == [3, 5, 40] and list(pc.RESAMPLE_OPTS) == pc.EDGE_NAMES[len(pc.GRID_NAMES):]
+    assert pr.downsample_tables(by["rate_44100"]["opts"])[0] == 441 and pr.downsample_tables(by["resample_3000"]["opts"])[0] == 16
+    for c in pc.EDGE_CASES:
+        sf = pr.full(c["opts"])["samp_freq"]
+        assert [len(w) for w in c["waves"]] == [int(round(s * sf)) for s in pc.EDGE_SECONDS] and max(pc.EDGE_SECONDS) <= 0.3
+        assert all(t > 0 for t in pc.frames_of(c))
+        assert all(np.abs(w.astype(np.int32)).max() < 32767 for w in c["waves"])                 # under clipping
+    # the post-processing: the scan's chunk of 256 frames and its carry
+    assert pc.frames_of(next(c for c in pc.CASES if c["name"] == pc.EDGE_SOURCE)) == [598]
+    T = pc.EDGE_LENGTHS
+    for edge in (pc.SCAN_CHUNK, 2 * pc.SCAN_CHUNK):
+        assert edge in T and edge + 1 in T and any(t <= edge for t in T) and any(t > edge for t in T)                            # both sides of 256 and of 512
+    assert {255, 256, 257, 512, 513, 598} == set(T)
+    dflt = pr.PROCESS_DEFAULTS
+    assert all(t >= dflt["normalization_left_context"] + dflt["normalization_right_context"] + 2 == 152 for t in T)   # an unclamped interior
+    o, waves = pc.long_and_short()                                                               # and through compute and the feeder
+    assert o == dict(samp_freq=8000.0) and [pr.num_frames(len(w), o)[1] for w in waves] == [598, 1, 0, 300]
+    assert np.array_equal(waves[0], GOLD[pc.EDGE_SOURCE]["waves"][0])
+    three = EDGE_PROC[("defaults", pc.EDGE_THREE)][0]
+    assert [m.shape[0] for m in three] == [598, 1, 300]
+    pairs = pc.EDGE_PROCESS_PAIRS
+    for p in ("defaults", "all_delay2", "ctx_10_3"):
+        assert [s for q, s in pairs if q == p] == pc.EDGE_INPUT_NAMES
+    assert [s for q, s in pairs if q in ("delta_window3", "raw_only")] == ["rows598", "rows598"] and len(pairs) == 3 * 7 + 2
+    for (pname, src), (raws, _) in EDGE_PROC.items():
+        want = [598, 1, 300] if src == pc.EDGE_THREE else [int(src[4:])]
+        assert [m.shape[0] for m in raws] == want
+        assert np.array_equal(raws[0], GOLD[pc.EDGE_SOURCE]["refs"][0][:want[0]])                # the tool's own rows
+
+
 @functools.lru_cache(maxsize=None)
 def restated(name):
-    c = GOLD[name]
+    c = ALL[name]
     return tuple(pr.compute(w.astype(np.float64), c["opts"]) for w in c["waves"])
 
 
-@pytest.mark.parametrize("name", pc.CASE_NAMES)
+@pytest.mark.parametrize("name", pc.CASE_NAMES + pc.EDGE_NAMES)
 def test_restatement_picks_the_tools_lag_on_every_frame(name):
-    c = GOLD[name]
+    c = ALL[name]
     lags = pr.lags(c["opts"]).astype(np.float64)
     floor, taken = 0.0, False
     for r, ref in zip(restated(name), c["refs"]):
@@ -110,6 +178,44 @@ def test_process_restatement_against_the_tool(pname):
         assert np.all(floor <= 2e-5)      # float32 logarithms and sums scaled by up to 10: sanity, as above
 
 
+def edge_floor(pname, src, prefix=pr.prefix_sums):
+    """Per utterance of the call: the float64 restatement's distance from the tool per column ([utterances x columns])."""
+    popts = next(p["opts"] for p in pc.PROCESS_CASES if p["name"] == pname)
+    raws, refs = EDGE_PROC[(pname, src)]
+    out = []
+    for raw, ref in zip(raws, refs):
+        mine = pr.process(raw, popts, prefix=prefix)
+        assert mine.shape == ref.shape
+        out.append(np.abs(mine - ref).max(axis=0))
+    return np.array(out)
+
+
+@pytest.mark.parametrize("pname,src", pc.EDGE_PROCESS_PAIRS)
+def test_process_restatement_against_the_tool_at_length(pname, src):
+    floor = edge_floor(pname, src).max(axis=0)
+    print(f"pitch reference floor, process {pname} on {src}: {floor}")
+    assert np.all(floor <= 2e-5)          # the same sanity cap as on the short inputs
+
+
+@pytest.mark.parametrize("pname,src", [(p, s) for p, s in pc.EDGE_PROCESS_PAIRS if p != "raw_only"])
+def test_a_dropped_scan_carry_is_caught_past_256_rows_only(pname, src):
+    """The teeth of the lengths: a post-processing whose prefix sums start again from zero every 256 rows (the kernel's scan with its
+    carry lost) is the restatement itself up to 256 rows, and on every longer utterance its normalised column is more than the
+    3 x reference floor the device gets away from the tool."""
+    popts = next(p["opts"] for p in pc.PROCESS_CASES if p["name"] == pname)
+    col = int(pr.full_process(popts)["add_pov_feature"])                    # the normalised column follows the POV one
+    floor = edge_floor(pname, src)[:, col]
+    wrong = edge_floor(pname, src, prefix=pr.prefix_sums_without_carry)[:, col]
+    rows = [m.shape[0] for m in EDGE_PROC[(pname, src)][0]]
+    print(f"pitch process without the carry, {pname} on {src}: rows {rows}, distance {wrong}, reference floor {floor}")
+    for t, w, f in zip(rows, wrong, floor):
+        if t <= pc.SCAN_CHUNK:
+            assert w <= f
+        else:
+            assert w > 3.0 * floor.max(), (t, w, floor)           # the pair's floor, as the device test takes it
+    assert any(t > pc.SCAN_CHUNK for t in rows) or src in ("rows255", "rows256")
+
+
 def test_frame_counts_against_the_sweep():
     from eesen_amd.api import Pitch
     assert sorted({r for r, _ in SWEEP}) == [8000.0, 11025.0, 16000.0]
@@ -133,6 +239,20 @@ def test_lags_against_restatement():
         want = pr.lags(o)
         assert np.array_equal(Pitch(**o).lags(), want) and np.array_equal(pitch_lags(pitch_opts(**o)), want)
     assert len(pr.lags({})) == 417
+
+
+def test_edge_lag_grids_on_the_host():
+    """The library's lag grid equals the restatement's at every edge size; 1024 states are accepted and one more is refused."""
+    from eesen_amd.api import Pitch, EesenError, pitch_lags, pitch_opts
+    for c in pc.EDGE_CASES:
+        want = pr.lags(c["opts"])
+        assert np.array_equal(Pitch(**c["opts"]).lags(), want) and np.array_equal(pitch_lags(pitch_opts(**c["opts"])), want)
+        assert [Pitch(**c["opts"]).shape(len(w))[0] for w in c["waves"]] == pc.frames_of(c)
+    over = dict(delta_pitch=pc.delta_pitch_for(pc.MAX_STATES + 1))
+    for refused in (lambda: Pitch(**over), lambda: pitch_lags(pitch_opts(**over))):
+        with pytest.raises(EesenError, match="more than 1024 lag states") as e:
+            refused()
+        assert e.value.code == -1                       # EESEN_ERR_INVALID
 
 
 def test_defaults_are_the_references():
