@@ -161,6 +161,10 @@ SIGNATURES = {
     "eesen_feeder_pipeline_shape": (_i, [_vp, _i, _i, _pi, _pi]),
     "eesen_feeder_submit_raw": (_i, [_vp, C.POINTER(_vp), _pi, _pi, C.POINTER(_vp), _i, _i, _pi]),
     "eesen_cmvn_norm": (_i, [_pd, _i, _i, _i, _pf]),
+    "eesen_cmvn_stats_parallel": (_i, [_i, _vp, C.POINTER(_vp), _pi, _pi, C.POINTER(_vp), _i, _i, _pd]),
+    "eesen_feeder_set_stats_tap": (_i, [_vp, _i]),
+    "eesen_feeder_stats": (_i, [_vp, _i, _pd, _pi]),
+    "eesen_cmvn_stats_bench": (_i, [_i, _vp, C.POINTER(_vp), _pi, _i, _i, _i, _pf]),
     "eesen_fbank_opts_default": (_i, [_vp]),
     "eesen_fbank_create": (_i, [_i, _vp, _vp, C.POINTER(_vp)]),
     "eesen_fbank_destroy": (_i, [_vp]),

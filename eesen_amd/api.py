@@ -1110,6 +1110,7 @@ class Feeder:
         self.h = C.c_void_p()
         check(self.lib.eesen_feeder_create(device, C.c_void_p(stream) if stream else None, slots, C.byref(self.h)))
         self._dims = {}
+        self._batch = {}    # slot -> (utterances, widest boundary) of its batch, for stats()
 
     def __del__(self):
         if getattr(self, "h", None) and self.h:
@@ -1171,6 +1172,7 @@ class Feeder:
         slot = C.c_int()
         check(self.lib.eesen_feeder_submit_raw(self.h, ptrs, frames.ctypes.data_as(C.POINTER(C.c_int)), None, cptr, S, D, C.byref(slot)))
         self._dims[slot.value] = self.pipeline_shape(D, 1)[1]
+        self._batch[slot.value] = (S, max(D, self._dims[slot.value]))
         return slot.value
 
     def submit(self, mats: Sequence[np.ndarray]) -> int:
@@ -1192,6 +1194,7 @@ class Feeder:
         check(self.lib.eesen_feeder_submit(self.h, ptrs, frames.ctypes.data_as(C.POINTER(C.c_int)), strides.ctypes.data_as(C.POINTER(C.c_int)),
                                            S, D, C.byref(slot)))
         self._dims[slot.value] = D
+        self._batch[slot.value] = (S, D)
         return slot.value
 
     def acquire(self, slot: int) -> CuMatrix:
@@ -1201,6 +1204,64 @@ class Feeder:
 
     def release(self, slot: int):
         check(self.lib.eesen_feeder_release(self.h, slot))
+
+    def set_stats_tap(self, boundary: int):
+        """CMVN statistics of what the pipeline holds at stage boundary `boundary` (0: what was submitted, k: what stage k-1 wrote;
+        -1: off), computed beside the batch assembly (`eesen_feeder_set_stats_tap`); read them with `stats(slot)`."""
+        check(self.lib.eesen_feeder_set_stats_tap(self.h, int(boundary)))
+
+    def stats(self, slot: int) -> List[np.ndarray]:
+        """Per utterance of the batch in `slot` the [2 x (D+1)] float64 statistics at the tapped boundary (`eesen_feeder_stats`)."""
+        if slot not in self._dims:
+            raise EesenError(-3, "slot holds no submitted batch")
+        S, widest = self._batch[slot]     # no stage narrows a matrix: the widest boundary is the first or the last
+        buf = np.zeros(S * 2 * (widest + 1), np.float64)
+        d = C.c_int()
+        check(self.lib.eesen_feeder_stats(self.h, int(slot), buf.ctypes.data_as(C.POINTER(C.c_double)), C.byref(d)))
+        n = 2 * (d.value + 1)
+        return [buf[s * n:(s + 1) * n].reshape(2, d.value + 1).copy() for s in range(S)]
+
+
+def cmvn_stats(mats: Sequence[np.ndarray], weights: Optional[Sequence[Optional[np.ndarray]]] = None, device: int = 0,
+               stream: Optional[int] = None) -> List[np.ndarray]:
+    """CMVN statistics on the device (`eesen_cmvn_stats_parallel`; the reference's AccCmvnStats): per matrix [T_s x D] the
+    [2 x (D+1)] float64 matrix of sums, count and sums of squares; weights[s] is None (all ones) or T_s per-frame weights."""
+    if not len(mats):
+        raise EesenError(-1, "empty minibatch")
+    mats = [m if (isinstance(m, np.ndarray) and m.dtype == np.float32 and m.ndim == 2 and m.strides[1] == 4 and m.strides[0] % 4 == 0
+                  and m.strides[0] >= 4 * m.shape[1]) else np.ascontiguousarray(m, np.float32) for m in mats]
+    D = mats[0].shape[1] if mats[0].ndim == 2 else 0
+    for m in mats:
+        if m.ndim != 2 or m.shape[1] != D:
+            raise EesenError(-1, f"feature dimension {m.shape[1] if m.ndim == 2 else m.shape} does not match {D}")
+    S = len(mats)
+    ptrs = (C.c_void_p * S)(*[m.ctypes.data for m in mats])
+    frames = np.array([m.shape[0] for m in mats], np.int32)
+    strides = np.array([m.strides[0] // 4 if m.shape[0] > 1 else max(D, 1) for m in mats], np.int32)
+    wptr = None
+    if weights is not None:
+        if len(weights) != S:
+            raise EesenError(-1, "one weight vector (or None) per utterance")
+        weights = [None if w is None else np.ascontiguousarray(w, np.float32).reshape(-1) for w in weights]
+        for w, m in zip(weights, mats):
+            if w is not None and len(w) != m.shape[0]:
+                raise EesenError(-1, f"weights have wrong dimension {len(w)} vs. {m.shape[0]}")
+        wptr = (C.c_void_p * S)(*[None if w is None else w.ctypes.data for w in weights])
+    out = np.zeros((S, 2, D + 1), np.float64)
+    check(_lib.load().eesen_cmvn_stats_parallel(device, C.c_void_p(stream) if stream else None, ptrs, frames.ctypes.data_as(C.POINTER(C.c_int)),
+                                               strides.ctypes.data_as(C.POINTER(C.c_int)), wptr, S, D, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return [out[s].copy() for s in range(S)]
+
+
+def cmvn_stats_bench(mats: Sequence[np.ndarray], iters: int = 20, device: int = 0) -> float:
+    """Average milliseconds of one statistics launch on these matrices (`eesen_cmvn_stats_bench`)."""
+    mats = [np.ascontiguousarray(m, np.float32) for m in mats]
+    S, D = len(mats), mats[0].shape[1]
+    ptrs = (C.c_void_p * S)(*[m.ctypes.data for m in mats])
+    frames = np.array([m.shape[0] for m in mats], np.int32)
+    ms = C.c_float()
+    check(_lib.load().eesen_cmvn_stats_bench(device, None, ptrs, frames.ctypes.data_as(C.POINTER(C.c_int)), S, D, int(iters), C.byref(ms)))
+    return ms.value
 
 
 def paste_feats(inputs: Sequence[Sequence[np.ndarray]], tolerance: int = 0, device: int = 0, stream: Optional[int] = None) -> List[Optional[np.ndarray]]:

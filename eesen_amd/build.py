@@ -14,8 +14,8 @@ _DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_DIR, "csrc")
 LIBDIR = os.path.join(_DIR, "lib")
 LIB = os.path.join(LIBDIR, "libeesen_hip.so")
-SOURCES = ["gemm.hip", "lstm.hip", "lstm_persistent.hip", "rec_plan.cpp", "ctc.hip", "ctc_decode.hip", "edit_distance.hip", "ce.hip", "optim.hip", "feeder.hip", "fbank.hip", "fbank_host.cpp", "pitch.hip", "pitch_host.cpp", "net.cpp", "ctc_host.cpp", "ce_host.cpp", "nnet_format.cpp", "lm.cpp", "lex.cpp", "capi.cpp", "comm.cpp"]
-HEADERS = ["common.h", "guard.h", "kernels.h", "rec_kernels.h", "net.h", "lm.h", "lex.h", "handles.h", "fbank.h", "pitch.h", "feat_layout.h", "dither.h", "tuning.h", "lstm_fwd_bf_step.inc", "ctc_word_beam.inc", os.path.join("..", "..", "include", "eesen_hip.h")]
+SOURCES = ["gemm.hip", "lstm.hip", "lstm_persistent.hip", "rec_plan.cpp", "ctc.hip", "ctc_decode.hip", "edit_distance.hip", "ce.hip", "optim.hip", "feeder.hip", "cmvn_stats.hip", "fbank.hip", "fbank_host.cpp", "pitch.hip", "pitch_host.cpp", "net.cpp", "ctc_host.cpp", "ce_host.cpp", "nnet_format.cpp", "lm.cpp", "lex.cpp", "capi.cpp", "comm.cpp"]
+HEADERS = ["common.h", "guard.h", "kernels.h", "rec_kernels.h", "net.h", "lm.h", "lex.h", "handles.h", "fbank.h", "cmvn_stats.h", "pitch.h", "feat_layout.h", "dither.h", "tuning.h", "lstm_fwd_bf_step.inc", "ctc_word_beam.inc", os.path.join("..", "..", "include", "eesen_hip.h")]
 FLAGS = (os.environ.get("EESEN_BUILD_DEFS", "").split()) + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # pitch.hip's search is float32 in a fixed order that a numpy restatement reproduces bit for bit: no fused multiply-add anywhere in that
 # file, the bodies of __fmul_rn / __fadd_rn in the HIP headers included (a pragma in the file does not reach those)
@@ -23,7 +23,7 @@ FILE_FLAGS = {"pitch.hip": ["-ffp-contract=off"]}
 
 BINDIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin")
 TOOLS = {"train-ctc-parallel": "train_ctc_parallel.cc", "train-ce-parallel": "train_ce_parallel.cc", "net-output-extract": "net_output_extract.cc", "ctc-align": "ctc_align.cc", "ctc-decode": "ctc_decode.cc", "compute-fbank-feats": "compute_fbank_feats.cc",
-         "compute-kaldi-pitch-feats": "compute_kaldi_pitch_feats.cc", "process-kaldi-pitch-feats": "process_kaldi_pitch_feats.cc", "paste-feats": "paste_feats.cc"}
+         "compute-kaldi-pitch-feats": "compute_kaldi_pitch_feats.cc", "process-kaldi-pitch-feats": "process_kaldi_pitch_feats.cc", "paste-feats": "paste_feats.cc", "compute-cmvn-stats": "compute_cmvn_stats.cc"}
 
 
 def csrc_digest() -> str:

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "cmvn_stats.h"
 #include "fbank.h"
 #include "guard.h"
 #include "pitch.h"
@@ -191,9 +192,14 @@ struct Feeder {
     // filterbank + pitch head stage: the filterbank matrix before the join, and the pitch tracker's scratch
     DevBuf<float> fbank;
     PitchScratch pitch;
+    // the statistics tap: the chunks' partial sums, the batch's statistics, and their pinned copy (read after `ready`)
+    DevBuf<double> stats_part, stats_d;
+    PinBuf stats_h;
+    int stats_D = 0;        // the dimension at the tapped boundary; 0: this batch was not tapped
   };
   struct Stage { int kind, a, b; size_t scale_off; };
   std::vector<Stage> pipe;
+  int tap = -1;             // the stage boundary whose CMVN statistics are computed beside the assembly (-1: none)
   std::vector<long> tab;    // a batch's tables while it can still be refused: no slot is taken before they are complete
   DevBuf<float> scales_d;
   // EESEN_FEAT_FBANK, the head stage that turns waveforms into features (fbank.hip); every waveform submitted gets a dither key of its own
@@ -286,12 +292,35 @@ struct Feeder {
       np.push_back(g);
     }
     EESEN_REQUIRE(n_cmvn <= 1, EESEN_ERR_INVALID, "at most one CMVN stage");
+    EESEN_REQUIRE(tap <= n, EESEN_ERR_INVALID, "the statistics tap sits on boundary " + std::to_string(tap) + ", beyond this pipeline: move it first (eesen_feeder_set_stats_tap)");
     drain();
     if (!scales.empty()) {
       scales_d.reserve(scales.size());
       EESEN_HIP_CHECK(hipMemcpy(scales_d.p, scales.data(), scales.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     pipe.swap(np);
+  }
+  void set_stats_tap(int boundary) {
+    EESEN_REQUIRE(boundary >= -1 && boundary <= (int)pipe.size(), EESEN_ERR_INVALID,
+                  "the statistics tap goes on boundary 0.." + std::to_string(pipe.size()) + " of the current pipeline, or -1 for none");
+    EESEN_HIP_CHECK(hipSetDevice(device));
+    drain();
+    tap = boundary;
+  }
+  // AccCmvnStats of every utterance at boundary b, as it lies packed in `x` (unread where the boundary holds no frame), into the slot's
+  // pinned block: enqueued on the copy stream behind whatever wrote the boundary
+  void tap_stats(Slot& sl, const std::vector<int>& dims, const BatchTables& t, const BatchTables& d, const long* total, int b, int S, const float* x) {
+    const int D = dims[b];
+    const size_t n = (size_t)S * 2 * (D + 1);
+    int longest = 0;
+    for (int s = 0; s < S; ++s) longest = std::max(longest, t.frames[(size_t)b * S + s]);
+    const int rows = cmvn_chunk_rows(D);
+    sl.stats_part.reserve(cmvn_partial_doubles(total[b] / D, S, D, rows));
+    sl.stats_d.reserve(n);
+    double* h = static_cast<double*>(sl.stats_h.reserve(n * sizeof(double)));
+    cmvn_stats_launch(x, d.off + (size_t)b * S, d.frames + (size_t)b * S, nullptr, S, D, longest, rows, sl.stats_part.p, sl.stats_d.p, copy);
+    EESEN_HIP_CHECK(hipMemcpyAsync(h, sl.stats_d.p, n * sizeof(double), hipMemcpyDeviceToHost, copy));
+    sl.stats_D = D;
   }
   void set_fbank(const eesen_fbank_opts_t& o) {
     std::unique_ptr<FbankPlan> np(new FbankPlan(o));
@@ -404,6 +433,8 @@ struct Feeder {
       EESEN_REQUIRE(!Dc || frames[s] == 0 || cmvn[s] != nullptr, EESEN_ERR_INVALID, "null CMVN vectors");
     }
     EESEN_REQUIRE(T > 0, EESEN_ERR_INVALID, "every utterance is empty after the front end");
+    const int tb = tap <= nst ? tap : -1;   // the tapped boundary (a plain submit has boundary 0 only)
+    EESEN_REQUIRE(tb < 0 || S <= 65535, EESEN_ERR_INVALID, "the statistics tap takes at most 65535 utterances per batch");
     if (h.kind) {   // the waveforms are [samples x 1]: their sample offsets are boundary 0's, written again as they are
       h.fb = fbank_layout(frames, S, fb_plan->dim, [this](int n) { return fb_plan->num_frames(n); }, t.off, t.prefix, t.fb_off);
       for (int s = 0; s < S; ++s) t.ids[s] = fb_next_id + s;
@@ -439,14 +470,20 @@ struct Feeder {
     const BatchTables d = batch_carve(sl.tab_d.p, nb, S, h.kind);
     if (total[0]) EESEN_HIP_CHECK(hipMemcpyAsync(sl.packed.p, host, (size_t)total[0] * sizeof(float), hipMemcpyHostToDevice, copy));
     EESEN_HIP_CHECK(hipMemcpyAsync(sl.tab_d.p, sl.tab_h.p, tab.size() * 8, hipMemcpyHostToDevice, copy));
+    sl.stats_D = 0;
+    if (tb == 0) tap_stats(sl, dims, t, d, total.data(), 0, S, sl.packed.p);
     for (int k = 0; k < nst; ++k) {
-      if (!total[k + 1]) continue;
+      if (!total[k + 1]) {   // nothing to write; a tap on it answers zeros
+        if (tb == k + 1) tap_stats(sl, dims, t, d, total.data(), k + 1, S, nullptr);
+        continue;
+      }
       const float* src = k % 2 ? sl.packed2.p : sl.packed.p;
       float* dst = k % 2 ? sl.packed.p : sl.packed2.p;
       long biggest = 0;
       for (int s = 0; s < S; ++s) biggest = std::max(biggest, (long)t.frames[(size_t)(k + 1) * S + s] * dims[k + 1]);
       if (k == 0 && h.kind) {
         head_stage(sl, h, d, S, src, dst, dims[1], biggest);
+        if (tb == 1) tap_stats(sl, dims, t, d, total.data(), 1, S, dst);
         continue;
       }
       const StageDev sd{pl[k].kind, pl[k].a, pl[k].b};
@@ -454,6 +491,7 @@ struct Feeder {
                          d.off + (size_t)k * S, d.frames + (size_t)k * S, dims[k], dst, d.off + (size_t)(k + 1) * S,
                          d.frames + (size_t)(k + 1) * S, dims[k + 1], sl.cmvn_d.p);
       check_launch("feat_stage_kernel");
+      if (tb == k + 1) tap_stats(sl, dims, t, d, total.data(), k + 1, S, dst);
     }
     assemble(sl, nst % 2 ? sl.packed2.p : sl.packed.p, d.off + (size_t)nst * S, d.frames + (size_t)nst * S, T, S, dims[nst]);
     sl.ready.record(copy);
@@ -477,6 +515,14 @@ struct Feeder {
     EESEN_HIP_CHECK(hipSetDevice(device));
     EESEN_HIP_CHECK(hipStreamWaitEvent(compute, sl.ready, 0));  // device-side wait: the host does not block
     *feats = sl.out.p; *T = sl.T; *S = sl.S; *ld = sl.ld;
+  }
+  void stats(int id, double* out, int* D) {
+    EESEN_REQUIRE(tap >= 0, EESEN_ERR_STATE, "the statistics tap is off (eesen_feeder_set_stats_tap)");
+    Slot& sl = checked(id);
+    EESEN_REQUIRE(sl.stats_D > 0, EESEN_ERR_STATE, "the slot's batch was submitted without the statistics tap");
+    sl.ready.wait();
+    std::memcpy(out, sl.stats_h.p, (size_t)sl.S * 2 * (sl.stats_D + 1) * sizeof(double));
+    *D = sl.stats_D;
   }
   void release(int id) {  // everything enqueued on the compute stream so far may read the slot; later work may not
     Slot& sl = checked(id);
@@ -514,6 +560,15 @@ int eesen_feeder_set_pipeline(eesen_feeder_t* f, const eesen_feat_stage_t* stage
     REQ_PTR(f);
     if (n_stages > 0) REQ_PTR(stages);
     f->set_pipeline(stages, n_stages);
+  });
+}
+int eesen_feeder_set_stats_tap(eesen_feeder_t* f, int boundary) {
+  return guard([&] { REQ_PTR(f); f->set_stats_tap(boundary); });
+}
+int eesen_feeder_stats(eesen_feeder_t* f, int slot, double* stats, int* D) {
+  return guard([&] {
+    REQ_PTR(f); REQ_PTR(stats); REQ_PTR(D);
+    f->stats(slot, stats, D);
   });
 }
 int eesen_feeder_set_fbank(eesen_feeder_t* f, const eesen_fbank_opts_t* opts) {

@@ -284,6 +284,14 @@ inline Spec parse_spec(const std::string& s) {
   if (sp.kind != "ark" && sp.kind != "scp") throw std::runtime_error("unsupported table kind in '" + s + "'");
   return sp;
 }
+// `path[:offset]` of a script-file entry: the byte offset behind the last ':' when only digits follow it
+inline std::streamoff split_scp_offset(std::string* loc) {
+  const size_t c = loc->rfind(':');
+  if (c == std::string::npos || c + 1 >= loc->size() || loc->find_first_not_of("0123456789", c + 1) != std::string::npos) return 0;
+  const std::streamoff off = std::stoll(loc->substr(c + 1));
+  *loc = loc->substr(0, c);
+  return off;
+}
 // SequentialBaseFloatMatrixReader (train-ctc-parallel.cc:124)
 class FeatureReader {
  public:
@@ -349,12 +357,7 @@ class FeatureReader {
       key_ = line.substr(k0, k1 - k0);
       const std::string whole = line.substr(r0);
       std::string loc = whole.substr(0, whole.find_first_of(" \t"));
-      std::streamoff off = 0;
-      const size_t c = loc.rfind(':');
-      if (c != std::string::npos && c + 1 < loc.size() && loc.find_first_not_of("0123456789", c + 1) == std::string::npos) {
-        off = std::stoll(loc.substr(c + 1));
-        loc = loc.substr(0, c);
-      }
+      const std::streamoff off = split_scp_offset(&loc);
       // a script entry may itself be a command: `key cmd args |`
       if (!whole.empty() && whole.find_last_not_of(" \t") != std::string::npos && whole[whole.find_last_not_of(" \t")] == '|') {
         InStream a(whole);
@@ -395,11 +398,11 @@ inline std::map<std::string, std::vector<int32_t>> read_targets(const std::strin
 }
 
 
-// BaseFloatMatrixWriter to `ark:file` (binary), `ark,t:file` (text) or `ark,scp:file.ark,file.scp` (the archive and a script of
+// What the matrix writers share: `ark:file` (binary), `ark,t:file` (text) or `ark,scp:file.ark,file.scp` (the archive and a script of
 // `key file.ark:offset` lines, the offset pointing at the object behind the key)
-class MatrixWriter {
+class TableWriterBase {
  public:
-  explicit MatrixWriter(const std::string& wspecifier) {
+  explicit TableWriterBase(const std::string& wspecifier) {
     const size_t colon = wspecifier.find(':');
     if (colon == std::string::npos) throw std::runtime_error("bad table specifier '" + wspecifier + "' (expected ark:... or ark,scp:...)");
     std::vector<std::string> opts;
@@ -421,37 +424,146 @@ class MatrixWriter {
     ark_path_ = path;
     out_.reset(new OutStream(path));
   }
-  void Write(const std::string& key, const float* data, int rows, int cols, int ld) {
+ protected:
+  std::ostream& Begin(const std::string& key) {   // the script line and `key `: the object follows
     std::ostream& f_ = out_->get();
     if (scp_) {   // the offset points behind `key `; text entries have no fixed size, so the stream says how far it got
       *scp_ << key << ' ' << ark_path_ << ':' << (long)f_.tellp() + (long)key.size() + 1 << "\n";
       scp_->flush();
     }
     f_ << key << ' ';
-    if (text_) {
-      f_ << " [";
-      f_.precision(9);
-      for (int r = 0; r < rows; ++r) {
-        f_ << "\n  ";
-        for (int c = 0; c < cols; ++c) f_ << data[(size_t)r * ld + c] << ' ';
-      }
-      f_ << "]\n";
-    } else {
-      f_.write("\0BFM ", 5);
-      const char four = 4;
-      const int32_t rc[2] = {rows, cols};
-      for (int i = 0; i < 2; ++i) { f_.write(&four, 1); f_.write(reinterpret_cast<const char*>(&rc[i]), 4); }
-      for (int r = 0; r < rows; ++r) f_.write(reinterpret_cast<const char*>(data + (size_t)r * ld), (size_t)cols * 4);
-    }
+    return f_;
+  }
+  static void End(std::ostream& f_) {
     f_.flush();   // every utterance leaves at once: downstream tools of a pipe (`... ark:- | latgen-faster ...`) start on it
     if (!f_) throw std::runtime_error("write error");
   }
- private:
   std::unique_ptr<OutStream> out_;
   std::unique_ptr<std::ofstream> scp_;
   std::string ark_path_;
   bool text_ = false;
 };
+
+// Matrix<Real>::Write (src/cpucompute/matrix.cc:1104-1140) behind the binary header: token FM / DM, the two sized ints, the rows; in
+// text ` [`, one line per row, `]`
+template <class Real>
+inline void write_matrix_body(std::ostream& f_, bool text, const Real* data, int rows, int cols, int ld, int precision) {
+  if (text) {
+    f_ << " [";
+    f_.precision(precision);
+    for (int r = 0; r < rows; ++r) {
+      f_ << "\n  ";
+      for (int c = 0; c < cols; ++c) f_ << data[(size_t)r * ld + c] << ' ';
+    }
+    f_ << "]\n";
+    return;
+  }
+  f_.write(sizeof(Real) == 8 ? "\0BDM " : "\0BFM ", 5);
+  const char four = 4;
+  const int32_t rc[2] = {rows, cols};
+  for (int i = 0; i < 2; ++i) { f_.write(&four, 1); f_.write(reinterpret_cast<const char*>(&rc[i]), 4); }
+  for (int r = 0; r < rows; ++r) f_.write(reinterpret_cast<const char*>(data + (size_t)r * ld), (size_t)cols * sizeof(Real));
+}
+
+// BaseFloatMatrixWriter
+class MatrixWriter : public TableWriterBase {
+ public:
+  using TableWriterBase::TableWriterBase;
+  void Write(const std::string& key, const float* data, int rows, int cols, int ld) {
+    std::ostream& f_ = Begin(key);
+    write_matrix_body(f_, text_, data, rows, cols, ld, 9);
+    End(f_);
+  }
+};
+
+// DoubleMatrixWriter (compute-cmvn-stats.cc:90): `DM` in binary; in text the reference's stream precision, 7 digits
+// (InitKaldiOutputStream, src/base/io-funcs-inl.h:188-193)
+class DoubleMatrixWriter : public TableWriterBase {
+ public:
+  using TableWriterBase::TableWriterBase;
+  void Write(const std::string& key, const double* data, int rows, int cols) {
+    std::ostream& f_ = Begin(key);
+    write_matrix_body(f_, text_, data, rows, cols, cols, 7);
+    End(f_);
+  }
+};
+
+// Vector<BaseFloat>::Read (src/cpucompute/vector.cc): binary `FV ` + sized int + floats, text ` [ 1 2 3 ]`
+inline std::vector<float> read_float_vector(std::istream& is) {
+  std::vector<float> v;
+  if (is.peek() == '\0') {
+    is.get(); is.get();
+    std::string tok;
+    is >> tok;
+    is.get();
+    if (tok != "FV" && tok != "DV") throw std::runtime_error("expected FV or DV, got " + tok);
+    const int32_t n = read_sized_int(is);
+    if (n < 0) throw std::runtime_error("negative vector size in table");
+    v.resize(n);
+    if (tok == "FV") {
+      is.read(reinterpret_cast<char*>(v.data()), (std::streamsize)n * 4);
+    } else {
+      std::vector<double> d(n);
+      is.read(reinterpret_cast<char*>(d.data()), (std::streamsize)n * 8);
+      for (int32_t i = 0; i < n; ++i) v[i] = (float)d[i];
+    }
+    need(is, "vector data");
+    return v;
+  }
+  char c;
+  do { need(is.get(c), "text vector"); } while (c != '[');
+  std::string body;
+  std::getline(is, body, ']');
+  std::istringstream ls(body);
+  float f;
+  while (ls >> f) v.push_back(f);
+  std::getline(is, body);  // rest of the closing line
+  return v;
+}
+// key -> object of an `ark:` or `scp:` table read whole: read_obj(stream) reads one object
+template <class T, class ReadObj>
+inline void read_whole_table(const std::string& rspecifier, ReadObj read_obj, std::vector<std::pair<std::string, T>>* out) {
+  const Spec sp = parse_spec(rspecifier);
+  InStream in(sp.path);
+  std::istream& f = in.get();
+  if (sp.kind == "ark") {
+    for (std::string key = read_key(f); !key.empty(); key = read_key(f)) out->emplace_back(key, read_obj(f));
+    in.CloseChecked();
+    return;
+  }
+  std::string line;
+  while (std::getline(f, line)) {
+    std::istringstream ls(line);
+    std::string key, loc;
+    if (!(ls >> key >> loc)) continue;
+    const std::streamoff off = split_scp_offset(&loc);
+    std::ifstream a(loc, std::ios::binary);
+    if (!a) throw std::runtime_error("cannot open " + loc);
+    a.seekg(off);
+    out->emplace_back(key, read_obj(a));
+  }
+}
+// RandomAccessBaseFloatVectorReader (compute-cmvn-stats.cc:84): the whole table in memory
+inline std::map<std::string, std::vector<float>> read_float_vectors(const std::string& rspecifier) {
+  std::vector<std::pair<std::string, std::vector<float>>> items;
+  read_whole_table<std::vector<float>>(rspecifier, read_float_vector, &items);
+  std::map<std::string, std::vector<float>> t;
+  for (auto& kv : items) t[kv.first] = std::move(kv.second);
+  return t;
+}
+// SequentialTokenVectorReader (compute-cmvn-stats.cc:93, TokenVectorHolder: one line of tokens per key): spk2utt, in file order
+inline std::vector<std::pair<std::string, std::vector<std::string>>> read_token_lists(const std::string& rspecifier) {
+  std::vector<std::pair<std::string, std::vector<std::string>>> out;
+  read_whole_table<std::vector<std::string>>(rspecifier, [](std::istream& is) {
+    std::string line;
+    std::getline(is, line);
+    std::istringstream ls(line);
+    std::vector<std::string> toks;
+    for (std::string t; ls >> t;) toks.push_back(t);
+    return toks;
+  }, &out);
+  return out;
+}
 
 // Int32VectorWriter to `ark:file` (binary) or `ark,t:file` (text): what read_int_vector above and the trainers' target readers take
 class IntVectorWriter {

@@ -15,7 +15,8 @@ Host-side data loading for the CLI mirror (eesen_amd/train_ctc_parallel.py); for
 Supported specifiers: `ark:path`, `ark,t:path`, `scp:path`, and the "extended filenames" of src/util/kaldi-io.cc the recipes
 use: `-` (stdin for readers, stdout for writers), `cmd |` (read the command's output: steps/train_ctc_parallel.sh:95-115
 always passes `ark,s,cs:apply-cmvn ... |` and `ark:gunzip -c labels.tr.gz|`) and `| cmd` (write into the command).
-Double-precision matrices are outside the hot path and raise.
+Double-precision matrices (CMVN statistics) have readers and a writer of their own (`read_mat64_*`, `write_mat64_ark`); the
+feature readers raise on them.
 """
 from __future__ import annotations
 
@@ -420,6 +421,43 @@ def read_token_map(spec: str) -> Dict[str, str]:
     return out
 
 
+def _read_float_vector(f: BinaryIO) -> np.ndarray:
+    """Vector<BaseFloat>::Read (cpucompute/vector.cc): binary `FV ` (or `DV `, converted) + sized int32 count + raw elements; text
+    ` [ 1 2 3 ]`."""
+    hdr = f.read(2)
+    if hdr == b"\x00B":
+        tok = f.read(3)
+        if tok not in (b"FV ", b"DV "):
+            raise KaldiIOError(f"expected FV or DV, got {tok!r}")
+        n = _read_sized_int(f)
+        w = 4 if tok == b"FV " else 8
+        if n < 0:
+            raise KaldiIOError("negative size of a float vector")
+        buf = f.read(w * n)
+        if len(buf) != w * n:
+            raise KaldiIOError("truncated float vector")
+        return np.frombuffer(buf, dtype="<f4" if w == 4 else "<f8").astype(np.float32)
+    txt = bytearray(hdr)
+    while b"]" not in txt:
+        chunk = f.readline()
+        if not chunk:
+            raise KaldiIOError("unterminated text vector")
+        txt += chunk
+    s = txt.decode()
+    return np.array(s[s.index("[") + 1: s.index("]")].split(), dtype=np.float32)
+
+
+def read_vec_float_table(spec: str) -> Dict[str, np.ndarray]:
+    """RandomAccessBaseFloatVectorReader (featbin/compute-cmvn-stats.cc:84): the whole table as a dict."""
+    return dict(_iter_table(spec, _read_float_vector))
+
+
+def read_token_lists(spec: str) -> List[Tuple[str, List[str]]]:
+    """SequentialTokenVectorReader (compute-cmvn-stats.cc:93; TokenVectorHolder: one line of tokens behind the key): spk2utt, in
+    the file's order."""
+    return [(k, v) for k, v in _iter_table(spec, lambda f: f.readline().decode().split())]
+
+
 def read_vec_int_table(spec: str) -> Dict[str, np.ndarray]:
     """RandomAccessInt32VectorReader (train-ctc-parallel.cc:125): the whole table as a dict."""
     return dict(_iter_table(spec, _read_int_vector))
@@ -440,6 +478,39 @@ def write_mat_ark(path: str, items, text: bool = False, scp_path: str = None):
             if scp:
                 scp.write(f"{key} {path}:{pos}\n")
             body = _matrix_bytes(m, text)
+            f.write(body)
+            pos += len(body)
+            f.flush()
+    if scp:
+        scp.close()
+
+
+def _g7(v) -> str:
+    """A number as the reference's text streams print it: 7 significant digits (InitKaldiOutputStream, base/io-funcs-inl.h:188-193)."""
+    return "%.7g" % float(v)
+
+
+def _matrix64_bytes(m: np.ndarray, text: bool) -> bytes:
+    """Matrix<double>::Write (cpucompute/matrix.cc:1104-1140): `DM ` + the two sized ints + raw fp64; text ` [` rows `]`."""
+    if text:
+        if m.size == 0:
+            return b" [ ]\n"
+        return b" [" + b"".join(b"\n  " + " ".join(_g7(v) for v in r).encode() + b" " for r in m) + b"]\n"
+    return b"\x00BDM " + b"\x04" + struct.pack("<i", m.shape[0]) + b"\x04" + struct.pack("<i", m.shape[1]) + m.astype("<f8").tobytes()
+
+
+def write_mat64_ark(path: str, items, text: bool = False, scp_path: str = None):
+    """DoubleMatrixWriter (compute-cmvn-stats.cc:90) to `ark:path` / `ark,t:path`, optionally with an scp of byte offsets (ark,scp:)."""
+    scp = open(scp_path, "w") if scp_path else None
+    with _open_out(path) as f:
+        pos = 0
+        for key, m in items:
+            m = np.ascontiguousarray(m, np.float64)
+            f.write(key.encode() + b" ")
+            pos += len(key.encode()) + 1
+            if scp:
+                scp.write(f"{key} {path}:{pos}\n")
+            body = _matrix64_bytes(m, text)
             f.write(body)
             pos += len(body)
             f.flush()

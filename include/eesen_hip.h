@@ -774,6 +774,28 @@ int eesen_feeder_submit_raw(eesen_feeder_t* f, const float* const* utts, const i
  * (row 0: sums and, last, the count; row 1: sums of squares), cols = dim + 1 -> offset_scale[2 x dim] */
 int eesen_cmvn_norm(const double* stats, int rows, int cols, int norm_vars, float* offset_scale);
 
+/* ---- CMVN statistics on the device (compute-cmvn-stats; INTEGRATION.md "CMVN statistics") -----------------------
+ * Per utterance the [2 x (D+1)] double matrix apply-cmvn reads: row 0 the sums of x * w and, last, the count (the sum of w); row 1
+ * the sums of (x * x) * w and a 0.  As in the reference the products are FLOAT products, rounded to fp32 before they are widened and
+ * added in fp64, and a row whose weight is 0 is skipped (a row of infinities under weight 0 leaves the statistics finite).  Sums are
+ * fp64 from the first add, combined in a fixed order without atomics: an utterance's statistics are the same bits in every call,
+ * whatever stands beside it in the batch. */
+/* AccCmvnStats (src/feat/cmvn.cc:30-62) for a minibatch of matrices on the host: utts[s] -> [frames[s] x D] with row stride
+ * strides[s] (NULL: D); weights NULL, or weights[s] NULL (all ones) or -> frames[s] floats; stats <- [S x 2 x (D+1)] doubles.
+ * Synchronises. */
+int eesen_cmvn_stats_parallel(int device, void* stream, const float* const* utts, const int* frames, const int* strides,
+                              const float* const* weights, int S, int D, double* stats);
+/* The same statistics of what the feeder's pipeline holds at stage boundary b (0: what was submitted, k: what stage k-1 wrote;
+ * -1: off, the default), computed beside the batch assembly; unweighted.  Drains the feeder like the other set_* calls;
+ * EESEN_ERR_INVALID for a boundary beyond the current pipeline, and eesen_feeder_set_pipeline refuses a pipeline that would leave
+ * the tap beyond its last boundary. */
+int eesen_feeder_set_stats_tap(eesen_feeder_t* f, int boundary);
+/* stats <- [S x 2 x (D+1)] of the batch in `slot`, *D <- the dimension at the tapped boundary; waits for the slot's batch.
+ * EESEN_ERR_STATE with the tap off, or for a batch submitted without it. */
+int eesen_feeder_stats(eesen_feeder_t* f, int slot, double* stats, int* D);
+/* average ms of `iters` back-to-back launches after one warm-up, without the copies (as eesen_fbank_bench) */
+int eesen_cmvn_stats_bench(int device, void* stream, const float* const* utts, const int* frames, int S, int D, int iters, float* avg_ms);
+
 /* ---- log-mel filterbank features from waveforms (compute-fbank-feats; INTEGRATION.md "Fbank") ------------------
  * Fbank::ComputeInternal (src/feat/feature-fbank.cc:104-183) over a minibatch of ragged waveforms in ONE launch: per frame
  * ExtractWindow (src/feat/feature-functions.cc:91-167: cut [reflected without snip_edges], dither, DC removal, raw log
