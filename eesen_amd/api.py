@@ -1149,7 +1149,8 @@ class Feeder:
 
     def submit_raw(self, mats: Sequence[np.ndarray], cmvn: Optional[Sequence[np.ndarray]] = None) -> int:
         """RAW utterance matrices [T_s x D_in] (+ per utterance the [2 x Dc] CMVN offsets / scales when the pipeline has a
-        CMVN stage); the assembled batch is [T*S x D_out] with T = the longest utterance behind the pipeline."""
+        CMVN stage, None allowed for an utterance without frames); the assembled batch is [T*S x D_out] with T = the longest
+        utterance behind the pipeline."""
         if not len(mats):
             raise EesenError(-1, "empty minibatch")
         mats = [np.ascontiguousarray(m, np.float32) for m in mats]
@@ -1164,11 +1165,13 @@ class Feeder:
         if cmvn is not None:
             if len(cmvn) != S:
                 raise EesenError(-1, "one CMVN vector pair per utterance")
-            cmvn = [np.ascontiguousarray(c, np.float32) for c in cmvn]
-            for c in cmvn:
-                if c.ndim != 2 or c.shape[0] != 2 or c.shape[1] != cmvn[0].shape[1]:
+            # None: a null pointer, which the library takes for an utterance without frames and refuses for any other
+            cmvn = [None if c is None else np.ascontiguousarray(c, np.float32) for c in cmvn]
+            given = [c for c in cmvn if c is not None]
+            for c in given:
+                if c.ndim != 2 or c.shape[0] != 2 or c.shape[1] != given[0].shape[1]:
                     raise EesenError(-1, "CMVN vectors must be [2 x dim] (offsets, scales)")
-            cptr = (C.c_void_p * S)(*[c.ctypes.data for c in cmvn])
+            cptr = (C.c_void_p * S)(*[None if c is None else c.ctypes.data for c in cmvn])
         slot = C.c_int()
         check(self.lib.eesen_feeder_submit_raw(self.h, ptrs, frames.ctypes.data_as(C.POINTER(C.c_int)), None, cptr, S, D, C.byref(slot)))
         self._dims[slot.value] = self.pipeline_shape(D, 1)[1]

@@ -119,8 +119,11 @@ def add_deltas(feats: np.ndarray, order: int = 2, window: int = 2) -> np.ndarray
 
 
 def run_pipeline(stages, feats: np.ndarray, stats=None):
-    """stages: [("cmvn", norm_vars), ("splice", L, R), ("subsample", n, offset), ("deltas", order, window)] in order."""
+    """stages: [("cmvn", norm_vars), ("splice", L, R), ("subsample", n, offset), ("deltas", order, window)] in order.
+    None where the tools write no output: no frame survives, or none came in (their tables cannot hold a matrix without rows)."""
     x = np.asarray(feats, F)
+    if x.shape[0] == 0:
+        return None
     for st in stages:
         if st[0] == "cmvn":
             x = apply_cmvn(stats, bool(st[1]), x)

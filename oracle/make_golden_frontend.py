@@ -41,9 +41,31 @@ def table(seed=777, D=13):
     return utts
 
 
-def run_reference(utts, tail: str, norm_vars: bool, tmp: str):
+def tool_env():
+    return dict(os.environ, PATH=BIN + os.pathsep + os.environ["PATH"])
+
+
+def write_raw(utts, tmp: str) -> str:
     ark, scp = os.path.join(tmp, "raw.ark"), os.path.join(tmp, "raw.scp")
     kaldi_io.write_mat_ark(ark, utts, scp_path=scp)
+    return scp
+
+
+def copy_feats(rspec: str, tmp: str):
+    """What the reference's copy-feats reads from `rspec` (a pipe of its tools), as {key: matrix}."""
+    out = os.path.join(tmp, "out.ark")
+    subprocess.run(f"copy-feats '{rspec}' ark:{out}", shell=True, check=True, env=tool_env(), stderr=subprocess.DEVNULL)
+    return dict(kaldi_io.read_mat_table(f"ark:{out}"))
+
+
+def run_reference_tail(utts, tail: str, tmp: str):
+    """The reference's filters `tail` alone (no CMVN) on `utts`: ({key: matrix}, the rspecifier)."""
+    rspec = f"ark:copy-feats scp:{write_raw(utts, tmp)} ark:- | " + tail
+    return copy_feats(rspec, tmp), rspec
+
+
+def run_reference(utts, tail: str, norm_vars: bool, tmp: str):
+    scp = write_raw(utts, tmp)
     with open(os.path.join(tmp, "utt2spk"), "w") as f:
         for k, _ in utts:
             f.write(f"{k} {k.split('_')[0]}\n")
@@ -53,15 +75,13 @@ def run_reference(utts, tail: str, norm_vars: bool, tmp: str):
     with open(os.path.join(tmp, "spk2utt"), "w") as f:
         for s, ks in spk2utt.items():
             f.write(s + " " + " ".join(ks) + "\n")
-    env = dict(os.environ, PATH=BIN + os.pathsep + os.environ["PATH"])
     cmvn_ark = os.path.join(tmp, "cmvn.ark")
-    subprocess.run(f"compute-cmvn-stats --spk2utt=ark:{tmp}/spk2utt scp:{scp} ark:{cmvn_ark}", shell=True, check=True, env=env,
+    subprocess.run(f"compute-cmvn-stats --spk2utt=ark:{tmp}/spk2utt scp:{scp} ark:{cmvn_ark}", shell=True, check=True, env=tool_env(),
                    stderr=subprocess.DEVNULL)
     rspec = (f"ark:apply-cmvn --norm-vars={'true' if norm_vars else 'false'} --utt2spk=ark:{tmp}/utt2spk ark:{cmvn_ark} scp:{scp} ark:- | " + tail)
-    out = os.path.join(tmp, "out.ark")
-    subprocess.run(f"copy-feats '{rspec}' ark:{out}", shell=True, check=True, env=env, stderr=subprocess.DEVNULL)
+    outs = copy_feats(rspec, tmp)
     stats = dict(kaldi_io.read_mat64_table(f"ark:{cmvn_ark}"))
-    return dict(kaldi_io.read_mat_table(f"ark:{out}")), stats, rspec
+    return outs, stats, rspec
 
 
 def main():
